@@ -11,6 +11,7 @@ A "step" = one complete simplex() of the workload with the tableau already resid
 device-side snapshot; the 32 MB host upload happens once, outside the timed region).
 
   python bench.py [--gpus N] [--steps K] [--warmup W]          (N > 1: spawns N ranks itself, one per GPU, RCCL)
+  python bench.py ... --dump-outputs DIR   (also writes the last timed step's result and tableau as DIR/<name>.npy, float64, <= 64 MB)
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...   (the driver's form)
 
 Prints ONE JSON line on rank 0.  Every result that has a reference answer is CHECKED (pivot digests of SURVEY.md
@@ -185,6 +186,31 @@ def resident_latency_floor(H, W, n_cus=256):
                       "fp64 vector 78.6 TFLOP/s = 128 flop/clk/CU at 2.4 GHz"}
 
 
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, t, res):
+    """--dump-outputs: what the caller of the timed path receives from its last step -- the simplex result and the tableau state
+    (jslp_engine_download) -- as out_dir/<name>.npy, float64, so that two builds can be compared output for output.  A tableau too
+    large for the 64 MB budget is cut to a fixed, seeded sample of its rows (tableau_rows.npy holds their indices)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    m, vibr, vibc, rbv, cbv = t.download()
+    out = {"simplex_result": np.array([float(getattr(res, name)) for name, _ in res._fields_], dtype=np.float64),
+           "var_index_by_row": vibr.astype(np.float64), "var_index_by_col": vibc.astype(np.float64),
+           "rows_by_var": rbv.astype(np.float64), "cols_by_var": cbv.astype(np.float64)}
+    room = DUMP_CAP_BYTES - sum(a.nbytes for a in out.values())
+    if m.nbytes > room:
+        keep = max(1, (room - 8 * m.shape[0]) // (8 * m.shape[1]))
+        rows = np.sort(np.random.default_rng(12345).choice(m.shape[0], size=min(keep, m.shape[0]), replace=False))
+        out["tableau_rows"] = rows.astype(np.float64)
+        m = m[rows]
+    out["tableau"] = np.ascontiguousarray(m, dtype=np.float64)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(out)
+
+
 def kernel_sources_sha():
     """identity of the tree a measurement belongs to, as far as the kernels go: sha256 over jslpsolver_amd/csrc/* and the C ABI header
     (the GPU boxes have no .git; tools/pmc_latest.py stamps the PMC summary with the same hash)"""
@@ -297,7 +323,12 @@ def main():
     ap.add_argument("--no-extras", action="store_true", help="profiling runs: only the timed headline steps")
     ap.add_argument("--sustain-s", type=float, default=6.0, help="seconds of back-to-back headline solves after the timed steps (0 = off)")
     ap.add_argument("--no-dropin", action="store_true", help="skip the end-to-end Solve() leg through the reference host (node)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed (result + tableau) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.only_relaxations:
+        ap.error("--dump-outputs writes the dense-LP headline's outputs: it cannot be combined with --only-relaxations")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(spawn_ranks(args.gpus, sys.argv[1:]))
@@ -400,6 +431,9 @@ def main():
             return res, pivots, elapsed, kern_ms, launches
 
         res, pivots, elapsed, kern_ms, launches = timed_steps(False, args.warmup, args.steps)
+        dumped = None
+        if args.dump_outputs and rank == 0:
+            dumped = dump_outputs(args.dump_outputs, t, res)  # (before verify() below hands the tableau over again)
         total_pivots = sum_over_ranks(float(pivots))
         value = total_pivots / elapsed
         pivots_per_solve = res.pivots_phase1 + max(res.pivots_phase2, 0)
@@ -582,6 +616,8 @@ def main():
                 "roofline": roofline,
             }
             line.update(extras)
+            if dumped is not None:
+                line["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped, "of": "the last timed step"}
             if dropin is not None:
                 line["dropin_js"] = dropin
 

@@ -69,3 +69,39 @@ def test_bench_reports_the_committed_issue_budget_only_for_its_own_tree():
     else:
         assert set(got) == {"note"}
     assert set(bench.pmc_sq("pivots", "another_kernel")) == {"note"}
+
+
+def test_bench_dumps_the_last_steps_outputs_within_the_budget(oracle_lib, tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the result and the downloaded tableau of the solve just run, float64, bit for bit; a tableau over the
+    budget is cut to a fixed, seeded sample of its rows"""
+    import numpy as np
+
+    import bench
+    from jslpsolver_amd import generators
+    from jslpsolver_amd.engine import Tableau
+    m, vibr, vibc = generators.dense_resource_allocation_tableau(12345, 100, 100)
+    t = Tableau(m, vibr, vibc, lib=oracle_lib)
+    try:
+        t.save()
+        res = t.simplex(check_cycles=False)
+        fm, fr, fc, rbv, cbv = t.download()
+        names = bench.dump_outputs(str(tmp_path / "full"), t, res)
+        got = {n: np.load(str(tmp_path / "full" / (n + ".npy"))) for n in names}
+        assert all(a.dtype == np.float64 for a in got.values())
+        assert "tableau_rows" not in got and np.array_equal(got["tableau"], fm)
+        assert np.array_equal(got["var_index_by_row"], fr) and np.array_equal(got["var_index_by_col"], fc)
+        assert np.array_equal(got["rows_by_var"], rbv) and np.array_equal(got["cols_by_var"], cbv)
+        assert got["simplex_result"][[i for i, (n, _) in enumerate(res._fields_) if n == "evaluation"][0]] == res.evaluation
+
+        monkeypatch.setattr(bench, "DUMP_CAP_BYTES", 40 * fm.shape[1] * 8)
+        cut = []
+        for k in range(2):
+            d = tmp_path / ("cut%d" % k)
+            bench.dump_outputs(str(d), t, res)
+            cut.append({n: np.load(str(d / (n + ".npy"))) for n in ("tableau", "tableau_rows")})
+            assert sum(os.path.getsize(str(d / f)) - 128 for f in os.listdir(str(d))) <= bench.DUMP_CAP_BYTES
+        rows = cut[0]["tableau_rows"].astype(np.int64)
+        assert 0 < len(rows) < fm.shape[0] and np.array_equal(cut[0]["tableau"], fm[rows])
+        assert np.array_equal(cut[0]["tableau_rows"], cut[1]["tableau_rows"]) and np.array_equal(cut[0]["tableau"], cut[1]["tableau"])
+    finally:
+        t.close()
