@@ -1239,6 +1239,12 @@ static int run_simplex(jslp_engine* e, int check_cycles) {
 #undef JSLP_RES_LAUNCH_LEAN
 #undef JSLP_RES_LAUNCH_LEAN_ONLY
             if (le == hipSuccess) e->resident_launches += 1;
+            if (le == hipSuccess && getenv("JSLP_DEBUG_LAUNCH")) {  // which instance ran, one parseable line per accepted launch (tests/test_grid_edges.py)
+                // (the instance's template key: the general build is compiled with CHK = true and reads check_cycles at run time)
+                static const int geo_of[7][3] = {{0, 0, 0}, {1024, 2, 8}, {512, 4, 8}, {512, 4, 16}, {512, 6, 12}, {512, 8, 8}, {512, 2, 32}};
+                fprintf(stderr, "[jslp] launch k_simplex_resident<%d,%d,%d> unr %d lean %d opt %d chk %d xl %d G %d rpb %d\n", geo_of[geometry][0], geo_of[geometry][1],
+                        geo_of[geometry][2], (int)unr, (int)lean, (int)(e->n_opt > 0), (int)(check_cycles != 0 || !lean), (int)(geometry == 6), rc.G, rc.rpb);
+            }
             if (le == hipSuccess && lean) {
                 // JSLP_INJECT_RESIDENT_ABORT_US=<n>: raise the host-abort word n microseconds into the launch -- the rollback path (kernel gives
                 // up mid-solve, slot 0 restored from the safety-net copy, the solve re-run through the streaming kernels) exercised on the
@@ -1351,6 +1357,8 @@ static int run_simplex(jslp_engine* e, int check_cycles) {
             void (*kp1)(FusedCtx, int) = e->ld <= JSLP_F_TW ? (e->n_unr > 0 ? k_fused_p1<1, true> : k_fused_p1<1, false>)
                                          : e->ld <= 2 * JSLP_F_TW ? (e->n_unr > 0 ? k_fused_p1<2, true> : k_fused_p1<2, false>)
                                          : e->ld <= 3 * JSLP_F_TW ? k_fused_p1<3, false> : k_fused_p1<4, false>;  // (fused_eligible: no unrestricted variables beyond two tiles)
+            if (getenv("JSLP_DEBUG_LAUNCH"))
+                fprintf(stderr, "[jslp] launch k_fused_p1<%d,%d>\n", (e->ld + JSLP_F_TW - 1) / JSLP_F_TW, (int)(e->ld <= 2 * JSLP_F_TW && e->n_unr > 0));
             for (;;) {
                 int launch = 0;
                 hipLaunchKernelGGL(kp1, dim3(f.G), dim3(JSLP_F_THREADS), 0, s, f, launch);
@@ -1383,6 +1391,7 @@ static int run_simplex(jslp_engine* e, int check_cycles) {
         // ---- phase 1 (and phase 2 when the fused pipeline does not apply): k_select + k_update per pivot ----
         int chunk = fused ? 1 : 8;
         long long done_prev = 0;
+        if (!p1_fused && getenv("JSLP_DEBUG_LAUNCH")) fprintf(stderr, "[jslp] launch select+update\n");
         for (; !p1_fused;) {
             if (e->timing && !fused) { int r = ensure_events(e, 2 * (size_t)chunk); if (r) return r; }
             for (int i = 0; i < chunk; i++) {
@@ -1430,6 +1439,10 @@ static int run_simplex(jslp_engine* e, int check_cycles) {
                 : e->ld <= 2 * JSLP_F_TW ? (unr ? (opt ? k_pivot_fused<2, true, true> : k_pivot_fused<2, true, false>)
                                                 : (opt ? k_pivot_fused<2, false, true> : k_pivot_fused<2, false, false>))
                 : e->ld <= 3 * JSLP_F_TW ? k_pivot_fused<3, false, false> : k_pivot_fused<4, false, false>;  // (fused_eligible: plain tableaus only beyond two tiles)
+            if (getenv("JSLP_DEBUG_LAUNCH")) {
+                const bool small = e->ld <= 2 * JSLP_F_TW;
+                fprintf(stderr, "[jslp] launch k_pivot_fused<%d,%d,%d>\n", (e->ld + JSLP_F_TW - 1) / JSLP_F_TW, (int)(small && unr), (int)(small && opt));
+            }
             int launch = 0;
             hipLaunchKernelGGL(kfused, dim3(f.G), dim3(JSLP_F_THREADS), 0, s, f, launch);
             launch++;
