@@ -1,4 +1,5 @@
-"""ctypes binding of the C ABI declared in include/jslp_engine.h.
+"""ctypes binding of the C ABI declared in include/jslp_engine.h (SYMBOLS) and of its HIP-only extension include/jslpx_branch.h
+(BRANCH_SYMBOLS).
 
 The same binding class serves two libraries that export identical symbols:
   * jslpsolver_amd/csrc/libjslp_hip.so -- the product (hand-written HIP kernels, gfx950)
@@ -127,6 +128,34 @@ SYMBOLS = {
 }
 
 
+class BranchRecord(C.Structure):
+    """struct jslpx_branch_record (include/jslpx_branch.h): a node's outcome as the branch-and-bound tree reads it, 32 bytes"""
+
+    _fields_ = [
+        ("flags", C.c_int32),
+        ("unbounded_var_index", C.c_int32),
+        ("branch_var_index", C.c_int32),
+        ("height", C.c_int32),
+        ("obj_cell", C.c_double),
+        ("branch_var_value", C.c_double),
+    ]
+
+
+BRANCH_FEASIBLE, BRANCH_BOUNDED, BRANCH_OPTIMAL, BRANCH_INTEGRAL = 1, 2, 4, 8
+# numpy twin of BranchRecord (the records of a batch as one structured array)
+BRANCH_RECORD_DTYPE = np.dtype([(name, np.int32 if ctype is C.c_int32 else np.float64) for name, ctype in BranchRecord._fields_])
+
+# name -> (restype, argtypes); must list EVERY symbol include/jslpx_branch.h declares.  The extension is exported by the HIP library
+# only: a Library resolves it when present (Library.has_branch) and the oracle goes without.
+BRANCH_SYMBOLS = {
+    "jslpx_branch_record_bytes": (C.c_int32, []),
+    "jslpx_engine_relax_batch_branch": (C.c_int, [C.c_void_p, C.c_int32, _i32p, _i8p, _i32p, _f64p, C.c_int, C.c_void_p]),
+    "jslpx_engine_relax_batch_branch_pinned": (C.c_int, [C.c_void_p, C.c_int32, _i32p, _i8p, _i32p, _f64p, C.c_int, _P(C.c_void_p)]),
+    "jslpx_engine_relax_batch_branch_device": (C.c_int, [C.c_void_p, C.c_int32, _i32p, _i8p, _i32p, _f64p, C.c_int, C.c_void_p]),
+    "jslpx_engine_results_from_branch_records": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, _P(SimplexResult)]),
+}
+
+
 class EngineError(RuntimeError):
     pass
 
@@ -144,6 +173,13 @@ class Library:
             fn.restype = restype
             fn.argtypes = argtypes
             setattr(self, name, fn)
+        self.has_branch = all(hasattr(self.dll, name) for name in BRANCH_SYMBOLS)
+        if self.has_branch:
+            for name, (restype, argtypes) in BRANCH_SYMBOLS.items():
+                fn = getattr(self.dll, name)
+                fn.restype = restype
+                fn.argtypes = argtypes
+                setattr(self, name, fn)
 
     @property
     def backend(self):

@@ -125,12 +125,16 @@ def _integer_values(model, rhs, rows):
 
 def is_integral(model, rhs, rows, precision):
     """mip-utils.ts:43-61"""
+    if isinstance(rows, _NodeEvalBranch):  # decided on the device (include/jslpx_branch.h)
+        return rows.integral
     _idx, values = _integer_values(model, rhs, rows)
     return not bool((np.abs(values - _js_round_vec(values)) > precision).any())
 
 
 def most_fractional_var(model, rhs, rows):
     """mip-utils.ts:100-126: first variable with the strictly biggest |v - round(v)|"""
+    if isinstance(rows, _NodeEvalBranch):
+        return rows.branch_var, rows.branch_value
     idx, values = _integer_values(model, rhs, rows)
     if values.size == 0:
         return None, 0.0
@@ -190,10 +194,24 @@ class _NodeEvalWatched:
         self.res, self.wrows, self.wvals = res, wrows, wvals
 
 
+class _NodeEvalBranch:
+    """the same from a BRANCH RECORD (include/jslpx_branch.h): isIntegral() and getMostFractionalVar() already decided on the device, over
+    the integer variables in model.integerVariables order -- 32 bytes per node whatever their number"""
+    __slots__ = ("res", "integral", "branch_var", "branch_value")
+
+    def __init__(self, res, record):
+        from ._capi import BRANCH_INTEGRAL
+        self.res = res
+        self.integral = bool(int(record["flags"]) & BRANCH_INTEGRAL)
+        k = int(record["branch_var_index"])
+        self.branch_var = k if k >= 0 else None
+        self.branch_value = float(record["branch_var_value"]) if k >= 0 else 0.0
+
+
 EVAL_STATS = {"seconds": 0.0, "batches": 0, "nodes": 0}  # speculative batches since the caller last zeroed it (bench.py)
 
 
-def branch_and_cut(tableau, model, speculate=1, evaluate_batch=None):
+def branch_and_cut(tableau, model, speculate=1, evaluate_batch=None, read_back=None):
     """branch-and-cut.ts:54-199.  Leaves `tableau` holding the incumbent; returns the iteration count and
     whether an integral node was accepted (tableau.__isIntegral).
 
@@ -203,6 +221,10 @@ def branch_and_cut(tableau, model, speculate=1, evaluate_batch=None):
     its cut list); the loop itself still pops, prunes and commits in the reference's order, so the incumbent,
     the iteration count and the result are those of the sequential run.  `evaluate_batch(cut_lists)` may shard
     the batch over several GPUs (jslpsolver_amd.sharding); default: the tableau's own applyCutsBatch.
+
+    read_back ("full" / "compact" / "branch"; None = JSLP_TREE_BRANCH=1 -> "branch", else "compact") picks what a speculative batch reads
+    back per node: whole RHS columns + row maps, the integer variables' rows and values, or the 32-byte branch record the engine reduces
+    them to (include/jslpx_branch.h).  Opt-in; whichever it is, the tree, its result and its iteration count are the same.
     """
     branches = BranchMinHeap()
     iterations = 0
@@ -226,8 +248,13 @@ def branch_and_cut(tableau, model, speculate=1, evaluate_batch=None):
     # (JSLP_TREE_COMPACT=0: whole columns per speculated node, as before round 5)
     # (the engine takes at most row_capacity watched variables -- a model with more integers than rows + cut capacity keeps the
     #  whole-column read-back instead of failing on its first speculative batch)
-    compact_ok = (evaluate_batch is None and os.environ.get("JSLP_TREE_COMPACT", "1") != "0" and hasattr(tableau, "applyCutsBatchWatched")
-                  and 0 < len(model.integer_index_array) <= getattr(tableau, "row_capacity", 0))
+    if read_back is None:
+        read_back = "branch" if os.environ.get("JSLP_TREE_BRANCH", "0") == "1" else "compact"
+    if read_back not in ("full", "compact", "branch"):
+        raise ValueError("branch_and_cut: read_back must be 'full', 'compact' or 'branch'")
+    compact_ok = (evaluate_batch is None and read_back != "full" and os.environ.get("JSLP_TREE_COMPACT", "1") != "0"
+                  and hasattr(tableau, "applyCutsBatchWatched") and 0 < len(model.integer_index_array) <= getattr(tableau, "row_capacity", 0))
+    branch_ok = compact_ok and read_back == "branch"
     watched_set = []
     watched_before = list(getattr(tableau, "watched", []) or [])  # the caller's own registration, put back when the tree is done
     saved = False
@@ -248,6 +275,9 @@ def branch_and_cut(tableau, model, speculate=1, evaluate_batch=None):
                 if not watched_set:
                     tableau.set_watched_variables(model.integer_index_array)
                     watched_set.append(True)
+                if branch_ok:  # the branching decision itself, made on the device (include/jslpx_branch.h)
+                    results, recs = tableau.applyCutsBatchBranch(cut_lists, check_cycles=check)
+                    return [_NodeEvalBranch(results[i], recs[i]) for i in range(len(cut_lists))]
                 results, wrows, wvals = tableau.applyCutsBatchWatched(cut_lists, check_cycles=check)
                 return [_NodeEvalWatched(results[i], wrows[i].copy(), wvals[i].copy()) for i in range(len(cut_lists))]
             results, rhs, vibr = tableau.applyCutsBatch(cut_lists, check_cycles=check)
@@ -280,7 +310,9 @@ def branch_and_cut(tableau, model, speculate=1, evaluate_batch=None):
                 speculated += len(batch)
             ev = cache.pop(seq)
             tableau._absorb(ev.res)
-            if isinstance(ev, _NodeEvalWatched):
+            if isinstance(ev, _NodeEvalBranch):
+                rhs, vibr = None, ev
+            elif isinstance(ev, _NodeEvalWatched):
                 rhs, vibr = None, _WatchedRows(ev.wrows, ev.wvals)
             else:
                 rhs, vibr = ev.rhs, ev.vibr
@@ -307,7 +339,7 @@ def branch_and_cut(tableau, model, speculate=1, evaluate_batch=None):
                         break
             if worse:
                 continue
-        rows = vibr if isinstance(vibr, _WatchedRows) else _rows_by_var(vibr)
+        rows = vibr if isinstance(vibr, (_WatchedRows, _NodeEvalBranch)) else _rows_by_var(vibr)
         if is_integral(model, rhs, rows, precision):
             found_integral = True
             if iterations == 1:

@@ -13,6 +13,7 @@
 #define JSLP_WITH_XL 1
 #endif
 #include "../../include/jslp_engine.h"
+#include "../../include/jslpx_branch.h"
 #include "jslp_kernels.hip.h"
 
 #include <math.h>
@@ -113,6 +114,9 @@ struct jslp_engine {
     int resident_handovers = 0;  // solves the lean resident kernel handed to the general one (cycle-check history beyond its LDS copy)
     int resident_launches = 0;   // cooperative launches of k_simplex_resident the runtime accepted
     int resident_refusals = 0;   // ... it refused (or that no build exists for): the solve went through the streaming kernels
+    std::vector<jslp_simplex_result> rec_results;  // per-node results of a branch-record call (the record is what the caller gets)
+    double* d_rec = nullptr; jslpx_branch_record* h_rec = nullptr; size_t rec_cap = 0;  // branch records of a batch (device / pinned, rec_cap each)
+    double* dev_rec = nullptr;  // jslpx_engine_relax_batch_branch_device: the caller's device memory the records go to
     double dev_prev_evaluation = 0.0;  // jslp_engine_relax_batch_device: the evaluation its nodes started from (results_from_states)
     int dev_prev_valid = 0;
     // checkpoints (incremental-branch-and-cut.ts:31-44): equally sized device buffers, recycled through a free list
@@ -588,6 +592,7 @@ extern "C" void jslp_engine_destroy(jslp_engine* e) {
     hipFree(e->f_st[0]); hipFree(e->f_st[1]);
     hipFree(e->d_cuts); if (e->h_cuts) hipHostFree(e->h_cuts);
     hipFree(e->d_out); if (e->h_out) hipHostFree(e->h_out);
+    hipFree(e->d_rec); if (e->h_rec) hipHostFree(e->h_rec);
     if (e->h_state) hipHostFree(e->h_state);
     for (auto ev : e->ev_pool) hipEventDestroy(ev);
     if (e->ev_begin) hipEventDestroy(e->ev_begin);
@@ -1942,13 +1947,16 @@ static int relax_batch_impl(jslp_engine* e, int32_t n_nodes, const int32_t* cut_
                             const int32_t* var_index, const double* value, int check_cycles, jslp_simplex_result* out,
                             double* rhs, int32_t* var_index_by_row, int32_t out_stride, int pinned, int want_rhs,
                             int want_rows, int checkpoint = -1, int compact = 0) {
+    // compact: 0 = full read-back, 1 = the watched variables' rows / RHS cells, 2 = the branch record (include/jslpx_branch.h): the node
+    // kernels' compact read-back stays in device memory and k_branch_record reduces it to 32 bytes per node (e->d_rec, or e->dev_rec)
     const auto t_enter = std::chrono::steady_clock::now();  // (JSLP_DEBUG_STALL)
     const bool dev_out = e && e->dev_states != nullptr;  // outcomes stay on the device (jslp_engine_relax_batch_device)
     if (e && !dev_out) e->dev_prev_valid = 0;
     if (!e || n_nodes < 0 || !cut_offsets || (!out && !dev_out)) return fail(JSLP_ERR_ARG, "relax_batch: null pointer");
     if (!e->uploaded) return fail(JSLP_ERR_STATE, "relax before upload");
     if (compact && (e->n_watch <= 0 || e->n_watch > e->cap_rows))
-        return fail(JSLP_ERR_ARG, "relax_watched: after set_watched_variables (at most row_capacity of them)");
+        return fail(JSLP_ERR_ARG, compact == 2 ? "relax_batch_branch: after set_watched_variables (at most row_capacity of them)"
+                                               : "relax_watched: after set_watched_variables (at most row_capacity of them)");
     // gather mode: >= 0 = the whole RHS column / row map with this row stride; < 0 = the watched variables only
     const int g_stride = compact ? -e->n_watch : (dev_out ? (int)e->dev_stride : (int)out_stride_of(e));
     const size_t row_stride = compact ? (size_t)e->n_watch : (dev_out ? (size_t)e->dev_stride : out_stride_of(e));  // entries per node in the read-back buffers
@@ -1968,7 +1976,7 @@ static int relax_batch_impl(jslp_engine* e, int32_t n_nodes, const int32_t* cut_
     int rc;
     // ---- ONE child of the saved root, slot 0 already in sync with the snapshot: one launch, one synchronisation ----------
     if (n_nodes == 1 && checkpoint < 0 && e->has_save && e->slot0_synced && !e->timing && e->force_path <= 1 &&
-        e->one_launch_nodes && cells <= wg_cells_child() && !e->ext_states && !dev_out) {
+        e->one_launch_nodes && cells <= wg_cells_child() && !e->ext_states && !dev_out && compact != 2) {
         rc = upload_cuts(e, 1, cut_offsets, type, var_index, value, false);
         if (rc) return rc;
         rc = ensure_out(e, 1);
@@ -2065,11 +2073,20 @@ static int relax_batch_impl(jslp_engine* e, int32_t n_nodes, const int32_t* cut_
     }
     rc = ensure_out(e, (size_t)n_nodes);  // laid out for ALL nodes: [states | rhs | rows]
     if (rc) return rc;
+    if (compact == 2 && (size_t)n_nodes > e->rec_cap) {
+        hipFree(e->d_rec);
+        if (e->h_rec) hipHostFree(e->h_rec);
+        e->d_rec = nullptr; e->h_rec = nullptr; e->rec_cap = 0;
+        const size_t cap = std::max<size_t>((size_t)n_nodes, 16);
+        HIPC(hipMalloc(&e->d_rec, sizeof(jslpx_branch_record) * cap));
+        HIPC(hipHostMalloc(&e->h_rec, sizeof(jslpx_branch_record) * cap));
+        e->rec_cap = cap;
+    }
     if (e->timing) HIPC(hipEventRecord(e->ev_begin, s));
     // where the kernels leave the outcomes: the device staging buffer (copied group by group on the copy stream) or, zero-copy,
     // the pinned host buffer itself - the stores cross PCIe while the other workgroups compute
     DevState* o_states = e->d_states; double* o_rhs = e->d_rhs; int32_t* o_rows = e->d_rows;
-    bool zc = zero_copy() != 0;
+    bool zc = zero_copy() != 0 && compact != 2;  // (branch records: the compact read-back they are reduced from stays on the device)
     unsigned* polled_flag = nullptr;  // set when the call ends by polling a completion flag instead of synchronising the streams
     unsigned polled_seq = 0;
     if (dev_out) { o_states = e->dev_states; o_rhs = e->dev_rhs; o_rows = e->dev_rows; zc = false; }
@@ -2083,7 +2100,7 @@ static int relax_batch_impl(jslp_engine* e, int32_t n_nodes, const int32_t* cut_
             zc = false;
         }
     }
-    if (!zc && !dev_out && !e->copy_stream) {
+    if (!zc && !dev_out && compact != 2 && !e->copy_stream) {
         // created on first use, and only by the calls that copy their outcomes back (JSLP_ZERO_COPY=0, no mapped pinned memory): a stream costs a Solve of a
         // tiny model more than its pivots do
         HIPC(hipStreamCreateWithFlags(&e->copy_stream, hipStreamNonBlocking));
@@ -2110,7 +2127,7 @@ static int relax_batch_impl(jslp_engine* e, int32_t n_nodes, const int32_t* cut_
             hipLaunchKernelGGL((k_node_queue<512, false>), dim3(group), dim3(512), lds, s, e->s, sn, cu, (int)n_nodes, order, e->d_queue, check_cycles,
                                cap, (int)e->cap_rows, want_rhs ? o_rhs : nullptr, want_rows ? o_rows : nullptr, o_states, g_stride);
         HIPC(hipGetLastError());
-        if (!zc && !dev_out) {
+        if (!zc && !dev_out && compact != 2) {
             HIPC(hipMemcpyAsync(e->h_states, e->d_states, sizeof(DevState) * (size_t)n_nodes, hipMemcpyDeviceToHost, s));
             if (want_rhs) HIPC(hipMemcpyAsync(e->h_rhs, e->d_rhs, sizeof(double) * (size_t)n_nodes * row_stride, hipMemcpyDeviceToHost, s));
             if (want_rows) HIPC(hipMemcpyAsync(e->h_rows, e->d_rows, sizeof(int32_t) * (size_t)n_nodes * row_stride, hipMemcpyDeviceToHost, s));
@@ -2210,7 +2227,7 @@ static int relax_batch_impl(jslp_engine* e, int32_t n_nodes, const int32_t* cut_
         }  // !one_launch
         // this group's outcomes cross PCIe on the copy stream while the next group computes (the three regions of the
         // read-back buffer are laid out for all nodes, so a group is one contiguous slice of each)
-        if (zc || dev_out) continue;
+        if (zc || dev_out || compact == 2) continue;
         HIPC(hipEventRecord(e->ev_group, s));
         HIPC(hipStreamWaitEvent(e->copy_stream, e->ev_group, 0));
         HIPC(hipMemcpyAsync(e->h_states + first, e->d_states + first, sizeof(DevState) * (size_t)g, hipMemcpyDeviceToHost, e->copy_stream));
@@ -2220,6 +2237,15 @@ static int relax_batch_impl(jslp_engine* e, int32_t n_nodes, const int32_t* cut_
         if (want_rows)
             HIPC(hipMemcpyAsync(e->h_rows + (size_t)first * row_stride, e->d_rows + (size_t)first * row_stride,
                                 sizeof(int32_t) * (size_t)g * row_stride, hipMemcpyDeviceToHost, e->copy_stream));
+    }
+    if (compact == 2) {  // the branch records of the whole batch, one workgroup per node, behind every node kernel on the stream
+        hipLaunchKernelGGL(k_branch_record, dim3(n_nodes), dim3(256), 0, s, o_states, o_rows, o_rhs, e->s.watch, (int)e->n_watch, e->precision,
+                           dev_out ? e->dev_rec : e->d_rec);
+        HIPC(hipGetLastError());
+        if (!dev_out) {
+            HIPC(hipMemcpyAsync(e->h_states, e->d_states, sizeof(DevState) * (size_t)n_nodes, hipMemcpyDeviceToHost, s));
+            HIPC(hipMemcpyAsync(e->h_rec, e->d_rec, sizeof(jslpx_branch_record) * (size_t)n_nodes, hipMemcpyDeviceToHost, s));
+        }
     }
     if (e->timing && wg) HIPC(hipEventRecord(e->ev_end, s));
     bool arrived = false;
@@ -2304,6 +2330,7 @@ static int relax_batch_impl(jslp_engine* e, int32_t n_nodes, const int32_t* cut_
                 memcpy(var_index_by_row + (size_t)i * out_stride, e->h_rows + (size_t)i * row_stride, sizeof(int32_t) * n_out);
         }
     }
+    if (compact == 2) { e->dev_prev_evaluation = prev_eval; e->dev_prev_valid = 1; }
     if (!pinned && compact) {  // same layout on both sides: one copy each (per-node copies cost more than the kernel's share of a node)
         if (rhs) memcpy(rhs, e->h_rhs, sizeof(double) * (size_t)n_nodes * row_stride);
         if (var_index_by_row) memcpy(var_index_by_row, e->h_rows, sizeof(int32_t) * (size_t)n_nodes * row_stride);
@@ -2454,6 +2481,79 @@ extern "C" int jslp_engine_relax_batch_watched_device(jslp_engine* e, int32_t n_
 }
 
 extern "C" int32_t jslp_engine_watched_count(const jslp_engine* e) { return e ? e->n_watch : 0; }
+
+// ---- branch records (include/jslpx_branch.h) --------------------------------------------------------------------------------------
+static_assert(sizeof(jslpx_branch_record) == 32, "jslpx_branch_record is 32 bytes");
+static_assert(BREC_FEASIBLE == JSLPX_BRANCH_FEASIBLE && BREC_BOUNDED == JSLPX_BRANCH_BOUNDED && BREC_OPTIMAL == JSLPX_BRANCH_OPTIMAL &&
+              BREC_INTEGRAL == JSLPX_BRANCH_INTEGRAL, "branch record flags");
+extern "C" int32_t jslpx_branch_record_bytes(void) { return (int32_t)sizeof(jslpx_branch_record); }
+
+// where relax_batch_impl leaves the per-node results of a record call (the engine's bookkeeping; the caller gets the records)
+static jslp_simplex_result* branch_results_scratch(jslp_engine* e, int32_t n_nodes) {
+    if ((int32_t)e->rec_results.size() < std::max(n_nodes, 1)) e->rec_results.resize((size_t)std::max(n_nodes, 1));
+    return e->rec_results.data();
+}
+
+extern "C" int jslpx_engine_relax_batch_branch(jslp_engine* e, int32_t n_nodes, const int32_t* cut_offsets, const int8_t* type,
+                                               const int32_t* var_index, const double* value, int check_cycles, jslpx_branch_record* out) {
+    if (!e || !out) return fail(JSLP_ERR_ARG, "relax_batch_branch: null pointer");
+    jslp_simplex_result* res = branch_results_scratch(e, std::max(n_nodes, 0));
+    const int rc = relax_batch_impl(e, n_nodes, cut_offsets, type, var_index, value, check_cycles, res, nullptr, nullptr, 0, 1, 1, 1, -1, 2);
+    if (rc) return rc;
+    if (n_nodes > 0) memcpy(out, e->h_rec, sizeof(jslpx_branch_record) * (size_t)n_nodes);
+    return JSLP_OK;
+}
+
+extern "C" int jslpx_engine_relax_batch_branch_pinned(jslp_engine* e, int32_t n_nodes, const int32_t* cut_offsets, const int8_t* type,
+                                                      const int32_t* var_index, const double* value, int check_cycles,
+                                                      const jslpx_branch_record** out) {
+    if (!e || !out) return fail(JSLP_ERR_ARG, "relax_batch_branch_pinned: null pointer");
+    jslp_simplex_result* res = branch_results_scratch(e, std::max(n_nodes, 0));
+    const int rc = relax_batch_impl(e, n_nodes, cut_offsets, type, var_index, value, check_cycles, res, nullptr, nullptr, 0, 1, 1, 1, -1, 2);
+    if (rc) return rc;
+    *out = n_nodes > 0 ? e->h_rec : nullptr;
+    return JSLP_OK;
+}
+
+// the records in the caller's device memory; the compact read-back they are reduced from and the 128-byte states the engine checks every
+// node with stay in its own staging buffers
+extern "C" int jslpx_engine_relax_batch_branch_device(jslp_engine* e, int32_t n_nodes, const int32_t* cut_offsets, const int8_t* type,
+                                                      const int32_t* var_index, const double* value, int check_cycles, void* d_records) {
+    if (!e || !d_records) return fail(JSLP_ERR_ARG, "relax_batch_branch_device: null pointer");
+    if ((reinterpret_cast<uintptr_t>(d_records) & 15) != 0) return fail(JSLP_ERR_ARG, "relax_batch_branch_device: records must be 16-byte aligned");
+    if (!e->uploaded) return fail(JSLP_ERR_STATE, "relax before upload");
+    if (e->n_watch <= 0 || e->n_watch > e->cap_rows)
+        return fail(JSLP_ERR_ARG, "relax_batch_branch: after set_watched_variables (at most row_capacity of them)");
+    HIPC(hipSetDevice(e->device));
+    int rc = ensure_out(e, (size_t)std::max(n_nodes, 1));
+    if (rc) return rc;
+    e->dev_states = e->d_states; e->dev_rhs = e->d_rhs; e->dev_rows = e->d_rows; e->dev_stride = e->n_watch; e->dev_rec = static_cast<double*>(d_records);
+    rc = relax_batch_impl(e, n_nodes, cut_offsets, type, var_index, value, check_cycles, nullptr, nullptr, nullptr, 0, 1, 1, 1, -1, 2);
+    e->dev_states = nullptr; e->dev_rhs = nullptr; e->dev_rows = nullptr; e->dev_stride = 0; e->dev_rec = nullptr;
+    return rc;
+}
+
+// records (host memory: this rank's or, after the exchange, another rank's) -> result structs, evaluation as fill_result derives it
+extern "C" int jslpx_engine_results_from_branch_records(jslp_engine* e, const void* records, int32_t n, jslp_simplex_result* out) {
+    if (!e || n < 0 || (n > 0 && (!records || !out))) return fail(JSLP_ERR_ARG, "results_from_branch_records: bad arguments");
+    const jslpx_branch_record* rec = static_cast<const jslpx_branch_record*>(records);
+    const double prev = e->dev_prev_valid ? e->dev_prev_evaluation : e->evaluation;
+    const double rc = js_round(1.0 / e->precision);
+    for (int32_t i = 0; i < n; i++) {
+        jslpx_branch_record r;
+        memcpy(&r, rec + i, sizeof r);
+        jslp_simplex_result& o = out[i];
+        memset(&o, 0, sizeof o);
+        o.feasible = (r.flags & JSLPX_BRANCH_FEASIBLE) != 0;
+        o.bounded = (r.flags & JSLPX_BRANCH_BOUNDED) != 0;
+        o.optimal = (r.flags & JSLPX_BRANCH_OPTIMAL) != 0;
+        o.unbounded_var_index = r.unbounded_var_index;
+        o.height = r.height;
+        o.obj_cell = r.obj_cell;
+        o.evaluation = o.optimal ? js_round((2.220446049250313e-16 + r.obj_cell) * rc) / rc : (!o.bounded ? -INFINITY : prev);
+    }
+    return JSLP_OK;
+}
 
 extern "C" int jslp_engine_set_counting(jslp_engine* e, int enabled) {
     if (!e) return fail(JSLP_ERR_ARG, "set_counting: null engine");

@@ -397,6 +397,81 @@ __global__ void __launch_bounds__(256) k_gather(Slots s, int first_slot, double*
     gather_slot(s, first_slot + blockIdx.x, rhs, rows, states, out_stride, first_out + blockIdx.x);
 }
 
+// ---- branch record (include/jslpx_branch.h): isIntegral() + getMostFractionalVar() of a node, reduced on the device --------------
+enum { BREC_FEASIBLE = 1, BREC_BOUNDED = 2, BREC_OPTIMAL = 4, BREC_INTEGRAL = 8 };
+// what one thread has seen of the watched list: any fraction > precision, the largest fraction (NaN ranks below every real one)
+// and the FIRST position holding it -- positions are handed out in ascending order per thread, so on a tie the earlier one stays
+struct BranchAcc {
+    double best;
+    int pos;
+    int nonint;
+};
+__device__ __forceinline__ void branch_acc_init(BranchAcc& a) { a.best = -1.0; a.pos = 0x7fffffff; a.nonint = 0; }
+// one counted (basic) watched variable at list position i with RHS value v (mip-utils.ts:43-61, 100-126)
+__device__ __forceinline__ void branch_acc_add(BranchAcc& a, double v, int i, double precision) {
+    const double f = floor(v);
+    const double r = (v - f >= 0.5) ? f + 1.0 : f;  // Math.round: ties toward +Infinity (the subtraction is exact)
+    const double frac = fabs(v - r);
+    a.nonint |= frac > precision ? 1 : 0;            // (NaN: false)
+    const double key = frac == frac ? frac : -1.0;
+    if (key > a.best) { a.best = key; a.pos = i; }
+}
+__device__ __forceinline__ void branch_acc_merge(BranchAcc& a, double best, int pos, int nonint) {
+    if (best > a.best || (best == a.best && pos < a.pos)) { a.best = best; a.pos = pos; }
+    a.nonint |= nonint;
+}
+// Every thread of the block calls this with its partial: wave64 shuffles, one LDS slot per wave, wave 0 finishes; thread 0 writes the
+// record as two 16-byte stores.  value_at(pos) re-reads the winner's RHS value (thread 0, only when there is a winner).
+template <class ValueAt>
+__device__ __forceinline__ void branch_record_store(BranchAcc a, const DevState* st, const int32_t* watch, ValueAt value_at, double* out, int o,
+                                                    int tid) {
+    __shared__ double rb_best[16];
+    __shared__ int rb_pos[16], rb_nonint[16];
+    const int lane = tid & 63, w = tid >> 6, nw = ((int)blockDim.x + 63) >> 6;
+    for (int off = 32; off > 0; off >>= 1) {
+        const double b = __shfl_down(a.best, off, 64);
+        const int p = __shfl_down(a.pos, off, 64), q = __shfl_down(a.nonint, off, 64);
+        branch_acc_merge(a, b, p, q);
+    }
+    __syncthreads();  // (a previous record of this block has been read out of the wave slots)
+    if (lane == 0) { rb_best[w] = a.best; rb_pos[w] = a.pos; rb_nonint[w] = a.nonint; }
+    __syncthreads();
+    if (w == 0) {
+        BranchAcc b;
+        branch_acc_init(b);
+        if (lane < nw) { b.best = rb_best[lane]; b.pos = rb_pos[lane]; b.nonint = rb_nonint[lane]; }
+        for (int off = 8; off > 0; off >>= 1) {
+            const double x = __shfl_down(b.best, off, 64);
+            const int p = __shfl_down(b.pos, off, 64), q = __shfl_down(b.nonint, off, 64);
+            branch_acc_merge(b, x, p, q);
+        }
+        if (lane == 0) {
+            const bool pick = b.best > 0.0;
+            const int flags = (st->feasible ? BREC_FEASIBLE : 0) | (st->bounded ? BREC_BOUNDED : 0) | (st->optimal ? BREC_OPTIMAL : 0) |
+                              (b.nonint ? 0 : BREC_INTEGRAL);
+            int4* dst = reinterpret_cast<int4*>(out + 4LL * o);
+            dst[0] = make_int4(flags, st->bounded ? -1 : st->unbounded_var, pick ? watch[b.pos] : -1, st->H);
+            reinterpret_cast<double2*>(dst + 1)[0] = make_double2(st->obj_cell, pick ? value_at(b.pos) : 0.0);
+        }
+    }
+}
+
+// The branch records of a batch from its compact read-back (states + the watched variables' rows / RHS cells, laid out [node][watched] in
+// device memory by any of the node kernels' compact gathers): ONE workgroup per node reduces the node's list -- every entry is a row in
+// (0, H) or -1 -- into the 32-byte record.  A launch of its own behind the node kernels, so that none of them carries a register or a
+// byte of LDS more (the 512-thread queue kernel is built to the last VGPR of its occupancy budget, JSLP_NODE512_WAVES).
+__global__ void __launch_bounds__(256) k_branch_record(const DevState* states, const int32_t* rows, const double* vals, const int32_t* watch,
+                                                       int n_watch, double precision, double* out) {
+    const int node = blockIdx.x, tid = threadIdx.x;
+    const int32_t* r = rows + (long long)node * n_watch;
+    const double* v = vals + (long long)node * n_watch;
+    BranchAcc a;
+    branch_acc_init(a);
+    for (int i = tid; i < n_watch; i += blockDim.x)
+        if (r[i] > 0) branch_acc_add(a, v[i], i, precision);
+    branch_record_store(a, states + node, watch, [&](int p) { return v[p]; }, out, node, tid);
+}
+
 // ---------------------------------------------------------------------------------------------------
 // ONE branch-and-bound child in ONE launch (slot 0, from the saved root): the restore of the rows the previous node
 // dirtied, the commit, addCutConstraints, the whole simplex() and the read-back, which goes straight into the pinned

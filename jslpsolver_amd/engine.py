@@ -238,6 +238,87 @@ class Tableau:
                        "jslp_engine_results_from_states")
         return out
 
+    # ---- branch records (include/jslpx_branch.h): isIntegral() / getMostFractionalVar() of every node, 32 bytes per node ----------
+    def _branch_native(self, what):
+        """True: the library computes the records (HIP, jslpx_* exported); False: the oracle, whose records are restated here from its
+        compact read-back (branch_record_from_watched).  A HIP library without the extension is an error, never a fallback."""
+        if self.lib.has_branch:
+            return True
+        if self.lib.backend == "oracle-c":
+            if self.watched_count() <= 0:
+                raise _capi.EngineError("%s failed (%d): relax_batch_branch: after set_watched_variables" % (what, _capi.JSLP_ERR_ARG))
+            return False
+        raise _capi.EngineError("%s: %s does not export the branch-record extension (include/jslpx_branch.h)" % (what, self.lib.path))
+
+    def _branch_restated(self, pk, check_cycles):
+        """the oracle's records: its compact read-back of the same call, restated"""
+        results, wrows, wvals = self.applyCutsBatchWatched(None, check_cycles=check_cycles, packed=pk)
+        n = pk[0]
+        res = [results[i] for i in range(n)]
+        # the evaluation a node without an optimum keeps (fill_result): what the call started from
+        self._branch_prev = next((r.evaluation for r in res if not r.optimal and r.bounded), self.evaluation)
+        return branch_record_from_watched(res, wrows[:n], wvals[:n], self.watched, self.precision)
+
+    def applyCutsBatchBranch(self, cut_lists, check_cycles=True, packed=None, copy=True):
+        """Independent branch-and-bound nodes in one call whose read-back is the BRANCH RECORD of each node (flags, height, raw objective
+        cell, isIntegral() and getMostFractionalVar() over the watched variables).  Returns (results, records): SimplexResult per node as
+        results_from_branch_records derives it (no pivot counts) and the records as a numpy structured array (_capi.BRANCH_RECORD_DTYPE).
+        copy=False: the records are a view of the engine's pinned buffer, valid until the next call on this tableau."""
+        pk = packed if packed is not None else self.pack_cut_lists(cut_lists)
+        n_nodes = pk[0]
+        if not self._branch_native("applyCutsBatchBranch"):
+            recs = self._branch_restated(pk, check_cycles)
+            return self.results_from_branch_records(recs, n_nodes), recs
+        if copy:
+            recs = np.zeros(max(n_nodes, 1), dtype=_capi.BRANCH_RECORD_DTYPE)
+            self.lib.check(self.lib.jslpx_engine_relax_batch_branch(self._h, n_nodes, *_cut_ptrs(pk), int(bool(check_cycles)),
+                                                                     _capi.C.c_void_p(recs.ctypes.data)), "jslpx_engine_relax_batch_branch")
+            recs = recs[:n_nodes]
+        else:
+            p = _capi.C.c_void_p()
+            self.lib.check(self.lib.jslpx_engine_relax_batch_branch_pinned(self._h, n_nodes, *_cut_ptrs(pk), int(bool(check_cycles)),
+                                                                            _capi.C.byref(p)), "jslpx_engine_relax_batch_branch_pinned")
+            recs = np.zeros(0, dtype=_capi.BRANCH_RECORD_DTYPE)
+            if n_nodes > 0:
+                buf = (_capi.C.c_char * (n_nodes * _capi.BRANCH_RECORD_DTYPE.itemsize)).from_address(p.value)
+                recs = np.frombuffer(buf, dtype=_capi.BRANCH_RECORD_DTYPE, count=n_nodes)
+        return self.results_from_branch_records(recs, n_nodes), recs
+
+    def applyCutsBatchBranchDevice(self, packed, check_cycles, records_ptr):
+        """jslpx_engine_relax_batch_branch_device: the records (32 bytes per node) left at `records_ptr`, memory of the engine's device
+        (a torch tensor's data_ptr(); host memory for the oracle, whose records are restated here); nothing else is copied back"""
+        if not self._branch_native("applyCutsBatchBranchDevice"):
+            recs = self._branch_restated(packed, check_cycles)
+            _capi.C.memmove(int(records_ptr), recs.ctypes.data, recs.nbytes)
+            return
+        self.lib.check(self.lib.jslpx_engine_relax_batch_branch_device(self._h, packed[0], *_cut_ptrs(packed), int(bool(check_cycles)),
+                                                                        _capi.C.c_void_p(records_ptr)), "jslpx_engine_relax_batch_branch_device")
+
+    def results_from_branch_records(self, records, n_nodes):
+        """branch records (host bytes or a structured array: this rank's or, after the exchange, another rank's) -> SimplexResult array,
+        evaluation as every other entry point derives it; pivot counts 0"""
+        out = (SimplexResult * max(n_nodes, 1))()
+        buf = np.ascontiguousarray(records).view(np.uint8).reshape(-1)
+        if buf.size < n_nodes * _capi.BRANCH_RECORD_DTYPE.itemsize:
+            raise ValueError("results_from_branch_records: %d bytes for %d records" % (buf.size, n_nodes))
+        if self.lib.has_branch:
+            self.lib.check(self.lib.jslpx_engine_results_from_branch_records(self._h, _capi.C.c_void_p(buf.ctypes.data), int(n_nodes), out),
+                           "jslpx_engine_results_from_branch_records")
+            return out
+        self._branch_native("results_from_branch_records")
+        recs = buf[:n_nodes * _capi.BRANCH_RECORD_DTYPE.itemsize].view(_capi.BRANCH_RECORD_DTYPE)
+        rc = _js_round(1.0 / self.precision)
+        prev = getattr(self, "_branch_prev", self.evaluation)
+        for i in range(n_nodes):
+            f = int(recs["flags"][i])
+            r = out[i]
+            r.feasible, r.bounded, r.optimal = int(bool(f & _capi.BRANCH_FEASIBLE)), int(bool(f & _capi.BRANCH_BOUNDED)), int(bool(f & _capi.BRANCH_OPTIMAL))
+            r.unbounded_var_index = int(recs["unbounded_var_index"][i])
+            r.height = int(recs["height"][i])
+            r.obj_cell = float(recs["obj_cell"][i])
+            r.evaluation = (_js_round((_EPSILON + r.obj_cell) * rc) / rc if r.optimal else (float("-inf") if not r.bounded else prev))
+        return out
+
     # ---- compact read-back, work counters, pinned host build --------------------------------------------------
     def set_watched_variables(self, var_indexes):
         """the variable indexes the branch-and-bound tree reads between relaxations (the integer variables)"""
@@ -530,6 +611,46 @@ class DevicePool:
         c = _capi.WorkCounters()
         self.lib.check(self.lib.jslp_pool_get_counters(self._p, _capi.C.byref(c)), "jslp_pool_get_counters")
         return c.as_dict()
+
+
+_EPSILON = 2.220446049250313e-16
+
+
+def _js_round(x):
+    """Math.round: nearest integer, ties toward +Infinity"""
+    if x != x or x in (float("inf"), float("-inf")):
+        return x
+    f = float(np.floor(x))
+    return f + 1.0 if x - f >= 0.5 else f
+
+
+def branch_record_from_watched(results, wrows, wvals, watched, precision):
+    """The branch record (include/jslpx_branch.h) restated from the compact read-back of the same nodes -- the oracle's records and the
+    tests' yardstick.  results: SimplexResult per node (or one); wrows / wvals: [n, w] rows (-1 = not basic) and RHS cells of the watched
+    variables `watched`, in registration order.  Returns a structured array (_capi.BRANCH_RECORD_DTYPE) of n records:
+    isIntegral() (mip-utils.ts:43-61) and getMostFractionalVar() (:100-126) over the basic watched variables, Math.round ties toward
+    +Infinity, fractions compared strictly (> precision, > the best so far: the first of equal fractions wins, NaN never does)."""
+    if isinstance(results, SimplexResult):
+        results = [results]
+    n = len(results)
+    rows = np.asarray(wrows, dtype=np.int64).reshape(n, -1)
+    vals = np.asarray(wvals, dtype=np.float64).reshape(n, -1)
+    watched = np.asarray(watched, dtype=np.int64)
+    out = np.zeros(n, dtype=_capi.BRANCH_RECORD_DTYPE)
+    with np.errstate(invalid="ignore"):
+        for i, r in enumerate(results):
+            basic = (rows[i] > 0) & (rows[i] < r.height)
+            v = vals[i]
+            f = np.floor(v)
+            frac = np.abs(v - np.where(v - f >= 0.5, f + 1.0, f))
+            integral = not bool(((frac > precision) & basic).any())
+            key = np.where(basic & ~np.isnan(frac), frac, -1.0)
+            k = int(np.argmax(key)) if key.size else 0  # first index of the maximum
+            pick = key.size > 0 and key[k] > 0.0
+            flags = ((_capi.BRANCH_FEASIBLE if r.feasible else 0) | (_capi.BRANCH_BOUNDED if r.bounded else 0) |
+                     (_capi.BRANCH_OPTIMAL if r.optimal else 0) | (_capi.BRANCH_INTEGRAL if integral else 0))
+            out[i] = (flags, r.unbounded_var_index, int(watched[k]) if pick else -1, r.height, r.obj_cell, float(v[k]) if pick else 0.0)
+    return out
 
 
 def pivot_digest(pairs):

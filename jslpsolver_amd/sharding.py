@@ -22,7 +22,7 @@ import ctypes
 
 import numpy as np
 
-from ._capi import SimplexResult
+from ._capi import BRANCH_RECORD_DTYPE, SimplexResult
 from .branch_and_cut import _NodeEval
 
 RES_BYTES = ctypes.sizeof(SimplexResult)
@@ -313,6 +313,87 @@ def evaluate_nodes_sharded_watched(tableau, cut_lists, check_cycles, group, pack
     return ShardedOutcomesWatched(blocks, n, world, per, w, rec, tableau)
 
 
+class ShardedOutcomesBranch:
+    """every node's BRANCH RECORD after the all-gather (include/jslpx_branch.h): rank r's block is [per records of 32 bytes], node i sits in
+    rank (i % world)'s block at slot i // world.  The records are the whole payload -- 32 bytes per node whatever the number of integer
+    variables -- and are converted lazily, node by node, as the tree asks for them."""
+
+    def __init__(self, blocks, n, world, per, tableau):
+        self.blocks, self.n, self.world, self.per, self.tableau = blocks, n, world, per, tableau  # blocks: [world, block_bytes] uint8
+        self.rb = BRANCH_RECORD_DTYPE.itemsize
+
+    def __len__(self):
+        return self.n
+
+    def records(self):
+        """all n records in node order (structured array)"""
+        recs = np.ascontiguousarray(self.blocks[:, :self.per * self.rb]).view(BRANCH_RECORD_DTYPE).reshape(self.world, self.per)
+        idx = np.arange(self.n)
+        return recs[idx % self.world, idx // self.world]
+
+    def record(self, i):
+        o = (i // self.world) * self.rb
+        return self.blocks[i % self.world, o:o + self.rb].view(BRANCH_RECORD_DTYPE)[0]
+
+    def result(self, i):
+        o = (i // self.world) * self.rb
+        return self.tableau.results_from_branch_records(self.blocks[i % self.world, o:o + self.rb], 1)[0]
+
+    def node(self, i):
+        from .branch_and_cut import _NodeEvalBranch
+        return _NodeEvalBranch(self.result(i), self.record(i))
+
+    def heights(self):
+        return self.records()["height"].astype(np.int32)
+
+
+def branch_block_bytes(per):
+    """bytes one rank contributes to the branch-record exchange for `per` nodes"""
+    return _align(per * BRANCH_RECORD_DTYPE.itemsize)
+
+
+def evaluate_nodes_sharded_branch(tableau, cut_lists, check_cycles, group, packed_mine=None, copy=True):
+    """The branch-record exchange: the engine writes, per node, the 32-byte branch record (isIntegral() / getMostFractionalVar() decided on
+    the device, include/jslpx_branch.h) in place into this rank's block -- device memory under RCCL -- which IS the all-gather's input; the
+    gathered block crosses to the host in one copy and nothing is converted per node up front.  The tableau's watched variables must have
+    been set (Tableau.set_watched_variables(model.integer_index_array)) -- identically on every rank."""
+    import time
+    import torch
+    import torch.distributed as dist
+
+    world = dist.get_world_size(group)
+    rank = dist.get_rank(group)
+    n = len(cut_lists)
+    if tableau.watched_count() <= 0:
+        raise ValueError("evaluate_nodes_sharded_branch: Tableau.set_watched_variables first")
+    per = max((n + world - 1) // world, 1)
+    block = branch_block_bytes(per)
+    on_gpu = tableau.lib.backend.startswith("hip")
+    gather_on_gpu = on_gpu and dist.get_backend(group) == "nccl"
+    local, out, host = _exchange_buffers(block, world, on_gpu, gather_on_gpu)
+    n_mine = len(range(rank, n, world))
+    if n_mine:
+        packed = packed_mine if packed_mine is not None else tableau.pack_cut_lists(shard(cut_lists, rank, world))
+        tableau.applyCutsBatchBranchDevice(packed, check_cycles, local.data_ptr())
+    t0 = time.perf_counter()
+    send = local
+    if on_gpu and not gather_on_gpu:  # HIP engines under a CPU process group (N virtual shards on one GPU)
+        send = local.cpu()
+    dist.all_gather_into_tensor(out.view(-1), send, group=group)
+    if gather_on_gpu:
+        host.copy_(out, non_blocking=True)  # ONE DMA into pinned memory
+        torch.cuda.current_stream().synchronize()
+        blocks = host.numpy()
+    else:
+        blocks = out.numpy()
+    if copy:
+        blocks = blocks.copy()  # (copy=False: the outcomes are VIEWS of the reused buffers, valid until this process's next exchange)
+    EXCHANGE_STATS["seconds"] += time.perf_counter() - t0
+    EXCHANGE_STATS["calls"] += 1
+    EXCHANGE_STATS["bytes"] += int(block)
+    return ShardedOutcomesBranch(blocks, n, world, per, tableau)
+
+
 def evaluate_nodes_sharded(tableau, cut_lists, check_cycles, group, packed_mine=None):
     """Every rank calls this with the same `cut_lists`; returns the outcomes of ALL nodes on every rank
     (ShardedOutcomes).  `packed_mine`: this rank's share already flattened by Tableau.pack_cut_lists."""
@@ -339,14 +420,20 @@ def evaluate_nodes_sharded(tableau, cut_lists, check_cycles, group, packed_mine=
     return ShardedOutcomes(blocks, n, world, stride)
 
 
-def make_sharded_evaluator(tableau, check_cycles, group, watched=None):
+def make_sharded_evaluator(tableau, check_cycles, group, watched=None, branch=False):
     """evaluate(cut_lists) for branch_and_cut(evaluate_batch=...).  `watched` = the variable indexes the tree reads between
     relaxations (the model's integer variables): the COMPACT exchange -- registered on the engine here, once (every rank passes the
-    same list); None = whole RHS columns + row maps (JSLP_SHARD_COMPACT=0 forces that form)."""
+    same list); None = whole RHS columns + row maps (JSLP_SHARD_COMPACT=0 forces that form).  branch=True (with `watched`): the
+    branch-record exchange instead, 32 bytes per node (evaluate_nodes_sharded_branch)."""
     import os
     # (ADVICE r05: the engine takes at most row_capacity watched variables; a model with more integers than that exchanges whole columns)
     if watched is not None and os.environ.get("JSLP_SHARD_COMPACT", "1") != "0" and 0 < len(watched) <= tableau.row_capacity:
         tableau.set_watched_variables(watched)
+        if branch:
+            def evaluate_branch(cut_lists):
+                out = evaluate_nodes_sharded_branch(tableau, cut_lists, check_cycles, group)
+                return [out.node(i) for i in range(len(out))]
+            return evaluate_branch
 
         def evaluate_compact(cut_lists):
             out = evaluate_nodes_sharded_watched(tableau, cut_lists, check_cycles, group)

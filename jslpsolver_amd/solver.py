@@ -2,6 +2,7 @@
 hot path running on the MI355X engine.  Model parsing and the branch-and-bound tree stay on the CPU.
 """
 import math
+import os
 import warnings
 
 from . import _capi
@@ -80,7 +81,8 @@ def _solve_on(t, m, n_int, incremental, speculate, group, full):
         evaluate = None
         if group is not None:
             from .sharding import make_sharded_evaluator
-            evaluate = make_sharded_evaluator(t, m.checkForCycles, group, watched=m.integer_index_array)
+            evaluate = make_sharded_evaluator(t, m.checkForCycles, group, watched=m.integer_index_array,
+                                              branch=os.environ.get("JSLP_SHARD_BRANCH", "0") == "1")
         if incremental:  # selectBranchAndCutService (main.ts:62-72)
             from .incremental_branch_and_cut import incremental_branch_and_cut
             iterations, integral = incremental_branch_and_cut(
