@@ -5,6 +5,6 @@ include/jslp_engine.h) and the thin host mirror of the reference interface for t
 """
 from .engine import Tableau, pivot_digest  # noqa: F401
 from .model import Model, UnsupportedModel  # noqa: F401
-from .solver import Solve  # noqa: F401
+from .solver import Solve, solve_many  # noqa: F401
 
-__all__ = ["Tableau", "Model", "Solve", "UnsupportedModel", "pivot_digest"]
+__all__ = ["Tableau", "Model", "Solve", "solve_many", "UnsupportedModel", "pivot_digest"]

@@ -1,5 +1,5 @@
-"""ctypes binding of the C ABI declared in include/jslp_engine.h (SYMBOLS) and of its HIP-only extension include/jslpx_branch.h
-(BRANCH_SYMBOLS).
+"""ctypes binding of the C ABI declared in include/jslp_engine.h (SYMBOLS) and of its HIP-only extensions include/jslpx_branch.h
+(BRANCH_SYMBOLS) and include/jslpm_many.h (MANY_SYMBOLS).
 
 The same binding class serves two libraries that export identical symbols:
   * jslpsolver_amd/csrc/libjslp_hip.so -- the product (hand-written HIP kernels, gfx950)
@@ -156,6 +156,13 @@ BRANCH_SYMBOLS = {
 }
 
 
+# name -> (restype, argtypes); must list EVERY symbol include/jslpm_many.h declares.  HIP library only, like BRANCH_SYMBOLS
+# (Library.has_many).
+MANY_SYMBOLS = {
+    "jslpm_simplex_many": (C.c_int, [_P(C.c_void_p), C.c_int32, _i32p, _P(SimplexResult), _i32p]),
+}
+
+
 class EngineError(RuntimeError):
     pass
 
@@ -173,13 +180,19 @@ class Library:
             fn.restype = restype
             fn.argtypes = argtypes
             setattr(self, name, fn)
-        self.has_branch = all(hasattr(self.dll, name) for name in BRANCH_SYMBOLS)
-        if self.has_branch:
-            for name, (restype, argtypes) in BRANCH_SYMBOLS.items():
-                fn = getattr(self.dll, name)
-                fn.restype = restype
-                fn.argtypes = argtypes
-                setattr(self, name, fn)
+        self.has_branch = self._bind_extension(BRANCH_SYMBOLS)
+        self.has_many = self._bind_extension(MANY_SYMBOLS)
+
+    def _bind_extension(self, symbols):
+        """bind a HIP-only extension when the library exports all of it; False otherwise"""
+        if not all(hasattr(self.dll, name) for name in symbols):
+            return False
+        for name, (restype, argtypes) in symbols.items():
+            fn = getattr(self.dll, name)
+            fn.restype = restype
+            fn.argtypes = argtypes
+            setattr(self, name, fn)
+        return True
 
     @property
     def backend(self):

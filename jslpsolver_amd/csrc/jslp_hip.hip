@@ -14,6 +14,7 @@
 #endif
 #include "../../include/jslp_engine.h"
 #include "../../include/jslpx_branch.h"
+#include "../../include/jslpm_many.h"
 #include "jslp_kernels.hip.h"
 
 #include <math.h>
@@ -318,7 +319,9 @@ static bool pool_give(const PooledRes& r) {
     return true;
 }
 
+static void release_many_resources();
 extern "C" void jslp_release_pooled_resources(void) {
+    release_many_resources();  // (the jslpm_simplex_many buffers)
     std::vector<PooledRes> drop;
     {
         std::lock_guard<std::mutex> lk(g_pool_mu);
@@ -2551,6 +2554,165 @@ extern "C" int jslpx_engine_results_from_branch_records(jslp_engine* e, const vo
         o.height = r.height;
         o.obj_cell = r.obj_cell;
         o.evaluation = o.optimal ? js_round((2.220446049250313e-16 + r.obj_cell) * rc) / rc : (!o.bounded ? -INFINITY : prev);
+    }
+    return JSLP_OK;
+}
+
+// ---- many independent LPs in one launch (include/jslpm_many.h) ------------------------------------------------------------------
+// Per device, kept from call to call: the descriptor table and the final states of a batch, [ManyLp x n | DevState x n] on the
+// device and its pinned twin.  One call at a time holds them (g_many_mu); jslp_release_pooled_resources frees them.
+struct ManyRes {
+    int device = -1;
+    char* d_buf = nullptr; char* h_buf = nullptr; size_t cap = 0;
+};
+static std::mutex g_many_mu;
+static std::vector<ManyRes> g_many;
+
+static void release_many_resources() {
+    std::lock_guard<std::mutex> lk(g_many_mu);
+    for (auto& r : g_many) {
+        hipSetDevice(r.device);
+        hipFree(r.d_buf);
+        if (r.h_buf) hipHostFree(r.h_buf);
+    }
+    g_many.clear();
+}
+
+static int many_buffers(int device, size_t bytes, ManyRes** out) {  // (caller holds g_many_mu)
+    ManyRes* r = nullptr;
+    for (auto& x : g_many) if (x.device == device) r = &x;
+    if (!r) { g_many.emplace_back(); r = &g_many.back(); r->device = device; }
+    if (r->cap < bytes) {
+        hipFree(r->d_buf); r->d_buf = nullptr;
+        if (r->h_buf) hipHostFree(r->h_buf);
+        r->h_buf = nullptr; r->cap = 0;
+        const size_t cap = std::max<size_t>(bytes, 64 * 1024);
+        HIPC(hipMalloc(&r->d_buf, cap));
+        HIPC(hipHostMalloc(&r->h_buf, cap));
+        r->cap = cap;
+    }
+    *out = r;
+    return JSLP_OK;
+}
+
+extern "C" int jslpm_simplex_many(jslp_engine* const* engines, int32_t n, const int32_t* check_cycles, jslp_simplex_result* out,
+                                  int32_t* status) {
+    if (n < 0 || (n > 0 && (!engines || !out))) return fail(JSLP_ERR_ARG, "simplex_many: bad arguments");
+    if (n == 0) return JSLP_OK;
+    char idx[32];
+    for (int32_t i = 0; i < n; i++) {
+        snprintf(idx, sizeof idx, "%d", (int)i);
+        if (!engines[i]) return fail(JSLP_ERR_STATE, "simplex_many: engine %s is null", idx);
+        if (!engines[i]->uploaded) return fail(JSLP_ERR_STATE, "simplex_many: engine %s: simplex before upload", idx);
+    }
+    {
+        std::vector<const jslp_engine*> sorted(engines, engines + n);
+        std::sort(sorted.begin(), sorted.end());
+        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return fail(JSLP_ERR_ARG, "simplex_many: an engine is listed twice");
+    }
+    const int device = engines[0]->device;
+    for (int32_t i = 1; i < n; i++)
+        if (engines[i]->device != device) return fail(JSLP_ERR_ARG, "simplex_many: engines on different devices");
+    HIPC(hipSetDevice(device));
+    if (status) for (int32_t i = 0; i < n; i++) status[i] = JSLP_OK;
+    int32_t first_bad = -1; int first_rc = JSLP_OK; char first_msg[sizeof g_err];
+    auto note = [&](int32_t i, int rc) {
+        if (status) status[i] = rc;
+        if (first_bad < 0 || i < first_bad) { first_bad = i; first_rc = rc; snprintf(first_msg, sizeof first_msg, "%s", g_err); }
+    };
+    // routing: the engines whose own policy runs simplex() in one workgroup with LDS selection state go into the batch
+    // (plain first, then optional objectives); every other engine afterwards, through its own path
+    std::vector<int32_t> plain, opt, rest;
+    size_t lds_plain = 0, lds_opt = 0;
+    for (int32_t i = 0; i < n; i++) {
+        const jslp_engine* e = engines[i];
+        const size_t lds = use_wg_single(e) ? wglds_smem(e) : 0;
+        if (!lds) rest.push_back(i);
+        else if (e->s.n_opt > 0) { opt.push_back(i); lds_opt = std::max(lds_opt, lds); }
+        else { plain.push_back(i); lds_plain = std::max(lds_plain, lds); }
+    }
+    const size_t nb = plain.size() + opt.size();
+    if (nb) {
+        std::lock_guard<std::mutex> lk(g_many_mu);
+        ManyRes* res = nullptr;
+        const size_t table_bytes = (sizeof(ManyLp) * nb + 255) & ~(size_t)255;
+        int rc = many_buffers(device, table_bytes + sizeof(DevState) * nb, &res);
+        if (rc) return rc;
+        ManyLp* h_lps = reinterpret_cast<ManyLp*>(res->h_buf);
+        ManyLp* d_lps = reinterpret_cast<ManyLp*>(res->d_buf);
+        DevState* h_st = reinterpret_cast<DevState*>(res->h_buf + table_bytes);
+        DevState* d_st = reinterpret_cast<DevState*>(res->d_buf + table_bytes);
+        std::vector<int32_t> order(plain);
+        order.insert(order.end(), opt.begin(), opt.end());
+        jslp_engine* const lead = engines[order[0]];
+        hipStream_t s = lead->stream;
+        for (size_t k = 0; k < nb; k++) {
+            jslp_engine* e = engines[order[k]];
+            e->slot0_synced = 0;
+            e->abort_injected = 0;
+            e->last_path = "workgroup-many";
+            ManyLp& m = h_lps[k];
+            m.s = e->s;
+            m.check_cycles = check_cycles ? check_cycles[order[k]] : 1;
+            m.iters_cap = iters_cap(e);
+            m.cap_rows = e->cap_rows;
+            m.pad = 0;
+            if (e != lead) {  // the launch runs after whatever the member's stream holds
+                HIPC(hipEventRecord(e->ev_end, e->stream));
+                HIPC(hipStreamWaitEvent(s, e->ev_end, 0));
+            }
+        }
+        HIPC(hipMemcpyAsync(d_lps, h_lps, sizeof(ManyLp) * nb, hipMemcpyHostToDevice, s));
+        HIPC(hipEventRecord(lead->ev_begin, s));
+        const bool dbg = getenv("JSLP_DEBUG_LAUNCH") != nullptr;
+        for (int variant = 0; variant < 2; variant++) {
+            const size_t cnt = variant ? opt.size() : plain.size();
+            if (!cnt) continue;
+            const size_t lds = variant ? lds_opt : lds_plain;
+            const ManyLp* lps = d_lps + (variant ? plain.size() : 0);
+            DevState* sts = d_st + (variant ? plain.size() : 0);
+            // one LP: the 1024-thread latency shape; a batch: the node batches' workgroup size (LDS builds exist for 512 and 1024)
+            const int shape = cnt == 1 || wg_batch_threads() == 1024 ? 1024 : 512;
+            if (shape == 1024 && variant)
+                hipLaunchKernelGGL((k_simplex_lds_many<1024, true>), dim3(cnt), dim3(1024), lds, s, lps, sts);
+            else if (shape == 1024)
+                hipLaunchKernelGGL((k_simplex_lds_many<1024, false>), dim3(cnt), dim3(1024), lds, s, lps, sts);
+            else if (variant)
+                hipLaunchKernelGGL((k_simplex_lds_many<512, true>), dim3(cnt), dim3(512), lds, s, lps, sts);
+            else
+                hipLaunchKernelGGL((k_simplex_lds_many<512, false>), dim3(cnt), dim3(512), lds, s, lps, sts);
+            HIPC(hipGetLastError());
+            if (dbg) fprintf(stderr, "[jslp] launch k_simplex_lds_many<%d,opt %d> n %zu lds %zu\n", shape, variant, cnt, lds);
+        }
+        HIPC(hipMemcpyAsync(h_st, d_st, sizeof(DevState) * nb, hipMemcpyDeviceToHost, s));
+        HIPC(hipEventRecord(lead->ev_end, s));
+        for (size_t k = 0; k < nb; k++) {  // every member's stream continues after the launch
+            jslp_engine* e = engines[order[k]];
+            if (e != lead) HIPC(hipStreamWaitEvent(e->stream, lead->ev_end, 0));
+        }
+        HIPC(hipStreamSynchronize(s));
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, lead->ev_begin, lead->ev_end) != hipSuccess) ms = 0;
+        for (size_t k = 0; k < nb; k++) {  // what jslp_engine_simplex does after run_simplex, per member
+            const int32_t i = order[k];
+            jslp_engine* e = engines[i];
+            e->total_ms += ms;
+            *e->h_state = h_st[k];
+            rc = state_error(*e->h_state);
+            if (!rc) {
+                account(e, *e->h_state, 0);
+                rc = fill_result(e, *e->h_state, 0, e->evaluation, &out[i], &e->evaluation);
+            }
+            if (rc) note(i, rc);
+        }
+    }
+    for (int32_t i : rest) {  // only once the batch has completed: a cooperative chip-wide launch must not meet its workgroups
+        const int rc = jslp_engine_simplex(engines[i], check_cycles ? check_cycles[i] : 1, &out[i]);
+        if (rc) note(i, rc);
+    }
+    if (first_bad >= 0) {
+        snprintf(g_err, sizeof g_err, "simplex_many: LP %d: %s", (int)first_bad, first_msg);
+        return first_rc;
     }
     return JSLP_OK;
 }

@@ -864,6 +864,48 @@ __global__ void __launch_bounds__(THREADS) k_simplex_lds(Slots s, int first_slot
     simplex_wg_lds<(THREADS >= 1024 ? WGL_UN1024 : WGL_UN512), OPT, (THREADS >= 1024 || WGL_PF512)>(c, sm, L, iters_cap);
 }
 
+// One independent LP of a jslpm_simplex_many batch: the slot-0 descriptor of its engine and the scalars k_simplex_lds takes as
+// arguments.  Built on the host, one entry per workgroup.
+struct ManyLp {
+    Slots s;
+    int32_t check_cycles, iters_cap, cap_rows, pad;
+};
+
+// A pointer loaded from memory is generic to the compiler (flat loads and stores, which wait on both the vector and the LDS
+// counters); a kernel argument is known to be global.  Casting through address space 1 tells the compiler where the descriptor's
+// pointers point, so the solve compiles to the global_load / global_store k_simplex_lds uses.
+template <class T>
+__device__ __forceinline__ T* many_global(T* p) {
+    typedef __attribute__((address_space(1))) T GT;
+    return (T*)(GT*)(uintptr_t)p;
+}
+__device__ __forceinline__ Slots many_slots(Slots s) {
+    s.A = many_global(s.A); s.vibr = many_global(s.vibr); s.vibc = many_global(s.vibc); s.rbv = many_global(s.rbv);
+    s.cbv = many_global(s.cbv); s.unr = many_global(s.unr); s.prow = many_global(s.prow); s.pcol = many_global(s.pcol);
+    s.dirty = many_global(s.dirty); s.rhs = many_global(s.rhs); s.oo = many_global(s.oo); s.st = many_global(s.st);
+    s.hist = many_global(s.hist); s.trace = many_global(s.trace); s.cnt = many_global(s.cnt); s.watch = many_global(s.watch);
+    s.watch_pos = many_global(s.watch_pos);
+    return s;
+}
+
+// simplex() of LP blockIdx.x of a batch of INDEPENDENT engines: k_simplex_lds on slot 0 of each engine, its own ld / cap_rows
+// carving the dynamic LDS (sized by the host for the largest member).  No workgroup talks to another: a batch larger than the
+// chip holds at once queues in the hardware.  The first lanes of wave 0 copy the final DevState to states[blockIdx.x] so the host
+// reads all of them with one copy.
+template <int THREADS, bool OPT = false>
+__global__ void __launch_bounds__(THREADS) k_simplex_lds_many(const ManyLp* __restrict__ lps, DevState* __restrict__ states) {
+    extern __shared__ __attribute__((aligned(16))) double lds_dyn[];
+    __shared__ SmemL sm;
+    const ManyLp m = lps[blockIdx.x];  // one uniform copy at entry: the solve reads the descriptor from registers, never through `lps`
+    const Ctx c = slot_ctx(many_slots(m.s), 0, m.check_cycles);
+    const WgLds L = wglds_carve(lds_dyn, m.s.ld, m.cap_rows);
+    simplex_wg_lds<(THREADS >= 1024 ? WGL_UN1024 : WGL_UN512), OPT, (THREADS >= 1024 || WGL_PF512)>(c, sm, L, m.iters_cap);
+    __syncthreads();
+    static_assert(sizeof(DevState) % 8 == 0 && sizeof(DevState) / 8 <= 64, "DevState is copied by one wave, a word per lane");
+    if (threadIdx.x < sizeof(DevState) / 8)  // (one 8-byte word per lane: a whole-struct copy by one thread would hold 32 VGPRs)
+        reinterpret_cast<long long*>(states + blockIdx.x)[threadIdx.x] = reinterpret_cast<const long long*>(c.st)[threadIdx.x];
+}
+
 // The LDS twin of k_node_wg: ONE branch-and-bound child per workgroup in ONE launch -- restore of the rows the previous node
 // dirtied, the index maps, addCutConstraints, simplex() and the read-back (see k_node_wg for the contract).
 #ifndef JSLP_NODE512_WAVES

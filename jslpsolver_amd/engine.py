@@ -616,6 +616,43 @@ class DevicePool:
 _EPSILON = 2.220446049250313e-16
 
 
+def simplex_many(tableaux, check_cycles=True):
+    """simplex() of many independent tableaus in one engine call (include/jslpm_many.h): the results, in order, each folded into its
+    Tableau exactly as Tableau.simplex() folds it.  `check_cycles` is one bool for all or one per tableau.
+
+    Every tableau must use the same Library.  The HIP library solves the batch with jslpm_simplex_many; the CPU oracle (which does not
+    export the extension) runs the same calls one by one; a HIP library without the extension is an error, never a fallback."""
+    tableaux = list(tableaux)
+    n = len(tableaux)
+    if isinstance(check_cycles, (bool, int, np.bool_)):
+        flags = [bool(check_cycles)] * n
+    else:
+        flags = [bool(c) for c in check_cycles]
+        if len(flags) != n:
+            raise ValueError("simplex_many: %d check_cycles flags for %d tableaus" % (len(flags), n))
+    if n == 0:
+        return []
+    lib = tableaux[0].lib
+    if any(t.lib is not lib for t in tableaux):
+        raise ValueError("simplex_many: every tableau must use the same engine library")
+    if not lib.has_many:
+        if lib.backend == "oracle-c":
+            return [t.simplex(check_cycles=c) for t, c in zip(tableaux, flags)]
+        raise _capi.EngineError("simplex_many: %s does not export the batch extension (include/jslpm_many.h)" % lib.path)
+    handles = (_capi.C.c_void_p * n)(*[t._h.value for t in tableaux])
+    cc = _capi.as_i32([int(c) for c in flags])
+    out = (SimplexResult * n)()
+    status = np.zeros(n, dtype=np.int32)
+    rc = lib.jslpm_simplex_many(handles, n, _capi.ptr_i32(cc), out, _capi.ptr_i32(status))
+    if rc != _capi.JSLP_OK and not status.any():  # refused before any work
+        lib.check(rc, "jslpm_simplex_many")
+    for t, res, st in zip(tableaux, out, status):  # (an LP that failed leaves its tableau's scalars alone, as simplex() does)
+        if st == _capi.JSLP_OK:
+            t._absorb(res)
+    lib.check(rc, "jslpm_simplex_many")
+    return list(out)
+
+
 def _js_round(x):
     """Math.round: nearest integer, ties toward +Infinity"""
     if x != x or x in (float("inf"), float("-inf")):

@@ -7,7 +7,7 @@ import warnings
 
 from . import _capi
 from .branch_and_cut import branch_and_cut, js_round
-from .engine import Tableau
+from .engine import Tableau, simplex_many
 from .model import Model, js_keys
 
 EPSILON = 2.220446049250313e-16
@@ -37,6 +37,32 @@ def Solve(model, precision=None, full=False, validate=False, lib=None, device=0,
     simplex, so results may differ on models it touches (a UserWarning says so once); `options.keep_solutions` is
     rejected (UnsupportedModel).
     """
+    m, t, n_int, incremental = _prepare(model, precision, lib, device, row_capacity_extra)
+    try:
+        return _solve_on(t, m, n_int, incremental, speculate, group, full)
+    finally:
+        t.close()  # also on errors (JSLP_ERR_CAPACITY ...): the engine goes back to the library's resource pool
+
+
+def solve_many(models, precision=None, lib=None, device=0):
+    """[Solve(m, precision, lib=lib, device=device) for m in models], in order, with the simplex() of every model without integer
+    variables solved in ONE engine call (engine.simplex_many: one workgroup per LP on the GPU).  Models with integer variables go
+    through Solve's branch-and-bound as they are.  A model Solve rejects raises the same exception before anything is solved."""
+    prepared = []
+    try:
+        for model in models:
+            prepared.append(_prepare(model, precision, lib, device, None))
+        lps = [(m, t) for m, t, n_int, _ in prepared if n_int == 0]
+        simplex_many([t for _, t in lps], check_cycles=[m.checkForCycles for m, _ in lps])
+        return [_solve_on(t, m, n_int, incremental, 1, None, False, simplex_done=n_int == 0)
+                for m, t, n_int, incremental in prepared]
+    finally:
+        for _, t, _, _ in prepared:
+            t.close()
+
+
+def _prepare(model, precision, lib, device, row_capacity_extra):
+    """Solve's set-up: the parsed model, its engine with the tableau uploaded, the integer count and the service choice"""
     global _presolve_warned
     if model is None:
         raise ValueError("Solver requires a model to operate on")  # main.ts:110-112
@@ -48,7 +74,7 @@ def Solve(model, precision=None, full=False, validate=False, lib=None, device=0,
         _presolve_warned = True
         warnings.warn("jslpsolver_amd.Solve does not run the reference's presolve pre-pass (src/tableau/presolve.ts): on models "
                       "where presolve fixes variables or proves infeasibility the result can differ from solver.Solve(); "
-                      "pass options.presolve = false to compare like with like, or use the reference host + binding", stacklevel=2)
+                      "pass options.presolve = false to compare like with like, or use the reference host + binding", stacklevel=3)
     matrix, vibr, vibc = m.build_tableau()
     n_int = len(m.integerVariables)
     # cut rows: at most one "min" and one "max" cut per integer variable (branch-and-cut.ts:166-179)
@@ -68,13 +94,10 @@ def Solve(model, precision=None, full=False, validate=False, lib=None, device=0,
     t = Tableau(matrix, vibr, vibc, m.unrestricted, precision=m.precision, row_capacity=matrix.shape[0] + extra,
                 device=device, lib=lib, optional_objectives=optional_rows,
                 integer_variables=[v["index"] for v in m.integerVariables] if m.useMIRCuts else None)
-    try:
-        return _solve_on(t, m, n_int, incremental, speculate, group, full)
-    finally:
-        t.close()  # also on errors (JSLP_ERR_CAPACITY ...): the engine goes back to the library's resource pool
+    return m, t, n_int, incremental
 
 
-def _solve_on(t, m, n_int, incremental, speculate, group, full):
+def _solve_on(t, m, n_int, incremental, speculate, group, full, simplex_done=False):
     iterations = 0
     integral = False
     if n_int > 0:  # tableau.ts:250-258
@@ -95,7 +118,7 @@ def _solve_on(t, m, n_int, incremental, speculate, group, full):
                 branching=m.options.get("branching") or "pseudocost")
         else:
             iterations, integral = branch_and_cut(t, m, speculate=speculate, evaluate_batch=evaluate)
-    else:
+    elif not simplex_done:  # (solve_many: the batch has run it)
         t.simplex(check_cycles=m.checkForCycles)
     rhs, rows = t.read_rhs()
     evaluation = t.evaluation if m.isMinimization else -t.evaluation  # tableau.ts:261
