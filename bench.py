@@ -2,21 +2,25 @@
 """bench.py -- headline measurement (BASELINE.json): simplex pivots/sec on the synthetic dense LP
 generateResourceAllocation({seed:12345, numVariables:2000, numConstraints:2000, density:1.0}) (config 3a:
 2001 x 2001 fp64 tableau, 9726 pivots, cycle check off -- the FASTER reference setting), 1 GPU; with --gpus N every
-rank solves its own replica (a single LP does not shard: SURVEY.md 8e "replicas only").  Riding along in the same JSON
-line: the same LP with the reference's DEFAULT cycle check on, the all-phase-1 instance 3b, and config 4's LP
-relaxations/sec (Monster_II): an independent node batch sharded over the ranks (weak scaling) and ONE real
-branch-and-bound tree sharded over the ranks with RCCL as the exchange step (strong scaling).
+rank solves its own replica (a single LP does not shard: SURVEY.md 8e "replicas only").  With --full, riding along in
+the same JSON line: the same LP with the reference's DEFAULT cycle check on, the all-phase-1 instance 3b, the streaming
+instance beyond the register file, the drop-in through the reference host, and config 4's LP relaxations/sec
+(Monster_II): an independent node batch sharded over the ranks (weak scaling) and ONE real branch-and-bound tree
+sharded over the ranks with RCCL as the exchange step (strong scaling).
 
 A "step" = one complete simplex() of the workload with the tableau already resident in HBM (restored from the
 device-side snapshot; the 32 MB host upload happens once, outside the timed region).
 
   python bench.py [--gpus N] [--steps K] [--warmup W]          (N > 1: spawns N ranks itself, one per GPU, RCCL)
   python bench.py ... --dump-outputs DIR   (also writes the last timed step's result and tableau as DIR/<name>.npy, float64, <= 64 MB)
+  python bench.py ... --full               (every other leg, check and baseline below; the --no-* options trim it)
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...   (the driver's form)
 
-Prints ONE JSON line on rank 0.  Every result that has a reference answer is CHECKED (pivot digests of SURVEY.md
-Appendix C, the reference's per-node outcomes and final result of Monster_II): a wrong answer exits non-zero instead
-of printing a number.  GPU legs run back to back first; the CPU baselines (the reference itself under node) last.
+Prints ONE JSON line on rank 0.  A plain run does only what the headline needs: set-up, warm-up, the timed steps, the
+dump if asked for, and the line (headline figure + the roofline of the timed steps' own event-timed kernel).  With
+--full every result that has a reference answer is CHECKED (pivot digests of SURVEY.md Appendix C, the reference's
+per-node outcomes and final result of Monster_II): a wrong answer exits non-zero instead of printing a number.  GPU
+legs run back to back first; the CPU baselines (the reference itself under node) last.
 """
 import argparse
 import hashlib
@@ -319,14 +323,18 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-sample-pivots", type=int, default=3000)
     ap.add_argument("--no-relaxations", action="store_true")
-    ap.add_argument("--only-relaxations", action="store_true", help="profiling runs: skip the dense-LP legs")
-    ap.add_argument("--no-extras", action="store_true", help="profiling runs: only the timed headline steps")
+    ap.add_argument("--only-relaxations", action="store_true", help="with --full, profiling runs: skip the dense-LP legs")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the other dense-LP legs (sustained, cycle check on, 3b, streaming instance)")
     ap.add_argument("--sustain-s", type=float, default=6.0, help="seconds of back-to-back headline solves after the timed steps (0 = off)")
     ap.add_argument("--no-dropin", action="store_true", help="skip the end-to-end Solve() leg through the reference host (node)")
     ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed (result + tableau) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the answer checks, the other legs and configurations, and the CPU baselines (the --no-* / --only-* options trim it)")
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.only_relaxations and not args.full:
+        ap.error("--only-relaxations selects legs of the full run: add --full")
     if args.dump_outputs and args.only_relaxations:
         ap.error("--dump-outputs writes the dense-LP headline's outputs: it cannot be combined with --only-relaxations")
 
@@ -361,7 +369,7 @@ def main():
             raise SystemExit("bench.py: process group is %s x %d, wanted %s x %d" % (dist.get_backend(), dist.get_world_size(), backend, args.gpus))
 
     dropin = None
-    if rank == 0 and world == 1 and not args.no_dropin and not args.only_relaxations:
+    if args.full and rank == 0 and world == 1 and not args.no_dropin and not args.only_relaxations:
         dropin = dropin_leg(with_cpu=not args.no_cpu_baseline)  # (a child process, before this one creates its HIP context)
 
     from jslpsolver_amd import _capi, generators
@@ -398,6 +406,7 @@ def main():
 
     line = None
     n = args.n
+    extra_legs = args.full and not args.no_extras  # (a plain run: the timed headline steps only)
     if not args.only_relaxations:
         # ---- workload: config 3a ------------------------------------------------------------------------
         m, vibr, vibc = generators.dense_resource_allocation_tableau(12345, n, n)
@@ -452,7 +461,7 @@ def main():
                 raise WrongAnswer("%s: not solved to optimality" % what)
             return got
 
-        digest = verify(False, DIGEST_3A.get(n), "config 3a (%d x %d), cycle check off" % (H, W))
+        digest = verify(False, DIGEST_3A.get(n), "config 3a (%d x %d), cycle check off" % (H, W)) if args.full else None
 
         # ---- roofline of the dominant kernel, from the timed steps themselves ---------------------------------------
         # unit of work = one pivot = 16*H*W algorithmic bytes; the register-resident kernel runs all pivots of
@@ -497,7 +506,7 @@ def main():
                 "issue": pmc_sq("pivots", kernel_name)})
 
         extras = {}
-        if not args.no_extras and rank == 0 and args.sustain_s > 0:
+        if extra_legs and rank == 0 and args.sustain_s > 0:
             # the timed region above is ~1 s: a few more seconds of the same solves back to back (also what a 5 s sampler of GPU
             # activity gets to see); same answer checked by the digest above
             t.restore(); t.simplex(check_cycles=False)
@@ -511,7 +520,7 @@ def main():
             el_s = time.perf_counter() - t0
             extras["sustained"] = {"solves": n_s, "seconds": el_s, "value": piv_s / el_s, "unit": "pivots/s",
                                    "note": "the headline workload repeated for ~%.0f s on rank 0, restore + simplex per solve, wall clock" % args.sustain_s}
-        if not args.no_extras:
+        if extra_legs:
             # ---- the reference's DEFAULT: checkForCycles on (model.ts:73; simplex.ts:415-440 after every selection) ----------
             # (every rank runs it: the timed region is bracketed by the same barriers; rank 0 reports its own replica)
             k2 = max(1, min(args.steps, 3))
@@ -531,7 +540,7 @@ def main():
         t.close()
 
         # ---- the other config-3 instance (3b: generateRandomLP, every pivot is a phase-1 pivot; ends infeasible) -------------
-        if rank == 0 and not args.no_extras:
+        if rank == 0 and extra_legs:
             m1, vibr1, vibc1, _op = generators.dense_random_lp_tableau(12345, n, n)
             t1 = Tableau(m1, vibr1, vibc1, device=device_index, lib=lib)
             t1.save()
@@ -555,7 +564,7 @@ def main():
         #      default policy runs one k_pivot_fused<2> launch per pivot -- 16 x H x W algorithmic bytes each: the kernel north_star's
         #      ">= 40 % of the HBM roofline" literally describes.  One solve (30 844 pivots), checked against the instance's known answer
         #      (tests/golden/stress_expect.json: data, written by tests/golden/gen_stress_expect.py), kernel time from HIP events per launch.
-        if rank == 0 and not args.no_extras and n >= 2000:
+        if rank == 0 and extra_legs and n >= 2000:
             sys.path.insert(0, os.path.join(ROOT, "tools"))
             import known_answers as KA
             # round 6: the instance is the reference's OWN golden at this shape (generateResourceAllocation(12345, 3000 vars, 5000 constraints),
@@ -610,11 +619,13 @@ def main():
                 "config": {"workload": "config 3a: generateResourceAllocation(seed 12345, %d vars x %d constraints, density 1.0), "
                                        "%dx%d fp64 tableau, %d pivots per solve, cycle check off; one replica per GPU"
                                        % (n, n, H, W, pivots_per_solve),
-                           "pivot_digest": digest, "pivot_digest_checked_against": DIGEST_3A.get(n) and "SURVEY.md Appendix C (the reference's own trace)",
                            "result_evaluation": evaluation, "parallelism": "replicas%d" % world,
                            "rccl_ranks": world if (world > 1 and backend == "nccl") else 0},
                 "roofline": roofline,
             }
+            if args.full:
+                line["config"].update({"pivot_digest": digest,
+                                       "pivot_digest_checked_against": DIGEST_3A.get(n) and "SURVEY.md Appendix C (the reference's own trace)"})
             line.update(extras)
             if dumped is not None:
                 line["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped, "of": "the last timed step"}
@@ -623,7 +634,7 @@ def main():
 
     # ---- LP relaxations/sec: Monster_II (config 4) ----------------------------------------------------------------------
     relax = None
-    if not args.no_relaxations:
+    if args.full and not args.no_relaxations:
         relax = relaxation_legs(ctx, args)
         if line is not None and relax is not None:
             line["relaxations"] = relax
@@ -632,7 +643,7 @@ def main():
 
     # ---- CPU baselines last: the GPU legs above ran back to back -----------------------------------------------------
     if rank == 0 and line is not None:
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             if relax is not None:
                 relax["cpu_baseline"] = cpu_relaxation_baseline()
                 if relax["cpu_baseline"] and relax["cpu_baseline"].get("value"):

@@ -11,6 +11,6 @@ bash tools/stress_round.sh $out/resident_stress.txt 2>&1 | tail -1
 [ -f build/libjslp_dev_final_dbg.so ] && (JSLP_HIP_LIBRARY=build/libjslp_dev_final_dbg.so timeout 200 python tools/resident_phase_timing.py 2000; python tools/resident_stamps.py) > $out/phase_timing.txt 2>&1
 timeout 600 python tools/fp32_sweep.py $out/fp32_sweep.md > /dev/null 2>&1
 timeout 300 python tools/pool_handoff.py 4 $out/pool_handoff.md > /dev/null 2>&1
-timeout 900 python bench.py > $out/bench.log 2>&1; echo "bench rc=$?"
+timeout 900 python bench.py --full > $out/bench.log 2>&1; echo "bench rc=$?"
 grep '^{' $out/bench.log > $out/bench_line.json; cut -c1-600 $out/bench_line.json
 du -sh $out
