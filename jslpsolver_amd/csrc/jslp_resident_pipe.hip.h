@@ -180,20 +180,29 @@ __device__ __forceinline__ bool cyc_suffix_is_square(const int2* lds, const int2
     return __syncthreads_or(found) != 0;
 }
 
-// the two 32-bit halves of a 64-bit word, each summed over the wave modulo 2^32 (every exchange pairs disjoint groups: lanes, pairs,
-// quads, the halves of a 16-lane row; then the four rows) -- the checksummed row hand-over's reduction
+// ---- a fold over a wave in registers: four DPP exchanges inside the 16-lane rows (lane ^ 1, lane ^ 2, the other quad of the 8-lane half,
+// the other half of the row: every lane of a row ends up with the row's result), then row_bcast:15 into rows 1 and 3 and row_bcast:31
+// into rows 2 and 3 -- lane 63 holds the wave's result, one readlane makes it uniform.  `ID` is the operation's identity: what the rows
+// that a broadcast skips combine with.
+#define JSLP_WAVE_FOLD32(X, OP, ID)                                                                                              \
+    do {                                                                                                                         \
+        X = OP(X, __builtin_amdgcn_update_dpp((int)(ID), X, 0xB1, 0xf, 0xf, false));                                             \
+        X = OP(X, __builtin_amdgcn_update_dpp((int)(ID), X, 0x4E, 0xf, 0xf, false));                                             \
+        X = OP(X, __builtin_amdgcn_update_dpp((int)(ID), X, 0x141, 0xf, 0xf, false));                                            \
+        X = OP(X, __builtin_amdgcn_update_dpp((int)(ID), X, 0x140, 0xf, 0xf, false));                                            \
+        X = OP(X, __builtin_amdgcn_update_dpp((int)(ID), X, 0x142, 0xa, 0xf, false));                                            \
+        X = OP(X, __builtin_amdgcn_update_dpp((int)(ID), X, 0x143, 0xc, 0xf, false));                                            \
+        X = __builtin_amdgcn_readlane(X, 63);                                                                                    \
+    } while (0)
+__device__ __forceinline__ int jslp_add_i32(int a, int b) { return (int)((unsigned)a + (unsigned)b); }
+// the two 32-bit halves of a 64-bit word, each summed over the wave modulo 2^32 -- the checksummed row hand-over's reduction
+// (round 7: the rows' sums reach lane 63 by two row broadcasts and come out in one readlane per half, instead of four readlanes and
+//  three scalar adds)
 __device__ __forceinline__ u64_t u64_wave_add_halves(u64_t x) {
-    unsigned lo = (unsigned)x, hi = (unsigned)(x >> 32);
-#define JSLP_ADD_DPP(CTRL)                                                                          \
-    lo += (unsigned)__builtin_amdgcn_update_dpp((int)lo, (int)lo, CTRL, 0xf, 0xf, false);           \
-    hi += (unsigned)__builtin_amdgcn_update_dpp((int)hi, (int)hi, CTRL, 0xf, 0xf, false);
-    JSLP_ADD_DPP(0xB1) JSLP_ADD_DPP(0x4E) JSLP_ADD_DPP(0x141) JSLP_ADD_DPP(0x140)
-#undef JSLP_ADD_DPP
-    const unsigned slo = ((unsigned)__builtin_amdgcn_readlane((int)lo, 0) + (unsigned)__builtin_amdgcn_readlane((int)lo, 16)) +
-                         ((unsigned)__builtin_amdgcn_readlane((int)lo, 32) + (unsigned)__builtin_amdgcn_readlane((int)lo, 48));
-    const unsigned shi = ((unsigned)__builtin_amdgcn_readlane((int)hi, 0) + (unsigned)__builtin_amdgcn_readlane((int)hi, 16)) +
-                         ((unsigned)__builtin_amdgcn_readlane((int)hi, 32) + (unsigned)__builtin_amdgcn_readlane((int)hi, 48));
-    return (u64_t)slo | ((u64_t)shi << 32);
+    int lo = (int)(unsigned)x, hi = (int)(unsigned)(x >> 32);
+    JSLP_WAVE_FOLD32(lo, jslp_add_i32, 0);
+    JSLP_WAVE_FOLD32(hi, jslp_add_i32, 0);
+    return (u64_t)(unsigned)lo | ((u64_t)(unsigned)hi << 32);
 }
 // a lane's checksum -> the wave's word
 #define JSLP_CK_WAVE(CK) u64_wave_add_halves((CK) * (u64_t)(unsigned)(2 * tid + 1))
@@ -1246,7 +1255,10 @@ __device__ __forceinline__ void resident_phase2_pipe(const ResCtx& f, RSmem& sm,
         cpend = !CM_AT_N;
         RT_MARK(5);
     }
-    JSLP_PIPE_SWAP_LDS_MAPS();  // (an exit in front of the pricing)
+    // (an exit at the loop top, in front of the pricing: no barrier since the row fetch, where a lagging wave may still read the maps --
+    //  QDIRECT only; the exits are uniform, so is this barrier)
+    if (QDIRECT) __syncthreads();
+    JSLP_PIPE_SWAP_LDS_MAPS();
     JSLP_PIPE_COMMIT_GLOBAL();  // (a basis change whose global half is still pending)
     if (pend && R.end_code != 5) {  // whoever leaves with a pivot pending (optimal, iteration cap, hand-over) brings the rows up to date
         const bool has_pc_p = colok && pc_p >= c0 && pc_p < c0 + CPT;
@@ -1768,5 +1780,6 @@ __device__ __forceinline__ void resident_phase1_pipe(const ResCtx& f, RSmem& sm,
 #undef JSLP_RT_RETRY
 #undef JSLP_PIPE_COMMIT_GLOBAL
 #undef JSLP_PIPE_SWAP_LDS_MAPS
+#undef JSLP_WAVE_FOLD32
 #undef JSLP_PIPE_HIST_GLOBAL
 #undef JSLP_PIPE_COMMIT_GLOBAL_NOW
