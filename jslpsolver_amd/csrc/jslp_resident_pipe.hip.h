@@ -842,7 +842,7 @@ __device__ __forceinline__ void resident_phase2_pipe(const ResCtx& f, RSmem& sm,
                 const double rhs = sm.rhsb[lane];
                 if (r >= 1 && r < r_end && !(-precision < colv && colv < precision)) {
                     if (colv > 0 && precision > rhs && rhs > -precision) kind = 1;
-                    else { quo = (UNR && R.neg) ? -rhs / colv : rhs / colv; kind = quo > precision ? 2 : 0; }  // simplex.ts:282
+                    else { quo = (UNR && R.neg) ? -rhs / colv : rhs / colv; kind = quo > precision && quo < INFINITY ? 2 : 0; }  // simplex.ts:282 (+Infinity: never below minQuotient's start)
                 }
             }
             int brdeg = kind == 1 ? r : 0x7fffffff;  // rows ascend with the lane: the smallest row is the first one
@@ -853,7 +853,7 @@ __device__ __forceinline__ void resident_phase2_pipe(const ResCtx& f, RSmem& sm,
             brdeg = ROWS > 16 ? min(__builtin_amdgcn_readlane(brdeg, 0), __builtin_amdgcn_readlane(brdeg, 16))
                               : __builtin_amdgcn_readlane(brdeg, 0);  // (ROWS <= 16: the candidates sit in the first 16-lane row; <= 32: in the first two)
             static_assert(ROWS <= 32, "the summary's DPP folds cover two 16-lane rows");
-            KI bk;  // quotients are > precision > 0: positive doubles order like their bit patterns; ties -> first row
+            KI bk;  // quotients are finite and > precision > 0: positive doubles order like their bit patterns; ties -> first row
             bk.k = kind == 2 ? (u64_t)__double_as_longlong(quo) : KI_NONE_KEY;
             bk.i = kind == 2 ? r : 0x7fffffff;
             bk.pad = 0;
@@ -1595,9 +1595,10 @@ __device__ __forceinline__ void resident_phase1_pipe(const ResCtx& f, RSmem& sm,
             const double coef = pv[j];
             if (col >= 1 && col < W && ((UNR && ((R.unr >> j) & 1u)) || coef < -precision)) {
                 const double quo = -r0[j] / coef;
-                // (my columns ascend: ties keep the earlier one.  UNR: an unrestricted column may have a zero coefficient -- the
-                //  reference's `maxQuotient < quotient` from -Infinity lets +Infinity win, never NaN or -Infinity)
-                const bool take = UNR ? (bq < quo) : (bi == 0 || bq < quo);
+                // (my columns ascend: ties keep the earlier one.  The reference's `maxQuotient < quotient` from -Infinity never takes
+                //  NaN or -Infinity -- a cost cell of +-Infinity or NaN makes them -- and lets +Infinity win: an unrestricted column
+                //  with a zero coefficient)
+                const bool take = bq < quo;
                 bq = take ? quo : bq;
                 bi = take ? col : bi;
             }

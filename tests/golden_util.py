@@ -56,3 +56,9 @@ def sha_rhs(rhs, vibr):
 
 def num(x):
     return _num(x)
+
+
+def canon_nan(a):
+    """every NaN made the one NaN JavaScript stores for the NaN literal (the bits of a NaN depend on the hardware that made it)"""
+    a = np.asarray(a, dtype=np.float64)
+    return np.where(np.isnan(a), np.float64("nan"), a)
