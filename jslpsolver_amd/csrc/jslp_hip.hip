@@ -1943,6 +1943,14 @@ extern "C" int jslp_engine_simplex_f32(jslp_engine* e, double precision, int che
     return JSLP_OK;
 }
 
+// JSLP_DEBUG_LAUNCH: which node kernel a relax call launched, one parseable stderr line per launch (tests/test_node_edges.py)
+static void debug_node_launch(const char* kernel, int grid, int n_nodes, size_t lds) {
+    char tail[64] = "";
+    if (n_nodes >= 0) snprintf(tail, sizeof tail, " n %d", n_nodes);
+    if (lds) fprintf(stderr, "[jslp] launch %s g %d%s lds %zu\n", kernel, grid, tail, lds);
+    else fprintf(stderr, "[jslp] launch %s g %d%s\n", kernel, grid, tail);
+}
+
 // Shared body of relax_batch / relax_batch_pinned.  Per-node-workgroup path: all groups are enqueued back to back,
 // their outcomes accumulate in ONE device buffer laid out for all n_nodes, one copy and one synchronisation end the
 // call.  `pinned` != 0: the caller reads the pinned buffer itself (no second host copy).
@@ -1976,6 +1984,9 @@ static int relax_batch_impl(jslp_engine* e, int32_t n_nodes, const int32_t* cut_
     hipStream_t s = e->stream;
     const int cap = iters_cap(e);
     const long long cells = (long long)e->cap_rows * e->ld;
+    const bool dbg = getenv("JSLP_DEBUG_LAUNCH") != nullptr;  // (read per call, as run_simplex does: tests switch it inside one process)
+    // the line sits in the same branch as the launch it names
+#define NODE_LAUNCH_LINE(name, grid, n, lds) do { if (dbg) debug_node_launch(name, (int)(grid), n, (size_t)(lds)); } while (0)
     int rc;
     // ---- ONE child of the saved root, slot 0 already in sync with the snapshot: one launch, one synchronisation ----------
     if (n_nodes == 1 && checkpoint < 0 && e->has_save && e->slot0_synced && !e->timing && e->force_path <= 1 &&
@@ -1998,18 +2009,23 @@ static int relax_batch_impl(jslp_engine* e, int32_t n_nodes, const int32_t* cut_
         HIPC(hipHostGetDevicePointer(&flag_dev, h_flag, 0));
         unsigned* d_flag = static_cast<unsigned*>(flag_dev);
         const unsigned seq = ++e->done_seq ? e->done_seq : ++e->done_seq;  // never 0 (the flag's initial value)
-        if (const size_t lds = wglds_smem(e); lds && e->s.n_opt > 0)
+        if (const size_t lds = wglds_smem(e); lds && e->s.n_opt > 0) {
+            NODE_LAUNCH_LINE("k_node_lds<1024,opt 1,cow 0>", 1, -1, lds);
             hipLaunchKernelGGL((k_node_lds<JSLP_WG_THREADS, true>), dim3(1), dim3(JSLP_WG_THREADS), lds, s, e->s, sn, cu, 0, check_cycles,
                                cap, (int)e->cap_rows, o_rhs, o_rows, o_state, compact ? g_stride : 0, 0, d_flag, seq);
-        else if (lds && node_cow_single())  // copy-on-write start, slot 0 made whole again behind the completion flag (jslp_wglds.hip.h)
+        } else if (lds && node_cow_single()) {  // copy-on-write start, slot 0 made whole again behind the completion flag (jslp_wglds.hip.h)
+            NODE_LAUNCH_LINE("k_node_lds<1024,opt 0,cow 1>", 1, -1, lds);
             hipLaunchKernelGGL((k_node_lds<JSLP_WG_THREADS, false, true>), dim3(1), dim3(JSLP_WG_THREADS), lds, s, e->s, sn, cu, 0, check_cycles,
                                cap, (int)e->cap_rows, o_rhs, o_rows, o_state, compact ? g_stride : 0, 0, d_flag, seq);
-        else if (lds)
+        } else if (lds) {
+            NODE_LAUNCH_LINE("k_node_lds<1024,opt 0,cow 0>", 1, -1, lds);
             hipLaunchKernelGGL((k_node_lds<JSLP_WG_THREADS>), dim3(1), dim3(JSLP_WG_THREADS), lds, s, e->s, sn, cu, 0, check_cycles,
                                cap, (int)e->cap_rows, o_rhs, o_rows, o_state, compact ? g_stride : 0, 0, d_flag, seq);
-        else
+        } else {
+            NODE_LAUNCH_LINE("k_node_wg<1024,4096>", 1, -1, 0);
             hipLaunchKernelGGL((k_node_wg<JSLP_WG_THREADS, 4096>), dim3(1), dim3(JSLP_WG_THREADS), 0, s, e->s, sn, cu, 0, check_cycles,
                                cap, (int)e->cap_rows, o_rhs, o_rows, o_state, compact ? g_stride : 0, 0, d_flag, seq);
+        }
         HIPC(hipGetLastError());
         // the kernel's last act is a system-scope release store of `seq` into pinned memory: poll it (a stream
         // synchronisation costs tens of microseconds of wake-up latency per node of a sequential tree walk)
@@ -2120,15 +2136,19 @@ static int relax_batch_impl(jslp_engine* e, int32_t n_nodes, const int32_t* cut_
         static const int order_full = [] { const char* t = getenv("JSLP_NODE_QUEUE_ORDER_FULL"); return t ? atoi(t) : 0; }();
         const bool pcie_bound = zc && !compact && (want_rhs || want_rows);
         const int32_t* order = (node_queue() == 2 && n_nodes > group && (order_full || !pcie_bound)) ? e->d_cut_order : (const int32_t*)nullptr;
-        if (e->s.n_opt > 0)  // optional objectives: the OPT build (eager restores)
+        if (e->s.n_opt > 0) {  // optional objectives: the OPT build (eager restores)
+            NODE_LAUNCH_LINE("k_node_queue<512,cow 0,opt 1>", group, (int)n_nodes, lds);
             hipLaunchKernelGGL((k_node_queue<512, false, true>), dim3(group), dim3(512), lds, s, e->s, sn, cu, (int)n_nodes, order, e->d_queue, check_cycles,
                                cap, (int)e->cap_rows, want_rhs ? o_rhs : nullptr, want_rows ? o_rows : nullptr, o_states, g_stride);
-        else if (node_cow())
+        } else if (node_cow()) {
+            NODE_LAUNCH_LINE("k_node_queue<512,cow 1,opt 0>", group, (int)n_nodes, lds);
             hipLaunchKernelGGL((k_node_queue<512, true>), dim3(group), dim3(512), lds, s, e->s, sn, cu, (int)n_nodes, order, e->d_queue, check_cycles,
                                cap, (int)e->cap_rows, want_rhs ? o_rhs : nullptr, want_rows ? o_rows : nullptr, o_states, g_stride);
-        else
+        } else {
+            NODE_LAUNCH_LINE("k_node_queue<512,cow 0,opt 0>", group, (int)n_nodes, lds);
             hipLaunchKernelGGL((k_node_queue<512, false>), dim3(group), dim3(512), lds, s, e->s, sn, cu, (int)n_nodes, order, e->d_queue, check_cycles,
                                cap, (int)e->cap_rows, want_rhs ? o_rhs : nullptr, want_rows ? o_rows : nullptr, o_states, g_stride);
+        }
         HIPC(hipGetLastError());
         if (!zc && !dev_out && compact != 2) {
             HIPC(hipMemcpyAsync(e->h_states, e->d_states, sizeof(DevState) * (size_t)n_nodes, hipMemcpyDeviceToHost, s));
@@ -2149,11 +2169,12 @@ static int relax_batch_impl(jslp_engine* e, int32_t n_nodes, const int32_t* cut_
             // by occupancy: the 1024-thread shape of the single-node path, one workgroup per CU
             static const int small_1024 = getenv("JSLP_SMALL_BATCH_1024") ? atoi(getenv("JSLP_SMALL_BATCH_1024")) : JSLP_SMALL_BATCH_1024_DEFAULT;
             const size_t lds = wglds_smem(e);
-            if (lds && e->s.n_opt > 0)  // optional objectives: the 1024-thread build only, whatever the batch size
+            if (lds && e->s.n_opt > 0) {  // optional objectives: the 1024-thread build only, whatever the batch size
+                NODE_LAUNCH_LINE("k_node_lds<1024,opt 1,cow 0>", g, -1, lds);
                 hipLaunchKernelGGL((k_node_lds<1024, true>), dim3(g), dim3(1024), lds, s, e->s, sn, cu, first, check_cycles, cap,
                                    (int)e->cap_rows, want_rhs ? o_rhs : nullptr, want_rows ? o_rows : nullptr, o_states,
                                    g_stride, first, (unsigned*)nullptr, 0u);
-            else if (lds && g <= small_1024) {
+            } else if (lds && g <= small_1024) {
                 // a batch that is ONE group, its outcomes written straight into pinned memory: the last workgroup raises the completion
                 // flag the host polls (below) instead of the two stream synchronisations that end the other shapes of this call
                 unsigned* d_flag = nullptr;
@@ -2173,23 +2194,28 @@ static int relax_batch_impl(jslp_engine* e, int32_t n_nodes, const int32_t* cut_
                 // dirtied from the root instead of restoring those rows first -- the eager restore was 8.6 k of the 78 k cycles of a node of an 8-node batch
                 // (tools/wglds_timing.py one 8, debug build), in front of everything else; JSLP_NODE_COW_SMALL=0: eager restores
                 static const int cow_small = getenv("JSLP_NODE_COW_SMALL") ? atoi(getenv("JSLP_NODE_COW_SMALL")) : 1;
-                if (cow_small && node_cow())
+                if (cow_small && node_cow()) {
+                    NODE_LAUNCH_LINE("k_node_lds<1024,opt 0,cow 1>", g, -1, lds);
                     hipLaunchKernelGGL((k_node_lds<1024, false, true>), dim3(g), dim3(1024), lds, s, e->s, sn, cu, first, check_cycles, cap,
                                        (int)e->cap_rows, want_rhs ? o_rhs : nullptr, want_rows ? o_rows : nullptr, o_states,
                                        g_stride, first, d_flag, seq, d_flag ? e->d_done_count : (int*)nullptr);
-                else
-                hipLaunchKernelGGL((k_node_lds<1024>), dim3(g), dim3(1024), lds, s, e->s, sn, cu, first, check_cycles, cap,
-                                   (int)e->cap_rows, want_rhs ? o_rhs : nullptr, want_rows ? o_rows : nullptr, o_states,
-                                   g_stride, first, d_flag, seq, d_flag ? e->d_done_count : (int*)nullptr);
-            }
-            else if (lds)
+                } else {
+                    NODE_LAUNCH_LINE("k_node_lds<1024,opt 0,cow 0>", g, -1, lds);
+                    hipLaunchKernelGGL((k_node_lds<1024>), dim3(g), dim3(1024), lds, s, e->s, sn, cu, first, check_cycles, cap,
+                                       (int)e->cap_rows, want_rhs ? o_rhs : nullptr, want_rows ? o_rows : nullptr, o_states,
+                                       g_stride, first, d_flag, seq, d_flag ? e->d_done_count : (int*)nullptr);
+                }
+            } else if (lds) {
+                NODE_LAUNCH_LINE("k_node_lds<512,opt 0,cow 0>", g, -1, lds);
                 hipLaunchKernelGGL((k_node_lds<512>), dim3(g), dim3(512), lds, s, e->s, sn, cu, first, check_cycles, cap,
                                    (int)e->cap_rows, want_rhs ? o_rhs : nullptr, want_rows ? o_rows : nullptr, o_states,
                                    g_stride, first, (unsigned*)nullptr, 0u);
-            else
+            } else {
+                NODE_LAUNCH_LINE("k_node_wg<512,2048>", g, -1, 0);
                 hipLaunchKernelGGL((k_node_wg<512, 2048>), dim3(g), dim3(512), 0, s, e->s, sn, cu, first, check_cycles, cap,
                                    (int)e->cap_rows, want_rhs ? o_rhs : nullptr, want_rows ? o_rows : nullptr, o_states,
                                    g_stride, first, (unsigned*)nullptr, 0u);
+            }
             HIPC(hipGetLastError());
         } else {
         rc = enqueue_restore(e, 0, g, checkpoint);
@@ -2202,21 +2228,29 @@ static int relax_batch_impl(jslp_engine* e, int32_t n_nodes, const int32_t* cut_
             const size_t lds = wglds_smem(e);
             const bool opt = lds && e->s.n_opt > 0;
             const int shape = (g == 1 || opt) ? 1024 : wg_batch_threads();
-            if (opt)
+            if (opt) {
+                NODE_LAUNCH_LINE("restore+add_cuts+simplex+gather k_simplex_lds<1024,opt 1>", g, -1, lds);
                 hipLaunchKernelGGL((k_simplex_lds<JSLP_WG_THREADS, true>), dim3(g), dim3(JSLP_WG_THREADS), lds, s, e->s, 0, check_cycles, cap, (int)e->cap_rows);
-            else if (lds && shape == 1024)
+            } else if (lds && shape == 1024) {
+                NODE_LAUNCH_LINE("restore+add_cuts+simplex+gather k_simplex_lds<1024,opt 0>", g, -1, lds);
                 hipLaunchKernelGGL((k_simplex_lds<JSLP_WG_THREADS>), dim3(g), dim3(JSLP_WG_THREADS), lds, s, e->s, 0, check_cycles, cap, (int)e->cap_rows);
-            else if (lds && shape == 512)
+            } else if (lds && shape == 512) {
+                NODE_LAUNCH_LINE("restore+add_cuts+simplex+gather k_simplex_lds<512,opt 0>", g, -1, lds);
                 hipLaunchKernelGGL((k_simplex_lds<512>), dim3(g), dim3(512), lds, s, e->s, 0, check_cycles, cap, (int)e->cap_rows);
-            else if (shape == 256)
+            } else if (shape == 256) {
+                NODE_LAUNCH_LINE("restore+add_cuts+simplex+gather k_simplex_wg<256,1024>", g, -1, 0);
                 hipLaunchKernelGGL((k_simplex_wg<256, 1024>), dim3(g), dim3(256), 0, s, e->s, 0, check_cycles, cap);
-            else if (shape == 512)
+            } else if (shape == 512) {
+                NODE_LAUNCH_LINE("restore+add_cuts+simplex+gather k_simplex_wg<512,2048>", g, -1, 0);
                 hipLaunchKernelGGL((k_simplex_wg<512, 2048>), dim3(g), dim3(512), 0, s, e->s, 0, check_cycles, cap);
-            else
+            } else {
+                NODE_LAUNCH_LINE("restore+add_cuts+simplex+gather k_simplex_wg<1024,4096>", g, -1, 0);
                 hipLaunchKernelGGL((k_simplex_wg<JSLP_WG_THREADS, 4096>), dim3(g), dim3(JSLP_WG_THREADS), 0, s, e->s, 0, check_cycles, cap);
+            }
             HIPC(hipGetLastError());
         } else {
             // big tableau: the chip-wide kernels on slot 0 (g == 1)
+            if (dbg) debug_node_launch("restore+add_cuts+simplex+gather chip-wide", g, -1, 0);
             HIPC(hipMemcpyAsync(e->h_state, e->s.st, sizeof(DevState), hipMemcpyDeviceToHost, s));
             HIPC(hipStreamSynchronize(s));
             rc = state_error(*e->h_state);
@@ -2340,6 +2374,8 @@ static int relax_batch_impl(jslp_engine* e, int32_t n_nodes, const int32_t* cut_
     }
     return JSLP_OK;
 }
+
+#undef NODE_LAUNCH_LINE
 
 extern "C" int jslp_engine_relax_batch(jslp_engine* e, int32_t n_nodes, const int32_t* cut_offsets, const int8_t* type,
                                        const int32_t* var_index, const double* value, int check_cycles,

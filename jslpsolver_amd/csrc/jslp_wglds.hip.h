@@ -1138,7 +1138,9 @@ __device__ __forceinline__ void slot0_whole_again(const Slots& s, const Snapshot
     for (int i = threadIdx.x >> 6; i < n; i += blockDim.x >> 6) {
         const int r = L.list[i];
         wglds_copy_row(dst + (long long)r * ld2, src + (long long)r * ld2, ld2, lane);
-        if (lane == 0) dirty[r] = 0;
+        // (the RHS mirror too: a node that a refused cut list ended never reached the epilogue that rewrites the mirror, which then still
+        //  held the PREVIOUS node's column 0 on rows no longer flagged -- the next eager restore left them as they were)
+        if (lane == 0) { dirty[r] = 0; s.rhs[r] = snap.rhs[r]; }
     }
 }
 
