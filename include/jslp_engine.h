@@ -218,7 +218,15 @@ int jslp_engine_checkpoint_release(jslp_engine* e, int32_t id);
  * applyIncrementalCuts' fast path (incremental-branch-and-cut.ts:248-253) for the children of one parent: every node
  * = restoreCheckpoint(checkpoint) + addCutConstraints(its cuts, normally the single new cut) + simplex() + the
  * read-back of jslp_engine_relax_batch.  checkpoint = -1 starts from the saved root instead (= relax_batch, the
- * fallback path :254-258).  The live tableau is left holding the LAST node.
+ * fallback path :254-258, with relax_batch's "unspecified" live tableau when there are several nodes).  From a checkpoint the
+ * live tableau is left holding the LAST node, however many there are (the engine evaluates the last of several children on the
+ * live tableau itself, behind the others), and the engine's evaluation is the last node's.  A call that is refused leaves the
+ * live tableau unspecified: restore() or checkpoint_restore() before using it.  The last child runs where the first one ran:
+ * of several children the FIRST reports a detected cycle (cycle_phase) without its cycle_start / cycle_length detail (0), as
+ * the nodes of a batch do that is evaluated in more than one group.
+ * Optional objectives: a checkpoint does not carry them, so a single child starts from the rows the live tableau holds, as the
+ * reference does.  Do not send several children in one call on a model with optional objectives: the other slots' objective rows
+ * are whatever an earlier batch left, which the sequential reference has no equivalent of.
  */
 int jslp_engine_relax_from(jslp_engine* e, int32_t checkpoint, int32_t n_nodes, const int32_t* cut_offsets,
                            const int8_t* type, const int32_t* var_index, const double* value, int check_cycles,

@@ -2090,6 +2090,9 @@ static int relax_batch_impl(jslp_engine* e, int32_t n_nodes, const int32_t* cut_
         rc = ensure_slots(e, group);
         if (rc) return rc;
     }
+    // children of a checkpoint leave the live tableau (slot 0) holding the LAST of them (include/jslp_engine.h), as the sequential
+    // reference does: the last of several nodes is a group of its own, in slot 0, behind the groups of the others
+    const int n_grouped = (checkpoint >= 0 && wg && n_nodes > 1) ? n_nodes - 1 : n_nodes;
     rc = ensure_out(e, (size_t)n_nodes);  // laid out for ALL nodes: [states | rhs | rows]
     if (rc) return rc;
     if (compact == 2 && (size_t)n_nodes > e->rec_cap) {
@@ -2156,8 +2159,8 @@ static int relax_batch_impl(jslp_engine* e, int32_t n_nodes, const int32_t* cut_
             if (want_rows) HIPC(hipMemcpyAsync(e->h_rows, e->d_rows, sizeof(int32_t) * (size_t)n_nodes * row_stride, hipMemcpyDeviceToHost, s));
         }
     } else
-    for (int first = 0; first < n_nodes; first += group) {
-        const int g = std::min(group, n_nodes - first);
+    for (int first = 0, g = 0; first < n_nodes; first += g) {
+        g = first < n_grouped ? std::min(group, n_grouped - first) : 1;
         // slots already in sync with the snapshot: restore of the dirty rows, cuts, simplex and gather in ONE launch per
         // group (what a workgroup restores and cuts stays in its XCD's L2 for its own pivots)
         const bool one_launch = wg && g > 1 && checkpoint < 0 && e->has_save && e->slot0_synced && g <= e->slots_synced &&
@@ -2351,13 +2354,14 @@ static int relax_batch_impl(jslp_engine* e, int32_t n_nodes, const int32_t* cut_
         rc = state_error(st);
         if (rc) { e->slot0_synced = 0; e->slots_synced = 0; return rc; }
         account(e, st, 1);
-        if (st.cycle_phase && wg && n_nodes > group) {
-            // the cycle message is rebuilt from the slot's history, which later groups have reused: report the hit
-            // (flags are exact) without the [start, length] detail
+        if (st.cycle_phase && wg && (n_nodes > group || (n_grouped < n_nodes && i == 0))) {
+            // the cycle message is rebuilt from the slot's history, which later groups have reused (of the children of a checkpoint in
+            // one group only the first: the last child ran in its slot after it): report the hit (flags are exact) without the
+            // [start, length] detail
             st.hist_n = 0;
         }
         double ev;
-        rc = fill_result(e, st, wg ? i % group : 0, prev_eval, &out[i], &ev);
+        rc = fill_result(e, st, wg && i < n_grouped ? i % group : 0, prev_eval, &out[i], &ev);
         if (rc) return rc;
         if (i == n_nodes - 1) e->evaluation = ev;
         if (!pinned && !compact) {

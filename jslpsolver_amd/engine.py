@@ -439,7 +439,10 @@ class Tableau:
     def applyCutsFrom(self, checkpoint, cut_lists, check_cycles=True):
         """applyIncrementalCuts' fast path (:248-253) for one or more children of `checkpoint` in ONE engine call:
         restoreCheckpoint + addCutConstraints(cuts) + simplex + read-back per node.  Returns per node
-        (result, rhs, varIndexByRow); the tableau scalars end as after the LAST node."""
+        (result, rhs, varIndexByRow).  The engine's live tableau and its evaluation end as after the LAST node (the last of several
+        children is evaluated on the live tableau itself); this object's `evaluation` / `feasible` are the caller's to fold, node by
+        node, with absorb_from().  A checkpoint carries no optional objectives: on a model that has them send one child per call (the
+        objective rows the other children would start from are whatever an earlier batch left in their slots)."""
         n_nodes, offs, t, v, x = self.pack_cut_lists(cut_lists)
         out = (SimplexResult * max(n_nodes, 1))()
         stride = self.row_capacity

@@ -113,6 +113,13 @@ class Dispatch:
                 out.append((MULTI + "k_simplex_wg<%d,%d>" % (shape, 4 * shape), g, None, 0))
         return out
 
+    def refused(self, first_kernel, n):
+        """the bookkeeping after a call of n nodes that ended in a refused cut list; first_kernel: the name on the call's first launch line"""
+        if first_kernel.startswith("k_node_") and n == 1:
+            self.synced0 = False  # the one-launch single node: slot 0 alone
+        elif not first_kernel.endswith("chip-wide"):  # (the chip-wide sequence stops at the refused cuts, behind its restore)
+            self.synced0, self.synced_n = False, 0
+
 
 class Stderr:
     """this process's stderr (the engine's fprintf included) in a file; lines() returns what arrived since the last look"""
@@ -308,10 +315,7 @@ class Root:
         else:
             raise AssertionError((self.name, what, "no error"))
         got = self.check_lines(len(nodes), what)
-        if got[0][0].startswith("k_node_") and len(nodes) == 1:
-            self.d.synced0 = False  # the one-launch single node: slot 0 alone
-        elif not got[0][0].endswith("chip-wide"):  # (the chip-wide sequence stops at the refused cuts, behind its restore)
-            self.d.synced0, self.d.synced_n = False, 0
+        self.d.refused(got[0][0], len(nodes))
 
     def big(self):
         """the family many times over: more nodes than the queue kernel has resident workgroups"""
