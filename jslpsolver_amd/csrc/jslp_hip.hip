@@ -41,6 +41,7 @@ static int fail(int code, const char* fmt, const char* a = "", const char* b = "
         hipError_t _e = (expr);                                                                 \
         if (_e != hipSuccess) return fail(JSLP_ERR_DEVICE, "%s: %s", #expr, hipGetErrorString(_e)); \
     } while (0)
+#define JSLP_TRY(expr) do { int _rc = (expr); if (_rc) return _rc; } while (0)  // (an engine call's own error code travels up unchanged)
 
 static const size_t WGLDS_MAX_BYTES = 64 * 1024;  // largest dynamic LDS the LDS-resident one-workgroup kernels are launched with
 struct jslp_engine {
@@ -70,7 +71,6 @@ struct jslp_engine {
     uint8_t* d_unr = nullptr;
     uint8_t* d_isint = nullptr;  // variable.isInteger per variable index (MIR cuts)
     int32_t n_opt = 0; double* snap_oo = nullptr;  // optional objectives (slot copies live in s.oo)
-    // cuts staging
     // cuts staging: ONE pinned host buffer -> ONE device buffer per call: [value | offs | var | type]
     char* d_cuts = nullptr; char* h_cuts = nullptr; size_t cuts_bytes = 0;
     int32_t* d_cut_offs = nullptr; int8_t* d_cut_type = nullptr; int32_t* d_cut_var = nullptr; double* d_cut_val = nullptr;
@@ -78,7 +78,6 @@ struct jslp_engine {
     std::vector<int32_t> order_scratch;
     bool queue_wgs_opt = false; int node_queue_launches = 0; long long resident_fetch_retries = 0;  // (which build the count below is for; batches that went through k_node_queue)
     int queue_wgs = 0; size_t queue_wgs_lds = 0;             // resident workgroups of k_node_queue<512> for this LDS size
-    // read-back staging (device + pinned host)
     // read-back staging: ONE device buffer -> ONE pinned buffer per group: [states | rhs | rows]
     char* d_out = nullptr; char* h_out = nullptr;
     double* d_rhs = nullptr; int32_t* d_rows = nullptr; DevState* d_states = nullptr;
@@ -94,8 +93,6 @@ struct jslp_engine {
     int host_matrix_out = 0;  // the host holds a pointer into h_up
     // the one-call-only redirection of the read-back (device pool: every member copies straight into the pool's buffer)
     DevState* ext_states = nullptr; double* ext_rhs = nullptr; int32_t* ext_rows = nullptr;
-    // jslp_engine_relax_batch_device: the caller's DEVICE buffers take the outcomes (no host copy at all)
-    DevState* dev_states = nullptr; double* dev_rhs = nullptr; int32_t* dev_rows = nullptr; int32_t dev_stride = 0;
     // compact read-back (jslp_engine_relax_watched)
     int32_t* d_watch = nullptr; int32_t n_watch = 0;
     // work counters
@@ -117,7 +114,6 @@ struct jslp_engine {
     int resident_refusals = 0;   // ... it refused (or that no build exists for): the solve went through the streaming kernels
     std::vector<jslp_simplex_result> rec_results;  // per-node results of a branch-record call (the record is what the caller gets)
     double* d_rec = nullptr; jslpx_branch_record* h_rec = nullptr; size_t rec_cap = 0;  // branch records of a batch (device / pinned, rec_cap each)
-    double* dev_rec = nullptr;  // jslpx_engine_relax_batch_branch_device: the caller's device memory the records go to
     double dev_prev_evaluation = 0.0;  // jslp_engine_relax_batch_device: the evaluation its nodes started from (results_from_states)
     int dev_prev_valid = 0;
     // checkpoints (incremental-branch-and-cut.ts:31-44): equally sized device buffers, recycled through a free list
@@ -171,78 +167,42 @@ static const long long WG_CELLS_BATCH = 4LL * 1024 * 1024;  // batches use one w
 #ifndef JSLP_SMALL_BATCH_1024_DEFAULT
 #define JSLP_SMALL_BATCH_1024_DEFAULT 256  // batches of at most this many nodes (one per CU) take the 1024-thread node kernel: 16 nodes 111 -> 102 us, 64 nodes 147 -> 132 us (r03_o); 0 = never
 #endif
-static int wg_batch_threads() {  // workgroup size of the per-node kernel when a call carries several nodes
-    static int v = -1;
-    if (v < 0) {
-        const char* t = getenv("JSLP_WG_BATCH_THREADS");  // tuning knob (tools/relax_batch_scaling.py)
-        v = t ? atoi(t) : 512;  // measured on Monster_II node batches (tools/wg_shape_sweep.sh): 512 > 1024 > 256
-        if (v != 256 && v != 1024) v = 512;
-    }
-    return v;
-}
-static int group_max() {  // nodes per group of a batch (= tableau copies alive at once)
-    static int v = -1;
-    if (v < 0) {
-        const char* t = getenv("JSLP_GROUP_MAX");  // tuning knob
-        v = t ? atoi(t) : 1024;
-        if (v < 1) v = 1024;
-    }
-    return v;
-}
-static int zero_copy() {  // batch outcomes written by the kernels straight into the pinned read-back buffer (no copy stream)
-    static int v = -1;
-    if (v < 0) {
-        const char* t = getenv("JSLP_ZERO_COPY");  // tuning knob
-        v = t ? atoi(t) : 1;
-    }
-    return v;
-}
-static int snapshot_transpose_on() {  // pivot-column reads of untouched rows from the transposed root
-    static int v = -1;
-    if (v < 0) {
-        const char* t = getenv("JSLP_SNAPSHOT_TRANSPOSE");  // tuning knob
-        v = t ? atoi(t) : 1;
-    }
-    return v;
-}
-static int batch_poll_on() {  // a one-group batch of the 1024-thread node kernel ends by polling its completion flag (JSLP_BATCH_POLL=0: stream synchronisation)
-    static int v = -1;
-    if (v < 0) { const char* t = getenv("JSLP_BATCH_POLL"); v = (t && t[0] == '0') ? 0 : 1; }
-    return v;
-}
-static int node_cow_single() {  // single-node call: copy-on-write start (JSLP_NODE_COW_SINGLE=0: restore eagerly, as the batch groups do)
-    static const int v = getenv("JSLP_NODE_COW_SINGLE") ? atoi(getenv("JSLP_NODE_COW_SINGLE")) : 1;
-    return v;
-}
-static int node_cow() {  // queue kernel: copy-on-write slots (no restore between nodes)
-    static int v = -1;
-    if (v < 0) {
-        const char* t = getenv("JSLP_NODE_COW");  // tuning knob
-        v = t ? atoi(t) : 1;
-    }
-    return v;
-}
-static int node_queue() {  // a batch in one launch of resident workgroups pulling nodes from a queue
-    static int v = -1;
-    if (v < 0) {
-        // tuning knob: 0 = one launch per group, 1 = the queue hands the nodes out in call order, 2 (default since round 6) = most cuts first.
-        // The cut count predicts a node's repair pivots, and 2416 nodes on 768 resident workgroups are 3.15 rounds: longest-first keeps the last
-        // workgroups to finish on the cheap nodes.  Round 2 measured it SLOWER (2.73 M/s against 2.94 M in call order: a node then cost ~3x what it
-        // costs now and the order array's extra trip per node showed); re-measured on round 6's kernels, same session, compact read-back,
-        // tools/wglds_timing.py: 4.94-5.06 M relaxations/s against 4.14-4.41 M in call order (+14 %); outcome digests identical (tools/queue_check.py)
-        const char* t = getenv("JSLP_NODE_QUEUE");
-        v = t ? atoi(t) : 2;
-    }
-    return v;
-}
-static long long wg_cells_child() {  // a single B&B child (few repair pivots) stays in one workgroup up to this
-    static long long v = -1;
-    if (v < 0) {
-        const char* t = getenv("JSLP_WG_CELLS_CHILD");  // tuning knob (tools/child_path_times.py)
-        v = t ? atoll(t) : 1536LL * 1024;
-    }
-    return v;
-}
+// ---- tuning knobs of the node path ------------------------------------------------------------------------------------
+// Every knob below is LATCHED: read from the environment at its first use and kept for the life of the process (the tests give each setting a
+// process of its own).  JSLP_DEBUG_LAUNCH is the one switch the node path reads on every call: tests turn it on and off inside one process.
+struct Knob { bool set; long long v; };  // set: the variable exists at all
+static Knob read_knob(const char* name, long long dflt) { const char* t = getenv(name); return Knob{t != nullptr, t ? atoll(t) : dflt}; }
+#define KNOB(type, fn, name, dflt) static type fn() { static const type v = (type)read_knob(name, dflt).v; return v; }
+// workgroup size of the per-node kernel when a call carries several nodes (tools/relax_batch_scaling.py); measured on Monster_II node batches (tools/wg_shape_sweep.sh): 512 > 1024 > 256
+KNOB(int, wg_batch_threads_raw, "JSLP_WG_BATCH_THREADS", 512)
+static int wg_batch_threads() { const int v = wg_batch_threads_raw(); return v == 256 || v == 1024 ? v : 512; }
+// nodes per group of a batch (= tableau copies alive at once); whether it was given at all decides what the queue's grid defaults to (plan_node_call)
+static Knob group_max_knob() { static const Knob k = read_knob("JSLP_GROUP_MAX", 1024); return k; }
+static int group_max() { const long long v = group_max_knob().v; return v < 1 ? 1024 : (int)v; }
+KNOB(int, zero_copy, "JSLP_ZERO_COPY", 1)  // batch outcomes written by the kernels straight into the pinned read-back buffer (no copy stream)
+KNOB(int, snapshot_transpose_on, "JSLP_SNAPSHOT_TRANSPOSE", 1)  // pivot-column reads of untouched rows from the transposed root
+KNOB(int, node_cow_single, "JSLP_NODE_COW_SINGLE", 1)  // single-node call: copy-on-write start (0: restore eagerly, as the batch groups do)
+KNOB(int, node_cow, "JSLP_NODE_COW", 1)  // queue kernel: copy-on-write slots (no restore between nodes)
+// (round 6) copy-on-write start in the small batch too, as the queue kernel and the single-node call have it: a node READS what its slot's earlier nodes
+// dirtied from the root instead of restoring those rows first -- the eager restore was 8.6 k of the 78 k cycles of a node of an 8-node batch
+// (tools/wglds_timing.py one 8, debug build), in front of everything else; JSLP_NODE_COW_SMALL=0: eager restores
+KNOB(int, node_cow_small, "JSLP_NODE_COW_SMALL", 1)
+// a batch that leaves most CUs idle anyway (speculative batches of a real tree: <= 16 nodes) is served by latency, not by occupancy: the 1024-thread shape of the single-node path, one workgroup per CU
+KNOB(int, small_batch_1024, "JSLP_SMALL_BATCH_1024", JSLP_SMALL_BATCH_1024_DEFAULT)
+// a batch in one launch of resident workgroups pulling nodes from a queue: 0 = one launch per group, 1 = the queue hands the nodes out in call order, 2 (default since round 6) = most cuts first.
+// The cut count predicts a node's repair pivots, and 2416 nodes on 768 resident workgroups are 3.15 rounds: longest-first keeps the last
+// workgroups to finish on the cheap nodes.  Round 2 measured it SLOWER (2.73 M/s against 2.94 M in call order: a node then cost ~3x what it
+// costs now and the order array's extra trip per node showed); re-measured on round 6's kernels, same session, compact read-back,
+// tools/wglds_timing.py: 4.94-5.06 M relaxations/s against 4.14-4.41 M in call order (+14 %); outcome digests identical (tools/queue_check.py)
+KNOB(int, node_queue, "JSLP_NODE_QUEUE", 2)
+// 1 hands the FULL read-back out longest-first too; its bound is the PCIe link and it measured 3.41-3.42 M against 3.52-3.54 M relaxations/s in call order: the heavy nodes' outcomes then leave in one burst
+KNOB(int, node_queue_order_full, "JSLP_NODE_QUEUE_ORDER_FULL", 0)
+KNOB(long long, wg_cells_child, "JSLP_WG_CELLS_CHILD", 1536LL * 1024)  // a single B&B child (few repair pivots) stays in one workgroup up to this (tools/child_path_times.py)
+#undef KNOB
+// a one-group batch of the 1024-thread node kernel ends by polling its completion flag (JSLP_BATCH_POLL=0: stream synchronisation; the first character decides)
+static int batch_poll_on() { static const int v = [] { const char* t = getenv("JSLP_BATCH_POLL"); return (t && t[0] == '0') ? 0 : 1; }(); return v; }
+// JSLP_DEBUG_STALL=<ms> (diagnosis): a dependent batch normally takes ~70 us; say on stderr when one took longer than that many milliseconds and where the time went (report_stall)
+static double debug_stall_ms() { static const double v = [] { const char* t = getenv("JSLP_DEBUG_STALL"); return t ? atof(t) : 0.0; }(); return v; }
 static const size_t HIST_CAP_MAIN = 1u << 20;
 static const size_t HIST_CAP_SLOT = 1u << 16;
 static const long long TRACE_CAP = 1LL << 20;
@@ -1943,6 +1903,87 @@ extern "C" int jslp_engine_simplex_f32(jslp_engine* e, double precision, int che
     return JSLP_OK;
 }
 
+// ---- node relaxation: restore + cuts + simplex + gather for a batch of nodes -------------------------------------------------------
+// What a caller asks of relax_batch_impl.  Every entry point fills one of these with named fields.
+// Full: the whole RHS column / row map of every node; Watched: the watched variables' rows / RHS cells only; BranchRecord (include/jslpx_branch.h):
+// the node kernels' compact (watched) read-back stays in device memory and k_branch_record reduces it to 32 bytes per node
+enum class ReadBack { Full, Watched, BranchRecord };
+struct CutLists {  // node i adds the cuts [offsets[i], offsets[i + 1])
+    int32_t n_nodes = 0; const int32_t* offsets = nullptr; const int8_t* type = nullptr; const int32_t* var_index = nullptr; const double* value = nullptr;
+};
+struct DeviceDest {  // the caller's DEVICE memory takes the outcomes (no host copy at all): `states` set = this destination
+    DevState* states = nullptr; double* rhs = nullptr; int32_t* rows = nullptr;
+    int32_t stride = 0; double* rec = nullptr;  // entries per node in rhs / rows; ReadBack::BranchRecord: where the records go
+};
+struct NodeCall {
+    CutLists cuts;
+    int check_cycles = 0;
+    int checkpoint = -1;  // the start: a checkpoint, or (-1) the saved root / the live tableau
+    ReadBack read_back = ReadBack::Full;
+    bool want_rhs = false, want_rows = false;
+    // where the outcomes go, exactly one of three:
+    jslp_simplex_result* out = nullptr;  // per-node results (1 and 2)
+    double* rhs = nullptr; int32_t* var_index_by_row = nullptr; int32_t out_stride = 0;  // 1. the caller's host arrays
+    bool pinned = false;                 // 2. the caller reads the engine's pinned buffers itself (no second host copy)
+    DeviceDest dev;                      // 3. the caller's device memory
+    bool to_device() const { return dev.states != nullptr; }
+    bool compact() const { return read_back != ReadBack::Full; }
+    bool records() const { return read_back == ReadBack::BranchRecord; }
+};
+
+// ---- the node kernels: one descriptor per instantiation the node path can launch ---------------------------------------------------
+struct NodeArgs {  // the union of what the node kernels take
+    const Slots* s; Snapshot sn; Cuts cu;
+    int check_cycles, iters_cap, cap_rows; double* rhs; int32_t* rows; DevState* states;
+    int out_stride;  // gather mode: >= 0 = the whole RHS column / row map with this row stride; < 0 = the watched variables only
+    int first = 0;   // k_node_lds / k_node_wg: first node of the launch = index of its outcome
+    unsigned* done_flag = nullptr; unsigned done_seq = 0; int* done_count = nullptr;
+    int n_nodes = -1; const int32_t* order = nullptr; int* queue = nullptr;  // k_node_queue (n_nodes: also the `n` of its debug line)
+};
+struct NodeKernel {
+    const char* name;       // the JSLP_DEBUG_LAUNCH line (tests/test_node_edges.py asserts every one)
+    int threads; bool lds;  // lds: launched with the tableau's dynamic LDS (wglds_smem)
+    void (*launch)(const NodeArgs&, int grid, size_t lds, hipStream_t); const void* fn;  // fn: for occupancy queries
+};
+// (a default argument does not travel through a function pointer: k_node_lds gets its done_count explicitly)
+template <auto K, int T> static void launch_node_lds(const NodeArgs& a, int grid, size_t lds, hipStream_t s) {
+    hipLaunchKernelGGL(K, dim3(grid), dim3(T), lds, s, *a.s, a.sn, a.cu, a.first, a.check_cycles, a.iters_cap, a.cap_rows, a.rhs, a.rows, a.states, a.out_stride, a.first, a.done_flag, a.done_seq, a.done_count);
+}
+template <auto K, int T> static void launch_node_wg(const NodeArgs& a, int grid, size_t, hipStream_t s) {
+    hipLaunchKernelGGL(K, dim3(grid), dim3(T), 0, s, *a.s, a.sn, a.cu, a.first, a.check_cycles, a.iters_cap, a.cap_rows, a.rhs, a.rows, a.states, a.out_stride, a.first, a.done_flag, a.done_seq);
+}
+template <auto K, int T> static void launch_node_queue(const NodeArgs& a, int grid, size_t lds, hipStream_t s) {
+    hipLaunchKernelGGL(K, dim3(grid), dim3(T), lds, s, *a.s, a.sn, a.cu, a.n_nodes, a.order, a.queue, a.check_cycles, a.iters_cap, a.cap_rows, a.rhs, a.rows, a.states, a.out_stride);
+}
+template <auto K, int T> static void launch_simplex_lds(const NodeArgs& a, int grid, size_t lds, hipStream_t s) {
+    hipLaunchKernelGGL(K, dim3(grid), dim3(T), lds, s, *a.s, 0, a.check_cycles, a.iters_cap, a.cap_rows);
+}
+template <auto K, int T> static void launch_simplex_wg(const NodeArgs& a, int grid, size_t, hipStream_t s) {
+    hipLaunchKernelGGL(K, dim3(grid), dim3(T), 0, s, *a.s, 0, a.check_cycles, a.iters_cap);
+}
+#define NODE_KERNEL(launcher, threads, lds, name, ...) \
+    {name, threads, lds, launcher<&__VA_ARGS__, threads>, reinterpret_cast<const void*>(&__VA_ARGS__)}
+// (the rows' order is the order the compiler instantiates the kernels in, and their code depends on it: k_simplex_wg<256,1024> came out with another register
+//  allocation behind <512,2048> -- a new row goes where tools/asm_digest.py shows every kernel's assembly unchanged)
+static const NodeKernel NODE_LDS_1024_OPT = NODE_KERNEL(launch_node_lds, 1024, true, "k_node_lds<1024,opt 1,cow 0>", k_node_lds<1024, true, false>);
+static const NodeKernel NODE_LDS_1024_COW = NODE_KERNEL(launch_node_lds, 1024, true, "k_node_lds<1024,opt 0,cow 1>", k_node_lds<1024, false, true>);
+static const NodeKernel NODE_LDS_1024 = NODE_KERNEL(launch_node_lds, 1024, true, "k_node_lds<1024,opt 0,cow 0>", k_node_lds<1024, false, false>);
+static const NodeKernel NODE_WG_1024 = NODE_KERNEL(launch_node_wg, 1024, false, "k_node_wg<1024,4096>", k_node_wg<1024, 4096>);
+static const NodeKernel NODE_QUEUE_OPT = NODE_KERNEL(launch_node_queue, 512, true, "k_node_queue<512,cow 0,opt 1>", k_node_queue<512, false, true>);
+static const NodeKernel NODE_QUEUE_COW = NODE_KERNEL(launch_node_queue, 512, true, "k_node_queue<512,cow 1,opt 0>", k_node_queue<512, true, false>);
+static const NodeKernel NODE_QUEUE = NODE_KERNEL(launch_node_queue, 512, true, "k_node_queue<512,cow 0,opt 0>", k_node_queue<512, false, false>);
+static const NodeKernel NODE_LDS_512 = NODE_KERNEL(launch_node_lds, 512, true, "k_node_lds<512,opt 0,cow 0>", k_node_lds<512, false, false>);
+static const NodeKernel NODE_WG_512 = NODE_KERNEL(launch_node_wg, 512, false, "k_node_wg<512,2048>", k_node_wg<512, 2048>);
+// the eager groups: k_restore + k_add_cuts in front, k_gather behind
+static const NodeKernel EAGER_LDS_1024_OPT = NODE_KERNEL(launch_simplex_lds, 1024, true, "restore+add_cuts+simplex+gather k_simplex_lds<1024,opt 1>", k_simplex_lds<1024, true>);
+static const NodeKernel EAGER_LDS_1024 = NODE_KERNEL(launch_simplex_lds, 1024, true, "restore+add_cuts+simplex+gather k_simplex_lds<1024,opt 0>", k_simplex_lds<1024, false>);
+static const NodeKernel EAGER_LDS_512 = NODE_KERNEL(launch_simplex_lds, 512, true, "restore+add_cuts+simplex+gather k_simplex_lds<512,opt 0>", k_simplex_lds<512, false>);
+static const NodeKernel EAGER_WG_256 = NODE_KERNEL(launch_simplex_wg, 256, false, "restore+add_cuts+simplex+gather k_simplex_wg<256,1024>", k_simplex_wg<256, 1024>);
+static const NodeKernel EAGER_WG_512 = NODE_KERNEL(launch_simplex_wg, 512, false, "restore+add_cuts+simplex+gather k_simplex_wg<512,2048>", k_simplex_wg<512, 2048>);
+static const NodeKernel EAGER_WG_1024 = NODE_KERNEL(launch_simplex_wg, 1024, false, "restore+add_cuts+simplex+gather k_simplex_wg<1024,4096>", k_simplex_wg<1024, 4096>);
+#undef NODE_KERNEL
+static_assert(JSLP_WG_THREADS == 1024, "the single-node shape of the table above");
+
 // JSLP_DEBUG_LAUNCH: which node kernel a relax call launched, one parseable stderr line per launch (tests/test_node_edges.py)
 static void debug_node_launch(const char* kernel, int grid, int n_nodes, size_t lds) {
     char tail[64] = "";
@@ -1950,443 +1991,407 @@ static void debug_node_launch(const char* kernel, int grid, int n_nodes, size_t 
     if (lds) fprintf(stderr, "[jslp] launch %s g %d%s lds %zu\n", kernel, grid, tail, lds);
     else fprintf(stderr, "[jslp] launch %s g %d%s\n", kernel, grid, tail);
 }
+// the one place a node kernel is launched: its line (when asked for), the launch, the launch's error
+static int launch_node_kernel(const NodeKernel& k, const NodeArgs& a, int grid, size_t lds, hipStream_t s, bool dbg) {
+    if (!k.lds) lds = 0;
+    if (dbg) debug_node_launch(k.name, grid, a.n_nodes, lds);
+    k.launch(a, grid, lds, s);
+    HIPC(hipGetLastError());
+    return JSLP_OK;
+}
 
-// Shared body of relax_batch / relax_batch_pinned.  Per-node-workgroup path: all groups are enqueued back to back,
-// their outcomes accumulate in ONE device buffer laid out for all n_nodes, one copy and one synchronisation end the
-// call.  `pinned` != 0: the caller reads the pinned buffer itself (no second host copy).
-static int relax_batch_impl(jslp_engine* e, int32_t n_nodes, const int32_t* cut_offsets, const int8_t* type,
-                            const int32_t* var_index, const double* value, int check_cycles, jslp_simplex_result* out,
-                            double* rhs, int32_t* var_index_by_row, int32_t out_stride, int pinned, int want_rhs,
-                            int want_rows, int checkpoint = -1, int compact = 0) {
-    // compact: 0 = full read-back, 1 = the watched variables' rows / RHS cells, 2 = the branch record (include/jslpx_branch.h): the node
-    // kernels' compact read-back stays in device memory and k_branch_record reduces it to 32 bytes per node (e->d_rec, or e->dev_rec)
-    const auto t_enter = std::chrono::steady_clock::now();  // (JSLP_DEBUG_STALL)
-    const bool dev_out = e && e->dev_states != nullptr;  // outcomes stay on the device (jslp_engine_relax_batch_device)
-    if (e && !dev_out) e->dev_prev_valid = 0;
-    if (!e || n_nodes < 0 || !cut_offsets || (!out && !dev_out)) return fail(JSLP_ERR_ARG, "relax_batch: null pointer");
-    if (!e->uploaded) return fail(JSLP_ERR_STATE, "relax before upload");
-    if (compact && (e->n_watch <= 0 || e->n_watch > e->cap_rows))
-        return fail(JSLP_ERR_ARG, compact == 2 ? "relax_batch_branch: after set_watched_variables (at most row_capacity of them)"
-                                               : "relax_watched: after set_watched_variables (at most row_capacity of them)");
-    // gather mode: >= 0 = the whole RHS column / row map with this row stride; < 0 = the watched variables only
-    const int g_stride = compact ? -e->n_watch : (dev_out ? (int)e->dev_stride : (int)out_stride_of(e));
-    const size_t row_stride = compact ? (size_t)e->n_watch : (dev_out ? (size_t)e->dev_stride : out_stride_of(e));  // entries per node in the read-back buffers
-    if (checkpoint >= 0) {
-        int rc0 = checkpoint_check(e, checkpoint, "relax_from");
-        if (rc0) return rc0;
-    }
-    if (!pinned && (rhs || var_index_by_row) && out_stride < e->cap_rows)
-        return fail(JSLP_ERR_ARG, "relax_batch: out_stride < row capacity");
-    if (n_nodes == 0) return JSLP_OK;
-    if (n_nodes > 1 && !e->has_save && checkpoint < 0)
-        return fail(JSLP_ERR_STATE, "relax_batch: several nodes need a saved root (save() first)");
-    HIPC(hipSetDevice(e->device));
-    hipStream_t s = e->stream;
-    const int cap = iters_cap(e);
-    const long long cells = (long long)e->cap_rows * e->ld;
-    const bool dbg = getenv("JSLP_DEBUG_LAUNCH") != nullptr;  // (read per call, as run_simplex does: tests switch it inside one process)
-    // the line sits in the same branch as the launch it names
-#define NODE_LAUNCH_LINE(name, grid, n, lds) do { if (dbg) debug_node_launch(name, (int)(grid), n, (size_t)(lds)); } while (0)
-    int rc;
-    // ---- ONE child of the saved root, slot 0 already in sync with the snapshot: one launch, one synchronisation ----------
-    if (n_nodes == 1 && checkpoint < 0 && e->has_save && e->slot0_synced && !e->timing && e->force_path <= 1 &&
-        e->one_launch_nodes && cells <= wg_cells_child() && !e->ext_states && !dev_out && compact != 2) {
-        rc = upload_cuts(e, 1, cut_offsets, type, var_index, value, false);
-        if (rc) return rc;
-        rc = ensure_out(e, 1);
-        if (rc) return rc;
-        void* out_dev = nullptr;
-        HIPC(hipHostGetDevicePointer(&out_dev, e->h_out, 0));
-        char* ob = static_cast<char*>(out_dev);
-        DevState* o_state = reinterpret_cast<DevState*>(ob);
-        double* o_rhs = want_rhs ? reinterpret_cast<double*>(ob + ((char*)e->h_rhs - e->h_out)) : nullptr;
-        int32_t* o_rows = want_rows ? reinterpret_cast<int32_t*>(ob + ((char*)e->h_rows - e->h_out)) : nullptr;
-        Cuts cu{e->d_cut_offs, e->d_cut_type, e->d_cut_var, e->d_cut_val};
-        Snapshot sn = root_snapshot(e);
-        e->last_path = "workgroup";
-        unsigned* h_flag = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(e->h_state) + sizeof(DevState));
-        void* flag_dev = nullptr;
-        HIPC(hipHostGetDevicePointer(&flag_dev, h_flag, 0));
-        unsigned* d_flag = static_cast<unsigned*>(flag_dev);
-        const unsigned seq = ++e->done_seq ? e->done_seq : ++e->done_seq;  // never 0 (the flag's initial value)
-        if (const size_t lds = wglds_smem(e); lds && e->s.n_opt > 0) {
-            NODE_LAUNCH_LINE("k_node_lds<1024,opt 1,cow 0>", 1, -1, lds);
-            hipLaunchKernelGGL((k_node_lds<JSLP_WG_THREADS, true>), dim3(1), dim3(JSLP_WG_THREADS), lds, s, e->s, sn, cu, 0, check_cycles,
-                               cap, (int)e->cap_rows, o_rhs, o_rows, o_state, compact ? g_stride : 0, 0, d_flag, seq);
-        } else if (lds && node_cow_single()) {  // copy-on-write start, slot 0 made whole again behind the completion flag (jslp_wglds.hip.h)
-            NODE_LAUNCH_LINE("k_node_lds<1024,opt 0,cow 1>", 1, -1, lds);
-            hipLaunchKernelGGL((k_node_lds<JSLP_WG_THREADS, false, true>), dim3(1), dim3(JSLP_WG_THREADS), lds, s, e->s, sn, cu, 0, check_cycles,
-                               cap, (int)e->cap_rows, o_rhs, o_rows, o_state, compact ? g_stride : 0, 0, d_flag, seq);
-        } else if (lds) {
-            NODE_LAUNCH_LINE("k_node_lds<1024,opt 0,cow 0>", 1, -1, lds);
-            hipLaunchKernelGGL((k_node_lds<JSLP_WG_THREADS>), dim3(1), dim3(JSLP_WG_THREADS), lds, s, e->s, sn, cu, 0, check_cycles,
-                               cap, (int)e->cap_rows, o_rhs, o_rows, o_state, compact ? g_stride : 0, 0, d_flag, seq);
-        } else {
-            NODE_LAUNCH_LINE("k_node_wg<1024,4096>", 1, -1, 0);
-            hipLaunchKernelGGL((k_node_wg<JSLP_WG_THREADS, 4096>), dim3(1), dim3(JSLP_WG_THREADS), 0, s, e->s, sn, cu, 0, check_cycles,
-                               cap, (int)e->cap_rows, o_rhs, o_rows, o_state, compact ? g_stride : 0, 0, d_flag, seq);
-        }
-        HIPC(hipGetLastError());
-        // the kernel's last act is a system-scope release store of `seq` into pinned memory: poll it (a stream
-        // synchronisation costs tens of microseconds of wake-up latency per node of a sequential tree walk)
-        {
-            unsigned spins = 0;
-            const auto t_begin = std::chrono::steady_clock::now();
-            bool arrived = false;
-            while (!(arrived = (__atomic_load_n(h_flag, __ATOMIC_ACQUIRE) == seq))) {
-                if ((++spins & 0x3fffu) == 0 &&
-                    std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count() > 5.0) break;
+// which kernel, from what the call site can observe (lds = wglds_smem(e): 0 = the tableau does not fit the LDS builds)
+static const NodeKernel& single_node_kernel(const jslp_engine* e, size_t lds) {
+    if (!lds) return NODE_WG_1024;
+    if (e->s.n_opt > 0) return NODE_LDS_1024_OPT;
+    return node_cow_single() ? NODE_LDS_1024_COW : NODE_LDS_1024;  // copy-on-write start, slot 0 made whole again behind the completion flag (jslp_wglds.hip.h)
+}
+static const NodeKernel& queue_kernel(const jslp_engine* e) {
+    if (e->s.n_opt > 0) return NODE_QUEUE_OPT;  // optional objectives: the OPT build (eager restores)
+    return node_cow() ? NODE_QUEUE_COW : NODE_QUEUE;
+}
+// a one-group batch small enough for the 1024-thread latency shape (small_batch_1024): the only shape that can end in a polled completion flag
+static bool small_batch_shape(const jslp_engine* e, size_t lds, int g) { return lds && e->s.n_opt == 0 && g <= small_batch_1024(); }
+static const NodeKernel& group_kernel(const jslp_engine* e, size_t lds, int g) {
+    if (!lds) return NODE_WG_512;
+    if (e->s.n_opt > 0) return NODE_LDS_1024_OPT;  // optional objectives: the 1024-thread build only, whatever the batch size
+    if (small_batch_shape(e, lds, g)) return node_cow_small() && node_cow() ? NODE_LDS_1024_COW : NODE_LDS_1024;
+    return NODE_LDS_512;
+}
+static const NodeKernel& eager_kernel(const jslp_engine* e, size_t lds, int g) {
+    // one node: the 1024-thread latency shape; a batch: smaller workgroups, more nodes in flight per CU
+    const bool opt = lds && e->s.n_opt > 0;
+    const int shape = (g == 1 || opt) ? 1024 : wg_batch_threads();
+    if (opt) return EAGER_LDS_1024_OPT;
+    if (lds && shape == 1024) return EAGER_LDS_1024;
+    if (lds && shape == 512) return EAGER_LDS_512;  // (no LDS build for 256 threads)
+    if (shape == 256) return EAGER_WG_256;
+    return shape == 512 ? EAGER_WG_512 : EAGER_WG_1024;
+}
+
+// ---- the completion flag: a node kernel's last act is a system-scope release store of a sequence number into pinned memory ------------
+struct DoneFlag { unsigned* host = nullptr; unsigned* dev = nullptr; unsigned seq = 0; };
+static hipError_t arm_done_flag(jslp_engine* e, DoneFlag* f) {
+    unsigned* h_flag = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(e->h_state) + sizeof(DevState));
+    void* flag_dev = nullptr;
+    const hipError_t err = hipHostGetDevicePointer(&flag_dev, h_flag, 0);
+    if (err != hipSuccess) return err;  // (no mapped pinned memory: the single child refuses, the batch ends with a stream synchronisation)
+    const unsigned seq = ++e->done_seq ? e->done_seq : ++e->done_seq;  // never 0 (the flag's initial value)
+    *f = DoneFlag{h_flag, static_cast<unsigned*>(flag_dev), seq};
+    return hipSuccess;
+}
+// poll it (a stream synchronisation costs tens of microseconds of wake-up latency per node of a sequential tree walk); false after 5 s: a
+// fault or a hang, and the caller synchronises the stream so that the runtime reports it
+static bool wait_done_flag(const unsigned* h_flag, unsigned seq, unsigned& spins) {
+    const auto t_begin = std::chrono::steady_clock::now();
+    for (spins = 0; __atomic_load_n(h_flag, __ATOMIC_ACQUIRE) != seq;) {
+        if ((++spins & 0x3fffu) == 0 && std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count() > 5.0) return false;
 #if defined(__x86_64__)
-                __builtin_ia32_pause();
+        __builtin_ia32_pause();
 #endif
-            }
-            if (!arrived) HIPC(hipStreamSynchronize(s));  // a fault or a hang: let the runtime report it
-        }
-        const DevState st = e->h_states[0];
-        rc = state_error(st);
-        if (rc) { e->slot0_synced = 0; return rc; }
-        account(e, st, 1);
-        if (e->counting) e->wc.cut_rows += cut_offsets[1];
-        double ev;
-        rc = fill_result(e, st, 0, e->evaluation, &out[0], &ev);
-        if (rc) return rc;
-        e->evaluation = ev;
-        if (!pinned) {
-            const size_t n_out = compact ? (size_t)e->n_watch : (size_t)st.H;
-            if (rhs) memcpy(rhs, e->h_rhs, sizeof(double) * n_out);
-            if (var_index_by_row) memcpy(var_index_by_row, e->h_rows, sizeof(int32_t) * n_out);
-        }
-        return JSLP_OK;
     }
-    rc = upload_cuts(e, n_nodes, cut_offsets, type, var_index, value);
-    if (rc) return rc;
-    Cuts cu{e->d_cut_offs, e->d_cut_type, e->d_cut_var, e->d_cut_val};
+    return true;
+}
+// JSLP_DEBUG_STALL: whether the time went in front of the wait (cut-list staging, the launch calls) or in it (the GPU side)
+static void report_stall(int n_nodes, bool polled, std::chrono::steady_clock::time_point t_enter, std::chrono::steady_clock::time_point t_wait, unsigned spins) {
+    const double host_ms = std::chrono::duration<double, std::milli>(t_wait - t_enter).count();
+    const double wait_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_wait).count();
+    if (!(host_ms + wait_ms > debug_stall_ms())) return;
+    if (polled)
+        fprintf(stderr, "[jslp] stall: a %d-node polled batch took %.3f ms in front of the poll (staging + launch) and %.3f ms polling (%u spins)\n", n_nodes, host_ms, wait_ms, spins);
+    else
+        fprintf(stderr, "[jslp] stall: a %d-node batch took %.3f ms to enqueue (staging + launches) and %.3f ms in hipStreamSynchronize\n", n_nodes, host_ms, wait_ms);
+}
+
+// ---- the phases of a node call --------------------------------------------------------------------------------------------------------
+static long long tableau_cells(const jslp_engine* e) { return (long long)e->cap_rows * e->ld; }
+// the checks, in the order the refused-call tests know (tests/test_branch_abi.py, tests/test_many_abi.py)
+static int node_call_check(jslp_engine* e, const NodeCall& c) {
+    if (e && !c.to_device()) e->dev_prev_valid = 0;
+    if (!e || c.cuts.n_nodes < 0 || !c.cuts.offsets || (!c.out && !c.to_device())) return fail(JSLP_ERR_ARG, "relax_batch: null pointer");
+    if (!e->uploaded) return fail(JSLP_ERR_STATE, "relax before upload");
+    if (c.compact() && (e->n_watch <= 0 || e->n_watch > e->cap_rows))
+        return fail(JSLP_ERR_ARG, c.records() ? "relax_batch_branch: after set_watched_variables (at most row_capacity of them)"
+                                              : "relax_watched: after set_watched_variables (at most row_capacity of them)");
+    if (c.checkpoint >= 0) JSLP_TRY(checkpoint_check(e, c.checkpoint, "relax_from"));
+    if (!c.pinned && (c.rhs || c.var_index_by_row) && c.out_stride < e->cap_rows) return fail(JSLP_ERR_ARG, "relax_batch: out_stride < row capacity");
+    if (c.cuts.n_nodes > 1 && !e->has_save && c.checkpoint < 0) return fail(JSLP_ERR_STATE, "relax_batch: several nodes need a saved root (save() first)");
+    return JSLP_OK;
+}
+
+// ONE child of the saved root, slot 0 already in sync with the snapshot: one launch, one polled flag
+static bool single_child_fast_path(const jslp_engine* e, const NodeCall& c) {
+    return c.cuts.n_nodes == 1 && c.checkpoint < 0 && e->has_save && e->slot0_synced && !e->timing && e->force_path <= 1 &&
+           e->one_launch_nodes && tableau_cells(e) <= wg_cells_child() && !e->ext_states && !c.to_device() && !c.records();
+}
+static int relax_single_child(jslp_engine* e, const NodeCall& c, bool dbg) {
+    JSLP_TRY(upload_cuts(e, 1, c.cuts.offsets, c.cuts.type, c.cuts.var_index, c.cuts.value, false));
+    JSLP_TRY(ensure_out(e, 1));
+    void* out_dev = nullptr;  // the kernel writes the outcome straight into the pinned read-back buffer
+    HIPC(hipHostGetDevicePointer(&out_dev, e->h_out, 0));
+    char* ob = static_cast<char*>(out_dev);
+    NodeArgs a{&e->s, root_snapshot(e), Cuts{e->d_cut_offs, e->d_cut_type, e->d_cut_var, e->d_cut_val}, c.check_cycles, iters_cap(e), (int)e->cap_rows};
+    a.rhs = c.want_rhs ? reinterpret_cast<double*>(ob + ((char*)e->h_rhs - e->h_out)) : nullptr;
+    a.rows = c.want_rows ? reinterpret_cast<int32_t*>(ob + ((char*)e->h_rows - e->h_out)) : nullptr;
+    a.states = reinterpret_cast<DevState*>(ob);
+    a.out_stride = c.compact() ? -e->n_watch : 0;
+    e->last_path = "workgroup";
+    DoneFlag flag;
+    if (const hipError_t err = arm_done_flag(e, &flag); err != hipSuccess)
+        return fail(JSLP_ERR_DEVICE, "%s: %s", "hipHostGetDevicePointer(&flag_dev, h_flag, 0)", hipGetErrorString(err));
+    a.done_flag = flag.dev; a.done_seq = flag.seq;
+    const size_t lds = wglds_smem(e);
+    JSLP_TRY(launch_node_kernel(single_node_kernel(e, lds), a, 1, lds, e->stream, dbg));
+    unsigned spins;
+    if (!wait_done_flag(flag.host, flag.seq, spins)) HIPC(hipStreamSynchronize(e->stream));
+    const DevState st = e->h_states[0];
+    int rc = state_error(st);
+    if (rc) { e->slot0_synced = 0; return rc; }
+    account(e, st, 1);
+    if (e->counting) e->wc.cut_rows += c.cuts.offsets[1];
+    double ev;
+    JSLP_TRY(fill_result(e, st, 0, e->evaluation, &c.out[0], &ev));
+    e->evaluation = ev;
+    if (!c.pinned) {
+        const size_t n_out = c.compact() ? (size_t)e->n_watch : (size_t)st.H;
+        if (c.rhs) memcpy(c.rhs, e->h_rhs, sizeof(double) * n_out);
+        if (c.var_index_by_row) memcpy(c.var_index_by_row, e->h_rows, sizeof(int32_t) * n_out);
+    }
+    return JSLP_OK;
+}
+
+struct NodePlan {
+    bool wg;           // one workgroup per node (else: the chip-wide kernels on slot 0, node by node)
+    int group;         // nodes per launch = tableau copies (slots) alive at once
+    int n_grouped;     // the nodes [0, n_grouped) run in groups of `group`, the rest one by one in slot 0
+    double prev_eval;  // what a node that reaches no optimum reports
+};
+static int plan_node_call(jslp_engine* e, const NodeCall& c, NodePlan* p) {
+    const int n_nodes = c.cuts.n_nodes;
+    const long long cells = tableau_cells(e);
     // branch-and-bound children (a saved root exists) need a handful of repair pivots each: one workgroup, one launch,
     // no host round trip.  A first solve / plain LP goes through the chip-wide path unless the tableau is tiny.
-    const bool wg = e->force_path == 1 ||
-                    (e->force_path == 0 && (((e->has_save || checkpoint >= 0) && cells <= (n_nodes > 1 ? WG_CELLS_BATCH : wg_cells_child())) || use_wg_single(e)));
+    p->wg = e->force_path == 1 ||
+            (e->force_path == 0 && (((e->has_save || c.checkpoint >= 0) && cells <= (n_nodes > 1 ? WG_CELLS_BATCH : wg_cells_child())) || use_wg_single(e)));
     // a node that does not reach an optimum keeps the evaluation it started with: the checkpoint's (restoreCheckpoint,
     // incremental-branch-and-cut.ts:105) or the live one (restore() leaves it alone)
-    const double prev_eval = checkpoint >= 0 ? e->ckpts[checkpoint].evaluation : e->evaluation;
+    p->prev_eval = c.checkpoint >= 0 ? e->ckpts[c.checkpoint].evaluation : e->evaluation;
     // group size: bounded by memory (<= 16 GiB of the 288 GB for tableau copies) and by what keeps every CU busy with several nodes
-    int group = 1;
-    if (wg) {
+    p->group = 1;
+    if (p->wg) {
         const long long max_slots = std::max<long long>(1, (16LL << 30) / (cells * 8));
-        group = (int)std::min<long long>(std::min<long long>(n_nodes, group_max()), max_slots);
+        p->group = (int)std::min<long long>(std::min<long long>(n_nodes, group_max()), max_slots);
         if (const size_t lds = wglds_smem(e); lds && node_queue() && wg_batch_threads() == 512 && n_nodes > 1) {
             // the queue kernel wants exactly as many slots as the chip keeps workgroups resident
             if (e->queue_wgs == 0 || e->queue_wgs_lds != lds || e->queue_wgs_opt != (e->s.n_opt > 0)) {
                 int per_cu = 0, cus = 0;
-                if (e->s.n_opt > 0) HIPC(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_node_queue<512, false, true>, 512, lds));
-                else HIPC(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_node_queue<512, true>, 512, lds));
+                // (the occupancy of the copy-on-write build whatever JSLP_NODE_COW says, of the OPT build with optional objectives)
+                const NodeKernel& occ = e->s.n_opt > 0 ? NODE_QUEUE_OPT : NODE_QUEUE_COW;
+                HIPC(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, occ.fn, occ.threads, lds));
                 e->queue_wgs_opt = e->s.n_opt > 0;
                 HIPC(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e->device));
                 e->queue_wgs = std::max(1, per_cu * cus);
                 e->queue_wgs_lds = lds;
             }
-            const char* t = getenv("JSLP_GROUP_MAX");
-            group = (int)std::min<long long>(std::min<long long>(n_nodes, t ? group_max() : e->queue_wgs), max_slots);
+            p->group = (int)std::min<long long>(std::min<long long>(n_nodes, group_max_knob().set ? group_max() : e->queue_wgs), max_slots);
         }
-        rc = ensure_slots(e, group);
-        if (rc) return rc;
+        JSLP_TRY(ensure_slots(e, p->group));
     }
     // children of a checkpoint leave the live tableau (slot 0) holding the LAST of them (include/jslp_engine.h), as the sequential
     // reference does: the last of several nodes is a group of its own, in slot 0, behind the groups of the others
-    const int n_grouped = (checkpoint >= 0 && wg && n_nodes > 1) ? n_nodes - 1 : n_nodes;
-    rc = ensure_out(e, (size_t)n_nodes);  // laid out for ALL nodes: [states | rhs | rows]
-    if (rc) return rc;
-    if (compact == 2 && (size_t)n_nodes > e->rec_cap) {
-        hipFree(e->d_rec);
-        if (e->h_rec) hipHostFree(e->h_rec);
-        e->d_rec = nullptr; e->h_rec = nullptr; e->rec_cap = 0;
-        const size_t cap = std::max<size_t>((size_t)n_nodes, 16);
-        HIPC(hipMalloc(&e->d_rec, sizeof(jslpx_branch_record) * cap));
-        HIPC(hipHostMalloc(&e->h_rec, sizeof(jslpx_branch_record) * cap));
-        e->rec_cap = cap;
-    }
-    if (e->timing) HIPC(hipEventRecord(e->ev_begin, s));
-    // where the kernels leave the outcomes: the device staging buffer (copied group by group on the copy stream) or, zero-copy,
-    // the pinned host buffer itself - the stores cross PCIe while the other workgroups compute
-    DevState* o_states = e->d_states; double* o_rhs = e->d_rhs; int32_t* o_rows = e->d_rows;
-    bool zc = zero_copy() != 0 && compact != 2;  // (branch records: the compact read-back they are reduced from stays on the device)
-    unsigned* polled_flag = nullptr;  // set when the call ends by polling a completion flag instead of synchronising the streams
-    unsigned polled_seq = 0;
-    if (dev_out) { o_states = e->dev_states; o_rhs = e->dev_rhs; o_rows = e->dev_rows; zc = false; }
-    if (zc) {
+    p->n_grouped = (c.checkpoint >= 0 && p->wg && n_nodes > 1) ? n_nodes - 1 : n_nodes;
+    return JSLP_OK;
+}
+static int ensure_records(jslp_engine* e, size_t n_nodes) {  // branch records of a batch: device + pinned
+    if (n_nodes <= e->rec_cap) return JSLP_OK;
+    hipFree(e->d_rec);
+    if (e->h_rec) hipHostFree(e->h_rec);
+    e->d_rec = nullptr; e->h_rec = nullptr; e->rec_cap = 0;
+    const size_t cap = std::max<size_t>(n_nodes, 16);
+    HIPC(hipMalloc(&e->d_rec, sizeof(jslpx_branch_record) * cap));
+    HIPC(hipHostMalloc(&e->h_rec, sizeof(jslpx_branch_record) * cap));
+    e->rec_cap = cap;
+    return JSLP_OK;
+}
+
+// where the kernels leave the outcomes: the device staging buffer (copied group by group on the copy stream), zero-copy the pinned host
+// buffer itself - the stores cross PCIe while the other workgroups compute -, or the caller's device memory
+struct NodeDest {
+    DevState* states; double* rhs; int32_t* rows;
+    bool zc;            // states / rhs / rows are the pinned host buffer as the device sees it
+    bool copies;        // ... the staging buffer, and the call copies it to the pinned buffer itself (neither: the caller's device memory, or branch records)
+    size_t row_stride;  // entries per node in rhs / rows
+};
+static int node_destination(jslp_engine* e, const NodeCall& c, NodeDest* d) {
+    d->row_stride = c.compact() ? (size_t)e->n_watch : (c.to_device() ? (size_t)c.dev.stride : out_stride_of(e));
+    d->states = e->d_states; d->rhs = e->d_rhs; d->rows = e->d_rows;
+    d->zc = zero_copy() != 0 && !c.records() && !c.to_device();  // (branch records: the compact read-back they are reduced from stays on the device)
+    if (c.to_device()) { d->states = c.dev.states; d->rhs = c.dev.rhs; d->rows = c.dev.rows; }
+    if (d->zc) {
         void *ps = nullptr, *pr = nullptr, *pw = nullptr;
-        if (hipHostGetDevicePointer(&ps, e->h_states, 0) == hipSuccess && hipHostGetDevicePointer(&pr, e->h_rhs, 0) == hipSuccess &&
-            hipHostGetDevicePointer(&pw, e->h_rows, 0) == hipSuccess) {
-            o_states = static_cast<DevState*>(ps); o_rhs = static_cast<double*>(pr); o_rows = static_cast<int32_t*>(pw);
-        } else {
-            (void)hipGetLastError();
-            zc = false;
-        }
+        d->zc = hipHostGetDevicePointer(&ps, e->h_states, 0) == hipSuccess && hipHostGetDevicePointer(&pr, e->h_rhs, 0) == hipSuccess &&
+                hipHostGetDevicePointer(&pw, e->h_rows, 0) == hipSuccess;
+        if (d->zc) { d->states = static_cast<DevState*>(ps); d->rhs = static_cast<double*>(pr); d->rows = static_cast<int32_t*>(pw); }
+        else (void)hipGetLastError();
     }
-    if (!zc && !dev_out && compact != 2 && !e->copy_stream) {
+    d->copies = !d->zc && !c.to_device() && !c.records();
+    if (d->copies && !e->copy_stream) {
         // created on first use, and only by the calls that copy their outcomes back (JSLP_ZERO_COPY=0, no mapped pinned memory): a stream costs a Solve of a
         // tiny model more than its pivots do
         HIPC(hipStreamCreateWithFlags(&e->copy_stream, hipStreamNonBlocking));
         HIPC(hipEventCreateWithFlags(&e->ev_group, hipEventDisableTiming));
     }
-    if (const size_t lds = wglds_smem(e); wg && lds && node_queue() && n_nodes > group && checkpoint < 0 && e->has_save && e->slot0_synced &&
-        group <= e->slots_synced && !e->timing && e->one_launch_nodes && wg_batch_threads() == 512) {
-        Snapshot sn = root_snapshot(e);
-        e->last_path = "workgroup";
-        e->node_queue_launches += 1;
-        // (an order only where it can matter: more nodes than resident workgroups -- a batch that starts all at once pays the order array's trip per node
-        //  for nothing: the four-member pool's 604-node shares lost 6 % to it; JSLP_NODE_QUEUE_ORDER_FULL=1 hands the FULL read-back out longest-first too; its bound is
-        //  the PCIe link and it measured 3.41-3.42 M against 3.52-3.54 M relaxations/s in call order: the heavy nodes' outcomes then leave in one burst)
-        static const int order_full = [] { const char* t = getenv("JSLP_NODE_QUEUE_ORDER_FULL"); return t ? atoi(t) : 0; }();
-        const bool pcie_bound = zc && !compact && (want_rhs || want_rows);
-        const int32_t* order = (node_queue() == 2 && n_nodes > group && (order_full || !pcie_bound)) ? e->d_cut_order : (const int32_t*)nullptr;
-        if (e->s.n_opt > 0) {  // optional objectives: the OPT build (eager restores)
-            NODE_LAUNCH_LINE("k_node_queue<512,cow 0,opt 1>", group, (int)n_nodes, lds);
-            hipLaunchKernelGGL((k_node_queue<512, false, true>), dim3(group), dim3(512), lds, s, e->s, sn, cu, (int)n_nodes, order, e->d_queue, check_cycles,
-                               cap, (int)e->cap_rows, want_rhs ? o_rhs : nullptr, want_rows ? o_rows : nullptr, o_states, g_stride);
-        } else if (node_cow()) {
-            NODE_LAUNCH_LINE("k_node_queue<512,cow 1,opt 0>", group, (int)n_nodes, lds);
-            hipLaunchKernelGGL((k_node_queue<512, true>), dim3(group), dim3(512), lds, s, e->s, sn, cu, (int)n_nodes, order, e->d_queue, check_cycles,
-                               cap, (int)e->cap_rows, want_rhs ? o_rhs : nullptr, want_rows ? o_rows : nullptr, o_states, g_stride);
-        } else {
-            NODE_LAUNCH_LINE("k_node_queue<512,cow 0,opt 0>", group, (int)n_nodes, lds);
-            hipLaunchKernelGGL((k_node_queue<512, false>), dim3(group), dim3(512), lds, s, e->s, sn, cu, (int)n_nodes, order, e->d_queue, check_cycles,
-                               cap, (int)e->cap_rows, want_rhs ? o_rhs : nullptr, want_rows ? o_rows : nullptr, o_states, g_stride);
-        }
-        HIPC(hipGetLastError());
-        if (!zc && !dev_out && compact != 2) {
-            HIPC(hipMemcpyAsync(e->h_states, e->d_states, sizeof(DevState) * (size_t)n_nodes, hipMemcpyDeviceToHost, s));
-            if (want_rhs) HIPC(hipMemcpyAsync(e->h_rhs, e->d_rhs, sizeof(double) * (size_t)n_nodes * row_stride, hipMemcpyDeviceToHost, s));
-            if (want_rows) HIPC(hipMemcpyAsync(e->h_rows, e->d_rows, sizeof(int32_t) * (size_t)n_nodes * row_stride, hipMemcpyDeviceToHost, s));
-        }
-    } else
-    for (int first = 0, g = 0; first < n_nodes; first += g) {
-        g = first < n_grouped ? std::min(group, n_grouped - first) : 1;
-        // slots already in sync with the snapshot: restore of the dirty rows, cuts, simplex and gather in ONE launch per
-        // group (what a workgroup restores and cuts stays in its XCD's L2 for its own pivots)
-        const bool one_launch = wg && g > 1 && checkpoint < 0 && e->has_save && e->slot0_synced && g <= e->slots_synced &&
-                                !e->timing && e->one_launch_nodes && wg_batch_threads() == 512;
-        if (one_launch) {
-            Snapshot sn = root_snapshot(e);
-            e->last_path = "workgroup";
-            // a batch that leaves most CUs idle anyway (speculative batches of a real tree: <= 16 nodes) is served by latency, not
-            // by occupancy: the 1024-thread shape of the single-node path, one workgroup per CU
-            static const int small_1024 = getenv("JSLP_SMALL_BATCH_1024") ? atoi(getenv("JSLP_SMALL_BATCH_1024")) : JSLP_SMALL_BATCH_1024_DEFAULT;
-            const size_t lds = wglds_smem(e);
-            if (lds && e->s.n_opt > 0) {  // optional objectives: the 1024-thread build only, whatever the batch size
-                NODE_LAUNCH_LINE("k_node_lds<1024,opt 1,cow 0>", g, -1, lds);
-                hipLaunchKernelGGL((k_node_lds<1024, true>), dim3(g), dim3(1024), lds, s, e->s, sn, cu, first, check_cycles, cap,
-                                   (int)e->cap_rows, want_rhs ? o_rhs : nullptr, want_rows ? o_rows : nullptr, o_states,
-                                   g_stride, first, (unsigned*)nullptr, 0u);
-            } else if (lds && g <= small_1024) {
-                // a batch that is ONE group, its outcomes written straight into pinned memory: the last workgroup raises the completion
-                // flag the host polls (below) instead of the two stream synchronisations that end the other shapes of this call
-                unsigned* d_flag = nullptr;
-                unsigned seq = 0;
-                if (g == n_nodes && zc && !dev_out && !e->ext_states && batch_poll_on()) {
-                    unsigned* h_flag = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(e->h_state) + sizeof(DevState));
-                    void* flag_dev = nullptr;
-                    if (hipHostGetDevicePointer(&flag_dev, h_flag, 0) == hipSuccess) {
-                        d_flag = static_cast<unsigned*>(flag_dev);
-                        seq = ++e->done_seq ? e->done_seq : ++e->done_seq;  // never 0 (the flag's initial value)
-                        polled_flag = h_flag; polled_seq = seq;
-                    } else {
-                        (void)hipGetLastError();
-                    }
-                }
-                // (round 6) copy-on-write start here too, as the queue kernel and the single-node call have it: a node READS what its slot's earlier nodes
-                // dirtied from the root instead of restoring those rows first -- the eager restore was 8.6 k of the 78 k cycles of a node of an 8-node batch
-                // (tools/wglds_timing.py one 8, debug build), in front of everything else; JSLP_NODE_COW_SMALL=0: eager restores
-                static const int cow_small = getenv("JSLP_NODE_COW_SMALL") ? atoi(getenv("JSLP_NODE_COW_SMALL")) : 1;
-                if (cow_small && node_cow()) {
-                    NODE_LAUNCH_LINE("k_node_lds<1024,opt 0,cow 1>", g, -1, lds);
-                    hipLaunchKernelGGL((k_node_lds<1024, false, true>), dim3(g), dim3(1024), lds, s, e->s, sn, cu, first, check_cycles, cap,
-                                       (int)e->cap_rows, want_rhs ? o_rhs : nullptr, want_rows ? o_rows : nullptr, o_states,
-                                       g_stride, first, d_flag, seq, d_flag ? e->d_done_count : (int*)nullptr);
-                } else {
-                    NODE_LAUNCH_LINE("k_node_lds<1024,opt 0,cow 0>", g, -1, lds);
-                    hipLaunchKernelGGL((k_node_lds<1024>), dim3(g), dim3(1024), lds, s, e->s, sn, cu, first, check_cycles, cap,
-                                       (int)e->cap_rows, want_rhs ? o_rhs : nullptr, want_rows ? o_rows : nullptr, o_states,
-                                       g_stride, first, d_flag, seq, d_flag ? e->d_done_count : (int*)nullptr);
-                }
-            } else if (lds) {
-                NODE_LAUNCH_LINE("k_node_lds<512,opt 0,cow 0>", g, -1, lds);
-                hipLaunchKernelGGL((k_node_lds<512>), dim3(g), dim3(512), lds, s, e->s, sn, cu, first, check_cycles, cap,
-                                   (int)e->cap_rows, want_rhs ? o_rhs : nullptr, want_rows ? o_rows : nullptr, o_states,
-                                   g_stride, first, (unsigned*)nullptr, 0u);
-            } else {
-                NODE_LAUNCH_LINE("k_node_wg<512,2048>", g, -1, 0);
-                hipLaunchKernelGGL((k_node_wg<512, 2048>), dim3(g), dim3(512), 0, s, e->s, sn, cu, first, check_cycles, cap,
-                                   (int)e->cap_rows, want_rhs ? o_rhs : nullptr, want_rows ? o_rows : nullptr, o_states,
-                                   g_stride, first, (unsigned*)nullptr, 0u);
-            }
-            HIPC(hipGetLastError());
-        } else {
-        rc = enqueue_restore(e, 0, g, checkpoint);
-        if (rc) return rc;
-        hipLaunchKernelGGL(k_add_cuts, dim3(g), dim3(256), 0, s, e->s, cu, 0, first, (int)e->cap_rows);
-        HIPC(hipGetLastError());
-        if (wg) {
-            e->last_path = "workgroup";
-            // one node: the 1024-thread latency shape; a batch: smaller workgroups, more nodes in flight per CU
-            const size_t lds = wglds_smem(e);
-            const bool opt = lds && e->s.n_opt > 0;
-            const int shape = (g == 1 || opt) ? 1024 : wg_batch_threads();
-            if (opt) {
-                NODE_LAUNCH_LINE("restore+add_cuts+simplex+gather k_simplex_lds<1024,opt 1>", g, -1, lds);
-                hipLaunchKernelGGL((k_simplex_lds<JSLP_WG_THREADS, true>), dim3(g), dim3(JSLP_WG_THREADS), lds, s, e->s, 0, check_cycles, cap, (int)e->cap_rows);
-            } else if (lds && shape == 1024) {
-                NODE_LAUNCH_LINE("restore+add_cuts+simplex+gather k_simplex_lds<1024,opt 0>", g, -1, lds);
-                hipLaunchKernelGGL((k_simplex_lds<JSLP_WG_THREADS>), dim3(g), dim3(JSLP_WG_THREADS), lds, s, e->s, 0, check_cycles, cap, (int)e->cap_rows);
-            } else if (lds && shape == 512) {
-                NODE_LAUNCH_LINE("restore+add_cuts+simplex+gather k_simplex_lds<512,opt 0>", g, -1, lds);
-                hipLaunchKernelGGL((k_simplex_lds<512>), dim3(g), dim3(512), lds, s, e->s, 0, check_cycles, cap, (int)e->cap_rows);
-            } else if (shape == 256) {
-                NODE_LAUNCH_LINE("restore+add_cuts+simplex+gather k_simplex_wg<256,1024>", g, -1, 0);
-                hipLaunchKernelGGL((k_simplex_wg<256, 1024>), dim3(g), dim3(256), 0, s, e->s, 0, check_cycles, cap);
-            } else if (shape == 512) {
-                NODE_LAUNCH_LINE("restore+add_cuts+simplex+gather k_simplex_wg<512,2048>", g, -1, 0);
-                hipLaunchKernelGGL((k_simplex_wg<512, 2048>), dim3(g), dim3(512), 0, s, e->s, 0, check_cycles, cap);
-            } else {
-                NODE_LAUNCH_LINE("restore+add_cuts+simplex+gather k_simplex_wg<1024,4096>", g, -1, 0);
-                hipLaunchKernelGGL((k_simplex_wg<JSLP_WG_THREADS, 4096>), dim3(g), dim3(JSLP_WG_THREADS), 0, s, e->s, 0, check_cycles, cap);
-            }
-            HIPC(hipGetLastError());
-        } else {
-            // big tableau: the chip-wide kernels on slot 0 (g == 1)
-            if (dbg) debug_node_launch("restore+add_cuts+simplex+gather chip-wide", g, -1, 0);
-            HIPC(hipMemcpyAsync(e->h_state, e->s.st, sizeof(DevState), hipMemcpyDeviceToHost, s));
-            HIPC(hipStreamSynchronize(s));
-            rc = state_error(*e->h_state);
-            if (rc) return rc;
-            rc = run_simplex(e, check_cycles);
-            if (rc) return rc;
-        }
-        hipLaunchKernelGGL(k_gather, dim3(g), dim3(256), 0, s, e->s, 0, want_rhs ? o_rhs : nullptr,
-                           want_rows ? o_rows : nullptr, o_states, g_stride, first);
-        HIPC(hipGetLastError());
-        }  // !one_launch
-        // this group's outcomes cross PCIe on the copy stream while the next group computes (the three regions of the
-        // read-back buffer are laid out for all nodes, so a group is one contiguous slice of each)
-        if (zc || dev_out || compact == 2) continue;
-        HIPC(hipEventRecord(e->ev_group, s));
+    return JSLP_OK;
+}
+// staging -> pinned for the nodes [first, first + g) (the three regions of the read-back buffer are laid out for all nodes, so a group
+// is one contiguous slice of each)
+static int copy_outcomes(jslp_engine* e, const NodeCall& c, const NodeDest& d, int first, int g, bool overlap) {
+    hipStream_t on = e->stream;
+    if (overlap) {  // a group's outcomes cross PCIe on the copy stream while the next group computes
+        HIPC(hipEventRecord(e->ev_group, e->stream));
         HIPC(hipStreamWaitEvent(e->copy_stream, e->ev_group, 0));
-        HIPC(hipMemcpyAsync(e->h_states + first, e->d_states + first, sizeof(DevState) * (size_t)g, hipMemcpyDeviceToHost, e->copy_stream));
-        if (want_rhs)
-            HIPC(hipMemcpyAsync(e->h_rhs + (size_t)first * row_stride, e->d_rhs + (size_t)first * row_stride,
-                                sizeof(double) * (size_t)g * row_stride, hipMemcpyDeviceToHost, e->copy_stream));
-        if (want_rows)
-            HIPC(hipMemcpyAsync(e->h_rows + (size_t)first * row_stride, e->d_rows + (size_t)first * row_stride,
-                                sizeof(int32_t) * (size_t)g * row_stride, hipMemcpyDeviceToHost, e->copy_stream));
+        on = e->copy_stream;
     }
-    if (compact == 2) {  // the branch records of the whole batch, one workgroup per node, behind every node kernel on the stream
-        hipLaunchKernelGGL(k_branch_record, dim3(n_nodes), dim3(256), 0, s, o_states, o_rows, o_rhs, e->s.watch, (int)e->n_watch, e->precision,
-                           dev_out ? e->dev_rec : e->d_rec);
-        HIPC(hipGetLastError());
-        if (!dev_out) {
-            HIPC(hipMemcpyAsync(e->h_states, e->d_states, sizeof(DevState) * (size_t)n_nodes, hipMemcpyDeviceToHost, s));
-            HIPC(hipMemcpyAsync(e->h_rec, e->d_rec, sizeof(jslpx_branch_record) * (size_t)n_nodes, hipMemcpyDeviceToHost, s));
-        }
+    const size_t off = (size_t)first * d.row_stride, len = (size_t)g * d.row_stride;
+    HIPC(hipMemcpyAsync(e->h_states + first, e->d_states + first, sizeof(DevState) * (size_t)g, hipMemcpyDeviceToHost, on));
+    if (c.want_rhs) HIPC(hipMemcpyAsync(e->h_rhs + off, e->d_rhs + off, sizeof(double) * len, hipMemcpyDeviceToHost, on));
+    if (c.want_rows) HIPC(hipMemcpyAsync(e->h_rows + off, e->d_rows + off, sizeof(int32_t) * len, hipMemcpyDeviceToHost, on));
+    return JSLP_OK;
+}
+
+// the slots [0, n) are in sync with the snapshot (the saved root except for their dirty rows) and nothing asks for the eager sequence: the node kernels may start from them
+static bool node_kernels_fit(const jslp_engine* e, const NodeCall& c, int n) {
+    return c.checkpoint < 0 && e->has_save && e->slot0_synced && n <= e->slots_synced && !e->timing && e->one_launch_nodes && wg_batch_threads() == 512;
+}
+// the whole batch in ONE launch of resident workgroups that pull nodes from a queue (more nodes than slots)
+static int enqueue_queue(jslp_engine* e, const NodeCall& c, const NodePlan& p, const NodeDest& d, NodeArgs a, bool dbg) {
+    const int n_nodes = c.cuts.n_nodes;
+    e->last_path = "workgroup";
+    e->node_queue_launches += 1;
+    // (an order only where it can matter: more nodes than resident workgroups -- a batch that starts all at once pays the order array's trip per node
+    //  for nothing: the four-member pool's 604-node shares lost 6 % to it; the full read-back stays in call order unless node_queue_order_full())
+    const bool pcie_bound = d.zc && !c.compact() && (c.want_rhs || c.want_rows);
+    a.n_nodes = n_nodes;
+    a.order = (node_queue() == 2 && n_nodes > p.group && (node_queue_order_full() || !pcie_bound)) ? e->d_cut_order : (const int32_t*)nullptr;
+    a.queue = e->d_queue;
+    JSLP_TRY(launch_node_kernel(queue_kernel(e), a, p.group, wglds_smem(e), e->stream, dbg));
+    return d.copies ? copy_outcomes(e, c, d, 0, n_nodes, false) : JSLP_OK;
+}
+// slots already in sync with the snapshot: restore of the dirty rows, cuts, simplex and gather in ONE launch per
+// group (what a workgroup restores and cuts stays in its XCD's L2 for its own pivots)
+static int enqueue_one_launch_group(jslp_engine* e, const NodeCall& c, const NodeDest& d, NodeArgs a, int first, int g, bool dbg, DoneFlag* polled) {
+    e->last_path = "workgroup";
+    const size_t lds = wglds_smem(e);
+    a.first = first;
+    // a batch that is ONE group, its outcomes written straight into pinned memory: the last workgroup raises the completion
+    // flag the host polls instead of the two stream synchronisations that end the other shapes of this call
+    if (small_batch_shape(e, lds, g) && g == c.cuts.n_nodes && d.zc && !e->ext_states && batch_poll_on()) {
+        if (arm_done_flag(e, polled) == hipSuccess) { a.done_flag = polled->dev; a.done_seq = polled->seq; a.done_count = e->d_done_count; }
+        else (void)hipGetLastError();
     }
-    if (e->timing && wg) HIPC(hipEventRecord(e->ev_end, s));
+    return launch_node_kernel(group_kernel(e, lds, g), a, g, lds, e->stream, dbg);
+}
+// restore, cuts, simplex and gather as launches of their own: any start, any tableau
+static int enqueue_eager_group(jslp_engine* e, const NodeCall& c, const NodePlan& p, const NodeArgs& a, int first, int g, bool dbg) {
+    hipStream_t s = e->stream;
+    JSLP_TRY(enqueue_restore(e, 0, g, c.checkpoint));
+    hipLaunchKernelGGL(k_add_cuts, dim3(g), dim3(256), 0, s, e->s, a.cu, 0, first, (int)e->cap_rows);
+    HIPC(hipGetLastError());
+    if (p.wg) {
+        e->last_path = "workgroup";
+        const size_t lds = wglds_smem(e);
+        JSLP_TRY(launch_node_kernel(eager_kernel(e, lds, g), a, g, lds, s, dbg));
+    } else {
+        // big tableau: the chip-wide kernels on slot 0 (g == 1)
+        if (dbg) debug_node_launch("restore+add_cuts+simplex+gather chip-wide", g, -1, 0);
+        HIPC(hipMemcpyAsync(e->h_state, e->s.st, sizeof(DevState), hipMemcpyDeviceToHost, s));
+        HIPC(hipStreamSynchronize(s));
+        JSLP_TRY(state_error(*e->h_state));
+        JSLP_TRY(run_simplex(e, c.check_cycles));
+    }
+    hipLaunchKernelGGL(k_gather, dim3(g), dim3(256), 0, s, e->s, 0, a.rhs, a.rows, a.states, a.out_stride, first);
+    HIPC(hipGetLastError());
+    return JSLP_OK;
+}
+// the end of every shape but the single child's: the polled flag of a small batch, else both streams
+static int wait_for_nodes(jslp_engine* e, int n_nodes, const DoneFlag& polled, std::chrono::steady_clock::time_point t_enter) {
     bool arrived = false;
-    if (polled_flag) {  // the small batch's last workgroup ends with a system-scope release store of `polled_seq` into pinned memory
+    if (polled.host) {
         unsigned spins = 0;
-        const auto t_begin = std::chrono::steady_clock::now();
-        while (!(arrived = (__atomic_load_n(polled_flag, __ATOMIC_ACQUIRE) == polled_seq))) {
-            if ((++spins & 0x3fffu) == 0 &&
-                std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count() > 5.0) break;
-#if defined(__x86_64__)
-            __builtin_ia32_pause();
-#endif
-        }
-        // JSLP_DEBUG_STALL=<ms> (diagnosis): a dependent batch normally takes ~70 us; say on stderr when one took longer than
-        // that many milliseconds and whether the time went in front of the poll (cut-list staging, the launch call) or in it (the GPU side)
-        static const double stall_ms = [] { const char* t = getenv("JSLP_DEBUG_STALL"); return t ? atof(t) : 0.0; }();
-        if (stall_ms > 0) {
-            const auto t_end = std::chrono::steady_clock::now();
-            const double host_ms = std::chrono::duration<double, std::milli>(t_begin - t_enter).count(), poll_ms = std::chrono::duration<double, std::milli>(t_end - t_begin).count();
-            if (host_ms + poll_ms > stall_ms)
-                fprintf(stderr, "[jslp] stall: a %d-node polled batch took %.3f ms in front of the poll (staging + launch) and %.3f ms polling (%u spins)\n", (int)n_nodes, host_ms, poll_ms, spins);
-        }
+        const auto t_poll = std::chrono::steady_clock::now();
+        arrived = wait_done_flag(polled.host, polled.seq, spins);
+        if (debug_stall_ms() > 0) report_stall(n_nodes, true, t_enter, t_poll, spins);
     }
     if (!arrived) {  // every other shape -- and a polled batch that did not show up in 5 s: let the runtime report the fault
         const auto t_sync = std::chrono::steady_clock::now();
         if (e->copy_stream) HIPC(hipStreamSynchronize(e->copy_stream));
-        HIPC(hipStreamSynchronize(s));
-        static const double stall_ms2 = [] { const char* t = getenv("JSLP_DEBUG_STALL"); return t ? atof(t) : 0.0; }();
-        if (stall_ms2 > 0) {  // (the same diagnostic for the synchronising shapes: enqueue time vs time inside the two stream synchronisations)
-            const auto t_end = std::chrono::steady_clock::now();
-            const double host_ms = std::chrono::duration<double, std::milli>(t_sync - t_enter).count(), sync_ms = std::chrono::duration<double, std::milli>(t_end - t_sync).count();
-            if (host_ms + sync_ms > stall_ms2)
-                fprintf(stderr, "[jslp] stall: a %d-node batch took %.3f ms to enqueue (staging + launches) and %.3f ms in hipStreamSynchronize\n", (int)n_nodes, host_ms, sync_ms);
-        }
+        HIPC(hipStreamSynchronize(e->stream));
+        if (debug_stall_ms() > 0) report_stall(n_nodes, false, t_enter, t_sync, 0);
     }
-    if (wg && e->timing) {
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, e->ev_begin, e->ev_end) == hipSuccess) e->total_ms += ms;
-    }
-    if (e->counting) e->wc.cut_rows += cut_offsets[n_nodes];
-    if (dev_out) {
+    return JSLP_OK;
+}
+
+// the 128-byte state of every node, in call order: the first error ends the call, the engine's evaluation is the last node's
+static int decode_outcomes(jslp_engine* e, const NodeCall& c, const NodePlan& p, const NodeDest& d) {
+    const int n_nodes = c.cuts.n_nodes;
+    if (c.to_device()) {
         // the outcomes stay on the device (the caller converts the gathered records with jslp_engine_results_from_states), but the
         // engine's own bookkeeping must not depend on where they went: the 128-byte records of THIS call come back (n x 128 B) so
         // that a node that ended in an error clears the slot-sync flags (later one-launch / copy-on-write batches must not start
         // from slots it left dirty), the work counters see the pivots, and the engine's evaluation is the last node's
-        HIPC(hipMemcpy(e->h_states, e->dev_states, sizeof(DevState) * (size_t)n_nodes, hipMemcpyDeviceToHost));
-        e->dev_prev_evaluation = prev_eval;  // what results_from_states hands a node that reaches no optimum (as the host path does)
+        HIPC(hipMemcpy(e->h_states, c.dev.states, sizeof(DevState) * (size_t)n_nodes, hipMemcpyDeviceToHost));
+        e->dev_prev_evaluation = p.prev_eval;  // what results_from_states hands a node that reaches no optimum (as the host path does)
         e->dev_prev_valid = 1;
-        for (int i = 0; i < n_nodes; i++) {
-            const DevState& st = e->h_states[i];
-            rc = state_error(st);
-            if (rc) { e->slot0_synced = 0; e->slots_synced = 0; return rc; }
-            account(e, st, 1);
-            if (i == n_nodes - 1) {
-                jslp_simplex_result last;
-                DevState rec = st;
-                rec.hist_n = 0;
-                rc = fill_result(e, rec, 0, prev_eval, &last, &e->evaluation);
-                if (rc) return rc;
-            }
-        }
-        return JSLP_OK;
     }
     for (int i = 0; i < n_nodes; i++) {
         DevState st = e->h_states[i];
-        rc = state_error(st);
+        int rc = state_error(st);
         if (rc) { e->slot0_synced = 0; e->slots_synced = 0; return rc; }
         account(e, st, 1);
-        if (st.cycle_phase && wg && (n_nodes > group || (n_grouped < n_nodes && i == 0))) {
+        if (c.to_device()) {  // (a record carries no pivot history: results_from_states reports a cycle without its detail, and so does this)
+            if (i < n_nodes - 1) continue;
+            jslp_simplex_result last;
+            st.hist_n = 0;
+            JSLP_TRY(fill_result(e, st, 0, p.prev_eval, &last, &e->evaluation));
+            continue;
+        }
+        if (st.cycle_phase && p.wg && (n_nodes > p.group || (p.n_grouped < n_nodes && i == 0))) {
             // the cycle message is rebuilt from the slot's history, which later groups have reused (of the children of a checkpoint in
             // one group only the first: the last child ran in its slot after it): report the hit (flags are exact) without the
             // [start, length] detail
             st.hist_n = 0;
         }
         double ev;
-        rc = fill_result(e, st, wg && i < n_grouped ? i % group : 0, prev_eval, &out[i], &ev);
-        if (rc) return rc;
+        JSLP_TRY(fill_result(e, st, p.wg && i < p.n_grouped ? i % p.group : 0, p.prev_eval, &c.out[i], &ev));
         if (i == n_nodes - 1) e->evaluation = ev;
-        if (!pinned && !compact) {
+        if (!c.pinned && !c.compact()) {
             const size_t n_out = (size_t)st.H;
-            if (rhs) memcpy(rhs + (size_t)i * out_stride, e->h_rhs + (size_t)i * row_stride, sizeof(double) * n_out);
-            if (var_index_by_row)
-                memcpy(var_index_by_row + (size_t)i * out_stride, e->h_rows + (size_t)i * row_stride, sizeof(int32_t) * n_out);
+            if (c.rhs) memcpy(c.rhs + (size_t)i * c.out_stride, e->h_rhs + (size_t)i * d.row_stride, sizeof(double) * n_out);
+            if (c.var_index_by_row) memcpy(c.var_index_by_row + (size_t)i * c.out_stride, e->h_rows + (size_t)i * d.row_stride, sizeof(int32_t) * n_out);
         }
     }
-    if (compact == 2) { e->dev_prev_evaluation = prev_eval; e->dev_prev_valid = 1; }
-    if (!pinned && compact) {  // same layout on both sides: one copy each (per-node copies cost more than the kernel's share of a node)
-        if (rhs) memcpy(rhs, e->h_rhs, sizeof(double) * (size_t)n_nodes * row_stride);
-        if (var_index_by_row) memcpy(var_index_by_row, e->h_rows, sizeof(int32_t) * (size_t)n_nodes * row_stride);
+    if (c.to_device()) return JSLP_OK;
+    if (c.records()) { e->dev_prev_evaluation = p.prev_eval; e->dev_prev_valid = 1; }
+    if (!c.pinned && c.compact()) {  // same layout on both sides: one copy each (per-node copies cost more than the kernel's share of a node)
+        if (c.rhs) memcpy(c.rhs, e->h_rhs, sizeof(double) * (size_t)n_nodes * d.row_stride);
+        if (c.var_index_by_row) memcpy(c.var_index_by_row, e->h_rows, sizeof(int32_t) * (size_t)n_nodes * d.row_stride);
     }
     return JSLP_OK;
 }
 
-#undef NODE_LAUNCH_LINE
+// Every node entry point ends here.  Per-node-workgroup path: all groups are enqueued back to back, their outcomes accumulate in ONE
+// buffer laid out for all n_nodes, one wait ends the call.
+static int relax_batch_impl(jslp_engine* e, const NodeCall& c) {
+    const auto t_enter = std::chrono::steady_clock::now();  // (JSLP_DEBUG_STALL)
+    int rc = node_call_check(e, c);
+    const int n_nodes = c.cuts.n_nodes;
+    if (rc || n_nodes == 0) return rc;
+    HIPC(hipSetDevice(e->device));
+    hipStream_t s = e->stream;
+    const bool dbg = getenv("JSLP_DEBUG_LAUNCH") != nullptr;  // (read per call, as run_simplex does: tests switch it inside one process)
+    if (single_child_fast_path(e, c)) return relax_single_child(e, c, dbg);
+    JSLP_TRY(upload_cuts(e, n_nodes, c.cuts.offsets, c.cuts.type, c.cuts.var_index, c.cuts.value));
+    NodePlan p;
+    JSLP_TRY(plan_node_call(e, c, &p));
+    JSLP_TRY(ensure_out(e, (size_t)n_nodes));  // laid out for ALL nodes: [states | rhs | rows]
+    if (c.records()) JSLP_TRY(ensure_records(e, (size_t)n_nodes));
+    if (e->timing) HIPC(hipEventRecord(e->ev_begin, s));
+    NodeDest d;
+    JSLP_TRY(node_destination(e, c, &d));
+    NodeArgs a{&e->s, root_snapshot(e), Cuts{e->d_cut_offs, e->d_cut_type, e->d_cut_var, e->d_cut_val}, c.check_cycles, iters_cap(e), (int)e->cap_rows,
+               c.want_rhs ? d.rhs : nullptr, c.want_rows ? d.rows : nullptr, d.states, c.compact() ? -e->n_watch : (int)d.row_stride};
+    DoneFlag polled;  // armed when the call ends by polling a completion flag instead of synchronising the streams
+    if (p.wg && wglds_smem(e) && node_queue() && n_nodes > p.group && node_kernels_fit(e, c, p.group)) {
+        JSLP_TRY(enqueue_queue(e, c, p, d, a, dbg));
+    } else {
+        for (int first = 0, g = 0; first < n_nodes; first += g) {
+            g = first < p.n_grouped ? std::min(p.group, p.n_grouped - first) : 1;
+            JSLP_TRY(p.wg && g > 1 && node_kernels_fit(e, c, g) ? enqueue_one_launch_group(e, c, d, a, first, g, dbg, &polled) : enqueue_eager_group(e, c, p, a, first, g, dbg));
+            if (d.copies) JSLP_TRY(copy_outcomes(e, c, d, first, g, true));
+        }
+    }
+    if (c.records()) {  // the branch records of the whole batch, one workgroup per node, behind every node kernel on the stream
+        hipLaunchKernelGGL(k_branch_record, dim3(n_nodes), dim3(256), 0, s, d.states, d.rows, d.rhs, e->s.watch, (int)e->n_watch, e->precision,
+                           c.to_device() ? c.dev.rec : e->d_rec);
+        HIPC(hipGetLastError());
+        if (!c.to_device()) {
+            HIPC(hipMemcpyAsync(e->h_states, e->d_states, sizeof(DevState) * (size_t)n_nodes, hipMemcpyDeviceToHost, s));
+            HIPC(hipMemcpyAsync(e->h_rec, e->d_rec, sizeof(jslpx_branch_record) * (size_t)n_nodes, hipMemcpyDeviceToHost, s));
+        }
+    }
+    if (e->timing && p.wg) HIPC(hipEventRecord(e->ev_end, s));
+    JSLP_TRY(wait_for_nodes(e, n_nodes, polled, t_enter));
+    float ms = 0;
+    if (p.wg && e->timing && hipEventElapsedTime(&ms, e->ev_begin, e->ev_end) == hipSuccess) e->total_ms += ms;
+    if (e->counting) e->wc.cut_rows += c.cuts.offsets[n_nodes];
+    return decode_outcomes(e, c, p, d);
+}
 
 extern "C" int jslp_engine_relax_batch(jslp_engine* e, int32_t n_nodes, const int32_t* cut_offsets, const int8_t* type,
                                        const int32_t* var_index, const double* value, int check_cycles,
                                        jslp_simplex_result* out, double* rhs, int32_t* var_index_by_row,
                                        int32_t out_stride) {
-    return relax_batch_impl(e, n_nodes, cut_offsets, type, var_index, value, check_cycles, out, rhs, var_index_by_row,
-                            out_stride, 0, rhs != nullptr, var_index_by_row != nullptr);
+    return jslp_engine_relax_from(e, -1, n_nodes, cut_offsets, type, var_index, value, check_cycles, out, rhs, var_index_by_row, out_stride);
 }
 
 // ---- outcomes left in DEVICE memory of the caller (the N > 1 process path: they are the input of an RCCL all-gather) -------------
@@ -2397,10 +2402,8 @@ extern "C" int jslp_engine_relax_batch_device(jslp_engine* e, int32_t n_nodes, c
                                               double* d_rhs, int32_t* d_rows, int32_t row_stride) {
     if (!e || !d_states || !d_rhs || !d_rows) return fail(JSLP_ERR_ARG, "relax_batch_device: null pointer");
     if (row_stride < e->cap_rows) return fail(JSLP_ERR_ARG, "relax_batch_device: row_stride < row capacity");
-    e->dev_states = static_cast<DevState*>(d_states); e->dev_rhs = d_rhs; e->dev_rows = d_rows; e->dev_stride = row_stride;
-    const int rc = relax_batch_impl(e, n_nodes, cut_offsets, type, var_index, value, check_cycles, nullptr, nullptr, nullptr, 0, 1, 1, 1);
-    e->dev_states = nullptr; e->dev_rhs = nullptr; e->dev_rows = nullptr; e->dev_stride = 0;
-    return rc;
+    return relax_batch_impl(e, NodeCall{.cuts = {n_nodes, cut_offsets, type, var_index, value}, .check_cycles = check_cycles, .want_rhs = true, .want_rows = true,
+                                        .dev = {.states = static_cast<DevState*>(d_states), .rhs = d_rhs, .rows = d_rows, .stride = row_stride}});
 }
 
 // `states`: n_nodes raw records in HOST memory (wherever they were evaluated: this rank's own or another rank's, after the
@@ -2426,9 +2429,8 @@ extern "C" int jslp_engine_relax_batch_pinned(jslp_engine* e, int32_t n_nodes, c
                                               int check_cycles, jslp_simplex_result* out, const double** rhs,
                                               const int32_t** var_index_by_row, int32_t* out_stride) {
     if (!e) return fail(JSLP_ERR_ARG, "relax_batch_pinned: null engine");
-    int rc = relax_batch_impl(e, n_nodes, cut_offsets, type, var_index, value, check_cycles, out, nullptr, nullptr, 0, 1,
-                              rhs != nullptr, var_index_by_row != nullptr);
-    if (rc) return rc;
+    JSLP_TRY(relax_batch_impl(e, NodeCall{.cuts = {n_nodes, cut_offsets, type, var_index, value}, .check_cycles = check_cycles,
+                                          .want_rhs = rhs != nullptr, .want_rows = var_index_by_row != nullptr, .out = out, .pinned = true}));
     if (rhs) *rhs = n_nodes > 0 ? e->h_rhs : nullptr;
     if (var_index_by_row) *var_index_by_row = n_nodes > 0 ? e->h_rows : nullptr;
     if (out_stride) *out_stride = (int32_t)out_stride_of(e);
@@ -2439,8 +2441,9 @@ extern "C" int jslp_engine_relax_from(jslp_engine* e, int32_t checkpoint, int32_
                                       const int8_t* type, const int32_t* var_index, const double* value, int check_cycles,
                                       jslp_simplex_result* out, double* rhs, int32_t* var_index_by_row,
                                       int32_t out_stride) {
-    return relax_batch_impl(e, n_nodes, cut_offsets, type, var_index, value, check_cycles, out, rhs, var_index_by_row,
-                            out_stride, 0, rhs != nullptr, var_index_by_row != nullptr, checkpoint < 0 ? -1 : checkpoint);
+    return relax_batch_impl(e, NodeCall{.cuts = {n_nodes, cut_offsets, type, var_index, value}, .check_cycles = check_cycles, .checkpoint = checkpoint < 0 ? -1 : checkpoint,
+                                        .want_rhs = rhs != nullptr, .want_rows = var_index_by_row != nullptr,
+                                        .out = out, .rhs = rhs, .var_index_by_row = var_index_by_row, .out_stride = out_stride});
 }
 
 extern "C" int jslp_engine_relax(jslp_engine* e, int32_t n_cuts, const int8_t* type, const int32_t* var_index,
@@ -2486,16 +2489,16 @@ extern "C" int jslp_engine_relax_watched(jslp_engine* e, int32_t n_cuts, const i
     if (!e) return fail(JSLP_ERR_ARG, "relax_watched: null engine");
     if (n_cuts < 0) return fail(JSLP_ERR_ARG, "relax_watched: negative cut count");
     const int32_t offs[2] = {0, n_cuts};
-    return relax_batch_impl(e, 1, offs, type, var_index, value, check_cycles, out, watched_value, watched_row, e->cap_rows, 0,
-                            watched_value != nullptr, watched_row != nullptr, -1, 1);
+    return jslp_engine_relax_batch_watched(e, 1, offs, type, var_index, value, check_cycles, out, watched_row, watched_value);
 }
 
 extern "C" int jslp_engine_relax_batch_watched(jslp_engine* e, int32_t n_nodes, const int32_t* cut_offsets, const int8_t* type,
                                                const int32_t* var_index, const double* value, int check_cycles,
                                                jslp_simplex_result* out, int32_t* watched_row, double* watched_value) {
     if (!e) return fail(JSLP_ERR_ARG, "relax_batch_watched: null engine");
-    return relax_batch_impl(e, n_nodes, cut_offsets, type, var_index, value, check_cycles, out, watched_value, watched_row, e->cap_rows, 0,
-                            watched_value != nullptr, watched_row != nullptr, -1, 1);
+    return relax_batch_impl(e, NodeCall{.cuts = {n_nodes, cut_offsets, type, var_index, value}, .check_cycles = check_cycles, .read_back = ReadBack::Watched,
+                                        .want_rhs = watched_value != nullptr, .want_rows = watched_row != nullptr,
+                                        .out = out, .rhs = watched_value, .var_index_by_row = watched_row, .out_stride = e->cap_rows});
 }
 
 extern "C" int jslp_engine_relax_batch_watched_pinned(jslp_engine* e, int32_t n_nodes, const int32_t* cut_offsets, const int8_t* type,
@@ -2503,9 +2506,8 @@ extern "C" int jslp_engine_relax_batch_watched_pinned(jslp_engine* e, int32_t n_
                                                       jslp_simplex_result* out, const int32_t** watched_row,
                                                       const double** watched_value) {
     if (!e) return fail(JSLP_ERR_ARG, "relax_batch_watched_pinned: null engine");
-    int rc = relax_batch_impl(e, n_nodes, cut_offsets, type, var_index, value, check_cycles, out, nullptr, nullptr, 0, 1,
-                              watched_value != nullptr, watched_row != nullptr, -1, 1);
-    if (rc) return rc;
+    JSLP_TRY(relax_batch_impl(e, NodeCall{.cuts = {n_nodes, cut_offsets, type, var_index, value}, .check_cycles = check_cycles, .read_back = ReadBack::Watched,
+                                          .want_rhs = watched_value != nullptr, .want_rows = watched_row != nullptr, .out = out, .pinned = true}));
     if (watched_row) *watched_row = n_nodes > 0 ? e->h_rows : nullptr;
     if (watched_value) *watched_value = n_nodes > 0 ? e->h_rhs : nullptr;
     return JSLP_OK;
@@ -2517,10 +2519,8 @@ extern "C" int jslp_engine_relax_batch_watched_device(jslp_engine* e, int32_t n_
                                                       const int32_t* var_index, const double* value, int check_cycles, void* d_states,
                                                       int32_t* d_watched_row, double* d_watched_value) {
     if (!e || !d_states || !d_watched_row || !d_watched_value) return fail(JSLP_ERR_ARG, "relax_batch_watched_device: null pointer");
-    e->dev_states = static_cast<DevState*>(d_states); e->dev_rhs = d_watched_value; e->dev_rows = d_watched_row; e->dev_stride = e->n_watch;
-    const int rc = relax_batch_impl(e, n_nodes, cut_offsets, type, var_index, value, check_cycles, nullptr, nullptr, nullptr, 0, 1, 1, 1, -1, 1);
-    e->dev_states = nullptr; e->dev_rhs = nullptr; e->dev_rows = nullptr; e->dev_stride = 0;
-    return rc;
+    return relax_batch_impl(e, NodeCall{.cuts = {n_nodes, cut_offsets, type, var_index, value}, .check_cycles = check_cycles, .read_back = ReadBack::Watched, .want_rhs = true, .want_rows = true,
+                                        .dev = {.states = static_cast<DevState*>(d_states), .rhs = d_watched_value, .rows = d_watched_row, .stride = e->n_watch}});
 }
 
 extern "C" int32_t jslp_engine_watched_count(const jslp_engine* e) { return e ? e->n_watch : 0; }
@@ -2541,8 +2541,8 @@ extern "C" int jslpx_engine_relax_batch_branch(jslp_engine* e, int32_t n_nodes, 
                                                const int32_t* var_index, const double* value, int check_cycles, jslpx_branch_record* out) {
     if (!e || !out) return fail(JSLP_ERR_ARG, "relax_batch_branch: null pointer");
     jslp_simplex_result* res = branch_results_scratch(e, std::max(n_nodes, 0));
-    const int rc = relax_batch_impl(e, n_nodes, cut_offsets, type, var_index, value, check_cycles, res, nullptr, nullptr, 0, 1, 1, 1, -1, 2);
-    if (rc) return rc;
+    JSLP_TRY(relax_batch_impl(e, NodeCall{.cuts = {n_nodes, cut_offsets, type, var_index, value}, .check_cycles = check_cycles, .read_back = ReadBack::BranchRecord,
+                                          .want_rhs = true, .want_rows = true, .out = res, .pinned = true}));
     if (n_nodes > 0) memcpy(out, e->h_rec, sizeof(jslpx_branch_record) * (size_t)n_nodes);
     return JSLP_OK;
 }
@@ -2552,8 +2552,8 @@ extern "C" int jslpx_engine_relax_batch_branch_pinned(jslp_engine* e, int32_t n_
                                                       const jslpx_branch_record** out) {
     if (!e || !out) return fail(JSLP_ERR_ARG, "relax_batch_branch_pinned: null pointer");
     jslp_simplex_result* res = branch_results_scratch(e, std::max(n_nodes, 0));
-    const int rc = relax_batch_impl(e, n_nodes, cut_offsets, type, var_index, value, check_cycles, res, nullptr, nullptr, 0, 1, 1, 1, -1, 2);
-    if (rc) return rc;
+    JSLP_TRY(relax_batch_impl(e, NodeCall{.cuts = {n_nodes, cut_offsets, type, var_index, value}, .check_cycles = check_cycles, .read_back = ReadBack::BranchRecord,
+                                          .want_rhs = true, .want_rows = true, .out = res, .pinned = true}));
     *out = n_nodes > 0 ? e->h_rec : nullptr;
     return JSLP_OK;
 }
@@ -2568,12 +2568,10 @@ extern "C" int jslpx_engine_relax_batch_branch_device(jslp_engine* e, int32_t n_
     if (e->n_watch <= 0 || e->n_watch > e->cap_rows)
         return fail(JSLP_ERR_ARG, "relax_batch_branch: after set_watched_variables (at most row_capacity of them)");
     HIPC(hipSetDevice(e->device));
-    int rc = ensure_out(e, (size_t)std::max(n_nodes, 1));
-    if (rc) return rc;
-    e->dev_states = e->d_states; e->dev_rhs = e->d_rhs; e->dev_rows = e->d_rows; e->dev_stride = e->n_watch; e->dev_rec = static_cast<double*>(d_records);
-    rc = relax_batch_impl(e, n_nodes, cut_offsets, type, var_index, value, check_cycles, nullptr, nullptr, nullptr, 0, 1, 1, 1, -1, 2);
-    e->dev_states = nullptr; e->dev_rhs = nullptr; e->dev_rows = nullptr; e->dev_stride = 0; e->dev_rec = nullptr;
-    return rc;
+    JSLP_TRY(ensure_out(e, (size_t)std::max(n_nodes, 1)));
+    // (the compact read-back stays in the engine's own staging buffers, which ensure_out has just laid out)
+    return relax_batch_impl(e, NodeCall{.cuts = {n_nodes, cut_offsets, type, var_index, value}, .check_cycles = check_cycles, .read_back = ReadBack::BranchRecord, .want_rhs = true, .want_rows = true,
+                                        .dev = {.states = e->d_states, .rhs = e->d_rhs, .rows = e->d_rows, .stride = e->n_watch, .rec = static_cast<double*>(d_records)}});
 }
 
 // records (host memory: this rank's or, after the exchange, another rank's) -> result structs, evaluation as fill_result derives it
@@ -3094,9 +3092,10 @@ static int pool_relax(jslp_pool* p, int32_t n_nodes, const int32_t* cut_offsets,
         m->ext_states = g_states + first;
         m->ext_rhs = g_rhs + (size_t)first * cap;
         m->ext_rows = g_rows + (size_t)first * cap;
-        const int r = relax_batch_impl(m, cnt, o.data(), type ? type + base : nullptr, var_index ? var_index + base : nullptr,
-                                       value ? value + base : nullptr, check_cycles, out + first, nullptr, nullptr, 0, 1,
-                                       want_rhs, want_rows, -1, compact);
+        // (pinned: the member's buffers ARE this range of the pool's, through ext_*)
+        const int r = relax_batch_impl(m, NodeCall{.cuts = {cnt, o.data(), type ? type + base : nullptr, var_index ? var_index + base : nullptr, value ? value + base : nullptr},
+                                                   .check_cycles = check_cycles, .read_back = compact ? ReadBack::Watched : ReadBack::Full,
+                                                   .want_rhs = want_rhs != 0, .want_rows = want_rows != 0, .out = out + first, .pinned = true});
         m->ext_states = nullptr; m->ext_rhs = nullptr; m->ext_rows = nullptr;
         if (r) return r;
         if (compact) {  // same layout on both sides: one copy per member
