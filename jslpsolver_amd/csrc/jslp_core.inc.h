@@ -2,8 +2,9 @@
 // solver), written once over `real_t` and compiled twice by jslp_kernels.hip.h:
 //   * real_t = double, at global scope: THE engine (bit-exact with the reference, every parity test runs on it)
 //   * real_t = float, in namespace f32: the fp32 twin behind jslp_engine_simplex_f32 -- the same pivoting rules on a
-//     half-as-wide tableau, used only by the fp32-vs-fp64 tolerance sweep; it has no reference
-//     to be exact against and never touches the fp64 state.
+//     half-as-wide tableau, used only by the fp32-vs-fp64 tolerance sweep; it never touches the
+//     fp64 state.  Its reference is this file read in IEEE binary32 -- every operation rounded once, `eliminate` twice --
+//     restated on the CPU by tests/fp32_reference.py; tests/test_fp32_exact.py holds the twin to it bit for bit.
 // Needs, at the point of inclusion: real_t, real2_t, rmul_rn / rsub_rn for real_t, DevState, the ST_* / ERR_* enums and
 // the JSLP_* launch constants.  No include guard on purpose.
 

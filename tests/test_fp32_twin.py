@@ -1,7 +1,8 @@
-"""The fp32 twin of the simplex core (jslp_engine_simplex_f32; SURVEY.md 8d config 5's fp32-vs-fp64 sweep).  It has no
-reference to be exact against: these tests pin what it must guarantee -- the fp64 state is untouched, on small
-well-conditioned models the fp32 run agrees with the fp64 run on the flags and, within fp32 accuracy, on the optimum --
-and that the test library refuses it."""
+"""The fp32 twin of the simplex core (jslp_engine_simplex_f32; SURVEY.md 8d config 5's fp32-vs-fp64 sweep).  Its exact
+reference is the core restated in IEEE binary32 (tests/fp32_reference.py, held bit for bit by tests/test_fp32_exact.py).
+These tests pin what it must guarantee next to the fp64 engine -- the fp64 state is untouched, on small well-conditioned
+models the fp32 run agrees with the fp64 run on the flags and, within fp32 accuracy, on the optimum -- and that the test
+library refuses it."""
 import numpy as np
 import pytest
 
