@@ -198,7 +198,15 @@ KNOB(int, node_queue, "JSLP_NODE_QUEUE", 2)
 // 1 hands the FULL read-back out longest-first too; its bound is the PCIe link and it measured 3.41-3.42 M against 3.52-3.54 M relaxations/s in call order: the heavy nodes' outcomes then leave in one burst
 KNOB(int, node_queue_order_full, "JSLP_NODE_QUEUE_ORDER_FULL", 0)
 KNOB(long long, wg_cells_child, "JSLP_WG_CELLS_CHILD", 1536LL * 1024)  // a single B&B child (few repair pivots) stays in one workgroup up to this (tools/child_path_times.py)
+// the solve path's two latched knobs
+KNOB(int, fused_wide_on, "JSLP_FUSED_WIDE", 1)  // 0: tableaus wider than 4096 columns through k_select + k_update, as before round 5
+KNOB(int, fused_p1_on, "JSLP_FUSED_P1", 1)  // 0: phase 1 of the large LPs through k_select + k_update instead of k_fused_p1 (one launch per pivot)
 #undef KNOB
+// ... and the switches simplex() reads on EVERY call, one reader each (tests flip them inside one process); JSLP_RES_GEOM / JSLP_RES_RPB (experiments) and
+// JSLP_INJECT_RESIDENT_ABORT_US are read where they act
+static bool res_lean_on() { const char* t = getenv("JSLP_RES_LEAN"); return !(t && atoi(t) == 0); }  // 0: the general build of the register-resident kernel only
+static int res_wide_tall() { const char* t = getenv("JSLP_RES_WIDE_TALL"); return t ? atoi(t) : -1; }  // -1: not given (resident_geometry)
+static bool debug_launch_on() { return getenv("JSLP_DEBUG_LAUNCH") != nullptr; }
 // a one-group batch of the 1024-thread node kernel ends by polling its completion flag (JSLP_BATCH_POLL=0: stream synchronisation; the first character decides)
 static int batch_poll_on() { static const int v = [] { const char* t = getenv("JSLP_BATCH_POLL"); return (t && t[0] == '0') ? 0 : 1; }(); return v; }
 // JSLP_DEBUG_STALL=<ms> (diagnosis): a dependent batch normally takes ~70 us; say on stderr when one took longer than that many milliseconds and where the time went (report_stall)
@@ -751,13 +759,23 @@ static bool use_wg_single(const jslp_engine* e) {
     return wglds_smem(e) != 0 && cells <= WG_CELLS_SPARSE && e->nnz >= 0 &&
            (double)e->nnz <= WG_SPARSE_DENSITY * (double)e->H0 * (double)e->W;
 }
+// ... that solve: the LDS-resident kernel when the tableau fits its LDS, else the generic one
+static int solve_one_workgroup(jslp_engine* e, int check_cycles) {
+    hipStream_t s = e->stream;
+    const int cap = iters_cap(e);
+    e->last_path = "workgroup";
+    if (const size_t lds = wglds_smem(e); lds && e->s.n_opt > 0)  // optional objectives: a build of their own (jslp_wglds.hip.h)
+        hipLaunchKernelGGL((k_simplex_lds<JSLP_WG_THREADS, true>), dim3(1), dim3(JSLP_WG_THREADS), lds, s, e->s, 0, check_cycles, cap, (int)e->cap_rows);
+    else if (lds)
+        hipLaunchKernelGGL((k_simplex_lds<JSLP_WG_THREADS>), dim3(1), dim3(JSLP_WG_THREADS), lds, s, e->s, 0, check_cycles, cap, (int)e->cap_rows);
+    else
+        hipLaunchKernelGGL((k_simplex_wg<JSLP_WG_THREADS, 4096>), dim3(1), dim3(JSLP_WG_THREADS), 0, s, e->s, 0, check_cycles, cap);
+    HIPC(hipGetLastError());
+    HIPC(hipMemcpyAsync(e->h_state, e->s.st, sizeof(DevState), hipMemcpyDeviceToHost, s));
+    return JSLP_OK;
+}
 
 #define JSLP_F_MAXNT 4
-static int fused_wide_on() {  // JSLP_FUSED_WIDE=0: tableaus wider than 4096 columns through k_select + k_update, as before round 5
-    static int v = -1;
-    if (v < 0) { const char* t = getenv("JSLP_FUSED_WIDE"); v = (t && t[0] == '0') ? 0 : 1; }
-    return v;
-}
 // the fused one-launch-per-pivot phase 2 (see k_pivot_fused for the preconditions)
 static bool fused_eligible(const jslp_engine* e) {
     if (e->force_path == 2) return false;
@@ -768,61 +786,48 @@ static bool fused_eligible(const jslp_engine* e) {
     return e->ld <= max_tiles * JSLP_F_TW && e->cap_rows <= 64 * JSLP_F_MAXG && e->precision >= 1e-15;
 }
 
-// Geometry of the register-resident kernel for this tableau: lanes x columns per lane must cover a row (ld), rows per
-// workgroup x 256 workgroups the height, and rows x columns per lane must fit the lane's registers.  0 = does not fit.
-//   1: <1024, 2, 8>   ld <= 2048, H <= 2048 (the headline shape)      2: <512, 4, 8>  (JSLP_RES_CPT=4, measured slower)
-//   3: <512, 4, 16>   ld <= 2048, H <= 4096                            4: <512, 6, 12> ld <= 3072, H <= 3072 (3001 x 3001: 72 MB)
-//   5: <512, 8, 8>    ld <= 4096, H <= 2048
-//   6: <512, 2, 32> XL ld <= 1024, H <= 1024, on the <= 32 workgroups of ONE XCD (round 4): the hand-offs of a pivot go through
-//      that XCD's L2 instead of memory.  Mid-size tableaus: Monster LP 625 x 553, Monster_II's root 945 x 925, 501 x 501 ...
-// (256-lane geometries -- ONE wave per SIMD, 512 registers per lane: <256, 8, 8> compiles without a spill -- were measured and
-//  dropped: 72.5 k against 105.7 k pivots/s on a 2001 x 2001 LP, 17.4 k on 4001 x 2001, r02_z: a lone wave per SIMD does not hide
-//  its own instruction latency)
-// Round 5: the XCD-local instances are compiled into the TEST library only (-DJSLP_CHAOS_BUILD implies -DJSLP_WITH_XL; a hipcc run with
-// -DJSLP_WITH_XL builds a product-like library with them): the default policy never picked the geometry (parity with the chip-wide kernel on
-// an eighth of the chip, profiles/r04_xl_times.md), and its two instances cost the shipped library 40 s of compile time and 320 spilled
-// SGPRs of dead weight.  The shipped library ignores JSLP_XL and refuses JSLP_FORCE_PATH=xl loudly (jslp_engine_create).
+// ---- the register-resident kernel: geometries, instances, policy -----------------------------------------------------------------------------
+#include "jslp_resident_table.hip.h"  // RES_GEOM (what each geometry number means) and resident_dispatch (key -> launch)
 static bool xl_fits(const jslp_engine* e, int H) {
-#ifndef JSLP_WITH_XL
-    (void)e; (void)H;
-    return false;
-#else
-    return (e->xl_on || e->force_xl) && e->n_unr == 0 && e->n_opt == 0 && e->ld <= 1024 && H <= JSLP_XL_MAXG * JSLP_R_MAXROWS && e->precision >= 1e-15 &&
-           !(getenv("JSLP_RES_LEAN") && atoi(getenv("JSLP_RES_LEAN")) == 0);
-#endif
+    return RES_WITH_XL && (e->xl_on || e->force_xl) && e->n_unr == 0 && e->n_opt == 0 && e->ld <= RES_GEOM[RES_GEOM_XL].max_ld && H <= JSLP_XL_MAXG * JSLP_R_MAXROWS &&
+           e->precision >= 1e-15 && res_lean_on();
 }
 // variable indexes that can be live in a tableau of height H: constraints and variables are numbered first, cut slacks continue from
 // lastElementIndex = width + height - 2 (tableau.ts:312-316) -- e->n_idx is the CAPACITY (every cut row the engine has room for)
 // (an uploaded tableau need not follow the reference's contiguous numbering -- Model index reuse / removal, a direct C-API caller --
 //  so the largest index upload() saw in the two maps counts too: the lean kernels' LDS copy of the "unrestricted" flags is indexed with it)
 static int live_index_bound(const jslp_engine* e, int H) { return std::min<int>(e->n_idx, std::max<int>(e->W + H + 2, e->max_uploaded_idx + 1)); }
-#if defined(JSLP_SPLIT_TU)
-extern "C" __attribute__((visibility("hidden"))) int jslpx_resident_launch_1(const int* key, unsigned grid, const void* rc, void* stream);
-extern "C" __attribute__((visibility("hidden"))) int jslpx_resident_launch_2(const int* key, unsigned grid, const void* rc, void* stream);
-#endif
+// The LEAN build takes this tableau: every one without unrestricted variables, optional objectives included (up to three rows of them in registers,
+// round 3: resident_geometry); with unrestricted variables (round 4: per-lane column masks, the flags of all variable indexes in LDS) when the live
+// indexes fit that LDS copy and there is no optional objective -- OPT && UNR is no instance: the fused pipeline takes those.
+// (for resident_geometry the n_opt == 0 term changes nothing -- it admits optional objectives only when there are no unrestricted variables, so
+//  with them n_unr == 0 has decided already; for the launch it is what keeps a key from naming an OPT && UNR instance)
+static bool lean_takes(const jslp_engine* e, int H) {
+    return res_lean_on() && (e->n_unr == 0 || (e->n_opt == 0 && live_index_bound(e, H) <= JSLP_R_LUNR));
+}
+static bool geometry_fits(const jslp_engine* e, int rpb, int g) { return e->ld <= RES_GEOM[g].max_ld && rpb <= RES_GEOM[g].rows; }
 static int resident_geometry(const jslp_engine* e, int H) {
     if (e->no_resident || e->force_path == 2 || e->precision < 1e-15) return 0;  // (see k_pivot_fused for the precision condition)
     const int rpb = (H + JSLP_F_MAXG - 1) / JSLP_F_MAXG;
+    const char* const gx = getenv("JSLP_RES_GEOM");
     // (JSLP_FORCE_PATH=resident keeps meaning the chip-wide geometries: the tests that force them at small sizes must keep covering them)
-    if (xl_fits(e, H) && !getenv("JSLP_RES_GEOM") && (e->force_xl || !e->force_resident)) return 6;
+    if (xl_fits(e, H) && !gx && (e->force_xl || !e->force_resident)) return RES_GEOM_XL;
+    const bool lean = lean_takes(e, H);
+    const bool wide_tall_off = res_wide_tall() == 0 && !e->force_resident;
     if (e->n_opt > 0) {
         // optional objectives: the lean build of the headline geometry keeps up to three rows of them in registers (round 3);
         // everything else (unrestricted variables, taller / wider tableaus, more rows) runs them through the fused pipeline
-        const bool lean_ok = !(getenv("JSLP_RES_LEAN") && atoi(getenv("JSLP_RES_LEAN")) == 0) && e->n_unr == 0;
-        if (!lean_ok || e->n_opt > 3) return 0;
-        if (e->ld <= 2048 && rpb <= 8) return 1;
+        if (!lean || e->n_opt > 3) return 0;
+        if (geometry_fits(e, rpb, 1)) return 1;
         // round 4: the tall geometry too (its lean phase 2 has the registers for three more rows per lane: 512 lanes x 4 columns);
         // the 6- and 8-column geometries do not (the objective rows would spill): the fused pipeline keeps those shapes
-        const char* wt = getenv("JSLP_RES_WIDE_TALL");
-        if (wt && atoi(wt) == 0 && !e->force_resident) return 0;
-        return (e->ld <= 2048 && rpb <= 16) ? 3 : 0;
+        return !wide_tall_off && geometry_fits(e, rpb, 3) ? 3 : 0;
     }
-    if (const char* gx = getenv("JSLP_RES_GEOM")) {  // experiments: force a geometry the tableau fits (lean build, no unrestricted variables)
-        static const int rows_of[6] = {0, 8, 8, 16, 12, 8}, ld_of[6] = {0, 2048, 2048, 2048, 3072, 4096};
+    if (gx) {  // experiments: force a geometry the tableau fits (lean build, no unrestricted variables)
         const int g = atoi(gx);
-        if (g >= 1 && g <= 5 && e->n_unr == 0 && e->ld <= ld_of[g] && rpb <= rows_of[g]) return g;
+        if (g >= 1 && g <= 5 && e->n_unr == 0 && geometry_fits(e, rpb, g)) return g;
     }
-    if (e->ld <= 2048 && rpb <= 8) return e->res_cpt == 4 ? 2 : 1;
+    if (geometry_fits(e, rpb, 1)) return e->res_cpt == 4 ? 2 : 1;
     // The taller / wider geometries hold 64-72 MB of tableau in the 128 MB of vector registers and spill ~0.5 KB per lane to
     // scratch (560+ scratch loads in the pivot loop): measured at the end of round 2 they LOSE to the streaming kernels --
     // 4001 x 2001: 22.3 k pivots/s against 36.4 k through k_pivot_fused; 2501 x 2001: 26.6 k against 48.8 k; 3001 x 3001: 21.5 k
@@ -832,18 +837,11 @@ static int resident_geometry(const jslp_engine* e, int H) {
     // streaming kernels 2-3x on these shapes (r03_j), so tableaus it can take -- no unrestricted variables -- get these geometries
     // by default for their phase 2 (phase 1 through the fused pipeline: run_simplex).  JSLP_RES_WIDE_TALL=0 switches that off, =1
     // also sends the general build's (unrestricted variables) there.
-    const char* wt_env = getenv("JSLP_RES_WIDE_TALL");  // (read per call: tests switch it inside one process)
-    const int wide_tall = wt_env ? atoi(wt_env) : -1;
-    const bool lean_env = !(getenv("JSLP_RES_LEAN") && atoi(getenv("JSLP_RES_LEAN")) == 0);
-    // (round 4: the lean build takes unrestricted variables too -- per-lane column masks, the flags of all variable indexes in LDS:
-    //  n_idx <= JSLP_R_LUNR; the tall / wide geometries have NO general build any more -- it spilled ~0.5 KB per lane and lost to the
-    //  streaming kernels -- so what the lean build cannot take goes to the fused pipeline)
-    const bool lean = lean_env && (e->n_unr == 0 || live_index_bound(e, H) <= JSLP_R_LUNR);
-    if (!lean) return 0;
-    if (!e->force_resident && wide_tall == 0) return 0;
-    if (e->ld <= 2048 && rpb <= 16) return 3;
-    if (e->ld <= 3072 && rpb <= 12) return 4;
-    if (e->ld <= 4096 && rpb <= 8) return 5;
+    // (round 4: the lean build takes unrestricted variables too -- lean_takes; the tall / wide geometries have NO general build any more -- it
+    //  spilled ~0.5 KB per lane and lost to the streaming kernels -- so what the lean build cannot take goes to the fused pipeline)
+    if (!lean || wide_tall_off) return 0;
+    for (int g = 3; g <= 5; g++)
+        if (geometry_fits(e, rpb, g)) return g;
     return 0;
 }
 static bool resident_eligible(const jslp_engine* e, int H) { return resident_geometry(e, H) != 0; }
@@ -928,14 +926,6 @@ static FusedCtx make_fused_ctx(const jslp_engine* e, const Ctx& c, int H) {
     }
     f.oo[0] = e->s.oo; f.oo[1] = e->f_oo1;
     return f;
-}
-static int fused_p1_on() {  // phase 1 of the large LPs through k_fused_p1 (one launch per pivot) instead of k_select + k_update
-    static int v = -1;
-    if (v < 0) {
-        const char* t = getenv("JSLP_FUSED_P1");  // tuning knob
-        v = t ? atoi(t) : 1;
-    }
-    return v;
 }
 
 static dim3 update_grid(const jslp_engine* e, int H) {
@@ -1027,451 +1017,437 @@ static void account(jslp_engine* e, const DevState& st, int is_relaxation) {
     e->wc.height_sum += st.H;
 }
 
-// simplex() of the live tableau (slot 0), leaving the final DevState in e->h_state
-static int run_simplex(jslp_engine* e, int check_cycles) {
+// ---- simplex() of the live tableau (slot 0) ------------------------------------------------------------------------------------------------
+// What one simplex() call fixes once (plan_solve); every phase below takes the engine and this.
+struct SolveRun {
+    Ctx c;                     // the streaming kernels' context; c.stop_at_phase2 = fused
+    int H = 0;                 // height: fixed during a simplex call, read once
+    int cap = 0;               // iteration cap (iters_cap)
+    int check_cycles = 0;
+    dim3 grid;                 // k_update's
+    int geometry = 0;          // of the register-resident kernel (RES_GEOM), 0: it does not take this tableau
+    bool lean = false;         // ... and its lean build does (lean_takes)
+    bool phase2_only = false;  // ... but only phase 2 of it (the tall / wide geometries: plan_solve)
+    bool fused = false;        // the fused one-launch-per-pivot pipeline applies (fused_eligible)
+    bool dbg = false;          // JSLP_DEBUG_LAUNCH: one parseable stderr line per launch decision (tests/test_grid_edges.py)
+};
+static int plan_solve(jslp_engine* e, int check_cycles, SolveRun* p) {
     hipStream_t s = e->stream;
-    e->slot0_synced = 0;  // the chip-wide kernels do not maintain the dirty-row flags (k_begin zeroes st.gen)
-    e->abort_injected = 0;
-    const int cap = iters_cap(e);
-    HIPC(hipEventRecord(e->ev_begin, s));
-    if (use_wg_single(e)) {
-        e->last_path = "workgroup";
-        if (const size_t lds = wglds_smem(e); lds && e->s.n_opt > 0)  // optional objectives: a build of their own (jslp_wglds.hip.h)
-            hipLaunchKernelGGL((k_simplex_lds<JSLP_WG_THREADS, true>), dim3(1), dim3(JSLP_WG_THREADS), lds, s, e->s, 0, check_cycles, cap, (int)e->cap_rows);
-        else if (lds)
-            hipLaunchKernelGGL((k_simplex_lds<JSLP_WG_THREADS>), dim3(1), dim3(JSLP_WG_THREADS), lds, s, e->s, 0, check_cycles, cap, (int)e->cap_rows);
-        else
-            hipLaunchKernelGGL((k_simplex_wg<JSLP_WG_THREADS, 4096>), dim3(1), dim3(JSLP_WG_THREADS), 0, s, e->s, 0, check_cycles, cap);
-        HIPC(hipGetLastError());
-        HIPC(hipMemcpyAsync(e->h_state, e->s.st, sizeof(DevState), hipMemcpyDeviceToHost, s));
-        HIPC(hipEventRecord(e->ev_end, s));
-        HIPC(hipStreamSynchronize(s));
-    } else {
-        Ctx c = host_ctx(e, check_cycles);
-        const bool fused = fused_eligible(e);
-        e->last_path = "select+update";
-        c.stop_at_phase2 = fused ? 1 : 0;
-        // height is fixed during a simplex call; read it once
-        HIPC(hipMemcpyAsync(e->h_state, e->s.st, sizeof(DevState), hipMemcpyDeviceToHost, s));
-        HIPC(hipStreamSynchronize(s));
-        const int H = e->h_state->H;
-        const dim3 grid = update_grid(e, H);
-        hipLaunchKernelGGL(k_begin, dim3(1), dim3(1), 0, s, e->s, 0, cap);
-        // ---- register-resident path: the WHOLE simplex (phase 1 and phase 2) in one cooperative launch -------------
-        bool resident_done = false;
-        bool handed_to_streaming = false;  // the lean kernel left mid-solve and the general build cannot continue (optional objectives)
-        const int geometry = resident_geometry(e, H);
-        // `it_before`: pivots the solve had done when the kernel is launched (0, or a phase 1 done by the fused pipeline)
-        auto run_resident = [&](long long it_before) -> int {
-            const bool lean_on = !(getenv("JSLP_RES_LEAN") && atoi(getenv("JSLP_RES_LEAN")) == 0);
-            const bool lean_unr_ok = e->n_unr == 0 || (live_index_bound(e, H) <= JSLP_R_LUNR && e->n_opt == 0);  // (the lean build's LDS copy of the "unrestricted" flags)
-            int r = ensure_resident(e, lean_on && lean_unr_ok && check_cycles != 0);
-            if (r) return r;
-            ResCtx rc;
-            rc.c = c;
-            for (int i = 0; i < 2; i++) {
-                rc.gran[i] = e->r_gran + (size_t)i * JSLP_F_MAXG * JSLP_R_GRAN;
-                rc.rowflag[i] = e->r_gran + (size_t)2 * JSLP_F_MAXG * JSLP_R_GRAN + (size_t)i * JSLP_F_MAXG;
-                rc.rows_pub[i] = e->r_rows[i];
-            }
-            rc.decision[0] = e->r_gran + (size_t)2 * JSLP_F_MAXG * (JSLP_R_GRAN + 1);
-            rc.decision[1] = rc.decision[0] + 8;
-            rc.verdict[0] = rc.decision[0] + 16;
-            rc.verdict[1] = rc.decision[0] + 24;
-            rc.gor[0] = rc.decision[0] + 32;
-            rc.gor[1] = rc.gor[0] + JSLP_F_MAXG;
-            rc.gran16 = e->r_gran + JSLP_R_SYNC_WORDS_GENERAL;  // [2][MAXG] granules, 64 bytes apart
-            rc.hist_all = e->r_hist_all;
-            for (int i = 0; i < 2; i++) rc.rowflagc[i] = e->r_gran + JSLP_R_SYNC_WORDS_GENERAL + 2 * JSLP_F_MAXG * 8 + (size_t)i * JSLP_R_FLAGCOPIES * JSLP_F_MAXG;
-            rc.abort_flag = e->r_sync + 4;
-            HIPC(hipMemsetAsync(e->r_gran, 0, sizeof(u64_t) * JSLP_R_SYNC_WORDS, s));  // tags restart at 1
-            rc.census = e->r_gran + JSLP_R_SYNC_WORDS - JSLP_F_MAXG;
-            rc.cdev = e->r_ctx_dev;
-            HIPC(hipMemcpyAsync(e->r_ctx_dev, &rc.c, sizeof(Ctx), hipMemcpyHostToDevice, s));  // (200 bytes; the kernel's one committing thread reads the map / trace pointers from it)
-            {   // the host-abort word (pinned, behind the state and the retry counter) and its address behind the device copy of the context
-                unsigned* const h_abort = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(e->h_state) + sizeof(DevState) + 16);
-                *h_abort = 0u;
-                e->h_abort_ptr = h_abort;
-                HIPC(hipMemcpyAsync(reinterpret_cast<char*>(e->r_ctx_dev) + sizeof(Ctx), &e->h_abort_ptr, sizeof(unsigned*), hipMemcpyHostToDevice, s));
-            }
-            rc.rpb = geometry == 6 ? (H + JSLP_XL_MAXG - 1) / JSLP_XL_MAXG : (H + JSLP_F_MAXG - 1) / JSLP_F_MAXG;
-            if (const char* rx = getenv("JSLP_RES_RPB"); rx && geometry != 6) {  // experiments: more rows per workgroup = fewer workgroups (<= the geometry's rows)
-                static const int rows_of[6] = {0, 8, 8, 16, 12, 8};
-                const int want = atoi(rx);
-                if (want > rc.rpb && want <= rows_of[geometry]) rc.rpb = want;
-            }
-            rc.G = (H + rc.rpb - 1) / rc.rpb;
-            rc.H = H;
-            rc.n_idx = live_index_bound(e, H);
-            rc.iters_cap = cap;
-            rc.spin_limit = e->spin_limit;
-            rc.test_abort_epoch = e->test_abort_epoch;
-            rc.test_late_wave0 = e->test_late_wave0;
-            rc.dbg = nullptr;
-#ifdef JSLP_DEBUG_RESIDENT
-            static u64_t* dbg_buf = nullptr;
-            if (!dbg_buf) HIPC(hipMalloc(&dbg_buf, sizeof(u64_t) * (512 * JSLP_F_MAXG * 2 + 16384)));
-            HIPC(hipMemsetAsync(dbg_buf, 0, sizeof(u64_t) * (512 * JSLP_F_MAXG * 2 + 16384), s));
-            rc.dbg = dbg_buf;
-#endif
-            HIPC(hipMemsetAsync(e->r_sync, 0, sizeof(unsigned) * 16, s));
-            if (geometry == 6) {
-                // the XCD-local build's rows carry their epoch tag INSIDE the data and every launch's tags restart at 1: what an earlier
-                // launch left in the row slots would pass for this launch's rows (found by the Knapsack fixture's fifth relaxation: same
-                // pivots, another RHS) -- the slots start from zero (tag 0 is never used)
-                for (int i = 0; i < 2; i++) HIPC(hipMemsetAsync(e->r_rows[i], 0, (size_t)rc.G * e->ld * 16, s));
-            }
-            // Safety net.  The kernel commits every pivot's index-map swap as it goes but writes the matrix back only in
-            // its epilogue, and a timed-out hand-off (workgroups not co-resident, a stalled GPU) skips that epilogue: keep a
-            // copy of slot 0 (one pass over the matrix, ~15 us at 2001 x 2001 against a ~100 ms solve) to roll back to.
-            SnapshotW bk{e->rb_A, e->rb_vibr, e->rb_vibc, e->rb_rbv, e->rb_cbv, e->n_idx, nullptr, nullptr};
-            hipLaunchKernelGGL(k_res_backup, dim3(copy_grid(e, 1).x), dim3(256), 0, s, e->s, bk, e->r_backup_st, H, 1);
-            hipEvent_t k0 = nullptr, k1 = nullptr;
-            if (e->timing) { r = ensure_events(e, 2); if (r) return r; k0 = e->ev_pool[0]; k1 = e->ev_pool[1]; HIPC(hipEventRecord(k0, s)); }
-            void* args[] = {&rc};
-            // lane geometry: 1024 lanes x 2 columns, or 512 lanes x 4 columns (half the waves per workgroup barrier)
-            // up to 8 rows per workgroup: 1024 lanes x 2 columns (or 512 x 4, measured slower); 9..16 rows (2048 < H <= 4096):
-            // 512 lanes x 4 columns x 16 rows -- 2 waves per SIMD leave 256 VGPRs per lane for the 64 MB of tableau
-            hipError_t le = hipErrorInvalidValue;
-            const bool unr = e->n_unr > 0;  // unrestricted variables: the UNR build threads the per-column flags through
-            // The LEAN build (all-gather protocol only, software-pipelined phase 2: jslp_resident_pipe.hip.h) takes every solve
-            // without unrestricted variables; should its cycle-check history outgrow LDS it hands the solve over (status
-            // ST_RUNNING / ST_PHASE1_DONE instead of ST_DONE) and the general build continues it in a second launch.
-            bool lean = lean_on && lean_unr_ok;
-#define JSLP_RES_LAUNCH_LEAN(T, C, R)                                                                                               \
-    (unr ? (check_cycles ? hipLaunchCooperativeKernel((const void*)k_simplex_resident<T, C, R, true, true, false, true>, dim3(rc.G), dim3(T), args, 0, s)   \
-                         : hipLaunchCooperativeKernel((const void*)k_simplex_resident<T, C, R, true, true, false, false>, dim3(rc.G), dim3(T), args, 0, s)) \
-         : (check_cycles ? hipLaunchCooperativeKernel((const void*)k_simplex_resident<T, C, R, false, true, false, true>, dim3(rc.G), dim3(T), args, 0, s)  \
-                         : hipLaunchCooperativeKernel((const void*)k_simplex_resident<T, C, R, false, true, false, false>, dim3(rc.G), dim3(T), args, 0, s)))
-// (headline geometries: lean, else the general build)
-#define JSLP_RES_LAUNCH(T, C, R)                                                                                                    \
-    le = lean ? JSLP_RES_LAUNCH_LEAN(T, C, R)                                                                                       \
-       : unr  ? hipLaunchCooperativeKernel((const void*)k_simplex_resident<T, C, R, true>, dim3(rc.G), dim3(T), args, 0, s)        \
-              : hipLaunchCooperativeKernel((const void*)k_simplex_resident<T, C, R, false>, dim3(rc.G), dim3(T), args, 0, s)
-// (tall / wide geometries: lean only -- a hand-over the lean build cannot continue goes to the streaming kernels)
-#define JSLP_RES_LAUNCH_LEAN_ONLY(T, C, R)                                                                                          \
-    do { if (lean) le = JSLP_RES_LAUNCH_LEAN(T, C, R); } while (0)
-          resident_relaunch:
-#if defined(JSLP_SPLIT_TU)  /* the product build: the instances live in jslp_tu_resident.hip (two parts, compiled side by side with this unit) */
-            {
-                static const int geo[7][3] = {{0, 0, 0}, {1024, 2, 8}, {512, 4, 8}, {512, 4, 16}, {512, 6, 12}, {512, 8, 8}, {512, 2, 32}};
-                const int key[8] = {geo[geometry][0], geo[geometry][1], geo[geometry][2], unr ? 1 : 0, lean ? 1 : 0, e->n_opt > 0 ? 1 : 0, check_cycles ? 1 : 0, geometry == 6 ? 1 : 0};
-                int r1 = jslpx_resident_launch_1(key, (unsigned)rc.G, &rc, s);
-                if (r1 == -1) r1 = jslpx_resident_launch_2(key, (unsigned)rc.G, &rc, s);
-                le = r1 == -1 ? hipErrorInvalidValue : (hipError_t)r1;  // (-1: no such instance -- what the switch below leaves `le` at)
-            }
-#elif defined(JSLP_DEV_HEADLINE_ONLY)  /* development builds: only the headline lean instances are compiled; never shipped */
-            if (geometry != 1 || !lean || e->n_opt > 0) return fail(JSLP_ERR_UNSUPPORTED, "development build: headline lean geometry only");
-            le = check_cycles ? hipLaunchCooperativeKernel((const void*)k_simplex_resident<1024, 2, 8, false, true, false, true>, dim3(rc.G), dim3(1024), args, 0, s)
-                              : hipLaunchCooperativeKernel((const void*)k_simplex_resident<1024, 2, 8, false, true, false, false>, dim3(rc.G), dim3(1024), args, 0, s);
-#elif defined(JSLP_DEV_TALL_ONLY)  /* development builds: only the tall lean instances <512, 4, 16> (register budget work; -DJSLP_DEV_TALL_ONLY=2: the OPT ones); never shipped */
-            if (geometry != 3 || !lean || (e->n_opt > 0) != (JSLP_DEV_TALL_ONLY == 2) || unr) return fail(JSLP_ERR_UNSUPPORTED, "development build: tall lean geometry only");
-            le = check_cycles ? hipLaunchCooperativeKernel((const void*)k_simplex_resident<512, 4, 16, false, true, JSLP_DEV_TALL_ONLY == 2, true>, dim3(rc.G), dim3(512), args, 0, s)
-                              : hipLaunchCooperativeKernel((const void*)k_simplex_resident<512, 4, 16, false, true, JSLP_DEV_TALL_ONLY == 2, false>, dim3(rc.G), dim3(512), args, 0, s);
-#elif defined(JSLP_DEV_XL_ONLY)  /* development builds: only the XCD-local instances are compiled (40 s instead of 2.5 min); never shipped */
-            if (geometry != 6) return fail(JSLP_ERR_UNSUPPORTED, "development build: XCD-local geometry only");
-            le = check_cycles ? hipLaunchCooperativeKernel((const void*)k_simplex_resident<512, 2, 32, false, true, false, true, true>, dim3(JSLP_XL_SPREAD * rc.G), dim3(512), args, 0, s)
-                              : hipLaunchCooperativeKernel((const void*)k_simplex_resident<512, 2, 32, false, true, false, false, true>, dim3(JSLP_XL_SPREAD * rc.G), dim3(512), args, 0, s);
-#else
-            switch (geometry) {
-                case 1:
-                    if (e->n_opt > 0) {  // (resident_geometry admits optional objectives only here, and only for the lean build)
-                        if (!lean) break;  // a hand-over the general build cannot take: the fused pipeline continues (below)
-                        le = check_cycles ? hipLaunchCooperativeKernel((const void*)k_simplex_resident<1024, 2, 8, false, true, true, true>, dim3(rc.G), dim3(1024), args, 0, s)
-                                          : hipLaunchCooperativeKernel((const void*)k_simplex_resident<1024, 2, 8, false, true, true, false>, dim3(rc.G), dim3(1024), args, 0, s);
-                        break;
-                    }
-                    JSLP_RES_LAUNCH(1024, 2, 8);
-                    break;
-                case 2: JSLP_RES_LAUNCH(512, 4, 8); break;
-                case 3:
-                    if (e->n_opt > 0) {  // (lean build with the optional objective rows in registers; phase 1 came through the fused pipeline)
-                        if (lean) le = check_cycles ? hipLaunchCooperativeKernel((const void*)k_simplex_resident<512, 4, 16, false, true, true, true>, dim3(rc.G), dim3(512), args, 0, s)
-                                                    : hipLaunchCooperativeKernel((const void*)k_simplex_resident<512, 4, 16, false, true, true, false>, dim3(rc.G), dim3(512), args, 0, s);
-                        break;
-                    }
-                    JSLP_RES_LAUNCH_LEAN_ONLY(512, 4, 16);
-                    break;
-                case 4: JSLP_RES_LAUNCH_LEAN_ONLY(512, 6, 12); break;
-                case 5: JSLP_RES_LAUNCH_LEAN_ONLY(512, 8, 8); break;
-#ifdef JSLP_WITH_XL
-                case 6:  // XCD-local: every JSLP_XL_SPREAD-th block of the grid works (all of them on one XCD), the others return at once
-                    if (!lean) break;  // (a hand-over the general build cannot take at this geometry: the streaming kernels continue)
-                    le = check_cycles ? hipLaunchCooperativeKernel((const void*)k_simplex_resident<512, 2, 32, false, true, false, true, true>, dim3(JSLP_XL_SPREAD * rc.G), dim3(512), args, 0, s)
-                                      : hipLaunchCooperativeKernel((const void*)k_simplex_resident<512, 2, 32, false, true, false, false, true>, dim3(JSLP_XL_SPREAD * rc.G), dim3(512), args, 0, s);
-                    break;
-#endif
-            }
-#endif
-#undef JSLP_RES_LAUNCH
-#undef JSLP_RES_LAUNCH_LEAN
-#undef JSLP_RES_LAUNCH_LEAN_ONLY
-            if (le == hipSuccess) e->resident_launches += 1;
-            if (le == hipSuccess && getenv("JSLP_DEBUG_LAUNCH")) {  // which instance ran, one parseable line per accepted launch (tests/test_grid_edges.py)
-                // (the instance's template key: the general build is compiled with CHK = true and reads check_cycles at run time)
-                static const int geo_of[7][3] = {{0, 0, 0}, {1024, 2, 8}, {512, 4, 8}, {512, 4, 16}, {512, 6, 12}, {512, 8, 8}, {512, 2, 32}};
-                fprintf(stderr, "[jslp] launch k_simplex_resident<%d,%d,%d> unr %d lean %d opt %d chk %d xl %d G %d rpb %d\n", geo_of[geometry][0], geo_of[geometry][1],
-                        geo_of[geometry][2], (int)unr, (int)lean, (int)(e->n_opt > 0), (int)(check_cycles != 0 || !lean), (int)(geometry == 6), rc.G, rc.rpb);
-            }
-            if (le == hipSuccess && lean) {
-                // JSLP_INJECT_RESIDENT_ABORT_US=<n>: raise the host-abort word n microseconds into the launch -- the rollback path (kernel gives
-                // up mid-solve, slot 0 restored from the safety-net copy, the solve re-run through the streaming kernels) exercised on the
-                // library users load, whose kernels have no test hooks.  Read per launch (tests set it inside one process); once per solve.
-                // (parsed strictly -- a stray or garbage value no longer aborts every resident solve -- and announced once)
-                const char* inj = getenv("JSLP_INJECT_RESIDENT_ABORT_US");
-                if (inj && *inj && !e->abort_injected) {
-                    char* endp = nullptr;
-                    const long us = strtol(inj, &endp, 10);
-                    if (endp != inj && *endp == 0 && us >= 0 && us <= 10000000L) {
-                        static std::atomic<int> told{0};
-                        if (!told.exchange(1)) fprintf(stderr, "[jslp] JSLP_INJECT_RESIDENT_ABORT_US=%ld: every register-resident solve is aborted %ld us after its launch and re-run through the streaming kernels (fault injection)\n", us, us);
-                        e->abort_injected = 1;
-                        std::this_thread::sleep_for(std::chrono::microseconds(us));
-                        __atomic_store_n(e->h_abort_ptr, 1u, __ATOMIC_RELEASE);
-                    }
-                }
-            }
-            if (le == hipSuccess && lean) {  // did the lean kernel finish the solve?
-                unsigned* const h_retries = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(e->h_state) + sizeof(DevState) + 8);
-                HIPC(hipMemcpyAsync(e->h_state, e->s.st, sizeof(DevState), hipMemcpyDeviceToHost, s));
-                HIPC(hipMemcpyAsync(h_retries, e->r_sync + 5, sizeof(unsigned), hipMemcpyDeviceToHost, s));  // repeated looks of the checksummed row hand-over
-                HIPC(hipStreamSynchronize(s));
-                e->resident_fetch_retries += *h_retries;
-                if (e->h_state->err == ERR_NONE && e->h_state->status != ST_DONE) {
-                    e->resident_handovers += 1;
-                    if (e->n_opt > 0 || geometry >= 3) {
-                        // (XCD-local and tall / wide geometries: there is no general build of them)
-                        // optional objectives: the general build does not take them -- the streaming kernels continue from the state the
-                        // lean kernel left (tableau, maps and objective rows written back; status ST_RUNNING or ST_PHASE1_DONE)
-                        handed_to_streaming = true;
-                        if (e->timing) { float ms = 0; HIPC(hipEventRecord(k1, s)); HIPC(hipEventSynchronize(k1)); if (hipEventElapsedTime(&ms, k0, k1) == hipSuccess) e->upd_ms += ms; e->upd_launches += e->h_state->it1 + e->h_state->it2 - it_before; }
-                        return JSLP_OK;
-                    }
-                    lean = false;
-                    HIPC(hipMemsetAsync(e->r_gran, 0, sizeof(u64_t) * JSLP_R_SYNC_WORDS, s));  // the second launch's tags restart at 1
-                    goto resident_relaunch;
-                }
-            }
-            if (le == hipSuccess) {
-                if (e->timing) HIPC(hipEventRecord(k1, s));
-                HIPC(hipMemcpyAsync(e->h_state, e->s.st, sizeof(DevState), hipMemcpyDeviceToHost, s));
-                HIPC(hipStreamSynchronize(s));
-                if (e->timing) {
-                    float ms = 0;
-                    if (hipEventElapsedTime(&ms, k0, k1) == hipSuccess) e->upd_ms += ms;
-                    e->upd_launches += e->h_state->it1 + e->h_state->it2 - it_before;  // unit = one pivot (16*H*W algorithmic bytes)
-                }
-                if (e->h_state->err == ERR_BARRIER) {
-                    // roll slot 0 back to its state before the launch and solve through the streaming kernels instead
-                    hipLaunchKernelGGL(k_res_backup, dim3(copy_grid(e, 1).x), dim3(256), 0, s, e->s, bk, e->r_backup_st, H, 0);
-                    HIPC(hipGetLastError());
-                    // ... and the host's copy of the state with it: the streaming loops below start from what h_state says (the tall /
-                    // wide geometries come here with ST_PHASE1_DONE: without this the aborted kernel's ST_DONE + ERR_BARRIER ended the
-                    // solve as a device error instead of finishing it through k_pivot_fused)
-                    HIPC(hipMemcpyAsync(e->h_state, e->s.st, sizeof(DevState), hipMemcpyDeviceToHost, s));
-                    HIPC(hipStreamSynchronize(s));
-                    e->resident_fallbacks += 1;
-                } else {
-                resident_done = true;
-                e->last_path = geometry == 6 ? "resident-xl" : "resident";
-                if (e->counting) {  // a dense streaming update touches every cell: rows x columns per pivot
-                    const long long piv = (long long)e->h_state->it1 + e->h_state->it2;
-                    e->wc.gated_cells += piv * (long long)(H - 1) * e->W;
-                    e->wc.gated_rows += piv * (long long)(H - 1);
-                }
-#ifdef JSLP_DEBUG_RESIDENT
-                {   // phase timing + micro-costs of the debug build (tools/resident_phase_timing.py reads this file)
-                    std::vector<u64_t> d(16384);
-                    HIPC(hipMemcpy(d.data(), rc.dbg + (size_t)512 * rc.G * 2, sizeof(u64_t) * 16384, hipMemcpyDeviceToHost));
-                    FILE* fb = fopen("gpurun_out/resident_r0.bin", "wb");
-                    if (fb) { fwrite(d.data(), 8, 16384, fb); fclose(fb); }
-                    HIPC(hipMemcpy(d.data(), rc.dbg, sizeof(u64_t) * 16384, hipMemcpyDeviceToHost));  // RT_STAMP: [8 epochs][MAXG][8 events]
-                    fb = fopen("gpurun_out/resident_stamps.bin", "wb");
-                    if (fb) { fwrite(d.data(), 8, 16384, fb); fclose(fb); }
-                }
-#endif
-                }  // !ERR_BARRIER
-            } else {
-                (void)hipGetLastError();  // not co-resident on this device: use one launch per pivot instead
-                e->resident_refusals += 1;
-                if (getenv("JSLP_DEBUG_LAUNCH"))
-                    fprintf(stderr, "[jslp] cooperative launch of k_simplex_resident refused (geometry %d, lean %d, unr %d, G %d): %s\n", geometry, (int)lean,
-                            (int)(e->n_unr > 0), rc.G, hipGetErrorString(le));
-            }
-            return JSLP_OK;
-        };
-        // The headline geometries run the WHOLE solve register-resident (phase 1 included).  The tall / wide ones (H > 2048 or more
-        // than 2048 columns) take only phase 2 there -- their phase-1 loop does not fit the 256 registers a lane has next to 64-72 MB
-        // of tableau (it spills: 22 k pivots/s against 33.7 k through k_fused_p1 on 4001 x 2001) while the lean kernel's pipelined
-        // phase 2 does (4 scratch loads per pivot): phase 1 goes through the fused pipeline first, which hands over with
-        // ST_PHASE1_DONE.  r03_j: 4001 x 2001 113.4 k pivots/s against 35.7 k fused, 2501 x 2001 128.6 k against 48.5 k,
-        // 2001 x 4001 75.5 k against 34.8 k.
-        const bool resident_phase2_only = geometry >= 3 && geometry != 6;  // (6 = XCD-local: the whole solve, like the headline geometry)
-        if (geometry != 0 && !resident_phase2_only) {
-            int r = run_resident(0);
-            if (r) return r;
-        }
-        if (!resident_done) {
-        // ---- phase 1 through the fused pipeline (one launch per pivot; k_fused_p1), when the fused pipeline applies -----------
-        bool p1_fused = false;
-        const bool phase1_over = handed_to_streaming && e->h_state->status == ST_PHASE1_DONE;  // (h_state is current in that case only)
-        if (phase1_over) p1_fused = true;
-        if (!phase1_over && fused && fused_p1_on()) {
-            int r = ensure_fused(e);
-            if (r) return r;
-            r = ensure_fused_oo(e);
-            if (r) return r;
-            const FusedCtx f = make_fused_ctx(e, c, H);
-            void (*kp1)(FusedCtx, int) = e->ld <= JSLP_F_TW ? (e->n_unr > 0 ? k_fused_p1<1, true> : k_fused_p1<1, false>)
-                                         : e->ld <= 2 * JSLP_F_TW ? (e->n_unr > 0 ? k_fused_p1<2, true> : k_fused_p1<2, false>)
-                                         : e->ld <= 3 * JSLP_F_TW ? k_fused_p1<3, false> : k_fused_p1<4, false>;  // (fused_eligible: no unrestricted variables beyond two tiles)
-            if (getenv("JSLP_DEBUG_LAUNCH"))
-                fprintf(stderr, "[jslp] launch k_fused_p1<%d,%d>\n", (e->ld + JSLP_F_TW - 1) / JSLP_F_TW, (int)(e->ld <= 2 * JSLP_F_TW && e->n_unr > 0));
-            for (;;) {
-                int launch = 0;
-                hipLaunchKernelGGL(kp1, dim3(f.G), dim3(JSLP_F_THREADS), 0, s, f, launch);
-                launch++;
-                int chunk1 = 2;
-                for (;;) {
-                    for (int i = 0; i < chunk1; i++) { hipLaunchKernelGGL(kp1, dim3(f.G), dim3(JSLP_F_THREADS), 0, s, f, launch); launch++; }
-                    HIPC(hipGetLastError());
-                    HIPC(hipMemcpyAsync(e->h_state, f.fst[launch & 1], sizeof(DevState), hipMemcpyDeviceToHost, s));
-                    HIPC(hipStreamSynchronize(s));
-                    if (e->h_state->status != ST_RUNNING) break;
-                    chunk1 = std::min(chunk1 * 2, 512);
-                }
-                hipLaunchKernelGGL(k_fused_finish, dim3(512), dim3(256), 0, s, f, launch - 1);  // state -> slot 0's, tableau -> buf[0]
-                HIPC(hipGetLastError());
-                if (e->h_state->status != ST_P1_SLOW) break;
-                // the one pivot k_fused_p1 cannot decide alone (see there): k_select + k_update, then the pipeline again
-                hipLaunchKernelGGL(k_p1_resume, dim3(1), dim3(1), 0, s, e->s.st, (int)ST_RUNNING);
-                hipLaunchKernelGGL(k_select, dim3(1), dim3(JSLP_WG_THREADS), 0, s, c);
-                hipLaunchKernelGGL(k_update, grid, dim3(JSLP_UPD_THREADS), 0, s, c);
-                HIPC(hipGetLastError());
-                HIPC(hipMemcpyAsync(e->h_state, e->s.st, sizeof(DevState), hipMemcpyDeviceToHost, s));
-                HIPC(hipStreamSynchronize(s));
-                e->p1_slow_pivots += 1;
-                if (e->h_state->status != ST_RUNNING) break;
-            }
-            p1_fused = true;
-            e->last_path = "fused";
-        }
-        // ---- phase 1 (and phase 2 when the fused pipeline does not apply): k_select + k_update per pivot ----
-        int chunk = fused ? 1 : 8;
-        long long done_prev = 0;
-        if (!p1_fused && getenv("JSLP_DEBUG_LAUNCH")) fprintf(stderr, "[jslp] launch select+update\n");
-        for (; !p1_fused;) {
-            if (e->timing && !fused) { int r = ensure_events(e, 2 * (size_t)chunk); if (r) return r; }
-            for (int i = 0; i < chunk; i++) {
-                hipLaunchKernelGGL(k_select, dim3(1), dim3(JSLP_WG_THREADS), 0, s, c);
-                if (e->timing && !fused) HIPC(hipEventRecord(e->ev_pool[2 * i], s));
-                hipLaunchKernelGGL(k_update, grid, dim3(JSLP_UPD_THREADS), 0, s, c);
-                if (e->timing && !fused) HIPC(hipEventRecord(e->ev_pool[2 * i + 1], s));
-            }
-            HIPC(hipGetLastError());
-            HIPC(hipMemcpyAsync(e->h_state, e->s.st, sizeof(DevState), hipMemcpyDeviceToHost, s));
-            HIPC(hipStreamSynchronize(s));
-            const DevState& st = *e->h_state;
-            if (e->timing && !fused) {
-                // launches after the solve ended are no-ops: only the first `real` of this chunk did a pivot
-                const long long done = (long long)st.it1 + st.it2;
-                const long long real = std::min<long long>(chunk, done - done_prev);
-                for (long long i = 0; i < real; i++) {
-                    float ms = 0;
-                    if (hipEventElapsedTime(&ms, e->ev_pool[2 * i], e->ev_pool[2 * i + 1]) == hipSuccess) e->upd_ms += ms;
-                }
-                e->upd_launches += real;
-                done_prev = done;
-            }
-            if (st.status != ST_RUNNING) break;
-            chunk = std::min(chunk * 2, 256);
-        }
-        // ---- phase 2 of the tall / wide geometries: register-resident (see above) ------------------------------
-        if (resident_phase2_only && e->h_state->status == ST_PHASE1_DONE && e->h_state->err == ERR_NONE) {
-            int r = run_resident((long long)e->h_state->it1 + e->h_state->it2);
-            if (r) return r;
-        }
-        // ---- phase 2: one fused launch per pivot ----------------------------------------------------------
-        while (!resident_done && e->h_state->status == ST_PHASE1_DONE) {
-            int r = ensure_fused(e);
-            if (r) return r;
-            r = ensure_fused_oo(e);
-            if (r) return r;
-            e->last_path = "fused";
-            const FusedCtx f = make_fused_ctx(e, c, H);
-            // column tiles per lane (ld <= 2048: one) x unrestricted variables present x optional objectives present
-            const bool unr = e->n_unr > 0, opt = e->n_opt > 0;
-            void (*kfused)(FusedCtx, int) =
-                e->ld <= JSLP_F_TW ? (unr ? (opt ? k_pivot_fused<1, true, true> : k_pivot_fused<1, true, false>)
-                                          : (opt ? k_pivot_fused<1, false, true> : k_pivot_fused<1, false, false>))
-                : e->ld <= 2 * JSLP_F_TW ? (unr ? (opt ? k_pivot_fused<2, true, true> : k_pivot_fused<2, true, false>)
-                                                : (opt ? k_pivot_fused<2, false, true> : k_pivot_fused<2, false, false>))
-                : e->ld <= 3 * JSLP_F_TW ? k_pivot_fused<3, false, false> : k_pivot_fused<4, false, false>;  // (fused_eligible: plain tableaus only beyond two tiles)
-            if (getenv("JSLP_DEBUG_LAUNCH")) {
-                const bool small = e->ld <= 2 * JSLP_F_TW;
-                fprintf(stderr, "[jslp] launch k_pivot_fused<%d,%d,%d>\n", (e->ld + JSLP_F_TW - 1) / JSLP_F_TW, (int)(small && unr), (int)(small && opt));
-            }
-            int launch = 0;
-            hipLaunchKernelGGL(kfused, dim3(f.G), dim3(JSLP_F_THREADS), 0, s, f, launch);
-            launch++;
-            chunk = 16;
-            long long it2_prev = e->h_state->it2;
-            for (;;) {
-                if (e->timing) { int r2 = ensure_events(e, 2 * (size_t)chunk); if (r2) return r2; }
-                for (int i = 0; i < chunk; i++) {
-                    if (e->timing) HIPC(hipEventRecord(e->ev_pool[2 * i], s));
-                    hipLaunchKernelGGL(kfused, dim3(f.G), dim3(JSLP_F_THREADS), 0, s, f, launch);
-                    if (e->timing) HIPC(hipEventRecord(e->ev_pool[2 * i + 1], s));
-                    launch++;
-                }
-                HIPC(hipGetLastError());
-                HIPC(hipMemcpyAsync(e->h_state, f.fst[launch & 1], sizeof(DevState), hipMemcpyDeviceToHost, s));
-                HIPC(hipStreamSynchronize(s));
-                const DevState& st = *e->h_state;
-                if (e->timing) {
-                    const long long real = std::min<long long>(chunk, (long long)st.it2 - it2_prev);
-                    for (long long i = 0; i < real; i++) {
-                        float ms = 0;
-                        if (hipEventElapsedTime(&ms, e->ev_pool[2 * i], e->ev_pool[2 * i + 1]) == hipSuccess) e->upd_ms += ms;
-                    }
-                    e->upd_launches += real;
-                    it2_prev = st.it2;
-                }
-                if (st.status != ST_RUNNING) break;
-                chunk = std::min(chunk * 2, 512);
-            }
-            hipLaunchKernelGGL(k_fused_finish, dim3(512), dim3(256), 0, s, f, launch - 1);
-            HIPC(hipGetLastError());
-            if (e->h_state->status == ST_P1_SLOW) {
-                // an entering column named by an optional objective with a ~0 main cost and a tiny pivot-row entry: that ONE pivot
-                // through k_select + k_update (see k_pivot_fused), then the pipeline again from its first launch
-                hipLaunchKernelGGL(k_p1_resume, dim3(1), dim3(1), 0, s, e->s.st, (int)ST_RUNNING);
-                hipLaunchKernelGGL(k_select, dim3(1), dim3(JSLP_WG_THREADS), 0, s, c);
-                hipLaunchKernelGGL(k_update, grid, dim3(JSLP_UPD_THREADS), 0, s, c);
-                HIPC(hipGetLastError());
-                HIPC(hipMemcpyAsync(e->h_state, e->s.st, sizeof(DevState), hipMemcpyDeviceToHost, s));
-                HIPC(hipStreamSynchronize(s));
-                e->p1_slow_pivots += 1;
-                if (e->h_state->status != ST_RUNNING) break;  // that pivot ended the solve
-                hipLaunchKernelGGL(k_p1_resume, dim3(1), dim3(1), 0, s, e->s.st, (int)ST_PHASE1_DONE);
-                e->h_state->status = ST_PHASE1_DONE;
-                continue;
-            }
-            HIPC(hipMemcpyAsync(e->h_state, e->s.st, sizeof(DevState), hipMemcpyDeviceToHost, s));
-            if (e->counting) {  // the fused launches stream every cell (phase 1 went through k_select: counted on the device)
-                e->wc.gated_cells += (long long)e->h_state->it2 * (long long)(H - 1) * e->W;
-                e->wc.gated_rows += (long long)e->h_state->it2 * (long long)(H - 1);
-            }
-            HIPC(hipStreamSynchronize(s));
-            break;
-        }
-        }  // !resident_done
-        HIPC(hipEventRecord(e->ev_end, s));
-        HIPC(hipStreamSynchronize(s));
+    p->check_cycles = check_cycles;
+    p->cap = iters_cap(e);
+    p->c = host_ctx(e, check_cycles);
+    p->fused = fused_eligible(e);
+    p->c.stop_at_phase2 = p->fused ? 1 : 0;
+    p->dbg = debug_launch_on();
+    e->last_path = "select+update";
+    // height is fixed during a simplex call; read it once
+    HIPC(hipMemcpyAsync(e->h_state, e->s.st, sizeof(DevState), hipMemcpyDeviceToHost, s));
+    HIPC(hipStreamSynchronize(s));
+    p->H = e->h_state->H;
+    p->grid = update_grid(e, p->H);
+    p->geometry = resident_geometry(e, p->H);
+    p->lean = lean_takes(e, p->H);
+    // The headline geometries run the WHOLE solve register-resident (phase 1 included).  The tall / wide ones (H > 2048 or more
+    // than 2048 columns) take only phase 2 there -- their phase-1 loop does not fit the 256 registers a lane has next to 64-72 MB
+    // of tableau (it spills: 22 k pivots/s against 33.7 k through k_fused_p1 on 4001 x 2001) while the lean kernel's pipelined
+    // phase 2 does (4 scratch loads per pivot): phase 1 goes through the fused pipeline first, which hands over with
+    // ST_PHASE1_DONE.  r03_j: 4001 x 2001 113.4 k pivots/s against 35.7 k fused, 2501 x 2001 128.6 k against 48.5 k,
+    // 2001 x 4001 75.5 k against 34.8 k.
+    p->phase2_only = p->geometry >= 3 && p->geometry != RES_GEOM_XL;  // (XCD-local: the whole solve, like the headline geometry)
+    return JSLP_OK;
+}
+static int fetch_state(jslp_engine* e, const DevState* from) {  // the host's copy of a device state, waited for
+    HIPC(hipMemcpyAsync(e->h_state, from, sizeof(DevState), hipMemcpyDeviceToHost, e->stream));
+    HIPC(hipStreamSynchronize(e->stream));
+    return JSLP_OK;
+}
+
+// ---- register-resident path: the WHOLE simplex (phase 1 and phase 2) in one cooperative launch -----------------------------------------------
+enum class Resident {
+    NotTried,
+    Done,        // the kernel finished the solve: e->h_state is final
+    Streaming,   // the lean kernel left mid-solve and no general build can continue: the streaming kernels go on from the state it wrote back
+    RolledBack,  // a hand-off timed out (or the host asked): slot 0 and e->h_state are what they were before the launch
+    Refused,     // the runtime refused the cooperative launch, or no such instance exists: nothing ran
+};
+// Word offsets of the hand-off areas in e->r_gran.  They mirror, term by term, the sums JSLP_R_SYNC_WORDS_GENERAL and JSLP_R_SYNC_WORDS are
+// written as (jslp_resident.hip.h): [2][G][8] granules | [2][G] row flags | 32 words of decision / verdict | [2][G] chip-wide OR flags || the lean kernel's
+// [2][G] summary granules, 64 bytes apart | [2][copies][G] row-flag copies | the row records | the XCD-local build's placement census
+enum : size_t {
+    R_OFF_GRAN = 0,
+    R_OFF_ROWFLAG = R_OFF_GRAN + 2 * JSLP_F_MAXG * JSLP_R_GRAN,
+    R_OFF_DECISION = R_OFF_ROWFLAG + 2 * JSLP_F_MAXG,  // decision[0], decision[1], verdict[0], verdict[1]: 8 words each
+    R_OFF_GOR = R_OFF_DECISION + 32,
+    R_OFF_GRAN16 = R_OFF_GOR + 2 * JSLP_F_MAXG,
+    R_OFF_ROWFLAGC = R_OFF_GRAN16 + 2 * JSLP_F_MAXG * 8,
+    R_OFF_REC = R_OFF_ROWFLAGC + 2 * JSLP_R_FLAGCOPIES * JSLP_F_MAXG,
+    R_OFF_CENSUS = R_OFF_REC + JSLP_R_REC_WORDS,
+    R_OFF_END = R_OFF_CENSUS + JSLP_F_MAXG,
+};
+static_assert(R_OFF_GRAN16 == JSLP_R_SYNC_WORDS_GENERAL && R_OFF_END == JSLP_R_SYNC_WORDS, "the offsets add up to the sizes the kernels' header states");
+static_assert((R_OFF_REC - R_OFF_GRAN16) * 8 == JSLP_R_REC_OFF, "the kernels reach the row records from gran16");
+// the kernel's argument, carved out of the hand-off words (ensure_resident first: it may move them)
+static ResCtx make_res_ctx(const jslp_engine* e, const SolveRun& p) {
+    ResCtx rc;
+    rc.c = p.c;
+    for (int i = 0; i < 2; i++) {
+        rc.gran[i] = e->r_gran + R_OFF_GRAN + (size_t)i * JSLP_F_MAXG * JSLP_R_GRAN;
+        rc.rowflag[i] = e->r_gran + R_OFF_ROWFLAG + (size_t)i * JSLP_F_MAXG;
+        rc.rows_pub[i] = e->r_rows[i];
+        rc.decision[i] = e->r_gran + R_OFF_DECISION + (size_t)i * 8;
+        rc.verdict[i] = e->r_gran + R_OFF_DECISION + 16 + (size_t)i * 8;
+        rc.gor[i] = e->r_gran + R_OFF_GOR + (size_t)i * JSLP_F_MAXG;
+        rc.rowflagc[i] = e->r_gran + R_OFF_ROWFLAGC + (size_t)i * JSLP_R_FLAGCOPIES * JSLP_F_MAXG;
     }
+    rc.gran16 = e->r_gran + R_OFF_GRAN16;  // [2][MAXG] granules, 64 bytes apart
+    rc.census = e->r_gran + R_OFF_CENSUS;
+    rc.hist_all = e->r_hist_all;
+    rc.abort_flag = e->r_sync + 4;
+    rc.cdev = e->r_ctx_dev;
+    const int maxg = p.geometry == RES_GEOM_XL ? JSLP_XL_MAXG : JSLP_F_MAXG;
+    rc.rpb = (p.H + maxg - 1) / maxg;
+    if (const char* rx = getenv("JSLP_RES_RPB"); rx && p.geometry != RES_GEOM_XL) {  // experiments: more rows per workgroup = fewer workgroups (<= the geometry's rows)
+        const int want = atoi(rx);
+        if (want > rc.rpb && want <= RES_GEOM[p.geometry].rows) rc.rpb = want;
+    }
+    rc.G = (p.H + rc.rpb - 1) / rc.rpb;
+    rc.H = p.H;
+    rc.n_idx = live_index_bound(e, p.H);
+    rc.iters_cap = p.cap;
+    rc.spin_limit = e->spin_limit;
+    rc.test_abort_epoch = e->test_abort_epoch;
+    rc.test_late_wave0 = e->test_late_wave0;
+    rc.dbg = nullptr;
+    return rc;
+}
+// what a launch needs on the stream in front of it: zeroed hand-off words, the device copy of the context, the host-abort word
+static int resident_setup(jslp_engine* e, const SolveRun& p, ResCtx& rc) {
+    hipStream_t s = e->stream;
+    HIPC(hipMemsetAsync(e->r_gran, 0, sizeof(u64_t) * JSLP_R_SYNC_WORDS, s));  // tags restart at 1
+    HIPC(hipMemcpyAsync(e->r_ctx_dev, &rc.c, sizeof(Ctx), hipMemcpyHostToDevice, s));  // (200 bytes; the kernel's one committing thread reads the map / trace pointers from it)
+    // the host-abort word (pinned, behind the state and the retry counter) and its address behind the device copy of the context
+    unsigned* const h_abort = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(e->h_state) + sizeof(DevState) + 16);
+    *h_abort = 0u;
+    e->h_abort_ptr = h_abort;
+    HIPC(hipMemcpyAsync(reinterpret_cast<char*>(e->r_ctx_dev) + sizeof(Ctx), &e->h_abort_ptr, sizeof(unsigned*), hipMemcpyHostToDevice, s));
+#ifdef JSLP_DEBUG_RESIDENT
+    static u64_t* dbg_buf = nullptr;
+    if (!dbg_buf) HIPC(hipMalloc(&dbg_buf, sizeof(u64_t) * (512 * JSLP_F_MAXG * 2 + 16384)));
+    HIPC(hipMemsetAsync(dbg_buf, 0, sizeof(u64_t) * (512 * JSLP_F_MAXG * 2 + 16384), s));
+    rc.dbg = dbg_buf;
+#endif
+    HIPC(hipMemsetAsync(e->r_sync, 0, sizeof(unsigned) * 16, s));
+    if (p.geometry == RES_GEOM_XL) {
+        // the XCD-local build's rows carry their epoch tag INSIDE the data and every launch's tags restart at 1: what an earlier
+        // launch left in the row slots would pass for this launch's rows (found by the Knapsack fixture's fifth relaxation: same
+        // pivots, another RHS) -- the slots start from zero (tag 0 is never used)
+        for (int i = 0; i < 2; i++) HIPC(hipMemsetAsync(e->r_rows[i], 0, (size_t)rc.G * e->ld * 16, s));
+    }
+    return JSLP_OK;
+}
+// Safety net.  The kernel commits every pivot's index-map swap as it goes but writes the matrix back only in
+// its epilogue, and a timed-out hand-off (workgroups not co-resident, a stalled GPU) skips that epilogue: keep a
+// copy of slot 0 (one pass over the matrix, ~15 us at 2001 x 2001 against a ~100 ms solve) to roll back to.
+static void resident_safety_net(jslp_engine* e, const SolveRun& p, int save) {  // save 1: slot 0 -> the copy; 0: the copy -> slot 0
+    SnapshotW bk{e->rb_A, e->rb_vibr, e->rb_vibc, e->rb_rbv, e->rb_cbv, e->n_idx, nullptr, nullptr};
+    hipLaunchKernelGGL(k_res_backup, dim3(copy_grid(e, 1).x), dim3(256), 0, e->stream, e->s, bk, e->r_backup_st, p.H, save);
+}
+// JSLP_INJECT_RESIDENT_ABORT_US=<n>: raise the host-abort word n microseconds into the launch -- the rollback path (kernel gives
+// up mid-solve, slot 0 restored from the safety-net copy, the solve re-run through the streaming kernels) exercised on the
+// library users load, whose kernels have no test hooks.  Read per launch (tests set it inside one process); once per solve.
+// (parsed strictly -- a stray or garbage value no longer aborts every resident solve -- and announced once)
+static void inject_resident_abort(jslp_engine* e) {
+    const char* inj = getenv("JSLP_INJECT_RESIDENT_ABORT_US");
+    if (!inj || !*inj || e->abort_injected) return;
+    char* endp = nullptr;
+    const long us = strtol(inj, &endp, 10);
+    if (endp == inj || *endp != 0 || us < 0 || us > 10000000L) return;
+    static std::atomic<int> told{0};
+    if (!told.exchange(1)) fprintf(stderr, "[jslp] JSLP_INJECT_RESIDENT_ABORT_US=%ld: every register-resident solve is aborted %ld us after its launch and re-run through the streaming kernels (fault injection)\n", us, us);
+    e->abort_injected = 1;
+    std::this_thread::sleep_for(std::chrono::microseconds(us));
+    __atomic_store_n(e->h_abort_ptr, 1u, __ATOMIC_RELEASE);
+}
+// One cooperative launch of the instance the plan's geometry and `lean` name; *le: what the runtime said (hipErrorInvalidValue: no such instance).
+// The LEAN build (all-gather protocol only, software-pipelined phase 2: jslp_resident_pipe.hip.h) takes every solve it can (lean_takes); the general
+// build is what a lean solve of the 8-row geometries is handed to (resident_attempt).  Lane geometry: up to 8 rows per workgroup: 1024 lanes x 2 columns
+// (or 512 x 4, half the waves per workgroup barrier, measured slower); 9..16 rows (2048 < H <= 4096): 512 lanes x 4 columns x 16 rows -- 2 waves per SIMD
+// leave 256 VGPRs per lane for the 64 MB of tableau.
+static int resident_launch(jslp_engine* e, const SolveRun& p, const ResCtx& rc, bool lean, hipError_t* le) {
+    const ResGeom& g = RES_GEOM[p.geometry];
+    const bool unr = e->n_unr > 0;  // unrestricted variables: the UNR build threads the per-column flags through
+    // (chk: the instance's template key -- the general build is compiled with CHK = true and reads check_cycles at run time)
+    const int key[8] = {g.threads, g.cols, g.rows, unr ? 1 : 0, lean ? 1 : 0, e->n_opt > 0 ? 1 : 0, (p.check_cycles != 0 || !lean) ? 1 : 0, p.geometry == RES_GEOM_XL ? 1 : 0};
+    const int r = resident_dispatch(key, (unsigned)rc.G, &rc, e->stream);
+    if (r == -1 && RES_DEV_REFUSAL) return fail(JSLP_ERR_UNSUPPORTED, "%s", RES_DEV_REFUSAL);
+    *le = r == -1 ? hipErrorInvalidValue : (hipError_t)r;  // (-1: no such instance -- the refusal branch counts it)
+    if (*le != hipSuccess) return JSLP_OK;
+    e->resident_launches += 1;
+    if (p.dbg)  // which instance ran, one parseable line per accepted launch (tests/test_grid_edges.py)
+        fprintf(stderr, "[jslp] launch k_simplex_resident<%d,%d,%d> unr %d lean %d opt %d chk %d xl %d G %d rpb %d\n", key[0], key[1], key[2], key[3], key[4], key[5],
+                key[6], key[7], rc.G, rc.rpb);
+    if (lean) inject_resident_abort(e);
+    return JSLP_OK;
+}
+// the launch's share of upd_ms / upd_launches, between the events around it; unit = one pivot (16*H*W algorithmic bytes)
+static void account_resident_time(jslp_engine* e, long long it_before) {
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, e->ev_pool[0], e->ev_pool[1]) == hipSuccess) e->upd_ms += ms;
+    e->upd_launches += e->h_state->it1 + e->h_state->it2 - it_before;
+}
+// an accepted launch has run to its end: the final state, or the roll back to the safety-net copy
+static int resident_finish(jslp_engine* e, const SolveRun& p, const ResCtx& rc, long long it_before, Resident* out) {
+    hipStream_t s = e->stream;
+    if (e->timing) HIPC(hipEventRecord(e->ev_pool[1], s));
+    JSLP_TRY(fetch_state(e, e->s.st));
+    if (e->timing) account_resident_time(e, it_before);
+    if (e->h_state->err == ERR_BARRIER) {
+        // roll slot 0 back to its state before the launch and solve through the streaming kernels instead
+        resident_safety_net(e, p, 0);
+        HIPC(hipGetLastError());
+        // ... and the host's copy of the state with it: the streaming loops start from what h_state says (the tall /
+        // wide geometries come here with ST_PHASE1_DONE: without this the aborted kernel's ST_DONE + ERR_BARRIER ended the
+        // solve as a device error instead of finishing it through k_pivot_fused)
+        JSLP_TRY(fetch_state(e, e->s.st));
+        e->resident_fallbacks += 1;
+        *out = Resident::RolledBack;
+        return JSLP_OK;
+    }
+    *out = Resident::Done;
+    e->last_path = p.geometry == RES_GEOM_XL ? "resident-xl" : "resident";
+    if (e->counting) {  // a dense streaming update touches every cell: rows x columns per pivot
+        const long long piv = (long long)e->h_state->it1 + e->h_state->it2;
+        e->wc.gated_cells += piv * (long long)(p.H - 1) * e->W;
+        e->wc.gated_rows += piv * (long long)(p.H - 1);
+    }
+#ifdef JSLP_DEBUG_RESIDENT
+    {   // phase timing + micro-costs of the debug build (tools/resident_phase_timing.py reads this file)
+        std::vector<u64_t> d(16384);
+        HIPC(hipMemcpy(d.data(), rc.dbg + (size_t)512 * rc.G * 2, sizeof(u64_t) * 16384, hipMemcpyDeviceToHost));
+        FILE* fb = fopen("gpurun_out/resident_r0.bin", "wb");
+        if (fb) { fwrite(d.data(), 8, 16384, fb); fclose(fb); }
+        HIPC(hipMemcpy(d.data(), rc.dbg, sizeof(u64_t) * 16384, hipMemcpyDeviceToHost));  // RT_STAMP: [8 epochs][MAXG][8 events]
+        fb = fopen("gpurun_out/resident_stamps.bin", "wb");
+        if (fb) { fwrite(d.data(), 8, 16384, fb); fclose(fb); }
+    }
+#else
+    (void)rc;
+#endif
+    return JSLP_OK;
+}
+// `it_before`: pivots the solve had done when the kernel is launched (0, or a phase 1 done by the fused pipeline)
+static int resident_attempt(jslp_engine* e, const SolveRun& p, long long it_before, Resident* out) {
+    hipStream_t s = e->stream;
+    // (the lean kernel's per-workgroup copies of the cycle-check history are carved once a lean solve with the check on comes by: ensure_resident)
+    JSLP_TRY(ensure_resident(e, p.lean && p.check_cycles != 0));
+    ResCtx rc = make_res_ctx(e, p);
+    JSLP_TRY(resident_setup(e, p, rc));
+    resident_safety_net(e, p, 1);
+    if (e->timing) { JSLP_TRY(ensure_events(e, 2)); HIPC(hipEventRecord(e->ev_pool[0], s)); }
+    // The lean build first.  Should its cycle-check history outgrow LDS it hands the solve over (status ST_RUNNING / ST_PHASE1_DONE instead of
+    // ST_DONE) and the general build continues it in a second launch: at most two trips
+    bool lean = p.lean;
+    hipError_t le = hipErrorInvalidValue;
+    for (int trip = 0; trip < 2; trip++) {
+        JSLP_TRY(resident_launch(e, p, rc, lean, &le));
+        if (le != hipSuccess || !lean) break;
+        // did the lean kernel finish the solve?
+        unsigned* const h_retries = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(e->h_state) + sizeof(DevState) + 8);
+        HIPC(hipMemcpyAsync(e->h_state, e->s.st, sizeof(DevState), hipMemcpyDeviceToHost, s));
+        HIPC(hipMemcpyAsync(h_retries, e->r_sync + 5, sizeof(unsigned), hipMemcpyDeviceToHost, s));  // repeated looks of the checksummed row hand-over
+        HIPC(hipStreamSynchronize(s));
+        e->resident_fetch_retries += *h_retries;
+        if (e->h_state->err != ERR_NONE || e->h_state->status == ST_DONE) break;
+        e->resident_handovers += 1;
+        if (e->n_opt > 0 || p.geometry >= 3) {
+            // (XCD-local and tall / wide geometries: there is no general build of them)
+            // optional objectives: the general build does not take them -- the streaming kernels continue from the state the
+            // lean kernel left (tableau, maps and objective rows written back; status ST_RUNNING or ST_PHASE1_DONE)
+            if (e->timing) { HIPC(hipEventRecord(e->ev_pool[1], s)); HIPC(hipEventSynchronize(e->ev_pool[1])); account_resident_time(e, it_before); }
+            *out = Resident::Streaming;
+            return JSLP_OK;
+        }
+        lean = false;
+        HIPC(hipMemsetAsync(e->r_gran, 0, sizeof(u64_t) * JSLP_R_SYNC_WORDS, s));  // the second launch's tags restart at 1
+    }
+    if (le == hipSuccess) return resident_finish(e, p, rc, it_before, out);
+    (void)hipGetLastError();  // not co-resident on this device: use one launch per pivot instead
+    e->resident_refusals += 1;
+    if (p.dbg)
+        fprintf(stderr, "[jslp] cooperative launch of k_simplex_resident refused (geometry %d, lean %d, unr %d, G %d): %s\n", p.geometry, (int)lean,
+                (int)(e->n_unr > 0), rc.G, hipGetErrorString(le));
+    *out = Resident::Refused;
+    return JSLP_OK;
+}
+
+// ---- the streaming kernels: k_select + k_update per pivot, or one fused launch per pivot -----------------------------------------------------
+struct FusedKernel {  // one descriptor per instantiation of k_fused_p1 / k_pivot_fused
+    void (*fn)(FusedCtx, int);
+    const char* name;  // the JSLP_DEBUG_LAUNCH line
+};
+// column tiles per lane (ld <= 2048: one) x unrestricted variables present; beyond two tiles plain tableaus only (fused_eligible)
+static const FusedKernel FUSED_P1[6] = {
+    {k_fused_p1<1, true>, "k_fused_p1<1,1>"}, {k_fused_p1<1, false>, "k_fused_p1<1,0>"}, {k_fused_p1<2, true>, "k_fused_p1<2,1>"},
+    {k_fused_p1<2, false>, "k_fused_p1<2,0>"}, {k_fused_p1<3, false>, "k_fused_p1<3,0>"}, {k_fused_p1<4, false>, "k_fused_p1<4,0>"}};
+// ... x optional objectives present
+static const FusedKernel PIVOT_FUSED[10] = {
+    {k_pivot_fused<1, true, true>, "k_pivot_fused<1,1,1>"}, {k_pivot_fused<1, true, false>, "k_pivot_fused<1,1,0>"},
+    {k_pivot_fused<1, false, true>, "k_pivot_fused<1,0,1>"}, {k_pivot_fused<1, false, false>, "k_pivot_fused<1,0,0>"},
+    {k_pivot_fused<2, true, true>, "k_pivot_fused<2,1,1>"}, {k_pivot_fused<2, true, false>, "k_pivot_fused<2,1,0>"},
+    {k_pivot_fused<2, false, true>, "k_pivot_fused<2,0,1>"}, {k_pivot_fused<2, false, false>, "k_pivot_fused<2,0,0>"},
+    {k_pivot_fused<3, false, false>, "k_pivot_fused<3,0,0>"}, {k_pivot_fused<4, false, false>, "k_pivot_fused<4,0,0>"}};
+static int fused_tiles(const jslp_engine* e) { return std::min((e->ld + JSLP_F_TW - 1) / JSLP_F_TW, JSLP_F_MAXNT); }
+static const FusedKernel& fused_p1_kernel(const jslp_engine* e) {
+    const int t = fused_tiles(e);
+    return FUSED_P1[t <= 2 ? 2 * (t - 1) + (e->n_unr > 0 ? 0 : 1) : t + 1];
+}
+static const FusedKernel& pivot_fused_kernel(const jslp_engine* e) {
+    const int t = fused_tiles(e);
+    return PIVOT_FUSED[t <= 2 ? 4 * (t - 1) + (e->n_unr > 0 ? 0 : 2) + (e->n_opt > 0 ? 0 : 1) : t + 5];
+}
+static void launch_fused(const jslp_engine* e, const FusedKernel& k, const FusedCtx& f, int launch) {
+    hipLaunchKernelGGL(k.fn, dim3(f.G), dim3(JSLP_F_THREADS), 0, e->stream, f, launch);
+}
+// add up the event pairs of the pivots of a chunk that really ran: launches after the solve ended are no-ops, only the first `real` did a pivot.
+// Returns the solve's pivot count, the next chunk's `done_prev`
+static long long account_chunk_time(jslp_engine* e, int chunk, long long done_prev) {
+    const long long done = (long long)e->h_state->it1 + e->h_state->it2;
+    const long long real = std::min<long long>(chunk, done - done_prev);
+    for (long long i = 0; i < real; i++) {
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, e->ev_pool[2 * i], e->ev_pool[2 * i + 1]) == hipSuccess) e->upd_ms += ms;
+    }
+    e->upd_launches += real;
+    return done;
+}
+// Pivots enqueued in chunks, the device state polled once per chunk (the GPU never waits for the host inside a chunk), the chunk doubled up to
+// `chunk_cap`, until the state leaves ST_RUNNING.  k == nullptr: k_select + k_update per pivot, the state is slot 0's; else one launch of the fused
+// kernel k per pivot, numbered by *launch, the state the pipeline's own (f->fst).  `timed`: an event pair around every k_update / fused launch
+static int stream_pivots(jslp_engine* e, const SolveRun& p, const FusedKernel* k, const FusedCtx* f, int* launch, int chunk, int chunk_cap, bool timed, long long done_prev) {
+    hipStream_t s = e->stream;
+    for (;;) {
+        if (timed) JSLP_TRY(ensure_events(e, 2 * (size_t)chunk));
+        for (int i = 0; i < chunk; i++) {
+            if (!k) hipLaunchKernelGGL(k_select, dim3(1), dim3(JSLP_WG_THREADS), 0, s, p.c);
+            if (timed) HIPC(hipEventRecord(e->ev_pool[2 * i], s));
+            if (k) launch_fused(e, *k, *f, (*launch)++);
+            else hipLaunchKernelGGL(k_update, p.grid, dim3(JSLP_UPD_THREADS), 0, s, p.c);
+            if (timed) HIPC(hipEventRecord(e->ev_pool[2 * i + 1], s));
+        }
+        HIPC(hipGetLastError());
+        JSLP_TRY(fetch_state(e, k ? f->fst[*launch & 1] : e->s.st));
+        if (timed) done_prev = account_chunk_time(e, chunk, done_prev);
+        if (e->h_state->status != ST_RUNNING) return JSLP_OK;
+        chunk = std::min(chunk * 2, chunk_cap);
+    }
+}
+// the ONE pivot a fused pipeline cannot decide alone (ST_P1_SLOW, see k_fused_p1 / k_pivot_fused): through k_select + k_update
+static int slow_pivot(jslp_engine* e, const SolveRun& p) {
+    hipStream_t s = e->stream;
+    hipLaunchKernelGGL(k_p1_resume, dim3(1), dim3(1), 0, s, e->s.st, (int)ST_RUNNING);
+    hipLaunchKernelGGL(k_select, dim3(1), dim3(JSLP_WG_THREADS), 0, s, p.c);
+    hipLaunchKernelGGL(k_update, p.grid, dim3(JSLP_UPD_THREADS), 0, s, p.c);
+    HIPC(hipGetLastError());
+    JSLP_TRY(fetch_state(e, e->s.st));
+    e->p1_slow_pivots += 1;
+    return JSLP_OK;
+}
+// phase 1 through the fused pipeline (one launch per pivot; k_fused_p1); hands over with ST_PHASE1_DONE
+static int fused_phase1(jslp_engine* e, const SolveRun& p) {
+    JSLP_TRY(ensure_fused(e));
+    JSLP_TRY(ensure_fused_oo(e));
+    const FusedCtx f = make_fused_ctx(e, p.c, p.H);
+    const FusedKernel& k = fused_p1_kernel(e);
+    if (p.dbg) fprintf(stderr, "[jslp] launch %s\n", k.name);
+    for (;;) {
+        int launch = 0;
+        launch_fused(e, k, f, launch++);
+        JSLP_TRY(stream_pivots(e, p, &k, &f, &launch, 2, 512, false, 0));
+        hipLaunchKernelGGL(k_fused_finish, dim3(512), dim3(256), 0, e->stream, f, launch - 1);  // state -> slot 0's, tableau -> buf[0]
+        HIPC(hipGetLastError());
+        if (e->h_state->status != ST_P1_SLOW) break;
+        JSLP_TRY(slow_pivot(e, p));  // ... then the pipeline again
+        if (e->h_state->status != ST_RUNNING) break;
+    }
+    e->last_path = "fused";
+    return JSLP_OK;
+}
+// phase 1 (and phase 2 when the fused pipeline does not apply): k_select + k_update per pivot
+static int select_update_loop(jslp_engine* e, const SolveRun& p) {
+    if (p.dbg) fprintf(stderr, "[jslp] launch select+update\n");
+    return stream_pivots(e, p, nullptr, nullptr, nullptr, p.fused ? 1 : 8, 256, e->timing && !p.fused, 0);
+}
+// phase 2: one fused launch per pivot (k_pivot_fused)
+static int fused_phase2(jslp_engine* e, const SolveRun& p) {
+    hipStream_t s = e->stream;
+    while (e->h_state->status == ST_PHASE1_DONE) {
+        JSLP_TRY(ensure_fused(e));
+        JSLP_TRY(ensure_fused_oo(e));
+        e->last_path = "fused";
+        const FusedCtx f = make_fused_ctx(e, p.c, p.H);
+        const FusedKernel& k = pivot_fused_kernel(e);
+        if (p.dbg) fprintf(stderr, "[jslp] launch %s\n", k.name);
+        int launch = 0;
+        launch_fused(e, k, f, launch++);
+        JSLP_TRY(stream_pivots(e, p, &k, &f, &launch, 16, 512, e->timing != 0, (long long)e->h_state->it1 + e->h_state->it2));
+        hipLaunchKernelGGL(k_fused_finish, dim3(512), dim3(256), 0, s, f, launch - 1);
+        HIPC(hipGetLastError());
+        if (e->h_state->status == ST_P1_SLOW) {
+            // an entering column named by an optional objective with a ~0 main cost and a tiny pivot-row entry: that ONE pivot
+            // through k_select + k_update (see k_pivot_fused), then the pipeline again from its first launch
+            JSLP_TRY(slow_pivot(e, p));
+            if (e->h_state->status != ST_RUNNING) break;  // that pivot ended the solve
+            hipLaunchKernelGGL(k_p1_resume, dim3(1), dim3(1), 0, s, e->s.st, (int)ST_PHASE1_DONE);
+            e->h_state->status = ST_PHASE1_DONE;
+            continue;
+        }
+        HIPC(hipMemcpyAsync(e->h_state, e->s.st, sizeof(DevState), hipMemcpyDeviceToHost, s));
+        if (e->counting) {  // the fused launches stream every cell (phase 1 went through k_select: counted on the device)
+            e->wc.gated_cells += (long long)e->h_state->it2 * (long long)(p.H - 1) * e->W;
+            e->wc.gated_rows += (long long)e->h_state->it2 * (long long)(p.H - 1);
+        }
+        HIPC(hipStreamSynchronize(s));
+        break;
+    }
+    return JSLP_OK;
+}
+// the closing events; e->h_state is the solve's final state
+static int close_solve(jslp_engine* e) {
+    HIPC(hipEventRecord(e->ev_end, e->stream));
+    HIPC(hipStreamSynchronize(e->stream));
     float ms = 0;
     if (hipEventElapsedTime(&ms, e->ev_begin, e->ev_end) == hipSuccess) e->total_ms += ms;
     return state_error(*e->h_state);
+}
+
+// simplex() of the live tableau (slot 0), leaving the final DevState in e->h_state
+static int run_simplex(jslp_engine* e, int check_cycles) {
+    e->slot0_synced = 0;  // the chip-wide kernels do not maintain the dirty-row flags (k_begin zeroes st.gen)
+    e->abort_injected = 0;
+    HIPC(hipEventRecord(e->ev_begin, e->stream));
+    if (use_wg_single(e)) {
+        JSLP_TRY(solve_one_workgroup(e, check_cycles));
+        return close_solve(e);
+    }
+    SolveRun p;
+    JSLP_TRY(plan_solve(e, check_cycles, &p));
+    hipLaunchKernelGGL(k_begin, dim3(1), dim3(1), 0, e->stream, e->s, 0, p.cap);
+    Resident res = Resident::NotTried;
+    if (p.geometry != 0 && !p.phase2_only) JSLP_TRY(resident_attempt(e, p, 0, &res));
+    if (res != Resident::Done) {
+        // (a lean kernel that left mid-solve may have left behind phase 1: h_state is current in that case only)
+        bool phase1_over = res == Resident::Streaming && e->h_state->status == ST_PHASE1_DONE;
+        if (!phase1_over && p.fused && fused_p1_on()) {
+            JSLP_TRY(fused_phase1(e, p));
+            phase1_over = true;
+        }
+        if (!phase1_over) JSLP_TRY(select_update_loop(e, p));
+        // phase 2 of the tall / wide geometries: register-resident (plan_solve)
+        if (p.phase2_only && e->h_state->status == ST_PHASE1_DONE && e->h_state->err == ERR_NONE)
+            JSLP_TRY(resident_attempt(e, p, (long long)e->h_state->it1 + e->h_state->it2, &res));
+        if (res != Resident::Done) JSLP_TRY(fused_phase2(e, p));
+    }
+    return close_solve(e);
 }
 
 extern "C" int jslp_engine_simplex(jslp_engine* e, int check_cycles, jslp_simplex_result* out) {
@@ -2348,7 +2324,7 @@ static int relax_batch_impl(jslp_engine* e, const NodeCall& c) {
     if (rc || n_nodes == 0) return rc;
     HIPC(hipSetDevice(e->device));
     hipStream_t s = e->stream;
-    const bool dbg = getenv("JSLP_DEBUG_LAUNCH") != nullptr;  // (read per call, as run_simplex does: tests switch it inside one process)
+    const bool dbg = debug_launch_on();  // (read per call, as run_simplex does: tests switch it inside one process)
     if (single_child_fast_path(e, c)) return relax_single_child(e, c, dbg);
     JSLP_TRY(upload_cuts(e, n_nodes, c.cuts.offsets, c.cuts.type, c.cuts.var_index, c.cuts.value));
     NodePlan p;
@@ -2702,7 +2678,7 @@ extern "C" int jslpm_simplex_many(jslp_engine* const* engines, int32_t n, const 
         }
         HIPC(hipMemcpyAsync(d_lps, h_lps, sizeof(ManyLp) * nb, hipMemcpyHostToDevice, s));
         HIPC(hipEventRecord(lead->ev_begin, s));
-        const bool dbg = getenv("JSLP_DEBUG_LAUNCH") != nullptr;
+        const bool dbg = debug_launch_on();
         for (int variant = 0; variant < 2; variant++) {
             const size_t cnt = variant ? opt.size() : plain.size();
             if (!cnt) continue;

@@ -1,7 +1,7 @@
 """Every register-resident instance of the product library at the edges of its grid and lanes, and the streaming kernels at their
 tile edges, HIP against the CPU oracle bit for bit.
 
-The suite's goldens land the 28 instances of `k_simplex_resident` in jslp_tu_resident.hip on a few grid sizes (mostly G = 251); the
+The suite's goldens land the 28 instances of `k_simplex_resident` in jslp_resident_table.hip.h on a few grid sizes (mostly G = 251); the
 full grid (G = 256) is where ONE wave gathers all four looks per lane of the ratio-test summaries and where a cooperative launch
 needs every CU.  Each case here names the geometry its shape must take, and the test reads WHICH instance ran from the engine's
 `JSLP_DEBUG_LAUNCH` line (one per accepted launch: key, G, rows per workgroup; or the streaming kernels' choice), so a policy change
@@ -35,7 +35,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 from resident_stress import int_instance  # noqa: E402  (the instance builder of the stress tool and its known answers)
 
-TU_RESIDENT = os.path.join(ROOT, "jslpsolver_amd", "csrc", "jslp_tu_resident.hip")
+TU_RESIDENT = os.path.join(ROOT, "jslpsolver_amd", "csrc", "jslp_resident_table.hip.h")  # the instance table the parts of jslp_tu_resident.hip compile
 SEED = 12345
 PREC = 1e-8
 MAXG = 256  # JSLP_F_MAXG
@@ -289,7 +289,7 @@ def policy(case):
 
 
 def product_instances():
-    """the (T, C, R, unr, lean, opt, chk, xl) of every k_simplex_resident instance jslp_tu_resident.hip launches, minus the XCD-local ones"""
+    """the (T, C, R, unr, lean, opt, chk, xl) of every k_simplex_resident instance jslp_resident_table.hip.h launches, minus the XCD-local ones"""
     src = open(TU_RESIDENT).read()
     keys = set()
     b = lambda s: int(s == "true")  # noqa: E731
