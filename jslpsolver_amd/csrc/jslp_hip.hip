@@ -16,6 +16,7 @@
 #include "../../include/jslpx_branch.h"
 #include "../../include/jslpm_many.h"
 #include "jslp_kernels.hip.h"
+#include "jslp_host_mem.h"
 
 #include <math.h>
 #include <stdio.h>
@@ -41,14 +42,18 @@ static int fail(int code, const char* fmt, const char* a = "", const char* b = "
         hipError_t _e = (expr);                                                                 \
         if (_e != hipSuccess) return fail(JSLP_ERR_DEVICE, "%s: %s", #expr, hipGetErrorString(_e)); \
     } while (0)
+// carve_into(arena, layout) with the error text of an allocation: the arena's name, not the layout's code
+#define HIPC_CARVE(arena, ...)                                                                                    \
+    do {                                                                                                          \
+        hipError_t _e = carve_into(arena, __VA_ARGS__);                                                           \
+        if (_e != hipSuccess) return fail(JSLP_ERR_DEVICE, "%s: %s", "carve_into(" #arena ")", hipGetErrorString(_e)); \
+    } while (0)
 #define JSLP_TRY(expr) do { int _rc = (expr); if (_rc) return _rc; } while (0)  // (an engine call's own error code travels up unchanged)
 
 static const size_t WGLDS_MAX_BYTES = 64 * 1024;  // largest dynamic LDS the LDS-resident one-workgroup kernels are launched with
 struct jslp_engine {
     int device = 0;
-    hipStream_t stream = nullptr;
-    hipStream_t copy_stream = nullptr;  // read-back of a finished group of nodes while the next group computes
-    hipEvent_t ev_group = nullptr;
+    PooledRes res;
     int32_t H0 = 0, W = 0, ld = 0, cap_rows = 0, n_idx = 0;
     double precision = 1e-8;
     int32_t batch = 50, use_partial = 0;
@@ -56,14 +61,12 @@ struct jslp_engine {
     int slot0_synced = 0;  // slot 0 = current snapshot except for its dirty rows (st.gen == st.s_gen): k_node_wg may be used
     int slots_synced = 0;  // slots 1 .. slots_synced-1 are in that state too (only slot 0 ever leaves it on its own)
     double evaluation = 0;
-    // slots (slot 0 = the live tableau).  All per-slot arrays live in ONE device allocation (slot_arena), the
-    // snapshot / flags / trace in another (static_arena): hipMalloc / hipFree cost ~0.1 ms apiece, and a Solve of a
+    // slots (slot 0 = the live tableau).  All per-slot arrays live in ONE device allocation (res.slot_arena), the
+    // snapshot / flags / trace in another (res.static_arena): an allocation and its release cost ~0.1 ms apiece, and a Solve of a
     // small model creates and destroys an engine
     int n_slots = 0;
     Slots s{};
-    char* slot_arena = nullptr; size_t slot_bytes = 0;
-    char* static_arena = nullptr; size_t static_bytes = 0;
-    char* spare_slot_arena = nullptr; size_t spare_slot_bytes = 0;  // handed over by the resource pool at create()
+    DevBuf spare_slot_arena;  // the slot arena of the bundle the resource pool handed over at create()
     // snapshot
     double* snap_A = nullptr; double* snap_rhs = nullptr;
     double* snap_AT = nullptr; int snap_ldT = 0;  // the saved root transposed (tableaus the LDS node kernels take; else nullptr)
@@ -71,39 +74,32 @@ struct jslp_engine {
     uint8_t* d_unr = nullptr;
     uint8_t* d_isint = nullptr;  // variable.isInteger per variable index (MIR cuts)
     int32_t n_opt = 0; double* snap_oo = nullptr;  // optional objectives (slot copies live in s.oo)
-    // cuts staging: ONE pinned host buffer -> ONE device buffer per call: [value | offs | var | type]
-    char* d_cuts = nullptr; char* h_cuts = nullptr; size_t cuts_bytes = 0;
+    DevBuf oo_mem, snap_oo_mem;                      // ... what s.oo and snap_oo point into (resize_optional_objectives)
+    // cuts staging (res.cuts): ONE pinned host buffer -> ONE device buffer per call: [value | offs | var | type]
     int32_t* d_cut_offs = nullptr; int8_t* d_cut_type = nullptr; int32_t* d_cut_var = nullptr; double* d_cut_val = nullptr;
     int32_t* d_cut_order = nullptr; int* d_queue = nullptr;  // batch hand-out order (most cuts first) + queue counter, uploaded with the cuts
     std::vector<int32_t> order_scratch;
     bool queue_wgs_opt = false; int node_queue_launches = 0; long long resident_fetch_retries = 0;  // (which build the count below is for; batches that went through k_node_queue)
     int queue_wgs = 0; size_t queue_wgs_lds = 0;             // resident workgroups of k_node_queue<512> for this LDS size
-    // read-back staging: ONE device buffer -> ONE pinned buffer per group: [states | rhs | rows]
-    char* d_out = nullptr; char* h_out = nullptr;
+    // read-back staging (res.out): ONE device buffer -> ONE pinned buffer per group: [states | rhs | rows]
     double* d_rhs = nullptr; int32_t* d_rows = nullptr; DevState* d_states = nullptr;
     double* h_rhs = nullptr; int32_t* h_rows = nullptr; DevState* h_states = nullptr;
-    size_t out_bytes_cap = 0;
-    DevState* h_state = nullptr;  // pinned, 1 entry, followed by the completion flag of the one-launch node kernel
+    DevState* h_state = nullptr;  // res.h_state: pinned, 1 entry, followed by the completion flag of the one-launch node kernel
     unsigned done_seq = 0;
-    // upload staging (pinned): [matrix, row stride W | vibr | vibc | unrestricted list]; the matrix part is what
-    // jslp_engine_host_matrix hands to the host to build the tableau in; d_up = device twin of the blob
+    // upload staging (res.up, pinned half): [matrix, row stride W | vibr | vibc | unrestricted list]; the matrix part is what
+    // jslp_engine_host_matrix hands to the host to build the tableau in; the device half = twin of the blob
     // (and of the matrix when it needs the W -> ld repack)
-    char* h_up = nullptr; size_t h_up_bytes = 0;
-    char* d_up = nullptr; size_t d_up_bytes = 0;
-    int host_matrix_out = 0;  // the host holds a pointer into h_up
-    // the one-call-only redirection of the read-back (device pool: every member copies straight into the pool's buffer)
-    DevState* ext_states = nullptr; double* ext_rhs = nullptr; int32_t* ext_rows = nullptr;
+    int host_matrix_out = 0;  // the host holds a pointer into res.up.h
     // compact read-back (jslp_engine_relax_watched)
-    int32_t* d_watch = nullptr; int32_t n_watch = 0;
+    DevBuf d_watch; int32_t n_watch = 0;
     // work counters
     int counting = 0;
-    cnt_t* d_cnt = nullptr;
+    DevBuf d_cnt;
     jslp_work_counters wc{};
     // snapshot generation as the device pool sees it: bumped by save() and upload()
     unsigned long long root_seq = 0;
     // safety net of the register-resident kernel: copy of slot 0 taken before the cooperative launch
-    char* r_arena = nullptr; size_t r_arena_bytes = 0;  // hand-off buffers + this backup in ONE allocation (parked in the resource pool)
-    DevState* r_backup_st = nullptr;
+    DevState* r_backup_st = nullptr;  // (hand-off buffers + this backup: res.r_arena, ONE allocation)
     double* rb_A = nullptr; int32_t *rb_vibr = nullptr, *rb_vibc = nullptr, *rb_rbv = nullptr, *rb_cbv = nullptr;
     int* d_done_count = nullptr;  // workgroups of a small batch that have delivered their outcome (k_node_lds: the last one raises the completion flag)
     unsigned long long* d_nnz = nullptr; long long nnz = -1;  // non-zero cells of the uploaded tableau (counted on the device)
@@ -113,12 +109,12 @@ struct jslp_engine {
     int resident_launches = 0;   // cooperative launches of k_simplex_resident the runtime accepted
     int resident_refusals = 0;   // ... it refused (or that no build exists for): the solve went through the streaming kernels
     std::vector<jslp_simplex_result> rec_results;  // per-node results of a branch-record call (the record is what the caller gets)
-    double* d_rec = nullptr; jslpx_branch_record* h_rec = nullptr; size_t rec_cap = 0;  // branch records of a batch (device / pinned, rec_cap each)
+    StagePair rec;  // branch records of a batch (device / pinned)
     double dev_prev_evaluation = 0.0;  // jslp_engine_relax_batch_device: the evaluation its nodes started from (results_from_states)
     int dev_prev_valid = 0;
     // checkpoints (incremental-branch-and-cut.ts:31-44): equally sized device buffers, recycled through a free list
     struct Ckpt {
-        char* mem = nullptr;
+        DevBuf mem;
         double* A = nullptr; double* rhs = nullptr;
         int32_t *vibr = nullptr, *vibc = nullptr, *rbv = nullptr, *cbv = nullptr;
         int32_t H = 0, last_element_index = 0;
@@ -126,10 +122,10 @@ struct jslp_engine {
         int live = 0;
     };
     std::vector<Ckpt> ckpts;
-    std::vector<char*> ck_free;
+    std::vector<DevBuf> ck_free;
     // fp32 twin of slot 0 (jslp_engine_simplex_f32), allocated on first use
     f32::Slots s32{};
-    char* arena32 = nullptr;
+    DevBuf arena32;
     // policy
     int force_path = 0;  // 0 auto, 1 workgroup kernel, 2 select+update kernels only, 3 fused phase 2
     int force_xl = 0, xl_on = 0;  // JSLP_FORCE_PATH=xl / JSLP_XL=0: the XCD-local register-resident geometry (resident_geometry 6)
@@ -137,11 +133,11 @@ struct jslp_engine {
     int32_t n_unr = 0;
     int nt = 0;  // JSLP_NT=1: non-temporal hints in the fused kernel
     // fused phase-2 pipeline (ping-pong buffer + per-workgroup candidates)
-    double* f_buf1 = nullptr; FCand* f_cands[2] = {nullptr, nullptr}; double* f_pcol[2] = {nullptr, nullptr};
-    uint8_t* f_uflags = nullptr;  // fused pipeline with unrestricted variables: 2 x (column flags | row flags)
-    double* f_oo1 = nullptr; int f_oo1_rows = 0;  // fused pipeline: the optional objectives' second (ping-pong) buffer
+    DevBuf f_buf1, f_cands[2], f_pcol[2], f_st[2];
+    DevBuf f_uflags;  // fused pipeline with unrestricted variables: 2 x (column flags | row flags)
+    int f_ready = 0;  // every buffer above exists and is zeroed (ensure_fused)
+    DevBuf f_oo1; int f_oo1_rows = 0;  // fused pipeline: the optional objectives' second (ping-pong) buffer
     long long p1_slow_pivots = 0;  // pivots the fused phase 1 handed to k_select + k_update (tiny pivot-row entries, see k_fused_p1)
-    DevState* f_st[2] = {nullptr, nullptr};
     // register-resident phase 2 (one cooperative launch): hand-off buffers
     u64_t* r_gran = nullptr;  // [2][G][8] granules then [2][G] row flags (one allocation, zeroed per launch)
     int32_t max_uploaded_idx = -1;  // largest variable index in the row / column maps of the last upload()
@@ -158,8 +154,7 @@ struct jslp_engine {
     int timing = 0;
     double upd_ms = 0, total_ms = 0;
     long long upd_launches = 0;
-    std::vector<hipEvent_t> ev_pool;
-    hipEvent_t ev_begin = nullptr, ev_end = nullptr;
+    std::vector<Event> ev_pool;
 };
 
 static const long long WG_CELLS_SINGLE = 64 * 1024;         // one workgroup beats 2 launches/pivot below this
@@ -226,38 +221,10 @@ extern "C" int jslp_device_count(void) {
 static int32_t round_up(int32_t x, int32_t m) { return (x + m - 1) / m * m; }
 static dim3 copy_grid(const jslp_engine* e, int slots);
 
-struct Carver {  // hands out 256-byte aligned pieces of one allocation; first pass (base == nullptr) just sizes it
-    char* base;
-    size_t off;
-    template <class T>
-    T* take(size_t count) {
-        off = (off + 255) & ~(size_t)255;
-        T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
-        off += sizeof(T) * count;
-        return p;
-    }
-};
-
-// ---- resource pool ---------------------------------------------------------------------------------------------------
-// A Solve() of a small model creates and destroys an engine; stream / event / pinned-memory creation and the two device
-// arenas cost ~4 ms per engine on this stack -- more than every pivot of the reference's fixtures.  Destroyed engines
-// therefore park those resources here (a handful of entries, arenas up to 1 GiB each) and the next create() on the same
-// device takes them over, re-carving the arenas when they are large enough.
-struct PooledRes {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev_begin = nullptr, ev_end = nullptr;
-    DevState* h_state = nullptr;
-    char* static_arena = nullptr; size_t static_bytes = 0;
-    char* slot_arena = nullptr; size_t slot_bytes = 0;
-    char* d_cuts = nullptr; char* h_cuts = nullptr; size_t cuts_bytes = 0;  // staging of the cut lists
-    char* d_out = nullptr; char* h_out = nullptr; size_t out_bytes = 0;     // read-back staging
-    char* h_up = nullptr; size_t h_up_bytes = 0; char* d_up = nullptr; size_t d_up_bytes = 0;  // upload staging
-    char* r_arena = nullptr; size_t r_arena_bytes = 0;  // the resident kernel's hand-off buffers + backup
-    hipStream_t copy_stream = nullptr; hipEvent_t ev_group = nullptr;  // read-back overlap of node batches
-};
+// ---- the resource pool's shelf (PooledRes: jslp_host_mem.h) --------------------------------------------------------------
+// (both shelves are never destroyed: a static destructor would call into a runtime that may be gone at exit; jslp_release_pooled_resources empties them)
 static std::mutex g_pool_mu;
-static std::vector<PooledRes> g_pool;
+static std::vector<PooledRes>& g_pool = *new std::vector<PooledRes>();
 static const size_t POOL_MAX_ENTRIES = 4;
 static const size_t POOL_MAX_ARENA = (size_t)1 << 30;
 
@@ -271,19 +238,19 @@ static bool pool_take(int device, PooledRes* out) {
     std::lock_guard<std::mutex> lk(g_pool_mu);
     for (size_t i = 0; i < g_pool.size(); i++)
         if (g_pool[i].device == device) {
-            *out = g_pool[i];
+            *out = std::move(g_pool[i]);
             g_pool.erase(g_pool.begin() + (long)i);
             return true;
         }
     return false;
 }
-static bool pool_give(const PooledRes& r) {
-    if (!pool_enabled() || r.static_bytes > POOL_MAX_ARENA || r.slot_bytes > POOL_MAX_ARENA || r.out_bytes > POOL_MAX_ARENA / 4 ||
-        r.h_up_bytes > POOL_MAX_ARENA / 4 || r.r_arena_bytes > POOL_MAX_ARENA)
+static bool pool_give(PooledRes&& r) {  // (refused: `r` is left as it was and dies with its owner)
+    if (!pool_enabled() || r.static_arena.bytes > POOL_MAX_ARENA || r.slot_arena.bytes > POOL_MAX_ARENA || r.out.bytes() > POOL_MAX_ARENA / 4 ||
+        r.up.bytes() > POOL_MAX_ARENA / 4 || r.r_arena.bytes > POOL_MAX_ARENA)
         return false;
     std::lock_guard<std::mutex> lk(g_pool_mu);
     if (g_pool.size() >= POOL_MAX_ENTRIES) return false;
-    g_pool.push_back(r);
+    g_pool.push_back(std::move(r));
     return true;
 }
 
@@ -297,27 +264,8 @@ extern "C" void jslp_release_pooled_resources(void) {
     }
     for (auto& r : drop) {
         hipSetDevice(r.device);
-        hipFree(r.static_arena); hipFree(r.slot_arena); hipFree(r.d_cuts); hipFree(r.d_out);
-        if (r.h_cuts) hipHostFree(r.h_cuts);
-        if (r.h_out) hipHostFree(r.h_out);
-        if (r.h_up) hipHostFree(r.h_up);
-        hipFree(r.d_up); hipFree(r.r_arena);
-        if (r.ev_group) hipEventDestroy(r.ev_group);
-        if (r.copy_stream) hipStreamDestroy(r.copy_stream);
-        if (r.h_state) hipHostFree(r.h_state);
-        if (r.ev_begin) hipEventDestroy(r.ev_begin);
-        if (r.ev_end) hipEventDestroy(r.ev_end);
-        if (r.stream) hipStreamDestroy(r.stream);
+        r = PooledRes();
     }
-}
-
-static void free_slots(jslp_engine* e, bool keep_arena = false) {
-    if (!keep_arena) { hipFree(e->slot_arena); e->slot_bytes = 0; }
-    hipFree(e->s.oo);
-    e->slot_arena = nullptr;
-    e->s.dirty = nullptr; e->s.oo = nullptr;
-    e->s.A = nullptr; e->s.vibr = e->s.vibc = e->s.rbv = e->s.cbv = nullptr;
-    e->s.prow = e->s.pcol = nullptr; e->s.rhs = nullptr; e->s.st = nullptr; e->s.hist = nullptr;
 }
 
 static void carve_slots(Slots& s, Carver& cv, int n) {
@@ -334,12 +282,39 @@ static void carve_slots(Slots& s, Carver& cv, int n) {
     s.hist = cv.take<int2>((size_t)s.hist_cap * n);
 }
 
-// (re)allocate the slot arrays for n slots, preserving slot 0
+// the fallible half of ensure_slots: `arena` (empty, or the spare) and `oo` carved / allocated for n slots, zeroed, the live tableau carried over
+static int fill_slots(jslp_engine* e, int n, const Slots& o, Slots& s, DevBuf& arena, DevBuf& oo) {
+    hipStream_t st = e->res.stream;
+    HIPC_CARVE(arena, [&](Carver& cv) { carve_slots(s, cv, n); });
+    // slot 0's matrix is zero-filled by upload(); other slots are filled by their first (full) restore
+    HIPC(hipMemsetAsync(s.dirty, 0, (size_t)s.pcol_stride * n, st));
+    HIPC(hipMemsetAsync(s.st, 0, sizeof(DevState) * n, st));  // gen = 0: slots hold no snapshot copy yet
+    s.n_opt = e->n_opt;
+    s.oo_stride = (long long)e->n_opt * e->ld;
+    s.oo = nullptr;
+    if (e->n_opt > 0) {
+        HIPC(oo.reserve(sizeof(double) * (size_t)s.oo_stride * n));
+        s.oo = oo.as<double>();
+        HIPC(hipMemsetAsync(s.oo, 0, sizeof(double) * (size_t)s.oo_stride * n, st));
+    }
+    if (e->n_slots == 0) return JSLP_OK;
+    // carry the live tableau over
+    HIPC(hipMemcpyAsync(s.A, o.A, sizeof(double) * o.A_stride, hipMemcpyDeviceToDevice, st));
+    HIPC(hipMemcpyAsync(s.vibr, o.vibr, sizeof(int32_t) * o.vibr_stride, hipMemcpyDeviceToDevice, st));
+    HIPC(hipMemcpyAsync(s.vibc, o.vibc, sizeof(int32_t) * o.vibc_stride, hipMemcpyDeviceToDevice, st));
+    HIPC(hipMemcpyAsync(s.rbv, o.rbv, sizeof(int32_t) * o.idx_stride, hipMemcpyDeviceToDevice, st));
+    HIPC(hipMemcpyAsync(s.cbv, o.cbv, sizeof(int32_t) * o.idx_stride, hipMemcpyDeviceToDevice, st));
+    HIPC(hipMemcpyAsync(s.st, o.st, sizeof(DevState), hipMemcpyDeviceToDevice, st));
+    HIPC(hipMemcpyAsync(s.dirty, o.dirty, (size_t)o.pcol_stride, hipMemcpyDeviceToDevice, st));
+    HIPC(hipMemcpyAsync(s.rhs, o.rhs, sizeof(double) * (size_t)o.pcol_stride, hipMemcpyDeviceToDevice, st));
+    if (e->n_opt > 0 && o.oo) HIPC(hipMemcpyAsync(s.oo, o.oo, sizeof(double) * (size_t)o.oo_stride, hipMemcpyDeviceToDevice, st));
+    HIPC(hipStreamSynchronize(st));
+    return JSLP_OK;
+}
+// (re)allocate the slot arrays for n slots, preserving slot 0; on failure the engine keeps what it had, its spare arena included
 static int ensure_slots(jslp_engine* e, int n) {
     if (n <= e->n_slots) return JSLP_OK;
-    Slots o = e->s, s = e->s;
-    char* old_arena = e->slot_arena;
-    const int old_n = e->n_slots;
+    Slots s = e->s;
     s.A_stride = (long long)e->cap_rows * e->ld;
     s.vibr_stride = e->cap_rows;
     s.vibc_stride = e->W;
@@ -350,82 +325,31 @@ static int ensure_slots(jslp_engine* e, int n) {
     s.ld = e->ld; s.W = e->W; s.batch = e->batch; s.use_partial = e->use_partial; s.precision = e->precision;
     s.has_unr = e->n_unr > 0 ? 1 : 0;
     s.unr = e->d_unr;
-    Carver sizing{nullptr, 0};
-    carve_slots(s, sizing, n);
-    char* arena = nullptr;
-    size_t arena_bytes = sizing.off + 256;
-    if (e->spare_slot_arena && e->spare_slot_bytes >= arena_bytes) {  // from the resource pool
-        arena = e->spare_slot_arena;
-        arena_bytes = e->spare_slot_bytes;
-        e->spare_slot_arena = nullptr;
-    } else {
-        HIPC(hipMalloc(&arena, arena_bytes));
-    }
-    Carver cv{arena, 0};
-    carve_slots(s, cv, n);
-    // slot 0's matrix is zero-filled by upload(); other slots are filled by their first (full) restore
-    HIPC(hipMemsetAsync(s.dirty, 0, (size_t)s.pcol_stride * n, e->stream));
-    HIPC(hipMemsetAsync(s.st, 0, sizeof(DevState) * n, e->stream));  // gen = 0: slots hold no snapshot copy yet
-    s.n_opt = e->n_opt;
-    s.oo_stride = (long long)e->n_opt * e->ld;
-    s.oo = nullptr;
-    if (e->n_opt > 0) {
-        HIPC(hipMalloc(&s.oo, sizeof(double) * (size_t)s.oo_stride * n));
-        HIPC(hipMemsetAsync(s.oo, 0, sizeof(double) * (size_t)s.oo_stride * n, e->stream));
-    }
-    if (old_n > 0) {  // carry the live tableau over
-        HIPC(hipMemcpyAsync(s.A, o.A, sizeof(double) * o.A_stride, hipMemcpyDeviceToDevice, e->stream));
-        HIPC(hipMemcpyAsync(s.vibr, o.vibr, sizeof(int32_t) * o.vibr_stride, hipMemcpyDeviceToDevice, e->stream));
-        HIPC(hipMemcpyAsync(s.vibc, o.vibc, sizeof(int32_t) * o.vibc_stride, hipMemcpyDeviceToDevice, e->stream));
-        HIPC(hipMemcpyAsync(s.rbv, o.rbv, sizeof(int32_t) * o.idx_stride, hipMemcpyDeviceToDevice, e->stream));
-        HIPC(hipMemcpyAsync(s.cbv, o.cbv, sizeof(int32_t) * o.idx_stride, hipMemcpyDeviceToDevice, e->stream));
-        HIPC(hipMemcpyAsync(s.st, o.st, sizeof(DevState), hipMemcpyDeviceToDevice, e->stream));
-        HIPC(hipMemcpyAsync(s.dirty, o.dirty, (size_t)o.pcol_stride, hipMemcpyDeviceToDevice, e->stream));
-        HIPC(hipMemcpyAsync(s.rhs, o.rhs, sizeof(double) * (size_t)o.pcol_stride, hipMemcpyDeviceToDevice, e->stream));
-        if (e->n_opt > 0 && o.oo) HIPC(hipMemcpyAsync(s.oo, o.oo, sizeof(double) * (size_t)o.oo_stride, hipMemcpyDeviceToDevice, e->stream));
-        HIPC(hipStreamSynchronize(e->stream));
-        hipFree(old_arena);
-        hipFree(o.oo);
+    const bool from_spare = e->spare_slot_arena.bytes >= carve_bytes([&](Carver& cv) { carve_slots(s, cv, n); });  // from the resource pool
+    DevBuf arena, oo;
+    if (from_spare) arena = std::move(e->spare_slot_arena);
+    if (const int rc = fill_slots(e, n, e->s, s, arena, oo)) {
+        if (from_spare) e->spare_slot_arena = std::move(arena);
+        return rc;
     }
     e->s = s;
-    e->slot_arena = arena;
-    e->slot_bytes = arena_bytes;
+    e->res.slot_arena = std::move(arena);  // (the old arena and the old objective rows go: slot 0 has been carried over)
+    e->oo_mem = std::move(oo);
     e->n_slots = n;
     e->slots_synced = std::min(e->slots_synced, 1);  // only slot 0 was carried over
-    if (e->spare_slot_arena) { hipFree(e->spare_slot_arena); e->spare_slot_arena = nullptr; }  // too small: not needed any more
+    e->spare_slot_arena.reset();                     // too small: not needed any more
     return JSLP_OK;
 }
 
-// forget every checkpoint; their buffers go to the free list (or back to the driver)
-static void drop_checkpoints(jslp_engine* e, int free_memory) {
+// forget every checkpoint; their buffers go to the free list
+static void drop_checkpoints(jslp_engine* e) {
     for (auto& c : e->ckpts)
-        if (c.live) e->ck_free.push_back(c.mem);
+        if (c.live) e->ck_free.push_back(std::move(c.mem));
     e->ckpts.clear();
-    if (free_memory) {
-        for (char* m : e->ck_free) hipFree(m);
-        e->ck_free.clear();
-    }
 }
 
-extern "C" int jslp_engine_create(jslp_engine** out, int device, int32_t height, int32_t width, int32_t row_capacity,
-                                  double precision) {
-    if (!out || height < 1 || width < 1 || row_capacity < height) return fail(JSLP_ERR_ARG, "create: bad dimensions");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-        return fail(JSLP_ERR_DEVICE, "create: no HIP device visible (this engine has no CPU fallback)");
-    if (device < 0 || device >= ndev) return fail(JSLP_ERR_ARG, "create: device ordinal out of range");
-    HIPC(hipSetDevice(device));
-    jslp_engine* e = new jslp_engine();
-    e->device = device;
-    e->H0 = height; e->W = width; e->cap_rows = row_capacity; e->precision = precision;
-    e->ld = round_up(width, 16);
-    e->n_idx = width + 2 * row_capacity + 2;
-    // partial pricing parameters (simplex.ts:118-127)
-    const int32_t n_columns = width - 1;
-    int32_t b = (int32_t)floor(sqrt((double)n_columns));
-    b = std::min(500, std::max(50, b));
-    e->batch = b;
-    e->use_partial = n_columns > b * 2;
+// every getenv of create(), read per engine
+static int read_engine_policy(jslp_engine* e) {
     const char* fp = getenv("JSLP_FORCE_PATH");
     if (fp && !strcmp(fp, "wg")) e->force_path = 1;
     if (fp && !strcmp(fp, "sp")) e->force_path = 2;
@@ -434,7 +358,7 @@ extern "C" int jslp_engine_create(jslp_engine** out, int device, int32_t height,
 #ifdef JSLP_WITH_XL
     if (fp && !strcmp(fp, "xl")) { e->force_path = 3; e->force_resident = 1; e->force_xl = 1; }  // the XCD-local resident geometry whatever the size (<= 1024 x 1024)
 #else
-    if (fp && !strcmp(fp, "xl")) { delete e; return fail(JSLP_ERR_UNSUPPORTED, "JSLP_FORCE_PATH=xl: the XCD-local kernels are compiled into the test library only (libjslp_hip_chaos.so, or build with -DJSLP_WITH_XL)"); }
+    if (fp && !strcmp(fp, "xl")) return fail(JSLP_ERR_UNSUPPORTED, "JSLP_FORCE_PATH=xl: the XCD-local kernels are compiled into the test library only (libjslp_hip_chaos.so, or build with -DJSLP_WITH_XL)");
 #endif
     // JSLP_XL=1: the XCD-local geometry for every tableau it takes.  OFF by default: as measured in round 4 (profiles/r04_xl_*) it is
     // correct on every golden but not faster than what these sizes had -- 6.4-6.8 us per pivot on dense 501 x 501 / 1001 x 1001 against
@@ -459,69 +383,71 @@ extern "C" int jslp_engine_create(jslp_engine** out, int device, int32_t height,
     e->test_abort_epoch = ta ? atoi(ta) : -1;
     const char* tl = getenv("JSLP_TEST_RESIDENT_LATE_WAVE0");  // tests only: wave 0 of every workgroup reaches each row fetch late
     e->test_late_wave0 = tl ? atoi(tl) : 0;
-    int rc = JSLP_OK;
-    PooledRes pooled;
-    const bool have = pool_take(device, &pooled);
-    auto init = [&]() -> int {
-        if (have) {
-            e->stream = pooled.stream; e->ev_begin = pooled.ev_begin; e->ev_end = pooled.ev_end; e->h_state = pooled.h_state;
-            e->spare_slot_arena = pooled.slot_arena; e->spare_slot_bytes = pooled.slot_bytes;
-            e->d_cuts = pooled.d_cuts; e->h_cuts = pooled.h_cuts; e->cuts_bytes = pooled.cuts_bytes;
-            e->d_out = pooled.d_out; e->h_out = pooled.h_out; e->out_bytes_cap = pooled.out_bytes;
-            e->h_up = pooled.h_up; e->h_up_bytes = pooled.h_up_bytes; e->d_up = pooled.d_up; e->d_up_bytes = pooled.d_up_bytes;
-            e->r_arena = pooled.r_arena; e->r_arena_bytes = pooled.r_arena_bytes;
-            e->copy_stream = pooled.copy_stream; e->ev_group = pooled.ev_group;
-        } else {
-            HIPC(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
-        }
-        {   // snapshot, unrestricted flags and pivot trace: one allocation
-            const size_t cells = (size_t)e->cap_rows * e->ld;
-            for (int pass = 0; pass < 2; pass++) {
-                Carver cv{pass ? e->static_arena : nullptr, 0};
-                e->d_unr = cv.take<uint8_t>((size_t)e->n_idx);
-                e->d_isint = cv.take<uint8_t>((size_t)e->n_idx);
-                e->snap_A = cv.take<double>(cells);
-                e->snap_rhs = cv.take<double>((size_t)e->cap_rows);
-                e->snap_ldT = (e->cap_rows + 1) & ~1;
-                e->snap_AT = wglds_bytes(e->ld, e->cap_rows) <= WGLDS_MAX_BYTES ? cv.take<double>((size_t)e->snap_ldT * e->W) : nullptr;
-                e->snap_vibr = cv.take<int32_t>((size_t)e->cap_rows);
-                e->snap_vibc = cv.take<int32_t>((size_t)e->W);
-                e->snap_rbv = cv.take<int32_t>((size_t)e->n_idx);
-                e->snap_cbv = cv.take<int32_t>((size_t)e->n_idx);
-                e->s.trace = cv.take<int2>((size_t)TRACE_CAP);
-                e->d_nnz = cv.take<unsigned long long>(1);
-                e->d_done_count = cv.take<int>(1);
-                if (!pass) {
-                    e->static_bytes = cv.off + 256;
-                    if (have && pooled.static_bytes >= e->static_bytes) {
-                        e->static_arena = pooled.static_arena;
-                        e->static_bytes = pooled.static_bytes;
-                    } else {
-                        if (have) hipFree(pooled.static_arena);
-                        HIPC(hipMalloc(&e->static_arena, e->static_bytes));
-                    }
-                }
-            }
-            e->s.trace_cap = TRACE_CAP;
-        }
-        HIPC(hipMemsetAsync(e->d_unr, 0, e->n_idx, e->stream));
-        HIPC(hipMemsetAsync(e->d_done_count, 0, sizeof(int), e->stream));
-        int r = ensure_slots(e, 1);
-        if (r) return r;
-        if (!have) {
-            HIPC(hipHostMalloc(&e->h_state, sizeof(DevState) + 64));
-            memset(e->h_state, 0, sizeof(DevState) + 64);
-            HIPC(hipEventCreate(&e->ev_begin));
-            HIPC(hipEventCreate(&e->ev_end));
-        }
-        // (no synchronisation here: the two memsets above are ordered in front of everything this engine will ever enqueue -- one
-        //  stream --, and a Solve() of a mid-size LP creates an engine per call)
-        // the completion flag lives behind the pinned state and travels with it through the resource pool: continue the
-        // previous owner's sequence (a fresh counter would meet the old owner's numbers again)
-        e->done_seq = *reinterpret_cast<unsigned*>(reinterpret_cast<char*>(e->h_state) + sizeof(DevState));
-        return JSLP_OK;
-    };
-    rc = init();
+    return JSLP_OK;
+}
+// snapshot, unrestricted flags and pivot trace: one allocation
+static void carve_static(jslp_engine* e, Carver& cv) {
+    e->d_unr = cv.take<uint8_t>((size_t)e->n_idx);
+    e->d_isint = cv.take<uint8_t>((size_t)e->n_idx);
+    e->snap_A = cv.take<double>((size_t)e->cap_rows * e->ld);
+    e->snap_rhs = cv.take<double>((size_t)e->cap_rows);
+    e->snap_ldT = (e->cap_rows + 1) & ~1;
+    e->snap_AT = wglds_bytes(e->ld, e->cap_rows) <= WGLDS_MAX_BYTES ? cv.take<double>((size_t)e->snap_ldT * e->W) : nullptr;
+    e->snap_vibr = cv.take<int32_t>((size_t)e->cap_rows);
+    e->snap_vibc = cv.take<int32_t>((size_t)e->W);
+    e->snap_rbv = cv.take<int32_t>((size_t)e->n_idx);
+    e->snap_cbv = cv.take<int32_t>((size_t)e->n_idx);
+    e->s.trace = cv.take<int2>((size_t)TRACE_CAP);
+    e->d_nnz = cv.take<unsigned long long>(1);
+    e->d_done_count = cv.take<int>(1);
+}
+// the device side of create(): a parked bundle or a new stream, the arenas, slot 0, the pinned state
+static int engine_init(jslp_engine* e) {
+    const bool have = pool_take(e->device, &e->res);
+    e->res.device = e->device;
+    if (have) e->spare_slot_arena = std::move(e->res.slot_arena);
+    else HIPC(hipStreamCreateWithFlags(&e->res.stream.h, hipStreamNonBlocking));
+    HIPC_CARVE(e->res.static_arena, [&](Carver& cv) { carve_static(e, cv); });
+    e->s.trace_cap = TRACE_CAP;
+    HIPC(hipMemsetAsync(e->d_unr, 0, e->n_idx, e->res.stream));
+    HIPC(hipMemsetAsync(e->d_done_count, 0, sizeof(int), e->res.stream));
+    JSLP_TRY(ensure_slots(e, 1));
+    if (!have) {
+        HIPC(e->res.h_state.reserve(sizeof(DevState) + 64));
+        memset(e->res.h_state.p, 0, sizeof(DevState) + 64);
+        HIPC(hipEventCreate(&e->res.ev_begin.h));
+        HIPC(hipEventCreate(&e->res.ev_end.h));
+    }
+    e->h_state = e->res.h_state.as<DevState>();
+    // (no synchronisation here: the two memsets above are ordered in front of everything this engine will ever enqueue -- one
+    //  stream --, and a Solve() of a mid-size LP creates an engine per call)
+    // the completion flag lives behind the pinned state and travels with it through the resource pool: continue the
+    // previous owner's sequence (a fresh counter would meet the old owner's numbers again)
+    e->done_seq = *reinterpret_cast<unsigned*>(e->res.h_state.p + sizeof(DevState));
+    return JSLP_OK;
+}
+
+extern "C" int jslp_engine_create(jslp_engine** out, int device, int32_t height, int32_t width, int32_t row_capacity,
+                                  double precision) {
+    if (!out || height < 1 || width < 1 || row_capacity < height) return fail(JSLP_ERR_ARG, "create: bad dimensions");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
+        return fail(JSLP_ERR_DEVICE, "create: no HIP device visible (this engine has no CPU fallback)");
+    if (device < 0 || device >= ndev) return fail(JSLP_ERR_ARG, "create: device ordinal out of range");
+    HIPC(hipSetDevice(device));
+    jslp_engine* e = new jslp_engine();
+    e->device = device;
+    e->H0 = height; e->W = width; e->cap_rows = row_capacity; e->precision = precision;
+    e->ld = round_up(width, 16);
+    e->n_idx = width + 2 * row_capacity + 2;
+    // partial pricing parameters (simplex.ts:118-127)
+    const int32_t n_columns = width - 1;
+    int32_t b = (int32_t)floor(sqrt((double)n_columns));
+    b = std::min(500, std::max(50, b));
+    e->batch = b;
+    e->use_partial = n_columns > b * 2;
+    int rc = read_engine_policy(e);
+    if (!rc) rc = engine_init(e);
     if (rc) { jslp_engine_destroy(e); return rc; }
     *out = e;
     return JSLP_OK;
@@ -530,47 +456,9 @@ extern "C" int jslp_engine_create(jslp_engine** out, int device, int32_t height,
 extern "C" void jslp_engine_destroy(jslp_engine* e) {
     if (!e) return;
     hipSetDevice(e->device);
-    if (e->stream) hipStreamSynchronize(e->stream);
-    if (e->copy_stream) hipStreamSynchronize(e->copy_stream);
-    if (e->spare_slot_arena) hipFree(e->spare_slot_arena);
-    bool parked = false;
-    if (e->stream && e->ev_begin && e->ev_end && e->h_state && e->static_arena && e->slot_arena) {
-        PooledRes r;
-        r.device = e->device; r.stream = e->stream; r.ev_begin = e->ev_begin; r.ev_end = e->ev_end; r.h_state = e->h_state;
-        r.static_arena = e->static_arena; r.static_bytes = e->static_bytes;
-        r.slot_arena = e->slot_arena; r.slot_bytes = e->slot_bytes;
-        r.d_cuts = e->d_cuts; r.h_cuts = e->h_cuts; r.cuts_bytes = e->cuts_bytes;
-        r.d_out = e->d_out; r.h_out = e->h_out; r.out_bytes = e->out_bytes_cap;
-        r.h_up = e->h_up; r.h_up_bytes = e->h_up_bytes; r.d_up = e->d_up; r.d_up_bytes = e->d_up_bytes;
-        r.r_arena = e->r_arena; r.r_arena_bytes = e->r_arena_bytes;
-        r.copy_stream = e->copy_stream; r.ev_group = e->ev_group;
-        parked = pool_give(r);
-    }
-    free_slots(e, parked);
-    if (parked) {
-        e->static_arena = nullptr; e->h_state = nullptr; e->ev_begin = e->ev_end = nullptr; e->stream = nullptr;
-        e->d_cuts = e->h_cuts = nullptr; e->d_out = e->h_out = nullptr; e->h_up = e->d_up = nullptr; e->r_arena = nullptr;
-        e->copy_stream = nullptr; e->ev_group = nullptr;
-    }
-    if (e->h_up) hipHostFree(e->h_up);
-    hipFree(e->d_up); hipFree(e->d_watch); hipFree(e->d_cnt); hipFree(e->r_arena);
-    hipFree(e->static_arena); hipFree(e->snap_oo);
-    drop_checkpoints(e, 1);
-    hipFree(e->arena32);
-    hipFree(e->f_uflags);
-    hipFree(e->f_oo1);
-    hipFree(e->f_buf1); hipFree(e->f_cands[0]); hipFree(e->f_cands[1]); hipFree(e->f_pcol[0]); hipFree(e->f_pcol[1]);
-    hipFree(e->f_st[0]); hipFree(e->f_st[1]);
-    hipFree(e->d_cuts); if (e->h_cuts) hipHostFree(e->h_cuts);
-    hipFree(e->d_out); if (e->h_out) hipHostFree(e->h_out);
-    hipFree(e->d_rec); if (e->h_rec) hipHostFree(e->h_rec);
-    if (e->h_state) hipHostFree(e->h_state);
-    for (auto ev : e->ev_pool) hipEventDestroy(ev);
-    if (e->ev_begin) hipEventDestroy(e->ev_begin);
-    if (e->ev_end) hipEventDestroy(e->ev_end);
-    if (e->ev_group) hipEventDestroy(e->ev_group);
-    if (e->copy_stream) hipStreamDestroy(e->copy_stream);
-    if (e->stream) hipStreamDestroy(e->stream);
+    if (e->res.stream) hipStreamSynchronize(e->res.stream);
+    if (e->res.copy_stream) hipStreamSynchronize(e->res.copy_stream);
+    if (e->res.complete()) pool_give(std::move(e->res));  // parked -- or it dies with everything else the engine owns
     delete e;
 }
 
@@ -578,19 +466,24 @@ extern "C" void jslp_engine_destroy(jslp_engine* e) {
 static size_t up_matrix_bytes(const jslp_engine* e) { return ((sizeof(double) * (size_t)e->H0 * e->W) + 255) & ~(size_t)255; }
 static size_t up_blob_bytes(const jslp_engine* e) { return sizeof(int32_t) * ((size_t)e->H0 + e->W + e->n_idx); }
 static int ensure_up(jslp_engine* e) {
-    const size_t total = up_matrix_bytes(e) + up_blob_bytes(e);
-    if (e->h_up_bytes < total) {
-        if (e->h_up) hipHostFree(e->h_up);
-        e->h_up = nullptr; e->h_up_bytes = 0;
-        HIPC(hipHostMalloc(&e->h_up, total));
-        e->h_up_bytes = total;
-    }
-    if (e->d_up_bytes < total) {
-        hipFree(e->d_up);
-        e->d_up = nullptr; e->d_up_bytes = 0;
-        HIPC(hipMalloc(&e->d_up, total));
-        e->d_up_bytes = total;
-    }
+    HIPC(e->res.up.reserve(up_matrix_bytes(e) + up_blob_bytes(e)));
+    return JSLP_OK;
+}
+// the number of optional objectives changes: their rows in every slot (zeroed) and in the snapshot; nothing may be in flight.
+// The counts are committed only once both buffers exist: a failed call leaves an engine without optional objectives
+static int resize_optional_objectives(jslp_engine* e, int32_t n) {
+    e->oo_mem.reset(); e->snap_oo_mem.reset();
+    e->s.oo = nullptr; e->snap_oo = nullptr;
+    e->n_opt = 0; e->s.n_opt = 0; e->s.oo_stride = 0;
+    if (n == 0) return JSLP_OK;
+    const size_t per = sizeof(double) * (size_t)n * e->ld, all = per * std::max(1, e->n_slots);
+    HIPC(e->oo_mem.reserve(all));
+    HIPC(e->snap_oo_mem.reserve(per));
+    e->s.oo = e->oo_mem.as<double>(); e->snap_oo = e->snap_oo_mem.as<double>();
+    e->n_opt = n; e->s.n_opt = n;
+    e->s.oo_stride = (long long)n * e->ld;
+    HIPC(hipMemsetAsync(e->s.oo, 0, all, e->res.stream));
+    HIPC(hipStreamSynchronize(e->res.stream));
     return JSLP_OK;
 }
 
@@ -599,9 +492,9 @@ extern "C" int jslp_engine_host_matrix(jslp_engine* e, double** matrix, int64_t*
     HIPC(hipSetDevice(e->device));
     int rc = ensure_up(e);
     if (rc) return rc;
-    memset(e->h_up, 0, sizeof(double) * (size_t)e->H0 * e->W);  // a fresh Float64Array is zero-filled (tableau.ts:304)
+    memset(e->res.up.h.p, 0, sizeof(double) * (size_t)e->H0 * e->W);  // a fresh Float64Array is zero-filled (tableau.ts:304)
     e->host_matrix_out = 1;
-    *matrix = reinterpret_cast<double*>(e->h_up);
+    *matrix = reinterpret_cast<double*>(e->res.up.h.p);
     if (n_doubles) *n_doubles = (int64_t)e->H0 * e->W;
     return JSLP_OK;
 }
@@ -619,7 +512,7 @@ extern "C" int jslp_engine_upload(jslp_engine* e, const double* matrix, const in
     // everything crosses PCIe from pinned memory: the matrix as ONE DMA (straight from the buffer the host built it in when
     // it used jslp_engine_host_matrix), the maps as one small blob; the inverse maps, flags and state are built on the device
     const size_t mat = sizeof(double) * (size_t)H * W, mat_pad = up_matrix_bytes(e);
-    int32_t* b_vibr = reinterpret_cast<int32_t*>(e->h_up + mat_pad);
+    int32_t* b_vibr = reinterpret_cast<int32_t*>(e->res.up.h.p + mat_pad);
     int32_t* b_vibc = b_vibr + H;
     int32_t* b_unr = b_vibc + W;
     b_vibr[0] = -1; b_vibc[0] = -1;
@@ -642,18 +535,18 @@ extern "C" int jslp_engine_upload(jslp_engine* e, const double* matrix, const in
         if (v < 0 || v >= e->n_idx) return fail(JSLP_ERR_ARG, "upload: unrestricted variable index out of range");
         b_unr[i] = v;
     }
-    if (matrix != reinterpret_cast<const double*>(e->h_up)) memcpy(e->h_up, matrix, mat);  // pageable caller memory: stage it once
-    hipStream_t s = e->stream;
+    if (matrix != reinterpret_cast<const double*>(e->res.up.h.p)) memcpy(e->res.up.h.p, matrix, mat);  // pageable caller memory: stage it once
+    hipStream_t s = e->res.stream;
     const size_t blob = sizeof(int32_t) * ((size_t)H + W + (size_t)n_unrestricted);
-    char* d_blob = e->d_up + mat_pad;
+    char* d_blob = e->res.up.d.p + mat_pad;
     if (W == e->ld) {
-        HIPC(hipMemcpyAsync(e->s.A, e->h_up, mat, hipMemcpyHostToDevice, s));
-        HIPC(hipMemcpyAsync(d_blob, e->h_up + mat_pad, blob, hipMemcpyHostToDevice, s));
+        HIPC(hipMemcpyAsync(e->s.A, e->res.up.h.p, mat, hipMemcpyHostToDevice, s));
+        HIPC(hipMemcpyAsync(d_blob, e->res.up.h.p + mat_pad, blob, hipMemcpyHostToDevice, s));
     } else {  // one DMA for matrix + blob, then the W -> ld repack on the device (padding columns become 0)
-        HIPC(hipMemcpyAsync(e->d_up, e->h_up, mat_pad + blob, hipMemcpyHostToDevice, s));
+        HIPC(hipMemcpyAsync(e->res.up.d.p, e->res.up.h.p, mat_pad + blob, hipMemcpyHostToDevice, s));
         const long long cells = (long long)H * e->ld;
         hipLaunchKernelGGL(k_repack, dim3((unsigned)std::min<long long>(2048, (cells + 255) / 256)), dim3(256), 0, s, e->s.A,
-                           reinterpret_cast<const double*>(e->d_up), (int)H, (int)W, (int)e->ld);
+                           reinterpret_cast<const double*>(e->res.up.d.p), (int)H, (int)W, (int)e->ld);
     }
     HIPC(hipMemsetAsync(e->d_nnz, 0, sizeof(unsigned long long), s));
     hipLaunchKernelGGL(k_count_nnz, dim3(256), dim3(256), 0, s, e->s.A, (int)H, (int)e->ld, e->d_nnz);
@@ -672,32 +565,20 @@ extern "C" int jslp_engine_upload(jslp_engine* e, const double* matrix, const in
     e->root_seq += 1;
     e->slot0_synced = 0;
     e->slots_synced = 0;
-    drop_checkpoints(e, 0);
+    drop_checkpoints(e);
     e->evaluation = 0;
     e->n_unr = n_unrestricted;
     e->s.has_unr = n_unrestricted > 0 ? 1 : 0;
-    if (e->n_opt > 0) {  // a new model: optional objectives are set again by the caller
-        hipFree(e->s.oo); hipFree(e->snap_oo);
-        e->s.oo = nullptr; e->snap_oo = nullptr; e->s.n_opt = 0; e->s.oo_stride = 0; e->n_opt = 0;
-    }
-    return JSLP_OK;
+    return e->n_opt > 0 ? resize_optional_objectives(e, 0) : JSLP_OK;  // a new model: optional objectives are set again by the caller
 }
 
 extern "C" int jslp_engine_set_optional_objectives(jslp_engine* e, int32_t n, const double* rows) {
     if (!e || !e->uploaded) return fail(JSLP_ERR_STATE, "set_optional_objectives before upload");
     if (n < 0 || (n > 0 && !rows)) return fail(JSLP_ERR_ARG, "set_optional_objectives: bad arguments");
     HIPC(hipSetDevice(e->device));
-    HIPC(hipStreamSynchronize(e->stream));
-    hipFree(e->s.oo); hipFree(e->snap_oo);
-    e->s.oo = nullptr; e->snap_oo = nullptr;
-    e->n_opt = n;
-    e->s.n_opt = n;
-    e->s.oo_stride = (long long)n * e->ld;
+    HIPC(hipStreamSynchronize(e->res.stream));
+    JSLP_TRY(resize_optional_objectives(e, n));
     if (n > 0) {
-        const size_t per = (size_t)e->s.oo_stride;
-        HIPC(hipMalloc(&e->s.oo, sizeof(double) * per * std::max(1, e->n_slots)));
-        HIPC(hipMalloc(&e->snap_oo, sizeof(double) * per));
-        HIPC(hipMemset(e->s.oo, 0, sizeof(double) * per * std::max(1, e->n_slots)));
         HIPC(hipMemcpy2D(e->s.oo, sizeof(double) * e->ld, rows, sizeof(double) * e->W, sizeof(double) * e->W, n,
                          hipMemcpyHostToDevice));
     }
@@ -709,7 +590,7 @@ extern "C" int jslp_engine_get_optional_objectives(jslp_engine* e, double* rows,
     HIPC(hipSetDevice(e->device));
     if (n_out) *n_out = e->n_opt;
     if (rows && e->n_opt > 0) {
-        HIPC(hipStreamSynchronize(e->stream));
+        HIPC(hipStreamSynchronize(e->res.stream));
         HIPC(hipMemcpy2D(rows, sizeof(double) * e->W, e->s.oo, sizeof(double) * e->ld, sizeof(double) * e->W, e->n_opt,
                          hipMemcpyDeviceToHost));
     }
@@ -761,7 +642,7 @@ static bool use_wg_single(const jslp_engine* e) {
 }
 // ... that solve: the LDS-resident kernel when the tableau fits its LDS, else the generic one
 static int solve_one_workgroup(jslp_engine* e, int check_cycles) {
-    hipStream_t s = e->stream;
+    hipStream_t s = e->res.stream;
     const int cap = iters_cap(e);
     e->last_path = "workgroup";
     if (const size_t lds = wglds_smem(e); lds && e->s.n_opt > 0)  // optional objectives: a build of their own (jslp_wglds.hip.h)
@@ -856,11 +737,10 @@ static int ensure_resident(jslp_engine* e, bool want_hist = false) {
     const size_t slot_doubles = getenv("JSLP_RES_GEOM") ? (size_t)4096 + JSLP_PUB_SKEW / 8
                                 : (e->ld <= 2048 ? (size_t)e->ld : ((size_t)e->ld + 1023) / 1024 * 1024 + JSLP_PUB_SKEW / 8);
     if (e->r_sync && (!e->r_want_hist || e->r_hist_all) && e->r_slot_doubles >= slot_doubles) return JSLP_OK;
-    if (e->r_sync) HIPC(hipStreamSynchronize(e->stream));  // re-carving: nothing in flight may still use the old layout
+    if (e->r_sync) HIPC(hipStreamSynchronize(e->res.stream));  // re-carving: nothing in flight may still use the old layout
     // hand-off buffers and the safety-net copy of slot 0 (matrix, maps, state) carved from ONE allocation, which the
-    // resource pool hands from engine to engine (hipMalloc / hipFree of these cost a small Solve more than its pivots)
-    for (int pass = 0; pass < 2; pass++) {
-        Carver cv{pass ? e->r_arena : nullptr, 0};
+    // resource pool hands from engine to engine (allocating and freeing these cost a small Solve more than its pivots)
+    HIPC_CARVE(e->res.r_arena, [&](Carver& cv) {
         e->r_gran = cv.take<u64_t>(JSLP_R_SYNC_WORDS);
         // (slots ld doubles apart; the 6- and 8-column geometries' permuted layout -- jslp_resident_pipe.hip.h, SLOT -- takes lanes x columns per lane
         //  = 3072 / 4096 doubles plus a skew per slot)
@@ -875,56 +755,50 @@ static int ensure_resident(jslp_engine* e, bool want_hist = false) {
         e->r_backup_st = cv.take<DevState>(1);
         e->r_ctx_dev = reinterpret_cast<Ctx*>(cv.take<char>(sizeof(Ctx) + 16));  // (+ the address of the host-abort word: JSLP_HOST_ABORT_CHECK)
         e->r_slot_doubles = slot_doubles;
-        if (!pass && e->r_arena_bytes < cv.off + 256) {
-            hipFree(e->r_arena);
-            e->r_arena = nullptr; e->r_arena_bytes = 0; e->r_sync = nullptr;
-            HIPC(hipMalloc(&e->r_arena, cv.off + 256));
-            e->r_arena_bytes = cv.off + 256;
-        }
-    }
+    });
     return JSLP_OK;
 }
 
 static int ensure_fused(jslp_engine* e) {
-    if (e->f_buf1) return JSLP_OK;
+    if (e->f_ready) return JSLP_OK;  // (set last: a call that failed half way is not taken for done by the next)
     const size_t cells = (size_t)e->cap_rows * e->ld;
-    HIPC(hipMalloc(&e->f_buf1, sizeof(double) * cells));
-    HIPC(hipMemsetAsync(e->f_buf1, 0, sizeof(double) * cells, e->stream));
+    HIPC(e->f_buf1.reserve(sizeof(double) * cells));
+    HIPC(hipMemsetAsync(e->f_buf1.p, 0, sizeof(double) * cells, e->res.stream));
     for (int i = 0; i < 2; i++) {
-        HIPC(hipMalloc(&e->f_cands[i], sizeof(FCand) * JSLP_F_MAXG));
-        HIPC(hipMalloc(&e->f_pcol[i], sizeof(double) * e->cap_rows));
-        HIPC(hipMalloc(&e->f_st[i], sizeof(DevState)));
-        HIPC(hipMemsetAsync(e->f_st[i], 0, sizeof(DevState), e->stream));
+        HIPC(e->f_cands[i].reserve(sizeof(FCand) * JSLP_F_MAXG));
+        HIPC(e->f_pcol[i].reserve(sizeof(double) * e->cap_rows));
+        HIPC(e->f_st[i].reserve(sizeof(DevState)));
+        HIPC(hipMemsetAsync(e->f_st[i].p, 0, sizeof(DevState), e->res.stream));
     }
-    HIPC(hipMalloc(&e->f_uflags, 2 * ((size_t)e->ld + (size_t)e->cap_rows)));
-    HIPC(hipMemsetAsync(e->f_uflags, 0, 2 * ((size_t)e->ld + (size_t)e->cap_rows), e->stream));
+    HIPC(e->f_uflags.reserve(2 * ((size_t)e->ld + (size_t)e->cap_rows)));
+    HIPC(hipMemsetAsync(e->f_uflags.p, 0, 2 * ((size_t)e->ld + (size_t)e->cap_rows), e->res.stream));
+    e->f_ready = 1;
     return JSLP_OK;
 }
 
 static int ensure_fused_oo(jslp_engine* e) {  // (the number of optional objectives is set per model, after create())
     if (e->n_opt <= e->f_oo1_rows) return JSLP_OK;
-    HIPC(hipStreamSynchronize(e->stream));
-    hipFree(e->f_oo1);
-    e->f_oo1 = nullptr; e->f_oo1_rows = 0;
-    HIPC(hipMalloc(&e->f_oo1, sizeof(double) * (size_t)e->n_opt * e->ld));
-    HIPC(hipMemsetAsync(e->f_oo1, 0, sizeof(double) * (size_t)e->n_opt * e->ld, e->stream));
+    HIPC(hipStreamSynchronize(e->res.stream));
+    e->f_oo1_rows = 0;
+    HIPC(e->f_oo1.reserve(sizeof(double) * (size_t)e->n_opt * e->ld));
+    HIPC(hipMemsetAsync(e->f_oo1.p, 0, sizeof(double) * (size_t)e->n_opt * e->ld, e->res.stream));
     e->f_oo1_rows = e->n_opt;
     return JSLP_OK;
 }
 static FusedCtx make_fused_ctx(const jslp_engine* e, const Ctx& c, int H) {
     FusedCtx f;
     f.c = c;
-    f.buf[0] = e->s.A; f.buf[1] = e->f_buf1;
-    for (int i = 0; i < 2; i++) { f.cands[i] = e->f_cands[i]; f.pcol[i] = e->f_pcol[i]; f.fst[i] = e->f_st[i]; }
+    f.buf[0] = e->s.A; f.buf[1] = e->f_buf1.as<double>();
+    for (int i = 0; i < 2; i++) { f.cands[i] = e->f_cands[i].as<FCand>(); f.pcol[i] = e->f_pcol[i].as<double>(); f.fst[i] = e->f_st[i].as<DevState>(); }
     f.rpb = (H + JSLP_F_MAXG - 1) / JSLP_F_MAXG;
     f.G = (H + f.rpb - 1) / f.rpb;
     f.H = H;
     f.nt = e->nt;
     for (int i = 0; i < 2; i++) {
-        f.ucol[i] = e->f_uflags + (size_t)i * ((size_t)e->ld + e->cap_rows);
+        f.ucol[i] = e->f_uflags.as<uint8_t>() + (size_t)i * ((size_t)e->ld + e->cap_rows);
         f.urow[i] = f.ucol[i] + e->ld;
     }
-    f.oo[0] = e->s.oo; f.oo[1] = e->f_oo1;
+    f.oo[0] = e->s.oo; f.oo[1] = e->f_oo1.as<double>();
     return f;
 }
 
@@ -1001,9 +875,9 @@ static int fill_result(jslp_engine* e, const DevState& st, int slot, double prev
 
 static int ensure_events(jslp_engine* e, size_t n) {
     while (e->ev_pool.size() < n) {
-        hipEvent_t ev;
-        HIPC(hipEventCreate(&ev));
-        e->ev_pool.push_back(ev);
+        Event ev;
+        HIPC(hipEventCreate(&ev.h));
+        e->ev_pool.push_back(std::move(ev));
     }
     return JSLP_OK;
 }
@@ -1032,7 +906,7 @@ struct SolveRun {
     bool dbg = false;          // JSLP_DEBUG_LAUNCH: one parseable stderr line per launch decision (tests/test_grid_edges.py)
 };
 static int plan_solve(jslp_engine* e, int check_cycles, SolveRun* p) {
-    hipStream_t s = e->stream;
+    hipStream_t s = e->res.stream;
     p->check_cycles = check_cycles;
     p->cap = iters_cap(e);
     p->c = host_ctx(e, check_cycles);
@@ -1057,8 +931,8 @@ static int plan_solve(jslp_engine* e, int check_cycles, SolveRun* p) {
     return JSLP_OK;
 }
 static int fetch_state(jslp_engine* e, const DevState* from) {  // the host's copy of a device state, waited for
-    HIPC(hipMemcpyAsync(e->h_state, from, sizeof(DevState), hipMemcpyDeviceToHost, e->stream));
-    HIPC(hipStreamSynchronize(e->stream));
+    HIPC(hipMemcpyAsync(e->h_state, from, sizeof(DevState), hipMemcpyDeviceToHost, e->res.stream));
+    HIPC(hipStreamSynchronize(e->res.stream));
     return JSLP_OK;
 }
 
@@ -1122,7 +996,7 @@ static ResCtx make_res_ctx(const jslp_engine* e, const SolveRun& p) {
 }
 // what a launch needs on the stream in front of it: zeroed hand-off words, the device copy of the context, the host-abort word
 static int resident_setup(jslp_engine* e, const SolveRun& p, ResCtx& rc) {
-    hipStream_t s = e->stream;
+    hipStream_t s = e->res.stream;
     HIPC(hipMemsetAsync(e->r_gran, 0, sizeof(u64_t) * JSLP_R_SYNC_WORDS, s));  // tags restart at 1
     HIPC(hipMemcpyAsync(e->r_ctx_dev, &rc.c, sizeof(Ctx), hipMemcpyHostToDevice, s));  // (200 bytes; the kernel's one committing thread reads the map / trace pointers from it)
     // the host-abort word (pinned, behind the state and the retry counter) and its address behind the device copy of the context
@@ -1131,8 +1005,9 @@ static int resident_setup(jslp_engine* e, const SolveRun& p, ResCtx& rc) {
     e->h_abort_ptr = h_abort;
     HIPC(hipMemcpyAsync(reinterpret_cast<char*>(e->r_ctx_dev) + sizeof(Ctx), &e->h_abort_ptr, sizeof(unsigned*), hipMemcpyHostToDevice, s));
 #ifdef JSLP_DEBUG_RESIDENT
-    static u64_t* dbg_buf = nullptr;
-    if (!dbg_buf) HIPC(hipMalloc(&dbg_buf, sizeof(u64_t) * (512 * JSLP_F_MAXG * 2 + 16384)));
+    static DevBuf& dbg_mem = *new DevBuf();  // (never destroyed: see g_pool)
+    HIPC(dbg_mem.reserve(sizeof(u64_t) * (512 * JSLP_F_MAXG * 2 + 16384)));
+    u64_t* const dbg_buf = dbg_mem.as<u64_t>();
     HIPC(hipMemsetAsync(dbg_buf, 0, sizeof(u64_t) * (512 * JSLP_F_MAXG * 2 + 16384), s));
     rc.dbg = dbg_buf;
 #endif
@@ -1150,7 +1025,7 @@ static int resident_setup(jslp_engine* e, const SolveRun& p, ResCtx& rc) {
 // copy of slot 0 (one pass over the matrix, ~15 us at 2001 x 2001 against a ~100 ms solve) to roll back to.
 static void resident_safety_net(jslp_engine* e, const SolveRun& p, int save) {  // save 1: slot 0 -> the copy; 0: the copy -> slot 0
     SnapshotW bk{e->rb_A, e->rb_vibr, e->rb_vibc, e->rb_rbv, e->rb_cbv, e->n_idx, nullptr, nullptr};
-    hipLaunchKernelGGL(k_res_backup, dim3(copy_grid(e, 1).x), dim3(256), 0, e->stream, e->s, bk, e->r_backup_st, p.H, save);
+    hipLaunchKernelGGL(k_res_backup, dim3(copy_grid(e, 1).x), dim3(256), 0, e->res.stream, e->s, bk, e->r_backup_st, p.H, save);
 }
 // JSLP_INJECT_RESIDENT_ABORT_US=<n>: raise the host-abort word n microseconds into the launch -- the rollback path (kernel gives
 // up mid-solve, slot 0 restored from the safety-net copy, the solve re-run through the streaming kernels) exercised on the
@@ -1178,7 +1053,7 @@ static int resident_launch(jslp_engine* e, const SolveRun& p, const ResCtx& rc, 
     const bool unr = e->n_unr > 0;  // unrestricted variables: the UNR build threads the per-column flags through
     // (chk: the instance's template key -- the general build is compiled with CHK = true and reads check_cycles at run time)
     const int key[8] = {g.threads, g.cols, g.rows, unr ? 1 : 0, lean ? 1 : 0, e->n_opt > 0 ? 1 : 0, (p.check_cycles != 0 || !lean) ? 1 : 0, p.geometry == RES_GEOM_XL ? 1 : 0};
-    const int r = resident_dispatch(key, (unsigned)rc.G, &rc, e->stream);
+    const int r = resident_dispatch(key, (unsigned)rc.G, &rc, e->res.stream);
     if (r == -1 && RES_DEV_REFUSAL) return fail(JSLP_ERR_UNSUPPORTED, "%s", RES_DEV_REFUSAL);
     *le = r == -1 ? hipErrorInvalidValue : (hipError_t)r;  // (-1: no such instance -- the refusal branch counts it)
     if (*le != hipSuccess) return JSLP_OK;
@@ -1197,7 +1072,7 @@ static void account_resident_time(jslp_engine* e, long long it_before) {
 }
 // an accepted launch has run to its end: the final state, or the roll back to the safety-net copy
 static int resident_finish(jslp_engine* e, const SolveRun& p, const ResCtx& rc, long long it_before, Resident* out) {
-    hipStream_t s = e->stream;
+    hipStream_t s = e->res.stream;
     if (e->timing) HIPC(hipEventRecord(e->ev_pool[1], s));
     JSLP_TRY(fetch_state(e, e->s.st));
     if (e->timing) account_resident_time(e, it_before);
@@ -1237,7 +1112,7 @@ static int resident_finish(jslp_engine* e, const SolveRun& p, const ResCtx& rc, 
 }
 // `it_before`: pivots the solve had done when the kernel is launched (0, or a phase 1 done by the fused pipeline)
 static int resident_attempt(jslp_engine* e, const SolveRun& p, long long it_before, Resident* out) {
-    hipStream_t s = e->stream;
+    hipStream_t s = e->res.stream;
     // (the lean kernel's per-workgroup copies of the cycle-check history are carved once a lean solve with the check on comes by: ensure_resident)
     JSLP_TRY(ensure_resident(e, p.lean && p.check_cycles != 0));
     ResCtx rc = make_res_ctx(e, p);
@@ -1306,7 +1181,7 @@ static const FusedKernel& pivot_fused_kernel(const jslp_engine* e) {
     return PIVOT_FUSED[t <= 2 ? 4 * (t - 1) + (e->n_unr > 0 ? 0 : 2) + (e->n_opt > 0 ? 0 : 1) : t + 5];
 }
 static void launch_fused(const jslp_engine* e, const FusedKernel& k, const FusedCtx& f, int launch) {
-    hipLaunchKernelGGL(k.fn, dim3(f.G), dim3(JSLP_F_THREADS), 0, e->stream, f, launch);
+    hipLaunchKernelGGL(k.fn, dim3(f.G), dim3(JSLP_F_THREADS), 0, e->res.stream, f, launch);
 }
 // add up the event pairs of the pivots of a chunk that really ran: launches after the solve ended are no-ops, only the first `real` did a pivot.
 // Returns the solve's pivot count, the next chunk's `done_prev`
@@ -1324,7 +1199,7 @@ static long long account_chunk_time(jslp_engine* e, int chunk, long long done_pr
 // `chunk_cap`, until the state leaves ST_RUNNING.  k == nullptr: k_select + k_update per pivot, the state is slot 0's; else one launch of the fused
 // kernel k per pivot, numbered by *launch, the state the pipeline's own (f->fst).  `timed`: an event pair around every k_update / fused launch
 static int stream_pivots(jslp_engine* e, const SolveRun& p, const FusedKernel* k, const FusedCtx* f, int* launch, int chunk, int chunk_cap, bool timed, long long done_prev) {
-    hipStream_t s = e->stream;
+    hipStream_t s = e->res.stream;
     for (;;) {
         if (timed) JSLP_TRY(ensure_events(e, 2 * (size_t)chunk));
         for (int i = 0; i < chunk; i++) {
@@ -1343,7 +1218,7 @@ static int stream_pivots(jslp_engine* e, const SolveRun& p, const FusedKernel* k
 }
 // the ONE pivot a fused pipeline cannot decide alone (ST_P1_SLOW, see k_fused_p1 / k_pivot_fused): through k_select + k_update
 static int slow_pivot(jslp_engine* e, const SolveRun& p) {
-    hipStream_t s = e->stream;
+    hipStream_t s = e->res.stream;
     hipLaunchKernelGGL(k_p1_resume, dim3(1), dim3(1), 0, s, e->s.st, (int)ST_RUNNING);
     hipLaunchKernelGGL(k_select, dim3(1), dim3(JSLP_WG_THREADS), 0, s, p.c);
     hipLaunchKernelGGL(k_update, p.grid, dim3(JSLP_UPD_THREADS), 0, s, p.c);
@@ -1363,7 +1238,7 @@ static int fused_phase1(jslp_engine* e, const SolveRun& p) {
         int launch = 0;
         launch_fused(e, k, f, launch++);
         JSLP_TRY(stream_pivots(e, p, &k, &f, &launch, 2, 512, false, 0));
-        hipLaunchKernelGGL(k_fused_finish, dim3(512), dim3(256), 0, e->stream, f, launch - 1);  // state -> slot 0's, tableau -> buf[0]
+        hipLaunchKernelGGL(k_fused_finish, dim3(512), dim3(256), 0, e->res.stream, f, launch - 1);  // state -> slot 0's, tableau -> buf[0]
         HIPC(hipGetLastError());
         if (e->h_state->status != ST_P1_SLOW) break;
         JSLP_TRY(slow_pivot(e, p));  // ... then the pipeline again
@@ -1379,7 +1254,7 @@ static int select_update_loop(jslp_engine* e, const SolveRun& p) {
 }
 // phase 2: one fused launch per pivot (k_pivot_fused)
 static int fused_phase2(jslp_engine* e, const SolveRun& p) {
-    hipStream_t s = e->stream;
+    hipStream_t s = e->res.stream;
     while (e->h_state->status == ST_PHASE1_DONE) {
         JSLP_TRY(ensure_fused(e));
         JSLP_TRY(ensure_fused_oo(e));
@@ -1413,10 +1288,10 @@ static int fused_phase2(jslp_engine* e, const SolveRun& p) {
 }
 // the closing events; e->h_state is the solve's final state
 static int close_solve(jslp_engine* e) {
-    HIPC(hipEventRecord(e->ev_end, e->stream));
-    HIPC(hipStreamSynchronize(e->stream));
+    HIPC(hipEventRecord(e->res.ev_end, e->res.stream));
+    HIPC(hipStreamSynchronize(e->res.stream));
     float ms = 0;
-    if (hipEventElapsedTime(&ms, e->ev_begin, e->ev_end) == hipSuccess) e->total_ms += ms;
+    if (hipEventElapsedTime(&ms, e->res.ev_begin, e->res.ev_end) == hipSuccess) e->total_ms += ms;
     return state_error(*e->h_state);
 }
 
@@ -1424,14 +1299,14 @@ static int close_solve(jslp_engine* e) {
 static int run_simplex(jslp_engine* e, int check_cycles) {
     e->slot0_synced = 0;  // the chip-wide kernels do not maintain the dirty-row flags (k_begin zeroes st.gen)
     e->abort_injected = 0;
-    HIPC(hipEventRecord(e->ev_begin, e->stream));
+    HIPC(hipEventRecord(e->res.ev_begin, e->res.stream));
     if (use_wg_single(e)) {
         JSLP_TRY(solve_one_workgroup(e, check_cycles));
         return close_solve(e);
     }
     SolveRun p;
     JSLP_TRY(plan_solve(e, check_cycles, &p));
-    hipLaunchKernelGGL(k_begin, dim3(1), dim3(1), 0, e->stream, e->s, 0, p.cap);
+    hipLaunchKernelGGL(k_begin, dim3(1), dim3(1), 0, e->res.stream, e->s, 0, p.cap);
     Resident res = Resident::NotTried;
     if (p.geometry != 0 && !p.phase2_only) JSLP_TRY(resident_attempt(e, p, 0, &res));
     if (res != Resident::Done) {
@@ -1463,7 +1338,7 @@ extern "C" int jslp_engine_simplex(jslp_engine* e, int check_cycles, jslp_simple
 extern "C" int jslp_engine_pivot(jslp_engine* e, int32_t row, int32_t col) {
     if (!e || !e->uploaded) return fail(JSLP_ERR_STATE, "pivot before upload");
     HIPC(hipSetDevice(e->device));
-    hipStream_t s = e->stream;
+    hipStream_t s = e->res.stream;
     HIPC(hipMemcpyAsync(e->h_state, e->s.st, sizeof(DevState), hipMemcpyDeviceToHost, s));
     HIPC(hipStreamSynchronize(s));
     const int H = e->h_state->H;
@@ -1488,7 +1363,7 @@ static dim3 copy_grid(const jslp_engine* e, int slots) {
 // the saved root once more, column-major, for the node kernels' pivot-column reads (WgLds::snapT)
 static void launch_snapshot_transpose(jslp_engine* e) {
     if (!e->snap_AT) return;
-    hipLaunchKernelGGL(k_snapshot_transpose, dim3((e->W + 31) / 32, (e->cap_rows + 31) / 32), dim3(256), 0, e->stream, e->s.st, e->snap_A,
+    hipLaunchKernelGGL(k_snapshot_transpose, dim3((e->W + 31) / 32, (e->cap_rows + 31) / 32), dim3(256), 0, e->res.stream, e->s.st, e->snap_A,
                        (int)e->ld, (int)e->W, e->snap_AT, e->snap_ldT);
 }
 static Snapshot root_snapshot(const jslp_engine* e) {
@@ -1502,10 +1377,10 @@ extern "C" int jslp_engine_save(jslp_engine* e) {
     SnapshotW w{e->snap_A, e->snap_vibr, e->snap_vibc, e->snap_rbv, e->snap_cbv, e->n_idx, e->snap_oo, e->snap_rhs};
     e->slot0_synced = 0;  // new snapshot generation
     e->slots_synced = 0;
-    hipLaunchKernelGGL(k_save, dim3(copy_grid(e, 1).x), dim3(256), 0, e->stream, e->s, w);
+    hipLaunchKernelGGL(k_save, dim3(copy_grid(e, 1).x), dim3(256), 0, e->res.stream, e->s, w);
     launch_snapshot_transpose(e);
     HIPC(hipGetLastError());
-    HIPC(hipStreamSynchronize(e->stream));
+    HIPC(hipStreamSynchronize(e->res.stream));
     e->has_save = 1;
     e->root_seq += 1;
     return JSLP_OK;
@@ -1525,13 +1400,13 @@ static int enqueue_restore(jslp_engine* e, int first_slot, int n, int checkpoint
     if (checkpoint < 0) {
         if (!e->has_save) return JSLP_OK;  // backup.ts:54-56
         Snapshot sn = root_snapshot(e);
-        hipLaunchKernelGGL(k_restore, copy_grid(e, n), dim3(256), 0, e->stream, e->s, sn, first_slot);
+        hipLaunchKernelGGL(k_restore, copy_grid(e, n), dim3(256), 0, e->res.stream, e->s, sn, first_slot);
     } else {
         const jslp_engine::Ckpt& c = e->ckpts[checkpoint];
         Snapshot sn{c.A, c.vibr, c.vibc, c.rbv, c.cbv, e->n_idx, nullptr, c.H, c.last_element_index, c.rhs};
-        hipLaunchKernelGGL(k_restore, copy_grid(e, n), dim3(256), 0, e->stream, e->s, sn, first_slot);
+        hipLaunchKernelGGL(k_restore, copy_grid(e, n), dim3(256), 0, e->res.stream, e->s, sn, first_slot);
     }
-    hipLaunchKernelGGL(k_restore_commit, dim3(n), dim3(1), 0, e->stream, e->s, first_slot, checkpoint < 0 ? 1 : 0);
+    hipLaunchKernelGGL(k_restore_commit, dim3(n), dim3(1), 0, e->res.stream, e->s, first_slot, checkpoint < 0 ? 1 : 0);
     HIPC(hipGetLastError());
     return JSLP_OK;
 }
@@ -1547,38 +1422,36 @@ extern "C" int jslp_engine_checkpoint_create(jslp_engine* e, int32_t* id_out) {
     if (!e->uploaded) return fail(JSLP_ERR_STATE, "checkpoint_create before upload");
     HIPC(hipSetDevice(e->device));
     // height / lastElementIndex of the live tableau
-    HIPC(hipMemcpyAsync(e->h_state, e->s.st, sizeof(DevState), hipMemcpyDeviceToHost, e->stream));
-    HIPC(hipStreamSynchronize(e->stream));
+    HIPC(hipMemcpyAsync(e->h_state, e->s.st, sizeof(DevState), hipMemcpyDeviceToHost, e->res.stream));
+    HIPC(hipStreamSynchronize(e->res.stream));
     jslp_engine::Ckpt c;
-    for (int pass = 0; pass < 2; pass++) {  // every buffer is sized for the row capacity, so freed ones fit any later checkpoint
-        Carver cv{pass ? c.mem : nullptr, 0};
+    if (!e->ck_free.empty()) {  // every buffer is sized for the row capacity, so freed ones fit any later checkpoint
+        c.mem = std::move(e->ck_free.back());
+        e->ck_free.pop_back();
+    }
+    const hipError_t err = carve_into(c.mem, [&](Carver& cv) {
         c.A = cv.take<double>((size_t)e->cap_rows * e->ld);
         c.rhs = cv.take<double>((size_t)e->cap_rows);
         c.vibr = cv.take<int32_t>((size_t)e->cap_rows);
         c.vibc = cv.take<int32_t>((size_t)e->W);
         c.rbv = cv.take<int32_t>((size_t)e->n_idx);
         c.cbv = cv.take<int32_t>((size_t)e->n_idx);
-        if (!pass) {
-            if (!e->ck_free.empty()) {
-                c.mem = e->ck_free.back();
-                e->ck_free.pop_back();
-            } else if (hipMalloc(&c.mem, cv.off + 256) != hipSuccess) {
-                (void)hipGetLastError();
-                return fail(JSLP_ERR_NOMEM, "checkpoint_create: out of device memory");
-            }
-        }
+    });
+    if (err != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(JSLP_ERR_NOMEM, "checkpoint_create: out of device memory");
     }
     c.H = e->h_state->H;
     c.last_element_index = e->h_state->last_element_index;
     c.evaluation = e->evaluation;
     c.live = 1;
     SnapshotW w{c.A, c.vibr, c.vibc, c.rbv, c.cbv, e->n_idx, nullptr, c.rhs};
-    hipLaunchKernelGGL(k_checkpoint, dim3(copy_grid(e, 1).x), dim3(256), 0, e->stream, e->s, w, (int)c.H);
+    hipLaunchKernelGGL(k_checkpoint, dim3(copy_grid(e, 1).x), dim3(256), 0, e->res.stream, e->s, w, (int)c.H);
     HIPC(hipGetLastError());
     int32_t id = -1;
     for (size_t i = 0; i < e->ckpts.size(); i++)
         if (!e->ckpts[i].live) { id = (int32_t)i; break; }
-    if (id < 0) { id = (int32_t)e->ckpts.size(); e->ckpts.push_back(c); } else e->ckpts[id] = c;
+    if (id < 0) { id = (int32_t)e->ckpts.size(); e->ckpts.push_back(std::move(c)); } else e->ckpts[id] = std::move(c);
     *id_out = id;
     return JSLP_OK;  // stream-ordered: no synchronisation needed before the next engine call
 }
@@ -1589,7 +1462,7 @@ extern "C" int jslp_engine_checkpoint_restore(jslp_engine* e, int32_t id) {
     HIPC(hipSetDevice(e->device));
     rc = enqueue_restore(e, 0, 1, id);
     if (rc) return rc;
-    HIPC(hipStreamSynchronize(e->stream));
+    HIPC(hipStreamSynchronize(e->res.stream));
     e->evaluation = e->ckpts[id].evaluation;  // incremental-branch-and-cut.ts:105
     return JSLP_OK;
 }
@@ -1598,8 +1471,8 @@ extern "C" int jslp_engine_checkpoint_release(jslp_engine* e, int32_t id) {
     int rc = checkpoint_check(e, id, "checkpoint_release");
     if (rc) return rc;
     HIPC(hipSetDevice(e->device));
-    HIPC(hipStreamSynchronize(e->stream));  // a restore from it may still be in flight
-    e->ck_free.push_back(e->ckpts[id].mem);
+    HIPC(hipStreamSynchronize(e->res.stream));  // a restore from it may still be in flight
+    e->ck_free.push_back(std::move(e->ckpts[id].mem));
     e->ckpts[id] = jslp_engine::Ckpt();
     return JSLP_OK;
 }
@@ -1609,7 +1482,7 @@ extern "C" int jslp_engine_restore(jslp_engine* e) {
     HIPC(hipSetDevice(e->device));
     int rc = enqueue_restore(e, 0, 1);
     if (rc) return rc;
-    HIPC(hipStreamSynchronize(e->stream));
+    HIPC(hipStreamSynchronize(e->res.stream));
     return JSLP_OK;
 }
 
@@ -1625,21 +1498,19 @@ static int upload_cuts(jslp_engine* e, int32_t n_nodes, const int32_t* offs, con
     // [values | offsets | variables | types | hand-out order of a batch | its queue counter (0)]
     const size_t off_offs = 8 * C, off_var = off_offs + 4 * N1, off_type = off_var + 4 * C, off_order = (off_type + C + 3) & ~(size_t)3,
                  off_queue = off_order + 4 * (size_t)n_nodes, total = off_queue + 4;
-    if (total > e->cuts_bytes) {  // grow: allocate the new pair first, swap only when both exist
-        const size_t bytes = std::max<size_t>(2 * total, 4096);
-        char* nd = nullptr; char* nh = nullptr;
-        if (hipMalloc(&nd, bytes) != hipSuccess) { (void)hipGetLastError(); return fail(JSLP_ERR_NOMEM, "cuts: out of device memory"); }
-        if (hipHostMalloc(&nh, bytes) != hipSuccess) { (void)hipGetLastError(); hipFree(nd); return fail(JSLP_ERR_NOMEM, "cuts: out of pinned memory"); }
-        HIPC(hipStreamSynchronize(e->stream));  // nothing in flight may still read the old pair
-        hipFree(e->d_cuts);
-        if (e->h_cuts) hipHostFree(e->h_cuts);
-        e->d_cuts = nd; e->h_cuts = nh; e->cuts_bytes = bytes;
+    if (total > e->res.cuts.bytes()) {  // grow: the old pair goes only when both new halves exist
+        HIPC(hipStreamSynchronize(e->res.stream));  // nothing in flight may still read the old pair
+        bool pinned = false;
+        if (e->res.cuts.reserve(std::max<size_t>(2 * total, 4096), &pinned) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(JSLP_ERR_NOMEM, pinned ? "cuts: out of pinned memory" : "cuts: out of device memory");
+        }
     }
-    if (C) memcpy(e->h_cuts, value, 8 * C);
-    memcpy(e->h_cuts + off_offs, offs, 4 * N1);
-    if (C) { memcpy(e->h_cuts + off_var, var, 4 * C); memcpy(e->h_cuts + off_type, type, C); }
+    if (C) memcpy(e->res.cuts.h.p, value, 8 * C);
+    memcpy(e->res.cuts.h.p + off_offs, offs, 4 * N1);
+    if (C) { memcpy(e->res.cuts.h.p + off_var, var, 4 * C); memcpy(e->res.cuts.h.p + off_type, type, C); }
     if (node_queue() == 2) {  // most cuts first (a counting sort, stable): k_node_queue hands the nodes out in this order
-        int32_t* order = reinterpret_cast<int32_t*>(e->h_cuts + off_order);
+        int32_t* order = reinterpret_cast<int32_t*>(e->res.cuts.h.p + off_order);
         int most = 0;
         for (int32_t i = 0; i < n_nodes; i++) most = std::max(most, (int)(offs[i + 1] - offs[i]));
         std::vector<int32_t>& start = e->order_scratch;
@@ -1648,14 +1519,14 @@ static int upload_cuts(jslp_engine* e, int32_t n_nodes, const int32_t* offs, con
         for (int c = 0; c <= most; c++) start[(size_t)c + 1] += start[c];
         for (int32_t i = 0; i < n_nodes; i++) order[start[(size_t)(most - (offs[i + 1] - offs[i]))]++] = i;
     }
-    *reinterpret_cast<int32_t*>(e->h_cuts + off_queue) = 0;
+    *reinterpret_cast<int32_t*>(e->res.cuts.h.p + off_queue) = 0;
     // to_device == false: the one-launch node kernel reads the (tiny) cut list straight from the pinned buffer
-    char* base = e->d_cuts;
+    char* base = e->res.cuts.d.p;
     if (to_device) {
-        HIPC(hipMemcpyAsync(e->d_cuts, e->h_cuts, total, hipMemcpyHostToDevice, e->stream));
+        HIPC(hipMemcpyAsync(e->res.cuts.d.p, e->res.cuts.h.p, total, hipMemcpyHostToDevice, e->res.stream));
     } else {
         void* dev = nullptr;
-        HIPC(hipHostGetDevicePointer(&dev, e->h_cuts, 0));
+        HIPC(hipHostGetDevicePointer(&dev, e->res.cuts.h.p, 0));
         base = static_cast<char*>(dev);
     }
     e->d_cut_val = reinterpret_cast<double*>(base);
@@ -1677,10 +1548,10 @@ extern "C" int jslp_engine_add_cuts(jslp_engine* e, int32_t n, const int8_t* typ
     if (rc) return rc;
     if (e->counting) e->wc.cut_rows += n;
     Cuts cu{e->d_cut_offs, e->d_cut_type, e->d_cut_var, e->d_cut_val};
-    hipLaunchKernelGGL(k_add_cuts, dim3(1), dim3(256), 0, e->stream, e->s, cu, 0, 0, (int)e->cap_rows);
+    hipLaunchKernelGGL(k_add_cuts, dim3(1), dim3(256), 0, e->res.stream, e->s, cu, 0, 0, (int)e->cap_rows);
     HIPC(hipGetLastError());
-    HIPC(hipMemcpyAsync(e->h_state, e->s.st, sizeof(DevState), hipMemcpyDeviceToHost, e->stream));
-    HIPC(hipStreamSynchronize(e->stream));
+    HIPC(hipMemcpyAsync(e->h_state, e->s.st, sizeof(DevState), hipMemcpyDeviceToHost, e->res.stream));
+    HIPC(hipStreamSynchronize(e->res.stream));
     return state_error(*e->h_state);
 }
 
@@ -1691,34 +1562,26 @@ static size_t out_bytes(const jslp_engine* e, size_t nodes) {
 // rows per node in the engine's own read-back buffers: a multiple of 4, so that every node's slice starts 16-byte aligned and
 // the kernels write it with 8/16-byte stores per lane (4-byte stores into pinned host memory cost the Monster_II batch a
 // quarter of its time); the device pool lays its shared buffer out itself, with the plain row capacity
-static size_t out_stride_of(const jslp_engine* e) {
-    return e->ext_states ? (size_t)e->cap_rows : (((size_t)e->cap_rows + 3) & ~(size_t)3);
+struct PinnedDest { DevState* states = nullptr; double* rhs = nullptr; int32_t* rows = nullptr; };  // a range of the device pool's shared pinned buffer
+static size_t out_stride_of(const jslp_engine* e, const PinnedDest& shared = {}) {
+    return shared.states ? (size_t)e->cap_rows : (((size_t)e->cap_rows + 3) & ~(size_t)3);
 }
-static void out_layout(jslp_engine* e, size_t nodes) {
-    const size_t stride = out_stride_of(e);
+static void out_layout(jslp_engine* e, size_t nodes, const PinnedDest& shared) {
+    const size_t stride = out_stride_of(e, shared);
     const size_t o_rhs = (nodes * sizeof(DevState) + 63) & ~(size_t)63, o_rows = (o_rhs + nodes * stride * 8 + 63) & ~(size_t)63;
-    e->d_states = reinterpret_cast<DevState*>(e->d_out);
-    e->d_rhs = reinterpret_cast<double*>(e->d_out + o_rhs);
-    e->d_rows = reinterpret_cast<int32_t*>(e->d_out + o_rows);
-    e->h_states = reinterpret_cast<DevState*>(e->h_out);
-    e->h_rhs = reinterpret_cast<double*>(e->h_out + o_rhs);
-    e->h_rows = reinterpret_cast<int32_t*>(e->h_out + o_rows);
-    if (e->ext_states) {  // device pool: this call's outcomes go straight into the pool's pinned buffer
-        e->h_states = e->ext_states; e->h_rhs = e->ext_rhs; e->h_rows = e->ext_rows;
+    e->d_states = reinterpret_cast<DevState*>(e->res.out.d.p);
+    e->d_rhs = reinterpret_cast<double*>(e->res.out.d.p + o_rhs);
+    e->d_rows = reinterpret_cast<int32_t*>(e->res.out.d.p + o_rows);
+    e->h_states = reinterpret_cast<DevState*>(e->res.out.h.p);
+    e->h_rhs = reinterpret_cast<double*>(e->res.out.h.p + o_rhs);
+    e->h_rows = reinterpret_cast<int32_t*>(e->res.out.h.p + o_rows);
+    if (shared.states) {  // device pool: this call's outcomes go straight into the pool's pinned buffer
+        e->h_states = shared.states; e->h_rhs = shared.rhs; e->h_rows = shared.rows;
     }
 }
-static int ensure_out(jslp_engine* e, size_t nodes) {
-    if (out_bytes(e, nodes) > e->out_bytes_cap) {
-        hipFree(e->d_out);
-        if (e->h_out) hipHostFree(e->h_out);
-        e->d_out = e->h_out = nullptr;
-        e->out_bytes_cap = 0;
-        const size_t bytes = out_bytes(e, std::max<size_t>(nodes, 16));
-        HIPC(hipMalloc(&e->d_out, bytes));
-        HIPC(hipHostMalloc(&e->h_out, bytes));
-        e->out_bytes_cap = bytes;
-    }
-    out_layout(e, nodes);
+static int ensure_out(jslp_engine* e, size_t nodes, const PinnedDest& shared = {}) {
+    if (out_bytes(e, nodes) > e->res.out.bytes()) HIPC(e->res.out.reserve(out_bytes(e, std::max<size_t>(nodes, 16))));
+    out_layout(e, nodes, shared);
     return JSLP_OK;
 }
 
@@ -1727,10 +1590,10 @@ extern "C" int jslp_engine_read_rhs(jslp_engine* e, double* rhs, int32_t* var_in
     HIPC(hipSetDevice(e->device));
     int rc = ensure_out(e, 1);
     if (rc) return rc;
-    hipStream_t s = e->stream;
+    hipStream_t s = e->res.stream;
     hipLaunchKernelGGL(k_gather, dim3(1), dim3(256), 0, s, e->s, 0, e->d_rhs, e->d_rows, e->d_states, (int)e->cap_rows, 0);
     HIPC(hipGetLastError());
-    HIPC(hipMemcpyAsync(e->h_out, e->d_out, out_bytes(e, 1), hipMemcpyDeviceToHost, s));
+    HIPC(hipMemcpyAsync(e->res.out.h.p, e->res.out.d.p, out_bytes(e, 1), hipMemcpyDeviceToHost, s));
     HIPC(hipStreamSynchronize(s));
     const int H = e->h_states[0].H;
     if (rhs) memcpy(rhs, e->h_rhs, sizeof(double) * H);
@@ -1747,8 +1610,8 @@ extern "C" int jslp_engine_set_integer_variables(jslp_engine* e, const int32_t* 
         if (var_indexes[i] < 0 || var_indexes[i] >= e->n_idx) return fail(JSLP_ERR_ARG, "set_integer_variables: index out of range");
         flags[var_indexes[i]] = 1;
     }
-    HIPC(hipMemcpyAsync(e->d_isint, flags.data(), e->n_idx, hipMemcpyHostToDevice, e->stream));
-    HIPC(hipStreamSynchronize(e->stream));
+    HIPC(hipMemcpyAsync(e->d_isint, flags.data(), e->n_idx, hipMemcpyHostToDevice, e->res.stream));
+    HIPC(hipStreamSynchronize(e->res.stream));
     return JSLP_OK;
 }
 
@@ -1756,10 +1619,10 @@ extern "C" int jslp_engine_set_integer_variables(jslp_engine* e, const int32_t* 
 extern "C" int jslp_engine_apply_mir_cuts(jslp_engine* e, int32_t* n_added) {
     if (!e || !e->uploaded) return fail(JSLP_ERR_STATE, "apply_mir_cuts before upload");
     HIPC(hipSetDevice(e->device));
-    hipLaunchKernelGGL(k_mir_cuts, dim3(1), dim3(256), 0, e->stream, e->s, e->d_isint, 10, (int)e->cap_rows);
+    hipLaunchKernelGGL(k_mir_cuts, dim3(1), dim3(256), 0, e->res.stream, e->s, e->d_isint, 10, (int)e->cap_rows);
     HIPC(hipGetLastError());
-    HIPC(hipMemcpyAsync(e->h_state, e->s.st, sizeof(DevState), hipMemcpyDeviceToHost, e->stream));
-    HIPC(hipStreamSynchronize(e->stream));
+    HIPC(hipMemcpyAsync(e->h_state, e->s.st, sizeof(DevState), hipMemcpyDeviceToHost, e->res.stream));
+    HIPC(hipStreamSynchronize(e->res.stream));
     int rc = state_error(*e->h_state);
     if (rc) return rc;
     if (n_added) *n_added = e->h_state->mir_added;
@@ -1777,7 +1640,7 @@ extern "C" int jslp_engine_mir_round(jslp_engine* e, int check_cycles, int32_t* 
 
 // ---- fp32 twin -----------------------------------------------------------------------------------------------------
 static int ensure_f32(jslp_engine* e) {
-    if (e->arena32) return JSLP_OK;
+    if (e->arena32.p) return JSLP_OK;
     f32::Slots& s = e->s32;
     s.A_stride = (long long)e->cap_rows * e->ld;
     s.vibr_stride = e->cap_rows; s.vibc_stride = e->W; s.idx_stride = e->n_idx;
@@ -1787,8 +1650,7 @@ static int ensure_f32(jslp_engine* e) {
     s.oo = nullptr; s.oo_stride = 0; s.n_opt = 0;
     s.rhs = nullptr;
     s.trace = nullptr; s.trace_cap = 0;
-    for (int pass = 0; pass < 2; pass++) {
-        Carver cv{pass ? e->arena32 : nullptr, 0};
+    HIPC_CARVE(e->arena32, [&](Carver& cv) {
         s.A = cv.take<float>((size_t)s.A_stride);
         s.vibr = cv.take<int32_t>((size_t)s.vibr_stride);
         s.vibc = cv.take<int32_t>((size_t)s.vibc_stride);
@@ -1799,9 +1661,8 @@ static int ensure_f32(jslp_engine* e) {
         s.dirty = cv.take<uint8_t>((size_t)s.pcol_stride);
         s.st = cv.take<DevState>(1);
         s.hist = cv.take<int2>((size_t)s.hist_cap);
-        if (!pass) HIPC(hipMalloc(&e->arena32, cv.off + 256));
-    }
-    HIPC(hipMemsetAsync(e->arena32, 0, sizeof(float) * (size_t)s.A_stride, e->stream));  // padding columns / rows stay 0
+    });
+    HIPC(hipMemsetAsync(e->arena32.p, 0, sizeof(float) * (size_t)s.A_stride, e->res.stream));  // padding columns / rows stay 0
     return JSLP_OK;
 }
 
@@ -1816,7 +1677,7 @@ extern "C" int jslp_engine_simplex_f32(jslp_engine* e, double precision, int che
     if (rc) return rc;
     rc = ensure_out(e, 1);
     if (rc) return rc;
-    hipStream_t s = e->stream;
+    hipStream_t s = e->res.stream;
     f32::Slots& d = e->s32;
     d.unr = e->d_unr;
     d.has_unr = e->n_unr > 0 ? 1 : 0;
@@ -1834,7 +1695,7 @@ extern "C" int jslp_engine_simplex_f32(jslp_engine* e, double precision, int che
     c.batch = e->batch; c.use_partial = e->use_partial; c.precision = (float)precision; c.stop_at_phase2 = 0;
     c.has_unr = d.has_unr;
     const dim3 grid = update_grid(e, H);
-    HIPC(hipEventRecord(e->ev_begin, s));
+    HIPC(hipEventRecord(e->res.ev_begin, s));
     for (int chunk = 8;; chunk = std::min(chunk * 2, 256)) {
         for (int i = 0; i < chunk; i++) {
             hipLaunchKernelGGL(f32::k_select, dim3(1), dim3(JSLP_WG_THREADS), 0, s, c);
@@ -1845,17 +1706,17 @@ extern "C" int jslp_engine_simplex_f32(jslp_engine* e, double precision, int che
         HIPC(hipStreamSynchronize(s));
         if (e->h_state->status != ST_RUNNING) break;
     }
-    HIPC(hipEventRecord(e->ev_end, s));
+    HIPC(hipEventRecord(e->res.ev_end, s));
     hipLaunchKernelGGL(k32_gather, dim3(1), dim3(256), 0, s, d, e->d_rhs, e->d_rows, e->d_states);
     HIPC(hipGetLastError());
-    HIPC(hipMemcpyAsync(e->h_out, e->d_out, out_bytes(e, 1), hipMemcpyDeviceToHost, s));
+    HIPC(hipMemcpyAsync(e->res.out.h.p, e->res.out.d.p, out_bytes(e, 1), hipMemcpyDeviceToHost, s));
     HIPC(hipStreamSynchronize(s));
     const DevState st = e->h_states[0];
     rc = state_error(st);
     if (rc) return rc;
     if (device_ms) {
         float ms = 0;
-        *device_ms = hipEventElapsedTime(&ms, e->ev_begin, e->ev_end) == hipSuccess ? ms : -1.0;
+        *device_ms = hipEventElapsedTime(&ms, e->res.ev_begin, e->res.ev_end) == hipSuccess ? ms : -1.0;
     }
     memset(out, 0, sizeof *out);
     out->feasible = st.feasible;
@@ -1901,6 +1762,7 @@ struct NodeCall {
     jslp_simplex_result* out = nullptr;  // per-node results (1 and 2)
     double* rhs = nullptr; int32_t* var_index_by_row = nullptr; int32_t out_stride = 0;  // 1. the caller's host arrays
     bool pinned = false;                 // 2. the caller reads the engine's pinned buffers itself (no second host copy)
+    PinnedDest shared;                   //    ... or, with `pinned`, the device pool's: this call's range of its shared pinned buffer
     DeviceDest dev;                      // 3. the caller's device memory
     bool to_device() const { return dev.states != nullptr; }
     bool compact() const { return read_back != ReadBack::Full; }
@@ -2058,17 +1920,17 @@ static int node_call_check(jslp_engine* e, const NodeCall& c) {
 // ONE child of the saved root, slot 0 already in sync with the snapshot: one launch, one polled flag
 static bool single_child_fast_path(const jslp_engine* e, const NodeCall& c) {
     return c.cuts.n_nodes == 1 && c.checkpoint < 0 && e->has_save && e->slot0_synced && !e->timing && e->force_path <= 1 &&
-           e->one_launch_nodes && tableau_cells(e) <= wg_cells_child() && !e->ext_states && !c.to_device() && !c.records();
+           e->one_launch_nodes && tableau_cells(e) <= wg_cells_child() && !c.shared.states && !c.to_device() && !c.records();
 }
 static int relax_single_child(jslp_engine* e, const NodeCall& c, bool dbg) {
     JSLP_TRY(upload_cuts(e, 1, c.cuts.offsets, c.cuts.type, c.cuts.var_index, c.cuts.value, false));
     JSLP_TRY(ensure_out(e, 1));
     void* out_dev = nullptr;  // the kernel writes the outcome straight into the pinned read-back buffer
-    HIPC(hipHostGetDevicePointer(&out_dev, e->h_out, 0));
+    HIPC(hipHostGetDevicePointer(&out_dev, e->res.out.h.p, 0));
     char* ob = static_cast<char*>(out_dev);
     NodeArgs a{&e->s, root_snapshot(e), Cuts{e->d_cut_offs, e->d_cut_type, e->d_cut_var, e->d_cut_val}, c.check_cycles, iters_cap(e), (int)e->cap_rows};
-    a.rhs = c.want_rhs ? reinterpret_cast<double*>(ob + ((char*)e->h_rhs - e->h_out)) : nullptr;
-    a.rows = c.want_rows ? reinterpret_cast<int32_t*>(ob + ((char*)e->h_rows - e->h_out)) : nullptr;
+    a.rhs = c.want_rhs ? reinterpret_cast<double*>(ob + ((char*)e->h_rhs - e->res.out.h.p)) : nullptr;
+    a.rows = c.want_rows ? reinterpret_cast<int32_t*>(ob + ((char*)e->h_rows - e->res.out.h.p)) : nullptr;
     a.states = reinterpret_cast<DevState*>(ob);
     a.out_stride = c.compact() ? -e->n_watch : 0;
     e->last_path = "workgroup";
@@ -2077,9 +1939,9 @@ static int relax_single_child(jslp_engine* e, const NodeCall& c, bool dbg) {
         return fail(JSLP_ERR_DEVICE, "%s: %s", "hipHostGetDevicePointer(&flag_dev, h_flag, 0)", hipGetErrorString(err));
     a.done_flag = flag.dev; a.done_seq = flag.seq;
     const size_t lds = wglds_smem(e);
-    JSLP_TRY(launch_node_kernel(single_node_kernel(e, lds), a, 1, lds, e->stream, dbg));
+    JSLP_TRY(launch_node_kernel(single_node_kernel(e, lds), a, 1, lds, e->res.stream, dbg));
     unsigned spins;
-    if (!wait_done_flag(flag.host, flag.seq, spins)) HIPC(hipStreamSynchronize(e->stream));
+    if (!wait_done_flag(flag.host, flag.seq, spins)) HIPC(hipStreamSynchronize(e->res.stream));
     const DevState st = e->h_states[0];
     int rc = state_error(st);
     if (rc) { e->slot0_synced = 0; return rc; }
@@ -2139,14 +2001,7 @@ static int plan_node_call(jslp_engine* e, const NodeCall& c, NodePlan* p) {
     return JSLP_OK;
 }
 static int ensure_records(jslp_engine* e, size_t n_nodes) {  // branch records of a batch: device + pinned
-    if (n_nodes <= e->rec_cap) return JSLP_OK;
-    hipFree(e->d_rec);
-    if (e->h_rec) hipHostFree(e->h_rec);
-    e->d_rec = nullptr; e->h_rec = nullptr; e->rec_cap = 0;
-    const size_t cap = std::max<size_t>(n_nodes, 16);
-    HIPC(hipMalloc(&e->d_rec, sizeof(jslpx_branch_record) * cap));
-    HIPC(hipHostMalloc(&e->h_rec, sizeof(jslpx_branch_record) * cap));
-    e->rec_cap = cap;
+    if (sizeof(jslpx_branch_record) * n_nodes > e->rec.bytes()) HIPC(e->rec.reserve(sizeof(jslpx_branch_record) * std::max<size_t>(n_nodes, 16)));
     return JSLP_OK;
 }
 
@@ -2159,7 +2014,7 @@ struct NodeDest {
     size_t row_stride;  // entries per node in rhs / rows
 };
 static int node_destination(jslp_engine* e, const NodeCall& c, NodeDest* d) {
-    d->row_stride = c.compact() ? (size_t)e->n_watch : (c.to_device() ? (size_t)c.dev.stride : out_stride_of(e));
+    d->row_stride = c.compact() ? (size_t)e->n_watch : (c.to_device() ? (size_t)c.dev.stride : out_stride_of(e, c.shared));
     d->states = e->d_states; d->rhs = e->d_rhs; d->rows = e->d_rows;
     d->zc = zero_copy() != 0 && !c.records() && !c.to_device();  // (branch records: the compact read-back they are reduced from stays on the device)
     if (c.to_device()) { d->states = c.dev.states; d->rhs = c.dev.rhs; d->rows = c.dev.rows; }
@@ -2171,22 +2026,22 @@ static int node_destination(jslp_engine* e, const NodeCall& c, NodeDest* d) {
         else (void)hipGetLastError();
     }
     d->copies = !d->zc && !c.to_device() && !c.records();
-    if (d->copies && !e->copy_stream) {
+    if (d->copies && !e->res.copy_stream) {
         // created on first use, and only by the calls that copy their outcomes back (JSLP_ZERO_COPY=0, no mapped pinned memory): a stream costs a Solve of a
         // tiny model more than its pivots do
-        HIPC(hipStreamCreateWithFlags(&e->copy_stream, hipStreamNonBlocking));
-        HIPC(hipEventCreateWithFlags(&e->ev_group, hipEventDisableTiming));
+        HIPC(hipStreamCreateWithFlags(&e->res.copy_stream.h, hipStreamNonBlocking));
+        HIPC(hipEventCreateWithFlags(&e->res.ev_group.h, hipEventDisableTiming));
     }
     return JSLP_OK;
 }
 // staging -> pinned for the nodes [first, first + g) (the three regions of the read-back buffer are laid out for all nodes, so a group
 // is one contiguous slice of each)
 static int copy_outcomes(jslp_engine* e, const NodeCall& c, const NodeDest& d, int first, int g, bool overlap) {
-    hipStream_t on = e->stream;
+    hipStream_t on = e->res.stream;
     if (overlap) {  // a group's outcomes cross PCIe on the copy stream while the next group computes
-        HIPC(hipEventRecord(e->ev_group, e->stream));
-        HIPC(hipStreamWaitEvent(e->copy_stream, e->ev_group, 0));
-        on = e->copy_stream;
+        HIPC(hipEventRecord(e->res.ev_group, e->res.stream));
+        HIPC(hipStreamWaitEvent(e->res.copy_stream, e->res.ev_group, 0));
+        on = e->res.copy_stream;
     }
     const size_t off = (size_t)first * d.row_stride, len = (size_t)g * d.row_stride;
     HIPC(hipMemcpyAsync(e->h_states + first, e->d_states + first, sizeof(DevState) * (size_t)g, hipMemcpyDeviceToHost, on));
@@ -2210,7 +2065,7 @@ static int enqueue_queue(jslp_engine* e, const NodeCall& c, const NodePlan& p, c
     a.n_nodes = n_nodes;
     a.order = (node_queue() == 2 && n_nodes > p.group && (node_queue_order_full() || !pcie_bound)) ? e->d_cut_order : (const int32_t*)nullptr;
     a.queue = e->d_queue;
-    JSLP_TRY(launch_node_kernel(queue_kernel(e), a, p.group, wglds_smem(e), e->stream, dbg));
+    JSLP_TRY(launch_node_kernel(queue_kernel(e), a, p.group, wglds_smem(e), e->res.stream, dbg));
     return d.copies ? copy_outcomes(e, c, d, 0, n_nodes, false) : JSLP_OK;
 }
 // slots already in sync with the snapshot: restore of the dirty rows, cuts, simplex and gather in ONE launch per
@@ -2221,15 +2076,15 @@ static int enqueue_one_launch_group(jslp_engine* e, const NodeCall& c, const Nod
     a.first = first;
     // a batch that is ONE group, its outcomes written straight into pinned memory: the last workgroup raises the completion
     // flag the host polls instead of the two stream synchronisations that end the other shapes of this call
-    if (small_batch_shape(e, lds, g) && g == c.cuts.n_nodes && d.zc && !e->ext_states && batch_poll_on()) {
+    if (small_batch_shape(e, lds, g) && g == c.cuts.n_nodes && d.zc && !c.shared.states && batch_poll_on()) {
         if (arm_done_flag(e, polled) == hipSuccess) { a.done_flag = polled->dev; a.done_seq = polled->seq; a.done_count = e->d_done_count; }
         else (void)hipGetLastError();
     }
-    return launch_node_kernel(group_kernel(e, lds, g), a, g, lds, e->stream, dbg);
+    return launch_node_kernel(group_kernel(e, lds, g), a, g, lds, e->res.stream, dbg);
 }
 // restore, cuts, simplex and gather as launches of their own: any start, any tableau
 static int enqueue_eager_group(jslp_engine* e, const NodeCall& c, const NodePlan& p, const NodeArgs& a, int first, int g, bool dbg) {
-    hipStream_t s = e->stream;
+    hipStream_t s = e->res.stream;
     JSLP_TRY(enqueue_restore(e, 0, g, c.checkpoint));
     hipLaunchKernelGGL(k_add_cuts, dim3(g), dim3(256), 0, s, e->s, a.cu, 0, first, (int)e->cap_rows);
     HIPC(hipGetLastError());
@@ -2260,8 +2115,8 @@ static int wait_for_nodes(jslp_engine* e, int n_nodes, const DoneFlag& polled, s
     }
     if (!arrived) {  // every other shape -- and a polled batch that did not show up in 5 s: let the runtime report the fault
         const auto t_sync = std::chrono::steady_clock::now();
-        if (e->copy_stream) HIPC(hipStreamSynchronize(e->copy_stream));
-        HIPC(hipStreamSynchronize(e->stream));
+        if (e->res.copy_stream) HIPC(hipStreamSynchronize(e->res.copy_stream));
+        HIPC(hipStreamSynchronize(e->res.stream));
         if (debug_stall_ms() > 0) report_stall(n_nodes, false, t_enter, t_sync, 0);
     }
     return JSLP_OK;
@@ -2323,15 +2178,15 @@ static int relax_batch_impl(jslp_engine* e, const NodeCall& c) {
     const int n_nodes = c.cuts.n_nodes;
     if (rc || n_nodes == 0) return rc;
     HIPC(hipSetDevice(e->device));
-    hipStream_t s = e->stream;
+    hipStream_t s = e->res.stream;
     const bool dbg = debug_launch_on();  // (read per call, as run_simplex does: tests switch it inside one process)
     if (single_child_fast_path(e, c)) return relax_single_child(e, c, dbg);
     JSLP_TRY(upload_cuts(e, n_nodes, c.cuts.offsets, c.cuts.type, c.cuts.var_index, c.cuts.value));
     NodePlan p;
     JSLP_TRY(plan_node_call(e, c, &p));
-    JSLP_TRY(ensure_out(e, (size_t)n_nodes));  // laid out for ALL nodes: [states | rhs | rows]
+    JSLP_TRY(ensure_out(e, (size_t)n_nodes, c.shared));  // laid out for ALL nodes: [states | rhs | rows]
     if (c.records()) JSLP_TRY(ensure_records(e, (size_t)n_nodes));
-    if (e->timing) HIPC(hipEventRecord(e->ev_begin, s));
+    if (e->timing) HIPC(hipEventRecord(e->res.ev_begin, s));
     NodeDest d;
     JSLP_TRY(node_destination(e, c, &d));
     NodeArgs a{&e->s, root_snapshot(e), Cuts{e->d_cut_offs, e->d_cut_type, e->d_cut_var, e->d_cut_val}, c.check_cycles, iters_cap(e), (int)e->cap_rows,
@@ -2348,17 +2203,17 @@ static int relax_batch_impl(jslp_engine* e, const NodeCall& c) {
     }
     if (c.records()) {  // the branch records of the whole batch, one workgroup per node, behind every node kernel on the stream
         hipLaunchKernelGGL(k_branch_record, dim3(n_nodes), dim3(256), 0, s, d.states, d.rows, d.rhs, e->s.watch, (int)e->n_watch, e->precision,
-                           c.to_device() ? c.dev.rec : e->d_rec);
+                           c.to_device() ? c.dev.rec : e->rec.d.as<double>());
         HIPC(hipGetLastError());
         if (!c.to_device()) {
             HIPC(hipMemcpyAsync(e->h_states, e->d_states, sizeof(DevState) * (size_t)n_nodes, hipMemcpyDeviceToHost, s));
-            HIPC(hipMemcpyAsync(e->h_rec, e->d_rec, sizeof(jslpx_branch_record) * (size_t)n_nodes, hipMemcpyDeviceToHost, s));
+            HIPC(hipMemcpyAsync(e->rec.h.p, e->rec.d.p, sizeof(jslpx_branch_record) * (size_t)n_nodes, hipMemcpyDeviceToHost, s));
         }
     }
-    if (e->timing && p.wg) HIPC(hipEventRecord(e->ev_end, s));
+    if (e->timing && p.wg) HIPC(hipEventRecord(e->res.ev_end, s));
     JSLP_TRY(wait_for_nodes(e, n_nodes, polled, t_enter));
     float ms = 0;
-    if (p.wg && e->timing && hipEventElapsedTime(&ms, e->ev_begin, e->ev_end) == hipSuccess) e->total_ms += ms;
+    if (p.wg && e->timing && hipEventElapsedTime(&ms, e->res.ev_begin, e->res.ev_end) == hipSuccess) e->total_ms += ms;
     if (e->counting) e->wc.cut_rows += c.cuts.offsets[n_nodes];
     return decode_outcomes(e, c, p, d);
 }
@@ -2439,9 +2294,9 @@ extern "C" int jslp_engine_set_watched_variables(jslp_engine* e, const int32_t* 
     for (int32_t i = 0; i < n; i++)
         if (var_indexes[i] < 0 || var_indexes[i] >= e->n_idx) return fail(JSLP_ERR_ARG, "set_watched_variables: index out of range");
     HIPC(hipSetDevice(e->device));
-    HIPC(hipStreamSynchronize(e->stream));
-    hipFree(e->d_watch);
-    e->d_watch = nullptr; e->n_watch = 0; e->s.watch = nullptr; e->s.n_watch = 0; e->s.watch_pos = nullptr;
+    HIPC(hipStreamSynchronize(e->res.stream));
+    e->d_watch.reset();
+    e->n_watch = 0; e->s.watch = nullptr; e->s.n_watch = 0; e->s.watch_pos = nullptr;
     if (n > 0) {
         // [the list | variable index -> position in the list] (the second half only when no variable is listed twice)
         std::vector<int32_t> pos((size_t)e->n_idx, -1);
@@ -2450,11 +2305,12 @@ extern "C" int jslp_engine_set_watched_variables(jslp_engine* e, const int32_t* 
             if (pos[var_indexes[i]] >= 0) unique = false;
             pos[var_indexes[i]] = i;
         }
-        HIPC(hipMalloc(&e->d_watch, sizeof(int32_t) * ((size_t)n + (size_t)e->n_idx)));
-        HIPC(hipMemcpy(e->d_watch, var_indexes, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice));
-        HIPC(hipMemcpy(e->d_watch + n, pos.data(), sizeof(int32_t) * (size_t)e->n_idx, hipMemcpyHostToDevice));
-        e->n_watch = n; e->s.watch = e->d_watch; e->s.n_watch = n;
-        e->s.watch_pos = unique ? e->d_watch + n : nullptr;
+        HIPC(e->d_watch.reserve(sizeof(int32_t) * ((size_t)n + (size_t)e->n_idx)));
+        int32_t* const watch = e->d_watch.as<int32_t>();
+        HIPC(hipMemcpy(watch, var_indexes, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice));
+        HIPC(hipMemcpy(watch + n, pos.data(), sizeof(int32_t) * (size_t)e->n_idx, hipMemcpyHostToDevice));
+        e->n_watch = n; e->s.watch = watch; e->s.n_watch = n;
+        e->s.watch_pos = unique ? watch + n : nullptr;
     }
     return JSLP_OK;
 }
@@ -2519,7 +2375,7 @@ extern "C" int jslpx_engine_relax_batch_branch(jslp_engine* e, int32_t n_nodes, 
     jslp_simplex_result* res = branch_results_scratch(e, std::max(n_nodes, 0));
     JSLP_TRY(relax_batch_impl(e, NodeCall{.cuts = {n_nodes, cut_offsets, type, var_index, value}, .check_cycles = check_cycles, .read_back = ReadBack::BranchRecord,
                                           .want_rhs = true, .want_rows = true, .out = res, .pinned = true}));
-    if (n_nodes > 0) memcpy(out, e->h_rec, sizeof(jslpx_branch_record) * (size_t)n_nodes);
+    if (n_nodes > 0) memcpy(out, e->rec.h.p, sizeof(jslpx_branch_record) * (size_t)n_nodes);
     return JSLP_OK;
 }
 
@@ -2530,7 +2386,7 @@ extern "C" int jslpx_engine_relax_batch_branch_pinned(jslp_engine* e, int32_t n_
     jslp_simplex_result* res = branch_results_scratch(e, std::max(n_nodes, 0));
     JSLP_TRY(relax_batch_impl(e, NodeCall{.cuts = {n_nodes, cut_offsets, type, var_index, value}, .check_cycles = check_cycles, .read_back = ReadBack::BranchRecord,
                                           .want_rhs = true, .want_rows = true, .out = res, .pinned = true}));
-    *out = n_nodes > 0 ? e->h_rec : nullptr;
+    *out = n_nodes > 0 ? e->rec.h.as<jslpx_branch_record>() : nullptr;
     return JSLP_OK;
 }
 
@@ -2577,17 +2433,16 @@ extern "C" int jslpx_engine_results_from_branch_records(jslp_engine* e, const vo
 // device and its pinned twin.  One call at a time holds them (g_many_mu); jslp_release_pooled_resources frees them.
 struct ManyRes {
     int device = -1;
-    char* d_buf = nullptr; char* h_buf = nullptr; size_t cap = 0;
+    StagePair buf;
 };
 static std::mutex g_many_mu;
-static std::vector<ManyRes> g_many;
+static std::vector<ManyRes>& g_many = *new std::vector<ManyRes>();  // (never destroyed: see g_pool)
 
 static void release_many_resources() {
     std::lock_guard<std::mutex> lk(g_many_mu);
     for (auto& r : g_many) {
         hipSetDevice(r.device);
-        hipFree(r.d_buf);
-        if (r.h_buf) hipHostFree(r.h_buf);
+        r.buf = StagePair();
     }
     g_many.clear();
 }
@@ -2596,15 +2451,7 @@ static int many_buffers(int device, size_t bytes, ManyRes** out) {  // (caller h
     ManyRes* r = nullptr;
     for (auto& x : g_many) if (x.device == device) r = &x;
     if (!r) { g_many.emplace_back(); r = &g_many.back(); r->device = device; }
-    if (r->cap < bytes) {
-        hipFree(r->d_buf); r->d_buf = nullptr;
-        if (r->h_buf) hipHostFree(r->h_buf);
-        r->h_buf = nullptr; r->cap = 0;
-        const size_t cap = std::max<size_t>(bytes, 64 * 1024);
-        HIPC(hipMalloc(&r->d_buf, cap));
-        HIPC(hipHostMalloc(&r->h_buf, cap));
-        r->cap = cap;
-    }
+    if (r->buf.bytes() < bytes) HIPC(r->buf.reserve(std::max<size_t>(bytes, 64 * 1024)));
     *out = r;
     return JSLP_OK;
 }
@@ -2652,14 +2499,14 @@ extern "C" int jslpm_simplex_many(jslp_engine* const* engines, int32_t n, const 
         const size_t table_bytes = (sizeof(ManyLp) * nb + 255) & ~(size_t)255;
         int rc = many_buffers(device, table_bytes + sizeof(DevState) * nb, &res);
         if (rc) return rc;
-        ManyLp* h_lps = reinterpret_cast<ManyLp*>(res->h_buf);
-        ManyLp* d_lps = reinterpret_cast<ManyLp*>(res->d_buf);
-        DevState* h_st = reinterpret_cast<DevState*>(res->h_buf + table_bytes);
-        DevState* d_st = reinterpret_cast<DevState*>(res->d_buf + table_bytes);
+        ManyLp* h_lps = res->buf.h.as<ManyLp>();
+        ManyLp* d_lps = res->buf.d.as<ManyLp>();
+        DevState* h_st = reinterpret_cast<DevState*>(res->buf.h.p + table_bytes);
+        DevState* d_st = reinterpret_cast<DevState*>(res->buf.d.p + table_bytes);
         std::vector<int32_t> order(plain);
         order.insert(order.end(), opt.begin(), opt.end());
         jslp_engine* const lead = engines[order[0]];
-        hipStream_t s = lead->stream;
+        hipStream_t s = lead->res.stream;
         for (size_t k = 0; k < nb; k++) {
             jslp_engine* e = engines[order[k]];
             e->slot0_synced = 0;
@@ -2672,12 +2519,12 @@ extern "C" int jslpm_simplex_many(jslp_engine* const* engines, int32_t n, const 
             m.cap_rows = e->cap_rows;
             m.pad = 0;
             if (e != lead) {  // the launch runs after whatever the member's stream holds
-                HIPC(hipEventRecord(e->ev_end, e->stream));
-                HIPC(hipStreamWaitEvent(s, e->ev_end, 0));
+                HIPC(hipEventRecord(e->res.ev_end, e->res.stream));
+                HIPC(hipStreamWaitEvent(s, e->res.ev_end, 0));
             }
         }
         HIPC(hipMemcpyAsync(d_lps, h_lps, sizeof(ManyLp) * nb, hipMemcpyHostToDevice, s));
-        HIPC(hipEventRecord(lead->ev_begin, s));
+        HIPC(hipEventRecord(lead->res.ev_begin, s));
         const bool dbg = debug_launch_on();
         for (int variant = 0; variant < 2; variant++) {
             const size_t cnt = variant ? opt.size() : plain.size();
@@ -2699,14 +2546,14 @@ extern "C" int jslpm_simplex_many(jslp_engine* const* engines, int32_t n, const 
             if (dbg) fprintf(stderr, "[jslp] launch k_simplex_lds_many<%d,opt %d> n %zu lds %zu\n", shape, variant, cnt, lds);
         }
         HIPC(hipMemcpyAsync(h_st, d_st, sizeof(DevState) * nb, hipMemcpyDeviceToHost, s));
-        HIPC(hipEventRecord(lead->ev_end, s));
+        HIPC(hipEventRecord(lead->res.ev_end, s));
         for (size_t k = 0; k < nb; k++) {  // every member's stream continues after the launch
             jslp_engine* e = engines[order[k]];
-            if (e != lead) HIPC(hipStreamWaitEvent(e->stream, lead->ev_end, 0));
+            if (e != lead) HIPC(hipStreamWaitEvent(e->res.stream, lead->res.ev_end, 0));
         }
         HIPC(hipStreamSynchronize(s));
         float ms = 0;
-        if (hipEventElapsedTime(&ms, lead->ev_begin, lead->ev_end) != hipSuccess) ms = 0;
+        if (hipEventElapsedTime(&ms, lead->res.ev_begin, lead->res.ev_end) != hipSuccess) ms = 0;
         for (size_t k = 0; k < nb; k++) {  // what jslp_engine_simplex does after run_simplex, per member
             const int32_t i = order[k];
             jslp_engine* e = engines[i];
@@ -2734,11 +2581,11 @@ extern "C" int jslpm_simplex_many(jslp_engine* const* engines, int32_t n, const 
 extern "C" int jslp_engine_set_counting(jslp_engine* e, int enabled) {
     if (!e) return fail(JSLP_ERR_ARG, "set_counting: null engine");
     HIPC(hipSetDevice(e->device));
-    HIPC(hipStreamSynchronize(e->stream));
-    if (!e->d_cnt) HIPC(hipMalloc(&e->d_cnt, sizeof(cnt_t) * CNT_ALLOC));
-    HIPC(hipMemset(e->d_cnt, 0, sizeof(cnt_t) * CNT_ALLOC));
+    HIPC(hipStreamSynchronize(e->res.stream));
+    HIPC(e->d_cnt.reserve(sizeof(cnt_t) * CNT_ALLOC));
+    HIPC(hipMemset(e->d_cnt.p, 0, sizeof(cnt_t) * CNT_ALLOC));
     e->counting = enabled ? 1 : 0;
-    e->s.cnt = enabled ? e->d_cnt : nullptr;
+    e->s.cnt = enabled ? e->d_cnt.as<cnt_t>() : nullptr;
     e->wc = jslp_work_counters{};
     e->resident_fallbacks = e->resident_handovers = e->resident_launches = e->resident_refusals = e->node_queue_launches = 0;
     e->resident_fetch_retries = 0;
@@ -2754,11 +2601,11 @@ extern "C" int jslp_engine_get_counters(jslp_engine* e, jslp_work_counters* out)
     out->resident_refusals = e->resident_refusals;
     out->node_queue_launches = e->node_queue_launches;
     out->resident_fetch_retries = e->resident_fetch_retries;
-    if (e->d_cnt) {
+    if (e->d_cnt.p) {
         HIPC(hipSetDevice(e->device));
-        HIPC(hipStreamSynchronize(e->stream));
+        HIPC(hipStreamSynchronize(e->res.stream));
         cnt_t c[CNT_ALLOC];
-        HIPC(hipMemcpy(c, e->d_cnt, sizeof c, hipMemcpyDeviceToHost));
+        HIPC(hipMemcpy(c, e->d_cnt.p, sizeof c, hipMemcpyDeviceToHost));
 #ifdef JSLP_DEBUG_WGLDS
         {   // cycle accumulators of the LDS one-workgroup kernels (thread 0 of every workgroup, s_memtime), per section
             static const char* names[] = {"restore rows", "restore maps", "cuts", "begin + LDS load", "phase-1 row", "pricing", "column gather + ratio test",
@@ -2867,7 +2714,7 @@ struct jslp_pool {
     std::vector<PoolWorker*> workers;   // workers[i] drives members[i] (i >= 1); the primary runs on the calling thread
     unsigned long long synced_seq = ~0ull;
     int synced = 0;
-    char* h_out = nullptr; size_t h_out_bytes = 0;  // ONE pinned (portable) read-back buffer: [states | rhs | rows] for all nodes
+    PinBuf h_out;  // ONE pinned (portable) read-back buffer: [states | rhs | rows] for all nodes
     std::vector<std::vector<int32_t>> offs;         // per member: its cut offsets rebased to 0
 };
 
@@ -2882,7 +2729,6 @@ extern "C" void jslp_pool_destroy(jslp_pool* p) {
         delete w;
     }
     for (size_t i = 1; i < p->members.size(); i++) jslp_engine_destroy(p->members[i]);
-    if (p->h_out) hipHostFree(p->h_out);
     delete p;
 }
 
@@ -2938,18 +2784,10 @@ extern "C" int jslp_pool_create(jslp_pool** out, jslp_engine* primary, const int
 // one member adopts the primary's saved root: peer copies of the snapshot + a state fix-up + restore()
 static int pool_adopt_root(jslp_engine* m, const jslp_engine* src, int s_H, int s_lei) {
     HIPC(hipSetDevice(m->device));
-    hipStream_t s = m->stream;
+    hipStream_t s = m->res.stream;
     if (m->n_opt != src->n_opt) {  // optional objectives travel with the root (backup.ts:37-43)
         HIPC(hipStreamSynchronize(s));
-        hipFree(m->s.oo); hipFree(m->snap_oo);
-        m->s.oo = nullptr; m->snap_oo = nullptr;
-        m->n_opt = src->n_opt; m->s.n_opt = src->n_opt; m->s.oo_stride = (long long)src->n_opt * m->ld;
-        if (src->n_opt > 0) {
-            const size_t per = (size_t)m->s.oo_stride;
-            HIPC(hipMalloc(&m->s.oo, sizeof(double) * per * std::max(1, m->n_slots)));
-            HIPC(hipMalloc(&m->snap_oo, sizeof(double) * per));
-            HIPC(hipMemsetAsync(m->s.oo, 0, sizeof(double) * per * std::max(1, m->n_slots), s));
-        }
+        JSLP_TRY(resize_optional_objectives(m, src->n_opt));
     }
     const int sd = src->device, dd = m->device;
     HIPC(hipMemcpyPeerAsync(m->snap_A, dd, src->snap_A, sd, sizeof(double) * (size_t)s_H * m->ld, s));
@@ -2974,7 +2812,7 @@ static int pool_adopt_root(jslp_engine* m, const jslp_engine* src, int s_H, int 
     m->max_uploaded_idx = src->max_uploaded_idx;
     m->slot0_synced = 0;
     m->slots_synced = 0;
-    drop_checkpoints(m, 0);
+    drop_checkpoints(m);
     int rc = enqueue_restore(m, 0, 1);  // the member's live tableau = the root
     if (rc) return rc;
     HIPC(hipStreamSynchronize(s));
@@ -2995,7 +2833,7 @@ extern "C" int jslp_pool_sync_root(jslp_pool* p) {
     jslp_engine* e = p->members[0];
     if (!e->uploaded || !e->has_save) return fail(JSLP_ERR_STATE, "pool_sync_root: the primary has no saved root (save() first)");
     HIPC(hipSetDevice(e->device));
-    HIPC(hipStreamSynchronize(e->stream));
+    HIPC(hipStreamSynchronize(e->res.stream));
     DevState st;
     HIPC(hipMemcpy(&st, e->s.st, sizeof st, hipMemcpyDeviceToHost));
     const int s_H = st.s_H, s_lei = st.s_last_element_index;
@@ -3036,16 +2874,10 @@ static int pool_relax(jslp_pool* p, int32_t n_nodes, const int32_t* cut_offsets,
     // ONE pinned buffer for every member's outcomes, laid out for all nodes: [states | rhs | rows]
     const size_t cap = compact ? (size_t)e->n_watch : (size_t)e->cap_rows;  // entries per node in the shared buffer
     const size_t need = (size_t)n_nodes * (sizeof(DevState) + cap * 12);
-    if (need > p->h_out_bytes) {
-        if (p->h_out) hipHostFree(p->h_out);
-        p->h_out = nullptr; p->h_out_bytes = 0;
-        const size_t bytes = std::max<size_t>(need, (size_t)16 * (sizeof(DevState) + cap * 12));
-        HIPC(hipHostMalloc(&p->h_out, bytes, hipHostMallocPortable));
-        p->h_out_bytes = bytes;
-    }
-    DevState* g_states = reinterpret_cast<DevState*>(p->h_out);
-    double* g_rhs = reinterpret_cast<double*>(p->h_out + (size_t)n_nodes * sizeof(DevState));
-    int32_t* g_rows = reinterpret_cast<int32_t*>(p->h_out + (size_t)n_nodes * (sizeof(DevState) + cap * 8));
+    if (need > p->h_out.bytes) HIPC(p->h_out.reserve(std::max<size_t>(need, (size_t)16 * (sizeof(DevState) + cap * 12)), hipHostMallocPortable));
+    DevState* g_states = p->h_out.as<DevState>();
+    double* g_rhs = reinterpret_cast<double*>(p->h_out.p + (size_t)n_nodes * sizeof(DevState));
+    int32_t* g_rows = reinterpret_cast<int32_t*>(p->h_out.p + (size_t)n_nodes * (sizeof(DevState) + cap * 8));
     const int M = (int)p->members.size();
     // JSLP_DEBUG_POOL=1 (diagnosis, tools/pool_handoff.py): per call, when every member's job started and ended relative to the call's entry -- what of a
     // pool call is thread hand-off (the start delays, the join after the last end) and what is the members' own work
@@ -3065,14 +2897,11 @@ static int pool_relax(jslp_pool* p, int32_t n_nodes, const int32_t* cut_offsets,
         o.resize((size_t)cnt + 1);
         const int32_t base = cut_offsets[first];
         for (int i = 0; i <= cnt; i++) o[i] = cut_offsets[first + i] - base;
-        m->ext_states = g_states + first;
-        m->ext_rhs = g_rhs + (size_t)first * cap;
-        m->ext_rows = g_rows + (size_t)first * cap;
-        // (pinned: the member's buffers ARE this range of the pool's, through ext_*)
+        // (pinned: the member's buffers ARE this range of the pool's, through `shared`)
         const int r = relax_batch_impl(m, NodeCall{.cuts = {cnt, o.data(), type ? type + base : nullptr, var_index ? var_index + base : nullptr, value ? value + base : nullptr},
                                                    .check_cycles = check_cycles, .read_back = compact ? ReadBack::Watched : ReadBack::Full,
-                                                   .want_rhs = want_rhs != 0, .want_rows = want_rows != 0, .out = out + first, .pinned = true});
-        m->ext_states = nullptr; m->ext_rhs = nullptr; m->ext_rows = nullptr;
+                                                   .want_rhs = want_rhs != 0, .want_rows = want_rows != 0, .out = out + first, .pinned = true,
+                                                   .shared = {g_states + first, g_rhs + (size_t)first * cap, g_rows + (size_t)first * cap}});
         if (r) return r;
         if (compact) {  // same layout on both sides: one copy per member
             if (rhs) memcpy(rhs + (size_t)first * cap, g_rhs + (size_t)first * cap, sizeof(double) * (size_t)cnt * cap);
@@ -3114,9 +2943,9 @@ extern "C" int jslp_pool_relax_batch_pinned(jslp_pool* p, int32_t n_nodes, const
                         var_index_by_row != nullptr);
     if (rc) return rc;
     const size_t cap = (size_t)p->members[0]->cap_rows;
-    if (rhs) *rhs = n_nodes > 0 ? reinterpret_cast<const double*>(p->h_out + (size_t)n_nodes * sizeof(DevState)) : nullptr;
+    if (rhs) *rhs = n_nodes > 0 ? reinterpret_cast<const double*>(p->h_out.p + (size_t)n_nodes * sizeof(DevState)) : nullptr;
     if (var_index_by_row)
-        *var_index_by_row = n_nodes > 0 ? reinterpret_cast<const int32_t*>(p->h_out + (size_t)n_nodes * (sizeof(DevState) + cap * 8)) : nullptr;
+        *var_index_by_row = n_nodes > 0 ? reinterpret_cast<const int32_t*>(p->h_out.p + (size_t)n_nodes * (sizeof(DevState) + cap * 8)) : nullptr;
     if (out_stride) *out_stride = (int32_t)cap;
     return JSLP_OK;
 }
@@ -3151,9 +2980,9 @@ extern "C" int jslp_pool_relax_batch_watched_pinned(jslp_pool* p, int32_t n_node
                         watched_row != nullptr, 1);
     if (rc) return rc;
     const size_t nw = p && !p->members.empty() ? (size_t)p->members[0]->n_watch : 0;
-    if (watched_value) *watched_value = n_nodes > 0 ? reinterpret_cast<const double*>(p->h_out + (size_t)n_nodes * sizeof(DevState)) : nullptr;
+    if (watched_value) *watched_value = n_nodes > 0 ? reinterpret_cast<const double*>(p->h_out.p + (size_t)n_nodes * sizeof(DevState)) : nullptr;
     if (watched_row)
-        *watched_row = n_nodes > 0 ? reinterpret_cast<const int32_t*>(p->h_out + (size_t)n_nodes * (sizeof(DevState) + nw * 8)) : nullptr;
+        *watched_row = n_nodes > 0 ? reinterpret_cast<const int32_t*>(p->h_out.p + (size_t)n_nodes * (sizeof(DevState) + nw * 8)) : nullptr;
     return JSLP_OK;
 }
 
@@ -3197,7 +3026,7 @@ extern "C" int jslp_engine_dims(const jslp_engine* e, int32_t* height, int32_t* 
     if (!e) return fail(JSLP_ERR_ARG, "dims: null engine");
     if (height) {
         if (hipSetDevice(e->device) != hipSuccess) return fail(JSLP_ERR_DEVICE, "dims: hipSetDevice failed");
-        if (hipStreamSynchronize(e->stream) != hipSuccess) return fail(JSLP_ERR_DEVICE, "dims: stream synchronisation failed");
+        if (hipStreamSynchronize(e->res.stream) != hipSuccess) return fail(JSLP_ERR_DEVICE, "dims: stream synchronisation failed");
         DevState st;
         if (hipMemcpy(&st, e->s.st, sizeof st, hipMemcpyDeviceToHost) != hipSuccess)
             return fail(JSLP_ERR_DEVICE, "dims: state read-back failed");
@@ -3212,7 +3041,7 @@ extern "C" int jslp_engine_download(jslp_engine* e, double* matrix, int32_t* var
                                     int32_t* row_by_var_index, int32_t* col_by_var_index) {
     if (!e || !e->uploaded) return fail(JSLP_ERR_STATE, "download before upload");
     HIPC(hipSetDevice(e->device));
-    HIPC(hipStreamSynchronize(e->stream));
+    HIPC(hipStreamSynchronize(e->res.stream));
     DevState st;
     HIPC(hipMemcpy(&st, e->s.st, sizeof st, hipMemcpyDeviceToHost));
     const int H = st.H, W = e->W;
@@ -3228,7 +3057,7 @@ extern "C" int jslp_engine_download(jslp_engine* e, double* matrix, int32_t* var
 extern "C" int jslp_engine_pivot_trace(jslp_engine* e, int32_t* row_col, int64_t max_pairs, int64_t* n_pivots) {
     if (!e || !n_pivots) return fail(JSLP_ERR_ARG, "pivot_trace: null pointer");
     HIPC(hipSetDevice(e->device));
-    HIPC(hipStreamSynchronize(e->stream));
+    HIPC(hipStreamSynchronize(e->res.stream));
     DevState st;
     HIPC(hipMemcpy(&st, e->s.st, sizeof st, hipMemcpyDeviceToHost));
     *n_pivots = st.trace_n;
