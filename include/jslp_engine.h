@@ -167,8 +167,12 @@ int jslp_engine_relax_batch_pinned(jslp_engine* e, int32_t n_nodes, const int32_
  * capacity; a multiple of 4 keeps the kernels on their 16-byte stores) -- is written into memory of the ENGINE'S DEVICE that the
  * caller owns; nothing crosses PCIe.  results_from_states turns records (in host memory; this rank's or, after the exchange,
  * any rank's) into the result structs of the other entry points; a record carries no pivot history, so cycle_start /
- * cycle_length come back 0 (flags and cycle_phase are exact).  The oracle library implements the same three entry points over
- * plain host memory.
+ * cycle_length come back 0 (flags and cycle_phase are exact); called right after the `_device` call
+ * that wrote the records, a node without an optimum gets the evaluation that call started from.  The oracle library implements the same three entry points over plain host memory.
+ * What the caller owes: d_states, d_rhs and d_rows each large enough for n_nodes records / n_nodes x row_stride entries, and, when
+ * row_stride is a multiple of 4, d_rhs and d_rows aligned to 16 bytes (the 16-byte stores assume it; any other row_stride is written
+ * entry by entry and needs the types' own alignment only).  A node's slice is written up to its height, plus one padding entry
+ * behind an odd height when row_stride is a multiple of 4; nothing else of the caller's memory is touched.
  */
 int32_t jslp_engine_state_record_bytes(void);
 int jslp_engine_relax_batch_device(jslp_engine* e, int32_t n_nodes, const int32_t* cut_offsets, const int8_t* type,
@@ -319,6 +323,9 @@ int jslp_engine_get_counters(jslp_engine* e, jslp_work_counters* out);
  * landing in ONE pinned buffer (the _pinned variant hands that buffer out, valid until the next call on the pool).
  * The caller stays single-threaded and synchronous: the threads live inside the pool.  The primary's
  * live tableau is left holding the last node of ITS range.  destroy() frees the members it created, never the primary.
+ * A node that reaches no optimum reports the evaluation that the member owning it had when the call began: a fan-out sets every
+ * member's to the primary's, a non-empty range moves its member's to its last node's, an empty or a refused range leaves it alone.
+ * When members refuse their ranges the call fails with the code and the text of the lowest-numbered one of them.
  */
 typedef struct jslp_pool jslp_pool;
 int jslp_pool_create(jslp_pool** out, jslp_engine* primary, const int32_t* devices, int32_t n_devices);

@@ -35,6 +35,8 @@ def _pinned_view(ptr, shape):
     """numpy view of an engine-owned pinned buffer (np.ctypeslib.as_array costs ~2 us a time): one view object per (address, shape, type) -- the
     engine hands out the same buffer call after call; a re-allocated buffer has another address and gets another view"""
     key = (_capi.C.cast(ptr, _capi.C.c_void_p).value, shape, ptr._type_)
+    if key[0] is None:  # a call without nodes hands out no buffer
+        return np.empty((0,) + tuple(shape[1:]), dtype=np.dtype(ptr._type_))
     v = _VIEWS.get(key)
     if v is None:
         if len(_VIEWS) > 256:

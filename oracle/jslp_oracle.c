@@ -688,9 +688,12 @@ int jslp_engine_relax_batch(jslp_engine* e, int32_t n_nodes, const int32_t* cut_
     if (!e || n_nodes < 0 || !cut_offsets || !out) return fail(JSLP_ERR_ARG, "relax_batch: null");
     if ((rhs || var_index_by_row) && out_stride < e->cap_rows) return fail(JSLP_ERR_ARG, "relax_batch: out_stride < row capacity");
     /* each node starts from the saved root, but flags carry over exactly as in a sequential B&B only through
-       `evaluation` of non-optimal nodes; nodes here are independent, so reset it per node */
+       `evaluation` of non-optimal nodes; nodes here are independent, so reset it per node: every node of a call starts from the
+       evaluation the CALL started from (the product's fill_result), the engine's ends as the last node's */
+    const double start = e->evaluation;
     for (int32_t i = 0; i < n_nodes; i++) {
         const int32_t a = cut_offsets[i], n = cut_offsets[i + 1] - a;
+        e->evaluation = start;
         int rc = jslp_engine_relax(e, n, type ? type + a : 0, var_index ? var_index + a : 0, value ? value + a : 0,
                                    check_cycles, &out[i], rhs ? rhs + (size_t)i * out_stride : 0,
                                    var_index_by_row ? var_index_by_row + (size_t)i * out_stride : 0);
@@ -959,8 +962,10 @@ int jslp_engine_relax_batch_watched(jslp_engine* e, int32_t n_nodes, const int32
     if (!e || n_nodes < 0 || !cut_offsets || !out) return fail(JSLP_ERR_ARG, "relax_batch_watched: null");
     if (e->n_watch <= 0 || e->n_watch > e->cap_rows)
         return fail(JSLP_ERR_ARG, "relax_batch_watched: after set_watched_variables (at most row_capacity of them)");
+    const double start = e->evaluation; /* as relax_batch: every node of the call starts from the evaluation the call started from */
     for (int32_t i = 0; i < n_nodes; i++) {
         const int32_t a = cut_offsets[i], n = cut_offsets[i + 1] - a;
+        e->evaluation = start;
         int rc = jslp_engine_relax_watched(e, n, type ? type + a : 0, var_index ? var_index + a : 0, value ? value + a : 0, check_cycles,
                                            &out[i], watched_row ? watched_row + (size_t)i * e->n_watch : 0,
                                            watched_value ? watched_value + (size_t)i * e->n_watch : 0);
@@ -1105,17 +1110,31 @@ int jslp_pool_relax_batch(jslp_pool* p, int32_t n_nodes, const int32_t* cut_offs
         int rc = jslp_pool_sync_root(p);
         if (rc) return rc;
     }
-    for (int32_t mi = 0; mi < p->n; mi++) { /* the same contiguous ranges the product hands its members */
+    /* the same contiguous ranges the product hands its members.  Every member works through its own range whatever the others do (the
+       product's run side by side): a refused cut list ends its member's range, the call fails with the code and the text of the
+       lowest-numbered member that failed, and that member's evaluation stays what it was when the call began.  Every node of a range
+       starts from the evaluation its member had when the call began (see jslp_engine_relax_batch). */
+    int first_rc = JSLP_OK;
+    char first_err[sizeof g_err];
+    for (int32_t mi = 0; mi < p->n; mi++) {
         const int32_t first = (int32_t)((int64_t)n_nodes * mi / p->n), last = (int32_t)((int64_t)n_nodes * (mi + 1) / p->n);
+        jslp_engine* m = p->members[mi];
+        const double start = m->evaluation;
         for (int32_t i = first; i < last; i++) {
             const int32_t a = cut_offsets[i], n = cut_offsets[i + 1] - a;
-            int rc = jslp_engine_relax(p->members[mi], n, type ? type + a : 0, var_index ? var_index + a : 0, value ? value + a : 0,
+            m->evaluation = start;
+            int rc = jslp_engine_relax(m, n, type ? type + a : 0, var_index ? var_index + a : 0, value ? value + a : 0,
                                        check_cycles, &out[i], rhs ? rhs + (size_t)i * out_stride : 0,
                                        var_index_by_row ? var_index_by_row + (size_t)i * out_stride : 0);
-            if (rc) return rc;
+            if (rc) {
+                m->evaluation = start;
+                if (!first_rc) { first_rc = rc; memcpy(first_err, g_err, sizeof g_err); }
+                break;
+            }
         }
     }
-    return JSLP_OK;
+    if (first_rc) memcpy(g_err, first_err, sizeof g_err);
+    return first_rc;
 }
 
 int jslp_pool_relax_batch_pinned(jslp_pool* p, int32_t n_nodes, const int32_t* cut_offsets, const int8_t* type,
@@ -1174,17 +1193,27 @@ int jslp_pool_relax_batch_watched(jslp_pool* p, int32_t n_nodes, const int32_t* 
         if (rc) return rc;
     }
     const size_t nw = (size_t)e->n_watch;
+    int first_rc = JSLP_OK; /* members, failures and evaluations as in jslp_pool_relax_batch */
+    char first_err[sizeof g_err];
     for (int32_t mi = 0; mi < p->n; mi++) {
         const int32_t first = (int32_t)((int64_t)n_nodes * mi / p->n), last = (int32_t)((int64_t)n_nodes * (mi + 1) / p->n);
+        jslp_engine* m = p->members[mi];
+        const double start = m->evaluation;
         for (int32_t i = first; i < last; i++) {
             const int32_t a = cut_offsets[i], n = cut_offsets[i + 1] - a;
-            int rc = jslp_engine_relax_watched(p->members[mi], n, type ? type + a : 0, var_index ? var_index + a : 0, value ? value + a : 0,
+            m->evaluation = start;
+            int rc = jslp_engine_relax_watched(m, n, type ? type + a : 0, var_index ? var_index + a : 0, value ? value + a : 0,
                                                check_cycles, &out[i], watched_row ? watched_row + (size_t)i * nw : 0,
                                                watched_value ? watched_value + (size_t)i * nw : 0);
-            if (rc) return rc;
+            if (rc) {
+                m->evaluation = start;
+                if (!first_rc) { first_rc = rc; memcpy(first_err, g_err, sizeof g_err); }
+                break;
+            }
         }
     }
-    return JSLP_OK;
+    if (first_rc) memcpy(g_err, first_err, sizeof g_err);
+    return first_rc;
 }
 
 int jslp_pool_relax_batch_watched_pinned(jslp_pool* p, int32_t n_nodes, const int32_t* cut_offsets, const int8_t* type,

@@ -361,7 +361,9 @@ def test_families_on_the_oracle(oracle_lib):
                          "neither basic nor non-basic": _capi.JSLP_ERR_ARG, "spare + 1 cuts": _capi.JSLP_ERR_CAPACITY}, (name, codes)
         if name.startswith("stride 41x15") and "+" not in name:
             stride_cases |= {(root["cap"] % 4, w["height"] % 2) for w in want}
-    # out_stride modulo 4 (of the pool's plain row capacity) against odd and even final heights
+    # the row capacity modulo 4 against odd and even final heights: the engine's own read-back rounds its stride up to a multiple of 4, so here
+    # these roots all take the 16-byte stores; tests/test_pool_device_edges.py is where the residues meet both branches of the gather (the pool's
+    # shared buffer is laid out with the plain row capacity, a `_device` caller passes its own row_stride)
     assert stride_cases == {(c, o) for c in range(4) for o in range(2)}, stride_cases
     print({n: round(r["oracle_s"], 2) for n, r in p.items() if r["oracle_s"] > 0.5})
     slow = {n: round(r["oracle_s"], 1) for n, r in p.items() if r["oracle_s"] > 30}

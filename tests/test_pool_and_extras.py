@@ -76,16 +76,31 @@ def _check_pool_watched(lib, n_members, reps):
         pool.n_watched = len(ints)
         pool.applyCutsBatchWatched(nodes[:4], check_cycles=True)
     pool.set_watched_variables(ints)
+    # a node without an optimum keeps the evaluation its MEMBER had when the call began -- tableau.evaluation is left alone, simplex.ts:73-76 --:
+    # the fan-out sets every member's to the primary's, a share moves its member's to its last node's (include/jslp_engine.h, the pool comment)
+    member_eval = [t.evaluation] * n_members
+
+    def kept(res):
+        exp = []
+        for mi in range(n_members):
+            first, last = len(nodes) * mi // n_members, len(nodes) * (mi + 1) // n_members
+            exp += [res[i].evaluation if res[i].optimal else (float("-inf") if not res[i].bounded else member_eval[mi]) for i in range(first, last)]
+            if last > first:
+                member_eval[mi] = exp[-1]
+        return exp
+
     full_res, rhs, rows = pool.applyCutsBatch(nodes, check_cycles=True, copy=True)
+    assert [r.evaluation for r in full_res] == kept(full_res)
     ints_a = np.asarray(ints)
     for copy in (True, False):
         out, rows_w, vals_w = pool.applyCutsBatchWatched(nodes, check_cycles=True, copy=copy)
+        exp = kept(out)
         for i, call in enumerate(want):
             h = out[i].height
             assert bool(out[i].feasible) == call["feasible"] and h == call["height"]
             a_, b_ = out[i].as_dict(), full_res[i].as_dict()
-            if not call["feasible"]:  # (an infeasible node keeps the evaluation its ENGINE had before the call -- tableau.evaluation is
-                a_.pop("evaluation"), b_.pop("evaluation")  # left alone, simplex.ts:73-76 -- and the members' histories differ between the two calls)
+            if not call["feasible"]:  # (the members' histories differ between the two calls: the full call's was held to the rule above, this one's is here)
+                b_["evaluation"] = exp[i]
             assert a_ == b_
             assert G.sha_rhs(rhs[i, :h], rows[i, :h]) == call["rhsSha"]
             row_of = np.full(int(max(rows[i, :h].max(), ints_a.max())) + 1, -1, dtype=np.int64)
