@@ -1,5 +1,5 @@
 """ctypes binding of the C ABI declared in include/jslp_engine.h (SYMBOLS) and of its HIP-only extensions include/jslpx_branch.h
-(BRANCH_SYMBOLS) and include/jslpm_many.h (MANY_SYMBOLS).
+(BRANCH_SYMBOLS), include/jslpm_many.h (MANY_SYMBOLS) and include/jslpf_f32.h (F32_SYMBOLS).
 
 The same binding class serves two libraries that export identical symbols:
   * jslpsolver_amd/csrc/libjslp_hip.so -- the product (hand-written HIP kernels, gfx950)
@@ -162,6 +162,15 @@ MANY_SYMBOLS = {
     "jslpm_simplex_many": (C.c_int, [_P(C.c_void_p), C.c_int32, _i32p, _P(SimplexResult), _i32p]),
 }
 
+# name -> (restype, argtypes); must list EVERY symbol include/jslpf_f32.h declares.  HIP library only, like BRANCH_SYMBOLS
+# (Library.has_f32).
+F32_SYMBOLS = {
+    "jslpf_simplex_f32_sweep": (C.c_int, [C.c_void_p, _f64p, C.c_int32, C.c_int, C.c_int32, _P(SimplexResult), _f64p, _i32p, C.c_int32,
+                                          _i32p, _i32p, _f64p]),
+}
+JSLPF_PATH_AUTO, JSLPF_PATH_SELECT_UPDATE, JSLPF_PATH_ONE_LAUNCH = 0, 1, 2
+JSLPF_MAX_RUNS = 64
+
 
 class EngineError(RuntimeError):
     pass
@@ -182,6 +191,7 @@ class Library:
             setattr(self, name, fn)
         self.has_branch = self._bind_extension(BRANCH_SYMBOLS)
         self.has_many = self._bind_extension(MANY_SYMBOLS)
+        self.has_f32 = self._bind_extension(F32_SYMBOLS)
 
     def _bind_extension(self, symbols):
         """bind a HIP-only extension when the library exports all of it; False otherwise"""

@@ -15,6 +15,7 @@
 #include "../../include/jslp_engine.h"
 #include "../../include/jslpx_branch.h"
 #include "../../include/jslpm_many.h"
+#include "../../include/jslpf_f32.h"
 #include "jslp_kernels.hip.h"
 #include "jslp_host_mem.h"
 
@@ -126,6 +127,7 @@ struct jslp_engine {
     // fp32 twin of slot 0 (jslp_engine_simplex_f32), allocated on first use
     f32::Slots s32{};
     DevBuf arena32;
+    int32_t n32 = 0;  // tableau copies the arena holds (ensure_f32)
     // policy
     int force_path = 0;  // 0 auto, 1 workgroup kernel, 2 select+update kernels only, 3 fused phase 2
     int force_xl = 0, xl_on = 0;  // JSLP_FORCE_PATH=xl / JSLP_XL=0: the XCD-local register-resident geometry (resident_geometry 6)
@@ -1639,9 +1641,11 @@ extern "C" int jslp_engine_mir_round(jslp_engine* e, int check_cycles, int32_t* 
 }
 
 // ---- fp32 twin -----------------------------------------------------------------------------------------------------
-static int ensure_f32(jslp_engine* e) {
-    if (e->arena32.p) return JSLP_OK;
-    f32::Slots& s = e->s32;
+// the fp32 arena holds `n` copies (copy 0: what jslp_engine_simplex_f32 runs on; copies 0 .. n-1: the runs of a one-launch sweep,
+// include/jslpf_f32.h).  It only grows, into a fresh allocation: a failed reservation leaves the old arena and its slots in place
+static int ensure_f32(jslp_engine* e, int32_t n = 1) {
+    if (e->arena32.p && n <= e->n32) return JSLP_OK;
+    f32::Slots s = e->s32;
     s.A_stride = (long long)e->cap_rows * e->ld;
     s.vibr_stride = e->cap_rows; s.vibc_stride = e->W; s.idx_stride = e->n_idx;
     s.prow_stride = e->ld; s.pcol_stride = e->cap_rows;
@@ -1650,19 +1654,25 @@ static int ensure_f32(jslp_engine* e) {
     s.oo = nullptr; s.oo_stride = 0; s.n_opt = 0;
     s.rhs = nullptr;
     s.trace = nullptr; s.trace_cap = 0;
-    HIPC_CARVE(e->arena32, [&](Carver& cv) {
-        s.A = cv.take<float>((size_t)s.A_stride);
-        s.vibr = cv.take<int32_t>((size_t)s.vibr_stride);
-        s.vibc = cv.take<int32_t>((size_t)s.vibc_stride);
-        s.rbv = cv.take<int32_t>((size_t)s.idx_stride);
-        s.cbv = cv.take<int32_t>((size_t)s.idx_stride);
-        s.prow = cv.take<float>((size_t)s.prow_stride);
+    const size_t copies = (size_t)n;
+    DevBuf grown;
+    HIPC_CARVE(grown, [&](Carver& cv) {
+        s.A = cv.take<float>(copies * (size_t)s.A_stride);
+        s.vibr = cv.take<int32_t>(copies * (size_t)s.vibr_stride);
+        s.vibc = cv.take<int32_t>(copies * (size_t)s.vibc_stride);
+        s.rbv = cv.take<int32_t>(copies * (size_t)s.idx_stride);
+        s.cbv = cv.take<int32_t>(copies * (size_t)s.idx_stride);
+        s.prow = cv.take<float>((size_t)s.prow_stride);  // (the select + update kernels' vectors: copy 0 only)
         s.pcol = cv.take<float>((size_t)s.pcol_stride);
         s.dirty = cv.take<uint8_t>((size_t)s.pcol_stride);
-        s.st = cv.take<DevState>(1);
-        s.hist = cv.take<int2>((size_t)s.hist_cap);
+        s.st = cv.take<DevState>(copies);
+        s.hist = cv.take<int2>(copies * (size_t)s.hist_cap);
     });
-    HIPC(hipMemsetAsync(e->arena32.p, 0, sizeof(float) * (size_t)s.A_stride, e->res.stream));  // padding columns / rows stay 0
+    HIPC(hipStreamSynchronize(e->res.stream));  // nothing in flight reads the old arena
+    e->arena32 = std::move(grown);
+    e->s32 = s;
+    e->n32 = n;
+    HIPC(hipMemsetAsync(s.A, 0, sizeof(float) * copies * (size_t)s.A_stride, e->res.stream));  // padding columns / rows stay 0
     return JSLP_OK;
 }
 
@@ -3085,5 +3095,126 @@ extern "C" int jslp_engine_get_timing(jslp_engine* e, double* update_kernel_ms, 
     if (update_kernel_ms) *update_kernel_ms = e->upd_ms;
     if (update_kernel_launches) *update_kernel_launches = e->upd_launches;
     if (total_device_ms) *total_device_ms = e->total_ms;
+    return JSLP_OK;
+}
+
+// ---- the fp32 twin as a sweep (include/jslpf_f32.h) -----------------------------------------------------------------------------
+// Behind every other kernel of this translation unit: k32_simplex_lds is instantiated last.
+#include "jslp_f32_lds.hip.h"
+
+// dynamic LDS of k32_simplex_lds for this engine; 0 = its fp32 LDS state does not fit
+static size_t f32lds_smem(const jslp_engine* e) {
+    const size_t b = f32lds_bytes(e->ld, e->cap_rows);
+    return b <= WGLDS_MAX_BYTES ? b : 0;
+}
+// JSLPF_PATH_AUTO: use_wg_single's rule restated for k32_simplex_lds, without the force-path knobs (the bounds were measured for
+// the fp64 kernels; what the fp32 kernel measured against them: DESIGN.md section 4, profiles/f32_one_launch_times.md)
+static bool f32_auto_one_launch(const jslp_engine* e) {
+    if (!f32lds_smem(e)) return false;
+    const long long cells = (long long)e->cap_rows * e->ld;
+    if (cells <= WG_CELLS_SINGLE) return true;
+    return cells <= WG_CELLS_SPARSE && e->nnz >= 0 && (double)e->nnz <= WG_SPARSE_DENSITY * (double)e->H0 * (double)e->W;
+}
+// what jslp_engine_simplex_f32 makes of a finished fp32 state
+static void fill_f32_result(const jslp_engine* e, const DevState& st, double precision, jslp_simplex_result* out) {
+    memset(out, 0, sizeof *out);
+    out->feasible = st.feasible;
+    out->bounded = st.bounded;
+    out->optimal = st.optimal;
+    out->unbounded_var_index = st.bounded ? -1 : st.unbounded_var;
+    out->pivots_phase1 = st.it1;
+    out->pivots_phase2 = st.entered_phase2 ? st.it2 : -1;
+    out->cycle_phase = st.cycle_phase;
+    out->height = st.H;
+    out->obj_cell = st.obj_cell;
+    out->evaluation = e->evaluation;
+    if (st.optimal) {
+        const double rcoef = js_round(1.0 / precision);
+        out->evaluation = js_round((2.220446049250313e-16 + st.obj_cell) * rcoef) / rcoef;
+    } else if (!st.bounded) {
+        out->evaluation = -INFINITY;
+    }
+}
+
+extern "C" int jslpf_simplex_f32_sweep(jslp_engine* e, const double* precisions, int32_t n, int check_cycles, int32_t path,
+                                       jslp_simplex_result* out, double* rhs, int32_t* var_index_by_row, int32_t stride,
+                                       int32_t* status, int32_t* path_taken, double* device_ms) {
+    if (n < 0 || n > JSLPF_MAX_RUNS) return fail(JSLP_ERR_ARG, "simplex_f32_sweep: the number of runs must be in [0, 64]");
+    if (n > 0 && (!precisions || !out)) return fail(JSLP_ERR_ARG, "simplex_f32_sweep: null pointer");
+    if (path != JSLPF_PATH_AUTO && path != JSLPF_PATH_SELECT_UPDATE && path != JSLPF_PATH_ONE_LAUNCH)
+        return fail(JSLP_ERR_ARG, "simplex_f32_sweep: unknown path");
+    char idx[32];
+    for (int32_t i = 0; i < n; i++)
+        if (!(precisions[i] > 0)) {
+            snprintf(idx, sizeof idx, "%d", (int)i);
+            return fail(JSLP_ERR_ARG, "simplex_f32_sweep: run %s: precision must be positive", idx);
+        }
+    if (n == 0) return JSLP_OK;
+    if (!e) return fail(JSLP_ERR_STATE, "simplex_f32_sweep: null engine");
+    if (!e->uploaded) return fail(JSLP_ERR_STATE, "simplex_f32_sweep before upload");
+    if (e->n_opt > 0) return fail(JSLP_ERR_UNSUPPORTED, "simplex_f32_sweep: optional objectives are not part of the fp32 experiment");
+    const size_t lds = f32lds_smem(e);
+    if (path == JSLPF_PATH_ONE_LAUNCH && !lds)
+        return fail(JSLP_ERR_UNSUPPORTED, "simplex_f32_sweep: the tableau's fp32 LDS state does not fit one workgroup (k32_simplex_lds)");
+    HIPC(hipSetDevice(e->device));
+    hipStream_t s = e->res.stream;
+    if (rhs || var_index_by_row) {  // the live height decides whether the caller's arrays hold a run
+        HIPC(hipMemcpyAsync(e->h_state, e->s.st, sizeof(DevState), hipMemcpyDeviceToHost, s));
+        HIPC(hipStreamSynchronize(s));
+        if (stride < e->h_state->H) return fail(JSLP_ERR_ARG, "simplex_f32_sweep: stride below the live height");
+    }
+    const bool one_launch = path == JSLPF_PATH_ONE_LAUNCH || (path == JSLPF_PATH_AUTO && f32_auto_one_launch(e));
+    if (path_taken) *path_taken = one_launch ? JSLPF_PATH_ONE_LAUNCH : JSLPF_PATH_SELECT_UPDATE;
+    if (status) for (int32_t i = 0; i < n; i++) status[i] = JSLP_OK;
+    int32_t first_bad = -1; int first_rc = JSLP_OK; char first_msg[sizeof g_err];
+    auto note = [&](int32_t i, int rc) {
+        if (status) status[i] = rc;
+        if (first_bad < 0) { first_bad = i; first_rc = rc; snprintf(first_msg, sizeof first_msg, "%s", g_err); }
+    };
+    double total_ms = 0;
+    if (!one_launch) {
+        for (int32_t i = 0; i < n; i++) {
+            jslp_simplex_result r;
+            double ms = 0;
+            const int rc = jslp_engine_simplex_f32(e, precisions[i], check_cycles, &r, rhs ? rhs + (size_t)i * stride : nullptr,
+                                                   var_index_by_row ? var_index_by_row + (size_t)i * stride : nullptr, &ms);
+            if (rc) { note(i, rc); continue; }
+            out[i] = r;
+            total_ms = ms < 0 || total_ms < 0 ? -1.0 : total_ms + ms;
+        }
+    } else {
+        JSLP_TRY(ensure_f32(e, n));
+        JSLP_TRY(ensure_out(e, (size_t)n));
+        f32::Slots& d = e->s32;
+        d.unr = e->d_unr;
+        d.has_unr = e->n_unr > 0 ? 1 : 0;
+        F32Precisions precs{};
+        for (int32_t i = 0; i < n; i++) precs.v[i] = (float)precisions[i];
+        const int out_stride = (int)out_stride_of(e);
+        HIPC(hipEventRecord(e->res.ev_begin, s));
+        hipLaunchKernelGGL((k32_simplex_lds<JSLP_WG_THREADS>), dim3(n), dim3(JSLP_WG_THREADS), lds, s, e->s, d, precs, check_cycles ? 1 : 0,
+                           iters_cap(e), (int)e->cap_rows, e->d_rhs, e->d_rows, e->d_states, out_stride);
+        HIPC(hipGetLastError());
+        HIPC(hipEventRecord(e->res.ev_end, s));
+        if (debug_launch_on()) fprintf(stderr, "[jslp] launch k32_simplex_lds<%d> n %d lds %zu\n", JSLP_WG_THREADS, (int)n, lds);
+        HIPC(hipMemcpyAsync(e->res.out.h.p, e->res.out.d.p, out_bytes(e, (size_t)n), hipMemcpyDeviceToHost, s));
+        HIPC(hipStreamSynchronize(s));
+        float ms = 0;
+        total_ms = hipEventElapsedTime(&ms, e->res.ev_begin, e->res.ev_end) == hipSuccess ? ms : -1.0;
+        for (int32_t i = 0; i < n; i++) {
+            const DevState st = e->h_states[i];
+            const int rc = state_error(st);
+            if (rc) { note(i, rc); continue; }
+            fill_f32_result(e, st, precisions[i], &out[i]);
+            if (rhs) memcpy(rhs + (size_t)i * stride, e->h_rhs + (size_t)i * out_stride, sizeof(double) * st.H);
+            if (var_index_by_row) memcpy(var_index_by_row + (size_t)i * stride, e->h_rows + (size_t)i * out_stride, sizeof(int32_t) * st.H);
+        }
+    }
+    if (device_ms) *device_ms = total_ms;
+    if (first_bad >= 0) {
+        snprintf(idx, sizeof idx, "%d", (int)first_bad);
+        snprintf(g_err, sizeof g_err, "simplex_f32_sweep: run %s: %s", idx, first_msg);
+        return first_rc;
+    }
     return JSLP_OK;
 }

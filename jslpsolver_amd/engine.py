@@ -402,6 +402,34 @@ class Tableau:
                        "jslp_engine_simplex_f32")
         return res, rhs[:res.height], vibr[:res.height], ms.value
 
+    F32_PATHS = {"auto": _capi.JSLPF_PATH_AUTO, "select_update": _capi.JSLPF_PATH_SELECT_UPDATE, "one_launch": _capi.JSLPF_PATH_ONE_LAUNCH}
+
+    def simplex_f32_sweep(self, precisions, check_cycles=True, path="auto"):
+        """simplex_f32 at every tolerance of `precisions` in one call (include/jslpf_f32.h): path "one_launch" solves them in ONE kernel
+        launch, one workgroup per tolerance; "select_update" is the loop of simplex_f32, one run after the other; "auto" picks.
+        Returns (runs, path_taken, device ms of the call) with runs[i] = (result, rhs, varIndexByRow) -- what simplex_f32(precisions[i])
+        returns.  A run that ends on an error of its own (iteration cap ...) raises, naming the run."""
+        if not self.lib.has_f32:
+            raise _capi.EngineError("simplex_f32_sweep: %s does not export the fp32 sweep extension (include/jslpf_f32.h)" % self.lib.path)
+        if path not in self.F32_PATHS:
+            raise ValueError("simplex_f32_sweep: path must be one of %s" % ", ".join(sorted(self.F32_PATHS)))
+        prec = _capi.as_f64(list(precisions))
+        n = int(prec.shape[0])
+        out = (SimplexResult * max(n, 1))()
+        stride = self.row_capacity
+        rhs = np.empty((max(n, 1), stride), dtype=np.float64)
+        vibr = np.empty((max(n, 1), stride), dtype=np.int32)
+        taken = _capi.C.c_int32(0)
+        ms = _capi.C.c_double(0.0)
+        self.lib.check(self.lib.jslpf_simplex_f32_sweep(self._h, _capi.ptr_f64(prec), n, int(bool(check_cycles)), self.F32_PATHS[path], out,
+                                                        _capi.ptr_f64(rhs), _capi.ptr_i32(vibr), stride, None, _capi.C.byref(taken),
+                                                        _capi.C.byref(ms)), "jslpf_simplex_f32_sweep")
+        runs = []
+        for i in range(n):
+            res = SimplexResult.from_buffer_copy(out[i])
+            runs.append((res, rhs[i, :res.height].copy(), vibr[i, :res.height].copy()))
+        return runs, taken.value, ms.value
+
     # ---- MIR cuts (cutting-strategies.ts:74-212) --------------------------------------------------------
     def applyMIRCuts(self):
         """Tableau.applyMIRCuts (:199-212); returns the number of rows appended"""
