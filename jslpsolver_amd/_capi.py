@@ -1,5 +1,5 @@
 """ctypes binding of the C ABI declared in include/jslp_engine.h (SYMBOLS) and of its HIP-only extensions include/jslpx_branch.h
-(BRANCH_SYMBOLS), include/jslpm_many.h (MANY_SYMBOLS) and include/jslpf_f32.h (F32_SYMBOLS).
+(BRANCH_SYMBOLS), include/jslpm_many.h (MANY_SYMBOLS), include/jslpf_f32.h (F32_SYMBOLS) and include/jslpr_mir.h (MIR_SYMBOLS).
 
 The same binding class serves two libraries that export identical symbols:
   * jslpsolver_amd/csrc/libjslp_hip.so -- the product (hand-written HIP kernels, gfx950)
@@ -172,6 +172,31 @@ JSLPF_PATH_AUTO, JSLPF_PATH_SELECT_UPDATE, JSLPF_PATH_ONE_LAUNCH = 0, 1, 2
 JSLPF_MAX_RUNS = 64
 
 
+class MirOutcome(C.Structure):
+    """struct jslpr_mir_outcome (include/jslpr_mir.h): what the MIR loop of one node did, 32 bytes"""
+
+    _fields_ = [
+        ("rounds", C.c_int32),
+        ("rows_added", C.c_int32),
+        ("optimal_count", C.c_int32),
+        ("pivots", C.c_int32),
+        ("volume_before", C.c_double),
+        ("volume_after", C.c_double),
+    ]
+
+
+MIR_OUTCOME_DTYPE = np.dtype([(name, np.int32 if ctype is C.c_int32 else np.float64) for name, ctype in MirOutcome._fields_])
+JSLPR_MAX_ROUNDS = 64
+
+# name -> (restype, argtypes); must list EVERY symbol include/jslpr_mir.h declares.  HIP library only, like BRANCH_SYMBOLS
+# (Library.has_mir).
+MIR_SYMBOLS = {
+    "jslpr_mir_outcome_bytes": (C.c_int32, []),
+    "jslpr_engine_relax_mir": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _i32p, _i8p, _i32p, _f64p, C.c_int, C.c_int32, C.c_int32,
+                                         _P(SimplexResult), C.c_void_p, _f64p, _i32p, C.c_int32]),
+}
+
+
 class EngineError(RuntimeError):
     pass
 
@@ -192,6 +217,7 @@ class Library:
         self.has_branch = self._bind_extension(BRANCH_SYMBOLS)
         self.has_many = self._bind_extension(MANY_SYMBOLS)
         self.has_f32 = self._bind_extension(F32_SYMBOLS)
+        self.has_mir = self._bind_extension(MIR_SYMBOLS)
 
     def _bind_extension(self, symbols):
         """bind a HIP-only extension when the library exports all of it; False otherwise"""

@@ -149,15 +149,8 @@ def most_fractional_var(model, rhs, rows):
 def fractional_volume(model, rhs, vibr, precision):
     """computeFractionalVolume(ignoreIntegerValues = true) (mip-utils.ts:67-92): the product, in row order, of |value|
     over the basic integer variables that are not at an integer value"""
-    integer = model.integer_index_set
-    volume = -1.0
-    for r in range(1, len(vibr)):
-        if int(vibr[r]) in integer:
-            distance = abs(float(rhs[r]))
-            if min(distance - math.floor(distance), math.floor(distance + 1)) < precision:
-                continue
-            volume = distance if volume == -1.0 else volume * distance
-    return 0.0 if volume == -1.0 else volume
+    from .engine import fractional_volume_rows
+    return fractional_volume_rows(model.integer_index_set, rhs, vibr, precision)
 
 
 def mir_loop(tableau, model, rhs, vibr, check, max_rounds=None, need_feasible=False):
@@ -183,6 +176,15 @@ class _NodeEval:
 
     def __init__(self, res, rhs, vibr):
         self.res, self.rhs, self.vibr = res, rhs, vibr
+
+
+class _NodeEvalMIR:
+    """outcome of a node evaluated WITH its MIR loop (Tableau.applyCutsBatchMIR): the last simplex's result with the folded evaluation,
+    the loop's outcome record, and the whole RHS column / row map"""
+    __slots__ = ("res", "outcome", "rhs", "vibr")
+
+    def __init__(self, res, outcome, rhs, vibr):
+        self.res, self.outcome, self.rhs, self.vibr = res, outcome, rhs, vibr
 
 
 class _NodeEvalWatched:
@@ -225,6 +227,10 @@ def branch_and_cut(tableau, model, speculate=1, evaluate_batch=None, read_back=N
     read_back ("full" / "compact" / "branch"; None = JSLP_TREE_BRANCH=1 -> "branch", else "compact") picks what a speculative batch reads
     back per node: whole RHS columns + row maps, the integer variables' rows and values, or the 32-byte branch record the engine reduces
     them to (include/jslpx_branch.h).  Opt-in; whichever it is, the tree, its result and its iteration count are the same.
+
+    options.useMIRCuts: a speculative batch evaluates every node WITH its MIR loop (Tableau.applyCutsBatchMIR, include/jslpr_mir.h) and reads
+    whole columns back (read_back is ignored); the root, before save(), and the final re-evaluation of the incumbent keep the round-by-round
+    loop.  Without speculation JSLP_TREE_MIR=1 makes every node after the root one Tableau.applyCutsMIR call.
     """
     branches = BranchMinHeap()
     iterations = 0
@@ -240,8 +246,13 @@ def branch_and_cut(tableau, model, speculate=1, evaluate_batch=None, read_back=N
     precision = tableau.precision
     n_opt = getattr(tableau, "n_optional", 0)
     best_optional = [math.inf] * n_opt  # bestOptionalObjectivesEvaluations (:66-69)
-    if n_opt > 0 or model.useMIRCuts:
+    # a MIR node is a pure function of the saved root and its cut list like any other: its batches run each node's MIR loop inside the
+    # engine call (Tableau.applyCutsBatchMIR, whole columns read back).  A caller's evaluate_batch knows nothing of the loop
+    mir = bool(model.useMIRCuts)
+    if n_opt > 0 or (mir and evaluate_batch is not None):
         speculate = 1  # the tie-break below reads the live optional-objective cells / the MIR loop is driven per node
+    # JSLP_TREE_MIR=1 (read per call): without speculation, every node after the root is ONE engine call too (Tableau.applyCutsMIR)
+    mir_one_call = mir and n_opt == 0 and os.environ.get("JSLP_TREE_MIR", "0") == "1"
     if evaluate_batch is None and tableau.width * tableau.height0 > 1536 * 1024:
         speculate = 1  # one workgroup per node only pays for small tableaus; big ones go node by node through the chip-wide kernels
     cache = {}          # heap sequence number -> _NodeEval
@@ -253,7 +264,7 @@ def branch_and_cut(tableau, model, speculate=1, evaluate_batch=None, read_back=N
     if read_back not in ("full", "compact", "branch"):
         raise ValueError("branch_and_cut: read_back must be 'full', 'compact' or 'branch'")
     compact_ok = (evaluate_batch is None and read_back != "full" and os.environ.get("JSLP_TREE_COMPACT", "1") != "0"
-                  and hasattr(tableau, "applyCutsBatchWatched") and 0 < len(model.integer_index_array) <= getattr(tableau, "row_capacity", 0))
+                  and not mir and hasattr(tableau, "applyCutsBatchWatched") and 0 < len(model.integer_index_array) <= getattr(tableau, "row_capacity", 0))
     branch_ok = compact_ok and read_back == "branch"
     watched_set = []
     watched_before = list(getattr(tableau, "watched", []) or [])  # the caller's own registration, put back when the tree is done
@@ -268,6 +279,10 @@ def branch_and_cut(tableau, model, speculate=1, evaluate_batch=None, read_back=N
         try:
             if evaluate_batch is not None:
                 return evaluate_batch(cut_lists)
+            if mir:
+                results, outcomes, rhs, vibr = tableau.applyCutsBatchMIR(cut_lists, check_cycles=check)
+                return [_NodeEvalMIR(results[i], outcomes[i].copy(), rhs[i, :results[i].height].copy(), vibr[i, :results[i].height].copy())
+                        for i in range(len(cut_lists))]
             if compact_ok:
                 # the compact read-back (jslp_engine_relax_batch_watched): per node the integer variables' rows and values -- what the loop
                 # below reads (mip-utils.ts:43-61, 100-126) -- instead of whole RHS columns + row maps; the leaf the tree commits to is
@@ -309,13 +324,18 @@ def branch_and_cut(tableau, model, speculate=1, evaluate_batch=None, read_back=N
                     cache[sq] = ev
                 speculated += len(batch)
             ev = cache.pop(seq)
-            tableau._absorb(ev.res)
+            if isinstance(ev, _NodeEvalMIR):
+                tableau._absorb_mir(ev.res, ev.outcome)
+            else:
+                tableau._absorb(ev.res)
             if isinstance(ev, _NodeEvalBranch):
                 rhs, vibr = None, ev
             elif isinstance(ev, _NodeEvalWatched):
                 rhs, vibr = None, _WatchedRows(ev.wrows, ev.wvals)
             else:
                 rhs, vibr = ev.rhs, ev.vibr
+        elif mir_one_call and saved:
+            _res, _outcome, rhs, vibr = tableau.applyCutsMIR(cuts, check_cycles=check)  # :33-52 in one engine call
         else:
             _res, rhs, vibr = tableau.applyCuts(cuts, check_cycles=check)
             rhs, vibr = mir_loop(tableau, model, rhs, vibr, check)  # :38-52
@@ -373,8 +393,9 @@ def branch_and_cut(tableau, model, speculate=1, evaluate_batch=None, read_back=N
         _res, rhs, vibr = tableau.applyCuts(best_cuts, check_cycles=check)
         mir_loop(tableau, model, rhs, vibr, check)
     elif speculate > 1 and saved and last_cuts is not None:
-        # no incumbent: the reference's tableau is left on the node it evaluated last; put ours there too
-        tableau.applyCuts(last_cuts, check_cycles=check)
+        # no incumbent: the reference's tableau is left on the node it evaluated last, MIR rows included; put ours there too
+        _res, rhs, vibr = tableau.applyCuts(last_cuts, check_cycles=check)
+        mir_loop(tableau, model, rhs, vibr, check)
     if watched_set and watched_before != list(model.integer_index_array):
         tableau.set_watched_variables(watched_before)  # (the caller's registration was borrowed for the compact read-back)
     tableau.speculated_nodes = speculated

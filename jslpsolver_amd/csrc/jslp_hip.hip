@@ -16,6 +16,7 @@
 #include "../../include/jslpx_branch.h"
 #include "../../include/jslpm_many.h"
 #include "../../include/jslpf_f32.h"
+#include "../../include/jslpr_mir.h"
 #include "jslp_kernels.hip.h"
 #include "jslp_host_mem.h"
 
@@ -74,6 +75,8 @@ struct jslp_engine {
     int32_t *snap_vibr = nullptr, *snap_vibc = nullptr, *snap_rbv = nullptr, *snap_cbv = nullptr;
     uint8_t* d_unr = nullptr;
     uint8_t* d_isint = nullptr;  // variable.isInteger per variable index (MIR cuts)
+    int has_int = 0;             // jslp_engine_set_integer_variables registered at least one since the last upload
+    StagePair mir_rec;           // jslpr_engine_relax_mir: one MirRec per node (device / pinned), or the 8 bytes of k_fractional_volume
     int32_t n_opt = 0; double* snap_oo = nullptr;  // optional objectives (slot copies live in s.oo)
     DevBuf oo_mem, snap_oo_mem;                      // ... what s.oo and snap_oo point into (resize_optional_objectives)
     // cuts staging (res.cuts): ONE pinned host buffer -> ONE device buffer per call: [value | offs | var | type]
@@ -558,6 +561,7 @@ extern "C" int jslp_engine_upload(jslp_engine* e, const double* matrix, const in
     ub.unr = ub.vibc + W;
     ub.H = H; ub.n_unr = n_unrestricted; ub.n_idx = e->n_idx; ub.cap_rows = e->cap_rows;
     hipLaunchKernelGGL(k_upload_finish, dim3(1), dim3(1024), 0, s, e->s, ub, e->d_unr, e->d_isint);
+    e->has_int = 0;
     HIPC(hipGetLastError());
     HIPC(hipMemcpyAsync(e->h_state, e->d_nnz, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     HIPC(hipStreamSynchronize(s));  // the staging buffer (and the host's view of it) is free again
@@ -1614,6 +1618,7 @@ extern "C" int jslp_engine_set_integer_variables(jslp_engine* e, const int32_t* 
     }
     HIPC(hipMemcpyAsync(e->d_isint, flags.data(), e->n_idx, hipMemcpyHostToDevice, e->res.stream));
     HIPC(hipStreamSynchronize(e->res.stream));
+    e->has_int = n > 0;
     return JSLP_OK;
 }
 
@@ -1762,6 +1767,7 @@ struct DeviceDest {  // the caller's DEVICE memory takes the outcomes (no host c
     DevState* states = nullptr; double* rhs = nullptr; int32_t* rows = nullptr;
     int32_t stride = 0; double* rec = nullptr;  // entries per node in rhs / rows; ReadBack::BranchRecord: where the records go
 };
+struct MirCall { int32_t max_rounds, need_feasible; jslpr_mir_outcome* outcomes; };  // (include/jslpr_mir.h)
 struct NodeCall {
     CutLists cuts;
     int check_cycles = 0;
@@ -1774,6 +1780,7 @@ struct NodeCall {
     bool pinned = false;                 // 2. the caller reads the engine's pinned buffers itself (no second host copy)
     PinnedDest shared;                   //    ... or, with `pinned`, the device pool's: this call's range of its shared pinned buffer
     DeviceDest dev;                      // 3. the caller's device memory
+    const struct MirCall* mir = nullptr;  // jslpr_engine_relax_mir: every node runs its MIR loop inside the node kernel (one-launch shapes only)
     bool to_device() const { return dev.states != nullptr; }
     bool compact() const { return read_back != ReadBack::Full; }
     bool records() const { return read_back == ReadBack::BranchRecord; }
@@ -1787,6 +1794,7 @@ struct NodeArgs {  // the union of what the node kernels take
     int first = 0;   // k_node_lds / k_node_wg: first node of the launch = index of its outcome
     unsigned* done_flag = nullptr; unsigned done_seq = 0; int* done_count = nullptr;
     int n_nodes = -1; const int32_t* order = nullptr; int* queue = nullptr;  // k_node_queue (n_nodes: also the `n` of its debug line)
+    MirJob mj{};  // the MIR builds (jslp_mir_kernels.hip.h)
 };
 struct NodeKernel {
     const char* name;       // the JSLP_DEBUG_LAUNCH line (tests/test_node_edges.py asserts every one)
@@ -1830,6 +1838,26 @@ static const NodeKernel EAGER_WG_256 = NODE_KERNEL(launch_simplex_wg, 256, false
 static const NodeKernel EAGER_WG_512 = NODE_KERNEL(launch_simplex_wg, 512, false, "restore+add_cuts+simplex+gather k_simplex_wg<512,2048>", k_simplex_wg<512, 2048>);
 static const NodeKernel EAGER_WG_1024 = NODE_KERNEL(launch_simplex_wg, 1024, false, "restore+add_cuts+simplex+gather k_simplex_wg<1024,4096>", k_simplex_wg<1024, 4096>);
 #undef NODE_KERNEL
+// the MIR builds (include/jslpr_mir.h) live in a unit of their own (jslp_tu_mir.hip), which launches them by number: no row above moves
+#ifdef JSLP_SPLIT_TU
+extern "C" __attribute__((visibility("hidden"))) int jslpr_mir_launch_tu(int which, unsigned grid, size_t lds, const void* args, void* stream);
+static int mir_launch(int which, unsigned grid, size_t lds, const MirLaunch& m, hipStream_t s) { return jslpr_mir_launch_tu(which, grid, lds, &m, s); }
+#else
+static int mir_launch_impl(int which, unsigned grid, size_t lds, const void* bytes, hipStream_t st);  // (jslp_mir_kernels.hip.h, at the end of this file)
+static int mir_launch(int which, unsigned grid, size_t lds, const MirLaunch& m, hipStream_t s) { return mir_launch_impl(which, grid, lds, &m, s); }
+#endif
+template <int WHICH> static void launch_node_mir(const NodeArgs& a, int grid, size_t lds, hipStream_t s) {
+    MirLaunch m{};
+    m.s = *a.s; m.sn = a.sn; m.cu = a.cu; m.mj = a.mj;
+    m.check_cycles = a.check_cycles; m.iters_cap = a.iters_cap; m.cap_rows = a.cap_rows;
+    m.rhs = a.rhs; m.rows = a.rows; m.states = a.states; m.out_stride = a.out_stride; m.first = a.first;
+    m.done_flag = a.done_flag; m.done_seq = a.done_seq; m.done_count = a.done_count;
+    m.n_nodes = a.n_nodes; m.order = a.order; m.queue = a.queue;
+    (void)mir_launch(WHICH, (unsigned)grid, lds, m, s);  // (the unit only peeks at the launch's error: hipGetLastError in launch_node_kernel takes and reports it)
+}
+static const NodeKernel NODE_LDS_1024_MIR = {"k_node_lds<1024,opt 0,cow 0,mir 1>", 1024, true, launch_node_mir<MIR_K_NODE_LDS_1024>, nullptr};
+static const NodeKernel NODE_LDS_512_MIR = {"k_node_lds<512,opt 0,cow 0,mir 1>", 512, true, launch_node_mir<MIR_K_NODE_LDS_512>, nullptr};
+static const NodeKernel NODE_QUEUE_MIR = {"k_node_queue<512,cow 0,opt 0,mir 1>", 512, true, launch_node_mir<MIR_K_NODE_QUEUE_512>, nullptr};
 static_assert(JSLP_WG_THREADS == 1024, "the single-node shape of the table above");
 
 // JSLP_DEBUG_LAUNCH: which node kernel a relax call launched, one parseable stderr line per launch (tests/test_node_edges.py)
@@ -1849,18 +1877,21 @@ static int launch_node_kernel(const NodeKernel& k, const NodeArgs& a, int grid, 
 }
 
 // which kernel, from what the call site can observe (lds = wglds_smem(e): 0 = the tableau does not fit the LDS builds)
-static const NodeKernel& single_node_kernel(const jslp_engine* e, size_t lds) {
+static const NodeKernel& single_node_kernel(const jslp_engine* e, size_t lds, bool mir = false) {
+    if (mir) return NODE_LDS_1024_MIR;  // (eager start; mir_one_launch() has made sure of the LDS build)
     if (!lds) return NODE_WG_1024;
     if (e->s.n_opt > 0) return NODE_LDS_1024_OPT;
     return node_cow_single() ? NODE_LDS_1024_COW : NODE_LDS_1024;  // copy-on-write start, slot 0 made whole again behind the completion flag (jslp_wglds.hip.h)
 }
-static const NodeKernel& queue_kernel(const jslp_engine* e) {
+static const NodeKernel& queue_kernel(const jslp_engine* e, bool mir = false) {
+    if (mir) return NODE_QUEUE_MIR;
     if (e->s.n_opt > 0) return NODE_QUEUE_OPT;  // optional objectives: the OPT build (eager restores)
     return node_cow() ? NODE_QUEUE_COW : NODE_QUEUE;
 }
 // a one-group batch small enough for the 1024-thread latency shape (small_batch_1024): the only shape that can end in a polled completion flag
 static bool small_batch_shape(const jslp_engine* e, size_t lds, int g) { return lds && e->s.n_opt == 0 && g <= small_batch_1024(); }
-static const NodeKernel& group_kernel(const jslp_engine* e, size_t lds, int g) {
+static const NodeKernel& group_kernel(const jslp_engine* e, size_t lds, int g, bool mir = false) {
+    if (mir) return small_batch_shape(e, lds, g) ? NODE_LDS_1024_MIR : NODE_LDS_512_MIR;
     if (!lds) return NODE_WG_512;
     if (e->s.n_opt > 0) return NODE_LDS_1024_OPT;  // optional objectives: the 1024-thread build only, whatever the batch size
     if (small_batch_shape(e, lds, g)) return node_cow_small() && node_cow() ? NODE_LDS_1024_COW : NODE_LDS_1024;
@@ -1927,6 +1958,43 @@ static int node_call_check(jslp_engine* e, const NodeCall& c) {
     return JSLP_OK;
 }
 
+// ---- MIR node calls (include/jslpr_mir.h): where the kernels leave a node's MirRec, and what the host folds from it ------------------
+// zero_copy: the pinned half as the device sees it (what a polled completion flag needs); else the device half, copied behind the kernels
+static int mir_destination(jslp_engine* e, const NodeCall& c, size_t n_nodes, bool zero_copy, MirJob* mj) {
+    if (sizeof(MirRec) * n_nodes > e->mir_rec.bytes()) {
+        HIPC(hipStreamSynchronize(e->res.stream));
+        HIPC(e->mir_rec.reserve(sizeof(MirRec) * std::max<size_t>(n_nodes, 16)));
+    }
+    mj->is_int = e->d_isint; mj->max_rounds = c.mir->max_rounds; mj->need_feasible = c.mir->need_feasible;
+    mj->out = e->mir_rec.d.as<MirRec>();
+    if (zero_copy) {
+        void* p = nullptr;
+        HIPC(hipHostGetDevicePointer(&p, e->mir_rec.h.p, 0));
+        mj->out = static_cast<MirRec*>(p);
+    }
+    return JSLP_OK;
+}
+// node i's record -> its outcome, the evaluation folded over all its simplexes (fill_result knows the last one only), the host
+// half of the work counters for the simplexes before the last
+static void mir_fold(jslp_engine* e, const NodeCall& c, int i, const DevState& st, double prev_evaluation, jslp_simplex_result* out, double* evaluation_out) {
+    const MirRec& r = e->mir_rec.h.as<MirRec>()[i];
+    double ev = prev_evaluation;
+    if (r.fold_kind == 1) {
+        const double rc = js_round(1.0 / e->precision);
+        ev = js_round((2.220446049250313e-16 + r.fold_obj) * rc) / rc;
+    } else if (r.fold_kind == 2) {
+        ev = -INFINITY;
+    }
+    out->evaluation = ev;
+    *evaluation_out = ev;
+    c.mir->outcomes[i] = jslpr_mir_outcome{r.rounds, r.rows_added, r.optimal_count, r.pivots, r.volume_before, r.volume_after};
+    if (e->counting) {
+        e->wc.simplex_calls += r.rounds;
+        e->wc.pivots += (long long)r.pivots - ((long long)st.it1 + st.it2);
+        e->wc.height_sum += r.height_sum - st.H;
+    }
+}
+
 // ONE child of the saved root, slot 0 already in sync with the snapshot: one launch, one polled flag
 static bool single_child_fast_path(const jslp_engine* e, const NodeCall& c) {
     return c.cuts.n_nodes == 1 && c.checkpoint < 0 && e->has_save && e->slot0_synced && !e->timing && e->force_path <= 1 &&
@@ -1949,7 +2017,8 @@ static int relax_single_child(jslp_engine* e, const NodeCall& c, bool dbg) {
         return fail(JSLP_ERR_DEVICE, "%s: %s", "hipHostGetDevicePointer(&flag_dev, h_flag, 0)", hipGetErrorString(err));
     a.done_flag = flag.dev; a.done_seq = flag.seq;
     const size_t lds = wglds_smem(e);
-    JSLP_TRY(launch_node_kernel(single_node_kernel(e, lds), a, 1, lds, e->res.stream, dbg));
+    if (c.mir) JSLP_TRY(mir_destination(e, c, 1, true, &a.mj));
+    JSLP_TRY(launch_node_kernel(single_node_kernel(e, lds, c.mir != nullptr), a, 1, lds, e->res.stream, dbg));
     unsigned spins;
     if (!wait_done_flag(flag.host, flag.seq, spins)) HIPC(hipStreamSynchronize(e->res.stream));
     const DevState st = e->h_states[0];
@@ -1959,6 +2028,7 @@ static int relax_single_child(jslp_engine* e, const NodeCall& c, bool dbg) {
     if (e->counting) e->wc.cut_rows += c.cuts.offsets[1];
     double ev;
     JSLP_TRY(fill_result(e, st, 0, e->evaluation, &c.out[0], &ev));
+    if (c.mir) mir_fold(e, c, 0, st, e->evaluation, &c.out[0], &ev);
     e->evaluation = ev;
     if (!c.pinned) {
         const size_t n_out = c.compact() ? (size_t)e->n_watch : (size_t)st.H;
@@ -2075,7 +2145,7 @@ static int enqueue_queue(jslp_engine* e, const NodeCall& c, const NodePlan& p, c
     a.n_nodes = n_nodes;
     a.order = (node_queue() == 2 && n_nodes > p.group && (node_queue_order_full() || !pcie_bound)) ? e->d_cut_order : (const int32_t*)nullptr;
     a.queue = e->d_queue;
-    JSLP_TRY(launch_node_kernel(queue_kernel(e), a, p.group, wglds_smem(e), e->res.stream, dbg));
+    JSLP_TRY(launch_node_kernel(queue_kernel(e, c.mir != nullptr), a, p.group, wglds_smem(e), e->res.stream, dbg));
     return d.copies ? copy_outcomes(e, c, d, 0, n_nodes, false) : JSLP_OK;
 }
 // slots already in sync with the snapshot: restore of the dirty rows, cuts, simplex and gather in ONE launch per
@@ -2090,11 +2160,12 @@ static int enqueue_one_launch_group(jslp_engine* e, const NodeCall& c, const Nod
         if (arm_done_flag(e, polled) == hipSuccess) { a.done_flag = polled->dev; a.done_seq = polled->seq; a.done_count = e->d_done_count; }
         else (void)hipGetLastError();
     }
-    return launch_node_kernel(group_kernel(e, lds, g), a, g, lds, e->res.stream, dbg);
+    return launch_node_kernel(group_kernel(e, lds, g, c.mir != nullptr), a, g, lds, e->res.stream, dbg);
 }
 // restore, cuts, simplex and gather as launches of their own: any start, any tableau
 static int enqueue_eager_group(jslp_engine* e, const NodeCall& c, const NodePlan& p, const NodeArgs& a, int first, int g, bool dbg) {
     hipStream_t s = e->res.stream;
+    if (c.mir) return fail(JSLP_ERR_STATE, "internal: a MIR node call reached the eager sequence (mir_one_launch)");
     JSLP_TRY(enqueue_restore(e, 0, g, c.checkpoint));
     hipLaunchKernelGGL(k_add_cuts, dim3(g), dim3(256), 0, s, e->s, a.cu, 0, first, (int)e->cap_rows);
     HIPC(hipGetLastError());
@@ -2164,6 +2235,7 @@ static int decode_outcomes(jslp_engine* e, const NodeCall& c, const NodePlan& p,
         }
         double ev;
         JSLP_TRY(fill_result(e, st, p.wg && i < p.n_grouped ? i % p.group : 0, p.prev_eval, &c.out[i], &ev));
+        if (c.mir) mir_fold(e, c, i, st, p.prev_eval, &c.out[i], &ev);
         if (i == n_nodes - 1) e->evaluation = ev;
         if (!c.pinned && !c.compact()) {
             const size_t n_out = (size_t)st.H;
@@ -2201,6 +2273,7 @@ static int relax_batch_impl(jslp_engine* e, const NodeCall& c) {
     JSLP_TRY(node_destination(e, c, &d));
     NodeArgs a{&e->s, root_snapshot(e), Cuts{e->d_cut_offs, e->d_cut_type, e->d_cut_var, e->d_cut_val}, c.check_cycles, iters_cap(e), (int)e->cap_rows,
                c.want_rhs ? d.rhs : nullptr, c.want_rows ? d.rows : nullptr, d.states, c.compact() ? -e->n_watch : (int)d.row_stride};
+    if (c.mir) JSLP_TRY(mir_destination(e, c, (size_t)n_nodes, d.zc, &a.mj));
     DoneFlag polled;  // armed when the call ends by polling a completion flag instead of synchronising the streams
     if (p.wg && wglds_smem(e) && node_queue() && n_nodes > p.group && node_kernels_fit(e, c, p.group)) {
         JSLP_TRY(enqueue_queue(e, c, p, d, a, dbg));
@@ -2220,6 +2293,7 @@ static int relax_batch_impl(jslp_engine* e, const NodeCall& c) {
             HIPC(hipMemcpyAsync(e->rec.h.p, e->rec.d.p, sizeof(jslpx_branch_record) * (size_t)n_nodes, hipMemcpyDeviceToHost, s));
         }
     }
+    if (c.mir && !d.zc) HIPC(hipMemcpyAsync(e->mir_rec.h.p, e->mir_rec.d.p, sizeof(MirRec) * (size_t)n_nodes, hipMemcpyDeviceToHost, s));
     if (e->timing && p.wg) HIPC(hipEventRecord(e->res.ev_end, s));
     JSLP_TRY(wait_for_nodes(e, n_nodes, polled, t_enter));
     float ms = 0;
@@ -2295,6 +2369,111 @@ extern "C" int jslp_engine_relax(jslp_engine* e, int32_t n_cuts, const int8_t* t
     const int32_t offs[2] = {0, n_cuts};
     return jslp_engine_relax_batch(e, 1, offs, type, var_index, value, check_cycles, out, rhs, var_index_by_row,
                                    e->cap_rows);
+}
+
+// ---- a node with its MIR loop in one call (include/jslpr_mir.h) -------------------------------------------------------
+static_assert(sizeof(jslpr_mir_outcome) == 32 && JSLPR_MAX_ROUNDS == JSLPR_MAX_ROUNDS_DEV, "include/jslpr_mir.h and jslp_mir.hip.h agree");
+extern "C" int32_t jslpr_mir_outcome_bytes(void) { return (int32_t)sizeof(jslpr_mir_outcome); }
+
+// every node of the call would go through ONE launch of an LDS node kernel: what relax_batch_impl decides, asked beforehand
+static int mir_one_launch(jslp_engine* e, const NodeCall& c, bool* yes) {
+    *yes = false;
+    if (!wglds_smem(e) || c.checkpoint >= 0 || c.shared.states || !e->has_save) return JSLP_OK;
+    const int n_nodes = c.cuts.n_nodes;
+    NodePlan p;
+    JSLP_TRY(plan_node_call(e, c, &p));
+    // slots that are not in sync with the saved root yet are restored first -- what the eager sequence of a plain call begins with, and
+    // what leaves them in sync for every later call: a tree's MIR batches reach the one-launch shapes from their second call on at the latest
+    if (const int need = n_nodes == 1 ? 1 : p.group; p.wg && (!e->slot0_synced || need > e->slots_synced)) JSLP_TRY(enqueue_restore(e, 0, need));
+    if (single_child_fast_path(e, c)) { *yes = true; return JSLP_OK; }
+    if (!p.wg) return JSLP_OK;
+    if (node_queue() && n_nodes > p.group && node_kernels_fit(e, c, p.group)) { *yes = true; return JSLP_OK; }
+    for (int first = 0, g = 0; first < n_nodes; first += g) {
+        g = first < p.n_grouped ? std::min(p.group, p.n_grouped - first) : 1;
+        if (!(g > 1 && node_kernels_fit(e, c, g))) return JSLP_OK;
+    }
+    *yes = true;
+    return JSLP_OK;
+}
+// computeFractionalVolume(true) of the live tableau, computed on the device: 8 bytes come back
+static int device_volume(jslp_engine* e, double* volume) {
+    if (e->mir_rec.bytes() < sizeof(MirRec)) {
+        HIPC(hipStreamSynchronize(e->res.stream));
+        HIPC(e->mir_rec.reserve(sizeof(MirRec) * 16));
+    }
+    MirLaunch m{};
+    m.s = e->s; m.mj.is_int = e->d_isint; m.volume_out = e->mir_rec.d.as<double>();
+    if (mir_launch(MIR_K_VOLUME, 1, 0, m, e->res.stream) == -1) return fail(JSLP_ERR_STATE, "internal: no k_fractional_volume in this build");
+    HIPC(hipGetLastError());  // (the unit only peeked at the launch's error)
+    HIPC(hipMemcpyAsync(e->mir_rec.h.p, e->mir_rec.d.p, sizeof(double), hipMemcpyDeviceToHost, e->res.stream));
+    HIPC(hipStreamSynchronize(e->res.stream));
+    *volume = *e->mir_rec.h.as<double>();
+    return JSLP_OK;
+}
+// the same node through the engine's existing launches, one after the other: any start, any tableau (no saved root, a checkpoint,
+// k_node_wg, the chip-wide kernels)
+static int relax_mir_sequence(jslp_engine* e, const NodeCall& one, const MirCall& job, jslpr_mir_outcome* oc) {
+    JSLP_TRY(relax_batch_impl(e, one));
+    jslp_simplex_result& res = one.out[0];
+    *oc = jslpr_mir_outcome{0, 0, res.optimal, res.pivots_phase1 + std::max(res.pivots_phase2, 0), 0.0, 0.0};
+    if (job.need_feasible && !res.feasible) return JSLP_OK;
+    const int limit = job.max_rounds < 0 ? JSLPR_MAX_ROUNDS : job.max_rounds;
+    if (limit == 0) return JSLP_OK;
+    bool stopped = false;
+    double before = 0.0;
+    JSLP_TRY(device_volume(e, &before));
+    while (!stopped && oc->rounds < limit) {
+        int32_t n = 0;
+        JSLP_TRY(jslp_engine_apply_mir_cuts(e, &n));
+        JSLP_TRY(jslp_engine_simplex(e, one.check_cycles, &res));
+        oc->rounds += 1;
+        oc->rows_added += n;
+        oc->optimal_count += res.optimal;
+        oc->pivots += res.pivots_phase1 + std::max(res.pivots_phase2, 0);
+        double after = 0.0;
+        JSLP_TRY(device_volume(e, &after));
+        oc->volume_before = before;
+        oc->volume_after = after;
+        if (after >= 0.9 * before) stopped = true;
+        before = after;
+    }
+    if (!stopped && job.max_rounds < 0) return fail(JSLP_ERR_CAPACITY, "relax_mir: the MIR loop reached JSLPR_MAX_ROUNDS without a stop");
+    if (one.rhs || one.var_index_by_row) JSLP_TRY(jslp_engine_read_rhs(e, one.rhs, one.var_index_by_row));
+    return JSLP_OK;
+}
+
+extern "C" int jslpr_engine_relax_mir(jslp_engine* e, int32_t checkpoint, int32_t n_nodes, const int32_t* cut_offsets, const int8_t* type,
+                                      const int32_t* var_index, const double* value, int check_cycles, int32_t max_rounds, int32_t need_feasible,
+                                      jslp_simplex_result* out, jslpr_mir_outcome* mir, double* rhs, int32_t* var_index_by_row, int32_t out_stride) {
+    if (!e || !mir) return fail(JSLP_ERR_ARG, "relax_mir: null pointer");
+    if (checkpoint >= 0 && n_nodes != 1) return fail(JSLP_ERR_ARG, "relax_mir: a checkpoint start takes exactly one node");
+    if (max_rounds > JSLPR_MAX_ROUNDS) return fail(JSLP_ERR_ARG, "relax_mir: max_rounds > JSLPR_MAX_ROUNDS");
+    const MirCall job{max_rounds < 0 ? -1 : max_rounds, need_feasible ? 1 : 0, mir};
+    const NodeCall c{.cuts = {n_nodes, cut_offsets, type, var_index, value}, .check_cycles = check_cycles, .checkpoint = checkpoint < 0 ? -1 : checkpoint,
+                     .want_rhs = rhs != nullptr, .want_rows = var_index_by_row != nullptr,
+                     .out = out, .rhs = rhs, .var_index_by_row = var_index_by_row, .out_stride = out_stride, .mir = &job};
+    JSLP_TRY(node_call_check(e, c));
+    if (!e->has_int) return fail(JSLP_ERR_STATE, "relax_mir: after set_integer_variables");
+    if (e->s.n_opt > 0) return fail(JSLP_ERR_UNSUPPORTED, "relax_mir: optional objectives are not supported");
+    if (n_nodes == 0) return JSLP_OK;
+    HIPC(hipSetDevice(e->device));
+    bool one_launch = false;
+    JSLP_TRY(mir_one_launch(e, c, &one_launch));
+    if (one_launch) return relax_batch_impl(e, c);
+    // every other shape: node by node.  Each node's folded evaluation starts from the one the call began with
+    const double prev = e->evaluation;
+    for (int32_t i = 0; i < n_nodes; i++) {
+        const int32_t a = cut_offsets[i], offs[2] = {0, cut_offsets[i + 1] - a};
+        NodeCall one = c;
+        one.mir = nullptr;
+        one.cuts = {1, offs, type ? type + a : nullptr, var_index ? var_index + a : nullptr, value ? value + a : nullptr};
+        one.out = out + i;
+        one.rhs = rhs ? rhs + (size_t)i * out_stride : nullptr;
+        one.var_index_by_row = var_index_by_row ? var_index_by_row + (size_t)i * out_stride : nullptr;
+        e->evaluation = prev;
+        JSLP_TRY(relax_mir_sequence(e, one, job, &mir[i]));
+    }
+    return JSLP_OK;
 }
 
 // ---- compact read-back -----------------------------------------------------------------------------------------------
@@ -3218,3 +3397,7 @@ extern "C" int jslpf_simplex_f32_sweep(jslp_engine* e, const double* precisions,
     }
     return JSLP_OK;
 }
+
+#if !defined(JSLP_SPLIT_TU)
+#include "jslp_mir_kernels.hip.h"  // single-unit build: the MIR kernels behind everything else (the product: jslp_tu_mir.hip)
+#endif

@@ -983,11 +983,15 @@ __device__ __forceinline__ void gather_slot_lds(const Slots& s, const WgLds& L, 
     if (tid == 0) states[o] = *st;
 }
 
+#include "jslp_mir.hip.h"  // the MIR loop of a node (MIR builds of node_lds_run: jslp_mir_kernels.hip.h)
+
 // one node (= restore + cuts + simplex + read-back) of slot `slot`; false = the slot is not in sync with the snapshot
-template <int THREADS, bool COW = false, bool OPT = false>
+// MIR (include/jslpr_mir.h; eager slots only): the node's MIR-cut loop runs between its simplex and the read-back, mj says how
+template <int THREADS, bool COW = false, bool OPT = false, bool MIR = false>
 __device__ __forceinline__ bool node_lds_run(const Slots& s, const Snapshot& snap, const Cuts& cuts, SmemL& sm, const WgLds& L, int slot, int node, int o,
                                              int check_cycles, int iters_cap, int cap_rows, double* rhs_out, int32_t* rows_out,
-                                             DevState* state_out, int out_stride) {
+                                             DevState* state_out, int out_stride, const MirJob* mj = nullptr) {
+    static_assert(!MIR || (!COW && !OPT), "the MIR loop reads its source rows from the slot: eager slots, no optional objectives");
     WL_BEGIN(s.cnt);
     DevState* st = s.st + slot;
     const int tid = THREADS == 512 ? wgl_tid() : (int)threadIdx.x, lane = tid & 63, w = tid >> 6, nw = blockDim.x >> 6;
@@ -1104,6 +1108,7 @@ __device__ __forceinline__ bool node_lds_run(const Slots& s, const Snapshot& sna
     }
     // (copy-on-write nodes: the error word and the height the solve ends with are known here -- no global re-reads in front of the read-back)
     const int err_fin = simplex_wg_lds<(THREADS >= 1024 ? WGL_UN1024 : WGL_UN512), OPT, (THREADS >= 1024 || WGL_PF512)>(c, sm, Ln, iters_cap);
+    if constexpr (MIR) mir_node_loop<(THREADS >= 1024 ? WGL_UN1024 : WGL_UN512), (THREADS >= 1024 || WGL_PF512)>(c, s.idx_stride, sm, Ln, *mj, o, iters_cap, cap_rows);
 #ifdef JSLP_DEBUG_WGLDS
     wl_prev = __builtin_amdgcn_s_memtime();
 #endif

@@ -2,6 +2,8 @@
 the C ABI.  Method names follow the reference: simplex / pivot / save / restore / addCutConstraints /
 applyCuts, so parity tests read like the reference's own tests.
 """
+import math
+
 import numpy as np
 
 from . import _capi
@@ -80,6 +82,7 @@ class Tableau:
             self.lib.check(self.lib.jslp_engine_set_optional_objectives(self._h, int(oo.shape[0]), _capi.ptr_f64(oo)),
                            "jslp_engine_set_optional_objectives")
             self.n_optional = int(oo.shape[0])
+        self.integer_variables = frozenset(int(i) for i in integer_variables) if integer_variables is not None else frozenset()
         if integer_variables is not None and len(integer_variables) > 0:  # variable.isInteger for the MIR cuts
             iv = _capi.as_i32(list(integer_variables))
             self.lib.check(self.lib.jslp_engine_set_integer_variables(self._h, _capi.ptr_i32(iv), int(iv.shape[0])),
@@ -449,6 +452,139 @@ class Tableau:
         self._absorb(res)
         return n.value, res, rhs[:res.height], vibr[:res.height]
 
+    # ---- a node with its MIR loop in ONE engine call (include/jslpr_mir.h) ------------------------------
+    def _absorb_mir(self, res, outcome):
+        """fold the outcome of a node evaluated WITH its MIR loop: `res` is the last simplex()'s result with the evaluation already folded
+        over all of them (an optimal one sets it, an unbounded one sets -Infinity, any other keeps it), `outcome` says how many ended
+        optimal.  A node none of whose simplexes set the evaluation leaves this object's as it is.  unboundedVarIndex follows the LAST simplex
+        only: the 32-byte outcome record has no room for the variable of an earlier unbounded one (include/jslpr_mir.h)."""
+        self.last = res
+        self.feasible = bool(res.feasible)
+        self.bounded = bool(res.bounded)
+        n_opt = int(outcome["optimal_count"])
+        if n_opt > 0 or res.evaluation == float("-inf"):
+            self.evaluation = res.evaluation
+        if n_opt > 0 and self.simplexIters == 0:
+            self.bestPossibleEval = res.evaluation  # (the services evaluate the root round by round: they never get here)
+        self.simplexIters += n_opt
+        if not res.bounded:
+            self.unboundedVarIndex = res.unbounded_var_index
+        return res
+
+    def _mir_native(self, what):
+        """True: the library runs the loop (HIP, jslpr_* exported); False: the oracle, for which the call is restated below from
+        applyCuts / applyCutsFrom + mirRound.  A HIP library without the extension is an error, never a fallback."""
+        if self.lib.has_mir:
+            return True
+        if self.lib.backend == "oracle-c":
+            return False
+        raise _capi.EngineError("%s: %s does not export the MIR extension (include/jslpr_mir.h)" % (what, self.lib.path))
+
+    @staticmethod
+    def _mir_rounds_arg(max_rounds):
+        if max_rounds is None or max_rounds < 0:
+            return -1
+        if max_rounds > _capi.JSLPR_MAX_ROUNDS:
+            raise _capi.EngineError("relax_mir failed (%d): max_rounds > JSLPR_MAX_ROUNDS" % _capi.JSLP_ERR_ARG)
+        return int(max_rounds)
+
+    def _mir_restated(self, cuts, max_rounds, need_feasible, checkpoint, check_cycles):
+        """the sequence the one-call form stands for, call by call: (result, outcome, rhs, varIndexByRow), this object's scalars folded"""
+        if not self.integer_variables:
+            raise _capi.EngineError("relax_mir failed (%d): after set_integer_variables" % _capi.JSLP_ERR_STATE)
+        if self.n_optional > 0:
+            raise _capi.EngineError("relax_mir failed (%d): optional objectives" % _capi.JSLP_ERR_UNSUPPORTED)
+        if checkpoint is not None:
+            (res, rhs, vibr), = self.applyCutsFrom(checkpoint, [cuts], check_cycles=check_cycles)
+            self.absorb_from(checkpoint, res)
+        else:
+            res, rhs, vibr = self.applyCuts(cuts, check_cycles=check_cycles)
+        oc = np.zeros((), dtype=_capi.MIR_OUTCOME_DTYPE)
+        oc["optimal_count"] = int(bool(res.optimal))
+        oc["pivots"] = res.pivots_phase1 + max(res.pivots_phase2, 0)
+        if not (need_feasible and not self.feasible):
+            limit = _capi.JSLPR_MAX_ROUNDS if max_rounds < 0 else max_rounds
+            stopped = limit == 0
+            while int(oc["rounds"]) < limit:
+                before = fractional_volume_rows(self.integer_variables, rhs, vibr, self.precision)
+                n, res, rhs, vibr = self.mirRound(check_cycles=check_cycles)
+                after = fractional_volume_rows(self.integer_variables, rhs, vibr, self.precision)
+                oc["rounds"] += 1
+                oc["rows_added"] += n
+                oc["optimal_count"] += int(bool(res.optimal))
+                oc["pivots"] += res.pivots_phase1 + max(res.pivots_phase2, 0)
+                oc["volume_before"], oc["volume_after"] = before, after
+                if after >= 0.9 * before:
+                    stopped = True
+                    break
+            if max_rounds < 0 and not stopped:
+                raise _capi.EngineError("relax_mir failed (%d): the MIR loop reached JSLPR_MAX_ROUNDS" % _capi.JSLP_ERR_CAPACITY)
+        out = SimplexResult.from_buffer_copy(res)
+        out.evaluation = self.evaluation
+        return out, oc, rhs, vibr
+
+    def applyCutsMIR(self, cuts, max_rounds=None, need_feasible=False, checkpoint=None, check_cycles=True):
+        """A node WITH its MIR loop as ONE engine call (jslpr_engine_relax_mir): restore (or restoreCheckpoint) + addCutConstraints +
+        simplex, then -- unless need_feasible and the tableau is infeasible -- computeFractionalVolume / applyMIRCuts / simplex rounds until
+        the volume stops shrinking by 10 % or max_rounds (None: the default service's unbounded loop) is reached.  Returns (result of the
+        last simplex with the evaluation folded over all of them, outcome (_capi.MIR_OUTCOME_DTYPE), rhs, varIndexByRow); this object's
+        scalars are folded as the call-by-call sequence folds them."""
+        rounds = self._mir_rounds_arg(max_rounds)
+        if not self._mir_native("applyCutsMIR"):
+            return self._mir_restated(cuts, rounds, need_feasible, checkpoint, check_cycles)
+        n, t, v, x = self._pack_cuts(cuts)
+        offs = np.array([0, n], dtype=np.int32)
+        res = SimplexResult()
+        oc = np.zeros(1, dtype=_capi.MIR_OUTCOME_DTYPE)
+        rhs = np.empty(self.row_capacity, dtype=np.float64)
+        vibr = np.empty(self.row_capacity, dtype=np.int32)
+        self.lib.check(self.lib.jslpr_engine_relax_mir(self._h, -1 if checkpoint is None else checkpoint["id"], 1, _capi.ptr_i32(offs), _capi.ptr_i8(t),
+                                                       _capi.ptr_i32(v), _capi.ptr_f64(x), int(bool(check_cycles)), rounds, int(bool(need_feasible)),
+                                                       _capi.C.byref(res), _capi.C.c_void_p(oc.ctypes.data), _capi.ptr_f64(rhs), _capi.ptr_i32(vibr),
+                                                       self.row_capacity), "jslpr_engine_relax_mir")
+        if checkpoint is not None:
+            self.evaluation = checkpoint["evaluation"]
+            self.feasible = checkpoint["feasible"]
+        self._absorb_mir(res, oc[0])
+        return res, oc[0], rhs[:res.height], vibr[:res.height]
+
+    def applyCutsBatchMIR(self, cut_lists, max_rounds=None, need_feasible=False, check_cycles=True, packed=None):
+        """Independent nodes of the saved root, each with its MIR loop, in one call.  Returns (results, outcomes, rhs, varIndexByRow) as
+        applyCutsBatch lays them out (row stride = row_capacity).  Like applyCutsBatch it folds nothing into this object: the tree does,
+        node by node, with _absorb_mir.  Every node's folded evaluation starts from the evaluation the call began with."""
+        rounds = self._mir_rounds_arg(max_rounds)
+        pk = packed if packed is not None else self.pack_cut_lists(cut_lists)
+        n_nodes, offs, t, v, x = pk
+        out = (SimplexResult * max(n_nodes, 1))()
+        ocs = np.zeros(max(n_nodes, 1), dtype=_capi.MIR_OUTCOME_DTYPE)
+        stride = self.row_capacity
+        rhs = np.empty((max(n_nodes, 1), stride), dtype=np.float64)
+        vibr = np.empty((max(n_nodes, 1), stride), dtype=np.int32)
+        if self._mir_native("applyCutsBatchMIR"):
+            self.lib.check(self.lib.jslpr_engine_relax_mir(self._h, -1, n_nodes, _capi.ptr_i32(offs), _capi.ptr_i8(t), _capi.ptr_i32(v), _capi.ptr_f64(x),
+                                                           int(bool(check_cycles)), rounds, int(bool(need_feasible)), out,
+                                                           _capi.C.c_void_p(ocs.ctypes.data), _capi.ptr_f64(rhs), _capi.ptr_i32(vibr), stride),
+                           "jslpr_engine_relax_mir")
+            return [out[i] for i in range(n_nodes)], ocs[:n_nodes], rhs, vibr
+        scalars = ("last", "feasible", "bounded", "evaluation", "simplexIters", "bestPossibleEval", "unboundedVarIndex")
+        kept = {k: getattr(self, k) for k in scalars}
+        results = []
+        try:
+            for i in range(n_nodes):
+                for k, val in kept.items():
+                    setattr(self, k, val)
+                cuts = [{"type": "min" if t[j] == _capi.JSLP_CUT_MIN else "max", "varIndex": int(v[j]), "value": float(x[j])}
+                        for j in range(int(offs[i]), int(offs[i + 1]))]
+                res, oc, r, w = self._mir_restated(cuts, rounds, need_feasible, None, check_cycles)
+                results.append(res)
+                ocs[i] = oc
+                rhs[i, :res.height] = r
+                vibr[i, :res.height] = w
+        finally:
+            for k, val in kept.items():
+                setattr(self, k, val)
+        return results, ocs[:n_nodes], rhs, vibr
+
     # ---- checkpoints (incremental-branch-and-cut.ts:31-107) -------------------------------------------
     def createCheckpoint(self):
         """createCheckpoint (:55-70): the matrix and the index maps stay in HBM; the host part of a StateCheckpoint
@@ -684,6 +820,23 @@ def simplex_many(tableaux, check_cycles=True):
             t._absorb(res)
     lib.check(rc, "jslpm_simplex_many")
     return list(out)
+
+
+def fractional_volume_rows(integer, rhs, vibr, precision):
+    """computeFractionalVolume(ignoreIntegerValues = true) (mip-utils.ts:67-92): the product, in row order, of |value| over the basic
+    variables of the set `integer` that are not at an integer value.  Math.min(NaN, x) is NaN and NaN < precision is false: a NaN
+    row multiplies in."""
+    volume = -1.0
+    for r in range(1, len(vibr)):
+        if int(vibr[r]) in integer:
+            distance = abs(float(rhs[r]))
+            a = distance - math.floor(distance) if math.isfinite(distance) else math.nan
+            b = math.floor(distance + 1) if math.isfinite(distance) else distance
+            nearest = math.nan if (a != a or b != b) else min(a, b)
+            if nearest < precision:
+                continue
+            volume = distance if volume == -1.0 else volume * distance
+    return 0.0 if volume == -1.0 else volume
 
 
 def _js_round(x):

@@ -13,6 +13,7 @@ the hybrid switch after the first incumbent (:295-299, 418-428), pseudocost bran
 update from `tableau.evaluation` (:339, 354-365, 172-221), the checkpoint budget (:132, 442).
 """
 import math
+import os
 import time
 
 from .branch_and_cut import BranchMinHeap, _rows_by_var, is_integral, js_round, mir_loop
@@ -123,6 +124,8 @@ def incremental_branch_and_cut(tableau, model, node_selection="hybrid", branchin
     precision = tableau.precision
     n_opt = getattr(tableau, "n_optional", 0)
     best_optional = [math.inf] * n_opt
+    # JSLP_TREE_MIR=1 (read per call): every node after the root is evaluated WITH its MIR loop by one engine call
+    mir_one_call = bool(model.useMIRCuts) and n_opt == 0 and os.environ.get("JSLP_TREE_MIR", "0") == "1"
     pseudo = _PseudoCosts()
     solutions_found = 0
     use_depth_first = node_selection in ("depth-first", "hybrid")
@@ -150,14 +153,19 @@ def incremental_branch_and_cut(tableau, model, node_selection="hybrid", branchin
         if branch.relaxed > best_evaluation:
             continue
         parent_eval = tableau.evaluation
-        # applyIncrementalCuts (:246-259)
-        if branch.checkpoint is not None and branch.new_cut is not None:
-            (res, rhs, vibr), = tableau.applyCutsFrom(branch.checkpoint, [[branch.new_cut]], check_cycles=check)
-            tableau.absorb_from(branch.checkpoint, res)
-            incremental_nodes += 1
+        # applyIncrementalCuts (:246-259) and the MIR loop (:261-276)
+        from_checkpoint = branch.checkpoint is not None and branch.new_cut is not None
+        if mir_one_call and iterations > 0:  # both in ONE engine call (Tableau.applyCutsMIR); the root keeps the round-by-round path
+            _res, _outcome, rhs, vibr = tableau.applyCutsMIR([branch.new_cut] if from_checkpoint else branch.cuts, max_rounds=3, need_feasible=True,
+                                                             checkpoint=branch.checkpoint if from_checkpoint else None, check_cycles=check)
         else:
-            _res, rhs, vibr = tableau.applyCuts(branch.cuts, check_cycles=check)
-        rhs, vibr = mir_loop(tableau, model, rhs, vibr, check, max_rounds=3, need_feasible=True)  # :261-276
+            if from_checkpoint:
+                (res, rhs, vibr), = tableau.applyCutsFrom(branch.checkpoint, [[branch.new_cut]], check_cycles=check)
+                tableau.absorb_from(branch.checkpoint, res)
+            else:
+                _res, rhs, vibr = tableau.applyCuts(branch.cuts, check_cycles=check)
+            rhs, vibr = mir_loop(tableau, model, rhs, vibr, check, max_rounds=3, need_feasible=True)
+        incremental_nodes += 1 if from_checkpoint else 0
         iterations += 1
         if not tableau.feasible:
             continue

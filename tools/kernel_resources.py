@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Per-kernel register / scratch / LDS table of the engine as hipcc compiles it for gfx950 (`-Rpass-analysis=kernel-resource-usage`).
-  python tools/kernel_resources.py [filter] [-- extra hipcc flags]     e.g.  tools/kernel_resources.py resident -DJSLP_NODE512_WAVES=8
+  python tools/kernel_resources.py [filter] [--src unit.hip] [-- extra hipcc flags]     e.g.  tools/kernel_resources.py resident -DJSLP_NODE512_WAVES=8
+--src: another translation unit of jslpsolver_amd/csrc than jslp_hip.hip, e.g. --src jslp_tu_mir.hip (the MIR builds of the node kernels).
 Prints a markdown table (what profiles/rNN_kernel_resources.md holds)."""
 import os, re, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -8,10 +9,13 @@ args = sys.argv[1:]
 extra = []
 if "--" in args:
     i = args.index("--"); extra = args[i + 1:]; args = args[:i]
+src = "jslp_hip.hip"
+if "--src" in args:
+    i = args.index("--src"); src = args[i + 1]; args = args[:i] + args[i + 2:]
 flt = args[0] if args else ""
 cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-Wno-unused-value",
        "-I" + os.path.join(ROOT, "include"), "-Rpass-analysis=kernel-resource-usage", "-o", "/tmp/_kres.so",
-       os.path.join(ROOT, "jslpsolver_amd", "csrc", "jslp_hip.hip")] + extra
+       os.path.join(ROOT, "jslpsolver_amd", "csrc", src)] + extra
 out = subprocess.run(cmd, capture_output=True, text=True).stderr
 rows, cur = [], None
 for line in out.splitlines():
