@@ -844,6 +844,7 @@ static int state_error(const DevState& st) {
         case ERR_CAPACITY: return fail(JSLP_ERR_CAPACITY, "add_cuts: row / element-index capacity exceeded");
         case ERR_BARRIER: return fail(JSLP_ERR_DEVICE, "resident simplex kernel: grid barrier timed out (workgroups not co-resident?)");
         case ERR_NOT_SYNCED: return fail(JSLP_ERR_STATE, "internal: one-launch node kernel used on a slot that is not in sync with the snapshot");
+        case ERR_MIR_ROUNDS: return fail(JSLP_ERR_CAPACITY, "relax_mir: the MIR loop reached JSLPR_MAX_ROUNDS without a stop");
     }
     return fail(JSLP_ERR_DEVICE, "unknown device error code");
 }

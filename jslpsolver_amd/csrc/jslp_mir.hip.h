@@ -197,7 +197,7 @@ __device__ __forceinline__ void mir_node_loop(const Ctx& c, int idx_cap, SmemL& 
         before = after;
     }
     if (!stopped && err == ERR_NONE && mj.max_rounds < 0) {  // the unbounded loop must end whatever the data: a loud failure
-        if (t0) st->err = ERR_CAPACITY;
+        if (t0) st->err = ERR_MIR_ROUNDS;  // (a code of its own: the host names the round limit, as the sequenced form does, not a row capacity)
     }
     if (t0) mj.out[o] = ms.rec;
     __syncthreads();

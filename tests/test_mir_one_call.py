@@ -122,7 +122,7 @@ def by_hand(t, ints, cuts, max_rounds, need_feasible):
     if not (need_feasible and not res.feasible):
         while max_rounds < 0 or rounds < max_rounds:
             before = volume(ints, rhs, vibr, t.precision)
-            frac = [float(rhs[r]) - math.floor(float(rhs[r])) for r in range(1, len(vibr)) if int(vibr[r]) in ints]
+            frac = [float(x) - (math.floor(x) if math.isfinite(x) else float(x)) for x, v in zip(rhs[1:len(vibr)], vibr[1:]) if int(v) in ints]  # (NaN for a non-finite row)
             n, res, rhs, vibr = t.mirRound(check_cycles=True)
             per_round.append((sum(1 for f in frac if not (f < t.precision or f > 1 - t.precision)), n))
             after = volume(ints, rhs, vibr, t.precision)
