@@ -287,6 +287,19 @@ int32_t jslp_engine_watched_count(const jslp_engine* e);
  * to touch, counted by the kernels themselves when counting is on (off by default: it costs a reduction per pivot).
  * gated_cells = sum over pivots of (rows passing the reference's gate |A[r,c*]| > 1e-16, simplex.ts:370-375) x (columns of
  * the normalised pivot row that are non-zero, plus c*): the cells simplex.ts:376-387 reads and writes.
+ *
+ * The contract (tests/test_measure_modes.py holds every launch shape to it, against a count made from the downloaded tableau):
+ * every pivot of a counted call is counted exactly once, by the kernel that performed it.
+ *   - Gated count, as defined above (the rows r != r* with |A[r,c*]| > 1e-16 before the pivot, the cost row included, times the columns of
+ *     the final pivot row with |v| > 1e-16 plus c*): the one-workgroup kernels -- k_simplex_wg, k_simplex_lds, k_simplex_lds_many and every
+ *     node kernel -- and k_select + k_update, including the one pivot a fused pipeline hands to them (ST_P1_SLOW).
+ *   - Dense count, (H - 1) rows and (H - 1) x W cells per pivot: k_fused_p1, k_pivot_fused and k_simplex_resident, which stream every row
+ *     whatever the gate says.  They carry no counting code: the host adds the pivots each of their launches performed.
+ *   - The pivots of a register-resident launch that is rolled back (resident_aborts) are not counted; the streaming re-run counts its own.
+ *     A lean resident kernel that hands a solve on mid-way (resident_handovers) has its pivots counted, and whoever continues counts the rest.
+ *   - pivots, simplex_calls, relaxations, height_sum and cut_rows do not depend on the launch shape; restored_rows does (the product brings
+ *     back the rows a node dirtied, the sequential restatement every row).
+ * With counting off the eight work fields stay zero.  Counting changes no answer.
  */
 typedef struct jslp_work_counters {
     int64_t relaxations;    /* restore + addCutConstraints + simplex units (relax / relax_batch / relax_from nodes)   */
@@ -391,6 +404,19 @@ const char* jslp_engine_last_path(const jslp_engine* e);
  * Measurement hooks (bench.py): device time in milliseconds and launch count of the dominant kernel
  * (the row-update stream of pivot()) accumulated since the last reset, measured with HIP events on the
  * engine's own stream.  Timing is off by default (it adds an event pair per launch).
+ *
+ * Every set_timing call, on or off, zeroes the three values; with timing off they stay zero.  With timing on:
+ *   total_device_ms         the time between the first and the last operation of every simplex() / relax call on the engine's stream;
+ *   update_kernel_launches  the pivots of the kernels that stream the whole tableau, by launch shape of the solve:
+ *                             register-resident        the pivots performed inside the cooperative launch (behind a fused phase 1: phase 2's)
+ *                             fused                    the phase-2 pivots performed by k_pivot_fused launches (not phase 1, k_fused_p1's or
+ *                                                      k_select's, and not a pivot the pipeline hands to k_select + k_update)
+ *                             k_select + k_update      all pivots, when that pair runs the whole solve
+ *                             one-workgroup kernels    0 (simplex() in one workgroup, jslpm_simplex_many, every node kernel)
+ *   update_kernel_ms        the time between the event pairs around exactly those launches; they lie inside the call's outer pair.
+ * Timing changes no answer, but it changes the launch shape of node calls: a timed relax / relax_batch / relax_from runs the eager sequence
+ * (restore + add_cuts + simplex + gather as launches of their own), never the polled single-child kernel, the one-launch group kernels or
+ * the queue kernel; a timed jslpr_engine_relax_mir runs its loop call by call.
  */
 int jslp_engine_set_timing(jslp_engine* e, int enabled);
 int jslp_engine_get_timing(jslp_engine* e, double* update_kernel_ms, int64_t* update_kernel_launches,

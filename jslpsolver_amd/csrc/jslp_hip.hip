@@ -897,6 +897,15 @@ static void account(jslp_engine* e, const DevState& st, int is_relaxation) {
     e->wc.pivots += (long long)st.it1 + st.it2;
     e->wc.height_sum += st.H;
 }
+// The dense half of gated_cells / gated_rows (include/jslp_engine.h, jslp_work_counters): k_fused_p1, k_pivot_fused and k_simplex_resident stream every
+// row and every cell and carry no counting code, so the host adds (H - 1) rows x W cells for each pivot THEY performed -- every call site passes
+// the pivots of its own launches only.  The one-workgroup kernels and k_select (the slow pivot included) count through the gate on the device.
+static void count_dense(jslp_engine* e, int H, long long pivots) {
+    if (!e->counting || pivots <= 0) return;
+    e->wc.gated_cells += pivots * (long long)(H - 1) * e->W;
+    e->wc.gated_rows += pivots * (long long)(H - 1);
+}
+static long long pivots_done(const jslp_engine* e) { return (long long)e->h_state->it1 + e->h_state->it2; }  // of the host's copy of the state
 
 // ---- simplex() of the live tableau (slot 0) ------------------------------------------------------------------------------------------------
 // What one simplex() call fixes once (plan_solve); every phase below takes the engine and this.
@@ -1097,11 +1106,7 @@ static int resident_finish(jslp_engine* e, const SolveRun& p, const ResCtx& rc, 
     }
     *out = Resident::Done;
     e->last_path = p.geometry == RES_GEOM_XL ? "resident-xl" : "resident";
-    if (e->counting) {  // a dense streaming update touches every cell: rows x columns per pivot
-        const long long piv = (long long)e->h_state->it1 + e->h_state->it2;
-        e->wc.gated_cells += piv * (long long)(p.H - 1) * e->W;
-        e->wc.gated_rows += piv * (long long)(p.H - 1);
-    }
+    count_dense(e, p.H, pivots_done(e) - it_before);  // (not what a fused phase 1 in front of the launch did: that is counted there)
 #ifdef JSLP_DEBUG_RESIDENT
     {   // phase timing + micro-costs of the debug build (tools/resident_phase_timing.py reads this file)
         std::vector<u64_t> d(16384);
@@ -1146,6 +1151,7 @@ static int resident_attempt(jslp_engine* e, const SolveRun& p, long long it_befo
             // optional objectives: the general build does not take them -- the streaming kernels continue from the state the
             // lean kernel left (tableau, maps and objective rows written back; status ST_RUNNING or ST_PHASE1_DONE)
             if (e->timing) { HIPC(hipEventRecord(e->ev_pool[1], s)); HIPC(hipEventSynchronize(e->ev_pool[1])); account_resident_time(e, it_before); }
+            count_dense(e, p.H, pivots_done(e) - it_before);  // the pivots the lean kernel did before it left
             *out = Resident::Streaming;
             return JSLP_OK;
         }
@@ -1234,8 +1240,8 @@ static int slow_pivot(jslp_engine* e, const SolveRun& p) {
     e->p1_slow_pivots += 1;
     return JSLP_OK;
 }
-// phase 1 through the fused pipeline (one launch per pivot; k_fused_p1); hands over with ST_PHASE1_DONE
-static int fused_phase1(jslp_engine* e, const SolveRun& p) {
+// phase 1 through the fused pipeline (one launch per pivot; k_fused_p1); hands over with ST_PHASE1_DONE.  `done`: pivots the solve had done before
+static int fused_phase1(jslp_engine* e, const SolveRun& p, long long done) {
     JSLP_TRY(ensure_fused(e));
     JSLP_TRY(ensure_fused_oo(e));
     const FusedCtx f = make_fused_ctx(e, p.c, p.H);
@@ -1247,8 +1253,10 @@ static int fused_phase1(jslp_engine* e, const SolveRun& p) {
         JSLP_TRY(stream_pivots(e, p, &k, &f, &launch, 2, 512, false, 0));
         hipLaunchKernelGGL(k_fused_finish, dim3(512), dim3(256), 0, e->res.stream, f, launch - 1);  // state -> slot 0's, tableau -> buf[0]
         HIPC(hipGetLastError());
+        count_dense(e, p.H, pivots_done(e) - done);  // this run of the pipeline (the state stream_pivots fetched is the pipeline's last)
         if (e->h_state->status != ST_P1_SLOW) break;
-        JSLP_TRY(slow_pivot(e, p));  // ... then the pipeline again
+        JSLP_TRY(slow_pivot(e, p));  // ... then the pipeline again (k_select counted that pivot on the device)
+        done = pivots_done(e);
         if (e->h_state->status != ST_RUNNING) break;
     }
     e->last_path = "fused";
@@ -1270,10 +1278,12 @@ static int fused_phase2(jslp_engine* e, const SolveRun& p) {
         const FusedKernel& k = pivot_fused_kernel(e);
         if (p.dbg) fprintf(stderr, "[jslp] launch %s\n", k.name);
         int launch = 0;
+        const long long done = pivots_done(e);  // (e->h_state is current here: every way into this loop ends with a fetch of the state)
         launch_fused(e, k, f, launch++);
-        JSLP_TRY(stream_pivots(e, p, &k, &f, &launch, 16, 512, e->timing != 0, (long long)e->h_state->it1 + e->h_state->it2));
+        JSLP_TRY(stream_pivots(e, p, &k, &f, &launch, 16, 512, e->timing != 0, done));
         hipLaunchKernelGGL(k_fused_finish, dim3(512), dim3(256), 0, s, f, launch - 1);
         HIPC(hipGetLastError());
+        count_dense(e, p.H, pivots_done(e) - done);  // this run of the pipeline, not the pivot it hands over below
         if (e->h_state->status == ST_P1_SLOW) {
             // an entering column named by an optional objective with a ~0 main cost and a tiny pivot-row entry: that ONE pivot
             // through k_select + k_update (see k_pivot_fused), then the pipeline again from its first launch
@@ -1283,12 +1293,7 @@ static int fused_phase2(jslp_engine* e, const SolveRun& p) {
             e->h_state->status = ST_PHASE1_DONE;
             continue;
         }
-        HIPC(hipMemcpyAsync(e->h_state, e->s.st, sizeof(DevState), hipMemcpyDeviceToHost, s));
-        if (e->counting) {  // the fused launches stream every cell (phase 1 went through k_select: counted on the device)
-            e->wc.gated_cells += (long long)e->h_state->it2 * (long long)(p.H - 1) * e->W;
-            e->wc.gated_rows += (long long)e->h_state->it2 * (long long)(p.H - 1);
-        }
-        HIPC(hipStreamSynchronize(s));
+        JSLP_TRY(fetch_state(e, e->s.st));  // the solve's final state, as k_fused_finish adopted it (waited for: close_solve reads it)
         break;
     }
     return JSLP_OK;
@@ -1298,7 +1303,7 @@ static int close_solve(jslp_engine* e) {
     HIPC(hipEventRecord(e->res.ev_end, e->res.stream));
     HIPC(hipStreamSynchronize(e->res.stream));
     float ms = 0;
-    if (hipEventElapsedTime(&ms, e->res.ev_begin, e->res.ev_end) == hipSuccess) e->total_ms += ms;
+    if (e->timing && hipEventElapsedTime(&ms, e->res.ev_begin, e->res.ev_end) == hipSuccess) e->total_ms += ms;
     return state_error(*e->h_state);
 }
 
@@ -1320,7 +1325,8 @@ static int run_simplex(jslp_engine* e, int check_cycles) {
         // (a lean kernel that left mid-solve may have left behind phase 1: h_state is current in that case only)
         bool phase1_over = res == Resident::Streaming && e->h_state->status == ST_PHASE1_DONE;
         if (!phase1_over && p.fused && fused_p1_on()) {
-            JSLP_TRY(fused_phase1(e, p));
+            // (h_state is the solve's only behind a launch that ran: before that it still holds what plan_solve read in front of k_begin)
+            JSLP_TRY(fused_phase1(e, p, res == Resident::Streaming || res == Resident::RolledBack ? pivots_done(e) : 0));
             phase1_over = true;
         }
         if (!phase1_over) JSLP_TRY(select_update_loop(e, p));
@@ -2747,7 +2753,7 @@ extern "C" int jslpm_simplex_many(jslp_engine* const* engines, int32_t n, const 
         for (size_t k = 0; k < nb; k++) {  // what jslp_engine_simplex does after run_simplex, per member
             const int32_t i = order[k];
             jslp_engine* e = engines[i];
-            e->total_ms += ms;
+            if (e->timing) e->total_ms += ms;
             *e->h_state = h_st[k];
             rc = state_error(*e->h_state);
             if (!rc) {

@@ -886,6 +886,7 @@ int jslp_engine_relax_from(jslp_engine* e, int32_t checkpoint, int32_t n_nodes, 
         if (rc) return rc;
         rc = jslp_engine_simplex(e, check_cycles, &out[i]);
         if (rc) return rc;
+        if (e->counting) e->wc.relaxations += 1; /* a child of a checkpoint is a relaxation like a child of the root (jslp_work_counters) */
         rc = jslp_engine_read_rhs(e, rhs ? rhs + (size_t)i * out_stride : 0,
                                   var_index_by_row ? var_index_by_row + (size_t)i * out_stride : 0);
         if (rc) return rc;

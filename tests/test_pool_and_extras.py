@@ -470,6 +470,7 @@ def test_host_requested_abort_rolls_back_on_the_shipped_library(hip_lib, n, afte
     want = KA.expected_dense("ra", n, n)
     monkeypatch.setenv("JSLP_INJECT_RESIDENT_ABORT_US", str(after_us))
     t = Tableau(m, vibr, vibc, lib=hip_lib)
+    t.set_counting(True)
     res = t.simplex(check_cycles=check)
     c = t.get_counters()
     path = t.last_path()
@@ -477,6 +478,9 @@ def test_host_requested_abort_rolls_back_on_the_shipped_library(hip_lib, n, afte
     got = (len(tr), pivot_digest(tr), G.sha_matrix(t.download()[0]), bool(res.feasible))
     assert got == (want["pivots"], want["digest"], want["final_sha"], want["feasible"]), got
     assert c["resident_launches"] == 1 and c["resident_aborts"] == 1 and path in ("fused", "select+update"), (path, c)
+    # the abandoned launch's pivots are not counted (include/jslp_engine.h, jslp_work_counters): the fused re-run's are, densely, once each
+    H, W = m.shape
+    assert c["pivots"] == want["pivots"] and c["gated_cells"] == c["pivots"] * (H - 1) * W and c["gated_rows"] == c["pivots"] * (H - 1), c
     # ... and the same engine, knob off, takes the register-resident path again and gives the same answer
     monkeypatch.delenv("JSLP_INJECT_RESIDENT_ABORT_US")
     t2 = Tableau(m, vibr, vibc, lib=hip_lib)

@@ -54,6 +54,8 @@ def main():
                            tabs[names[i % len(names)]]["unr"], precision=tabs[names[i % len(names)]]["precision"], lib=lib)
                    for i in range(nmax)]
         sys.stderr.write("%s: %d engines created in %.1f s\n" % (wl, nmax, time.perf_counter() - t0))
+        for t in engines:  # total_device_ms is kept only while timing is on (one-workgroup solves take the same launches either way)
+            t.set_timing(True)
         which = [names[i % len(names)] for i in range(nmax)]
         checks = [tabs[w]["check"] for w in which]
 
