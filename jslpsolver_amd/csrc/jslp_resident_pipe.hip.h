@@ -682,6 +682,11 @@ __device__ __forceinline__ void resident_phase2_pipe(const ResCtx& f, RSmem& sm,
     //  600 B per lane and ran 4001 x 2001 at 23 k pivots/s instead of 125 k; it keeps the raw row and round 4's 8-byte flag word)
     constexpr bool NPUB = CKS && !OPT && !XL && CPT <= 4 && ROWS <= 8 && JSLP_PIPE_NORM_PUB != 0;
     constexpr bool QDIRECT = TAGGED || NPUB;  // quot comes with the fetch: no barrier behind it
+    // ONE (key, row) fold per ratio-test verdict instead of two (first degenerate row; smallest quotient): a degenerate row carries key 0 -- in the
+    // ratio-test wave and in the gather's close, the one wave everybody waits for at the gather's barrier.  The 8-row geometries with 2 / 4 columns
+    // per lane: config 3a 194.1 k -> 199.9 k pivots/s, with the cycle check 172.8 k -> 176.8 k.  The tall / wide geometries keep the two folds:
+    // with one, 4001 x 2001 ran 144.6 k -> 143.7 k and 2001 x 4001 with the cycle check 100.2 k -> 99.8 k (profiles/chain_diet.md)
+    constexpr bool ONE_FOLD = ROWS <= 8 && CPT <= 4;
     // the ratio test's transposition (entry i of the entering column from the ONE lane that holds it to lane i) through LDS: as `x = lane
     // == i ? readlane(a[i][j]) : x` the compiler precomputes the 64-bit lane masks, spills them and pays two reloads, two moves and two
     // selects per row on top of the readlanes -- in the one wave the summary waits for
@@ -845,17 +850,28 @@ __device__ __forceinline__ void resident_phase2_pipe(const ResCtx& f, RSmem& sm,
                     else { quo = (UNR && R.neg) ? -rhs / colv : rhs / colv; kind = quo > precision && quo < INFINITY ? 2 : 0; }  // simplex.ts:282 (+Infinity: never below minQuotient's start)
                 }
             }
-            int brdeg = kind == 1 ? r : 0x7fffffff;  // rows ascend with the lane: the smallest row is the first one
+            static_assert(ROWS <= 32, "the summary's DPP folds cover two 16-lane rows");
+            // ONE_FOLD: one fold yields the verdict.  A quotient candidate's key is the bit pattern of a double > precision >= 1e-15 (resident_geometry,
+            // jslp_hip.hip: smaller precisions never reach this kernel) -- never 0 -- so
+            // a degenerate row travels as key 0 with its row: ki_min takes the smaller key and, among equal keys, the smaller row (jslp_wglds.hip.h),
+            // which is "the first degenerate row, else the smallest quotient, the first row on ties"; deg is `key == 0`
+            int brdeg = ONE_FOLD ? 0x7fffffff : (kind == 1 ? r : 0x7fffffff);  // rows ascend with the lane: the smallest row is the first one
+            if (!ONE_FOLD) {
             brdeg = min(brdeg, __builtin_amdgcn_update_dpp(brdeg, brdeg, 0xB1, 0xf, 0xf, false));
             brdeg = min(brdeg, __builtin_amdgcn_update_dpp(brdeg, brdeg, 0x4E, 0xf, 0xf, false));
             brdeg = min(brdeg, __builtin_amdgcn_update_dpp(brdeg, brdeg, 0x141, 0xf, 0xf, false));
             if (ROWS > 8) brdeg = min(brdeg, __builtin_amdgcn_update_dpp(brdeg, brdeg, 0x140, 0xf, 0xf, false));  // (<= 8 rows: lanes 0..7 hold them, three exchanges fold them into lane 0)
             brdeg = ROWS > 16 ? min(__builtin_amdgcn_readlane(brdeg, 0), __builtin_amdgcn_readlane(brdeg, 16))
                               : __builtin_amdgcn_readlane(brdeg, 0);  // (ROWS <= 16: the candidates sit in the first 16-lane row; <= 32: in the first two)
-            static_assert(ROWS <= 32, "the summary's DPP folds cover two 16-lane rows");
+            }
             KI bk;  // quotients are finite and > precision > 0: positive doubles order like their bit patterns; ties -> first row
-            bk.k = kind == 2 ? (u64_t)__double_as_longlong(quo) : KI_NONE_KEY;
-            bk.i = kind == 2 ? r : 0x7fffffff;
+            if (ONE_FOLD) {
+                bk.k = kind == 2 ? (u64_t)__double_as_longlong(quo) : (kind == 1 ? 0ull : KI_NONE_KEY);
+                bk.i = kind != 0 ? r : 0x7fffffff;
+            } else {
+                bk.k = kind == 2 ? (u64_t)__double_as_longlong(quo) : KI_NONE_KEY;
+                bk.i = kind == 2 ? r : 0x7fffffff;
+            }
             bk.pad = 0;
             bk = ki_min(bk, ki_dpp<0xB1>(bk));
             bk = ki_min(bk, ki_dpp<0x4E>(bk));
@@ -863,7 +879,8 @@ __device__ __forceinline__ void resident_phase2_pipe(const ResCtx& f, RSmem& sm,
             if (ROWS > 8) bk = ki_min(bk, ki_dpp<0x140>(bk));
             bk = ROWS > 16 ? ki_min(ki_readlane(bk, 0), ki_readlane(bk, 16)) : ki_readlane(bk, 0);
             if (lane == 0) {
-                const bool deg = brdeg != 0x7fffffff;
+                const bool deg = ONE_FOLD ? bk.k == 0ull : brdeg != 0x7fffffff;
+                if (ONE_FOLD) brdeg = bk.i;
                 const bool have = bk.k != KI_NONE_KEY;
                 const int row = deg ? brdeg : (have ? bk.i : 0);  // the only row of mine that can win (0: none)
                 const u64_t qb = (deg || !have) ? 0ull : bk.k;
@@ -998,22 +1015,25 @@ __device__ __forceinline__ void resident_phase2_pipe(const ResCtx& f, RSmem& sm,
             for (int q = 0; q < JSLP_F_MAXG / 64; q++) {
                 const int row = (int)(gq[q].w & 0x7fffu);
                 const bool deg = (gq[q].w & 0x8000u) != 0u;
-                if (deg && row != 0) rdeg = min(rdeg, row);
+                if (!ONE_FOLD && deg && row != 0) rdeg = min(rdeg, row);
                 KI y;
-                const bool cand = !deg && row != 0;
+                // (ONE_FOLD: a degenerate row's granule carries quotient bits 0 -- the summary's format -- which IS its key: no fold of its own)
+                const bool cand = ONE_FOLD ? row != 0 : !deg && row != 0;
                 y.k = cand ? ((u64_t)gq[q].x | ((u64_t)gq[q].z << 32)) : KI_NONE_KEY;
                 y.i = cand ? row : 0x7fffffff;
                 y.pad = 0;
                 x = ki_min(x, y);
             }
+            if (!ONE_FOLD) {
             rdeg = min(rdeg, __builtin_amdgcn_update_dpp(rdeg, rdeg, 0xB1, 0xf, 0xf, false));
             rdeg = min(rdeg, __builtin_amdgcn_update_dpp(rdeg, rdeg, 0x4E, 0xf, 0xf, false));
             rdeg = min(rdeg, __builtin_amdgcn_update_dpp(rdeg, rdeg, 0x141, 0xf, 0xf, false));
             rdeg = min(rdeg, __builtin_amdgcn_update_dpp(rdeg, rdeg, 0x140, 0xf, 0xf, false));
             rdeg = min(min(__builtin_amdgcn_readlane(rdeg, 0), __builtin_amdgcn_readlane(rdeg, 16)),
                        min(__builtin_amdgcn_readlane(rdeg, 32), __builtin_amdgcn_readlane(rdeg, 48)));
+            }
             x = ki_wave_min(x);
-            if (lane == 0) { sm.part_k[0] = x.k; sm.part_r[0] = x.k == KI_NONE_KEY ? 0 : x.i; sm.part_rdeg[0] = rdeg; }
+            if (lane == 0) { sm.part_k[0] = x.k; sm.part_r[0] = x.k == KI_NONE_KEY ? 0 : x.i; if (!ONE_FOLD) sm.part_rdeg[0] = rdeg; }
         }
         RT_STAMP(2);  // my wave's 64 summaries are in
         RT_MARK(1);
@@ -1025,7 +1045,7 @@ __device__ __forceinline__ void resident_phase2_pipe(const ResCtx& f, RSmem& sm,
         // ---- D: every thread reads the polling wave's verdict ------------------------------------------------------------------
         int pr = 0, stop = 0;
         {
-            const int wr = sm.part_r[0], wrdeg = sm.part_rdeg[0];
+            const int wr = sm.part_r[0], wrdeg = ONE_FOLD ? 0x7fffffff : sm.part_rdeg[0];  // (ONE_FOLD: a degenerate winner is part_r itself)
             if (wrdeg != 0x7fffffff) pr = wrdeg;
             else if (wr != 0) pr = wr;
             else stop = 3;  // unbounded (simplex.ts:298-303)
