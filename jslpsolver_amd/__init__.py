@@ -3,8 +3,8 @@
 Only the hot path lives here: csrc/ (HIP kernels for gfx950 + the C ABI of
 include/jslp_engine.h) and the thin host mirror of the reference interface for that path.
 """
-from .engine import Tableau, pivot_digest  # noqa: F401
+from .engine import Tableau, TableauPack, pivot_digest  # noqa: F401
 from .model import Model, UnsupportedModel  # noqa: F401
-from .solver import Solve, solve_many  # noqa: F401
+from .solver import Solve, solve_many, solve_packed  # noqa: F401
 
-__all__ = ["Tableau", "Model", "Solve", "solve_many", "UnsupportedModel", "pivot_digest"]
+__all__ = ["Tableau", "TableauPack", "Model", "Solve", "solve_many", "solve_packed", "UnsupportedModel", "pivot_digest"]

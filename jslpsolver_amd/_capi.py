@@ -1,5 +1,6 @@
 """ctypes binding of the C ABI declared in include/jslp_engine.h (SYMBOLS) and of its HIP-only extensions include/jslpx_branch.h
-(BRANCH_SYMBOLS), include/jslpm_many.h (MANY_SYMBOLS), include/jslpf_f32.h (F32_SYMBOLS) and include/jslpr_mir.h (MIR_SYMBOLS).
+(BRANCH_SYMBOLS), include/jslpm_many.h (MANY_SYMBOLS), include/jslpf_f32.h (F32_SYMBOLS), include/jslpr_mir.h (MIR_SYMBOLS) and
+include/jslpp_packed.h (PACK_SYMBOLS).
 
 The same binding class serves two libraries that export identical symbols:
   * jslpsolver_amd/csrc/libjslp_hip.so -- the product (hand-written HIP kernels, gfx950)
@@ -197,6 +198,29 @@ MIR_SYMBOLS = {
 }
 
 
+# numpy twin of SimplexResult: the results of a pack as one structured array (no per-LP ctypes struct)
+RESULT_DTYPE = np.dtype([(name, np.int32 if ctype is C.c_int32 else np.float64) for name, ctype in SimplexResult._fields_])
+assert RESULT_DTYPE.itemsize == C.sizeof(SimplexResult)
+
+# name -> (restype, argtypes); must list EVERY symbol include/jslpp_packed.h declares.  HIP library only, like BRANCH_SYMBOLS
+# (Library.has_pack).
+PACK_SYMBOLS = {
+    "jslpp_lds_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
+    "jslpp_pack_create": (C.c_int, [_P(C.c_void_p), C.c_int, C.c_int32, _i32p, _i32p, _f64p, C.c_int32, C.c_int32]),
+    "jslpp_pack_destroy": (None, [C.c_void_p]),
+    "jslpp_pack_size": (C.c_int32, [C.c_void_p]),
+    "jslpp_pack_host_matrix": (C.c_int, [C.c_void_p, C.c_int32, _P(_f64p), _P(C.c_int64)]),
+    "jslpp_pack_set": (C.c_int, [C.c_void_p, C.c_int32, _f64p, _i32p, _i32p, _i32p, C.c_int32]),
+    "jslpp_pack_upload": (C.c_int, [C.c_void_p]),
+    "jslpp_pack_simplex": (C.c_int, [C.c_void_p, _i32p, C.c_void_p, _i32p, _f64p]),
+    "jslpp_pack_launches": (C.c_int32, [C.c_void_p]),
+    "jslpp_pack_read_rhs": (C.c_int, [C.c_void_p, _P(_f64p), _P(_i32p), _P(_P(C.c_int64))]),
+    "jslpp_pack_download": (C.c_int, [C.c_void_p, C.c_int32, _f64p, _i32p, _i32p, _i32p, _i32p]),
+    "jslpp_pack_pivot_trace": (C.c_int, [C.c_void_p, C.c_int32, _i32p, C.c_int64, _P(C.c_int64)]),
+}
+JSLPP_LDS_LIMIT = 65536
+
+
 class EngineError(RuntimeError):
     pass
 
@@ -218,6 +242,7 @@ class Library:
         self.has_many = self._bind_extension(MANY_SYMBOLS)
         self.has_f32 = self._bind_extension(F32_SYMBOLS)
         self.has_mir = self._bind_extension(MIR_SYMBOLS)
+        self.has_pack = self._bind_extension(PACK_SYMBOLS)
 
     def _bind_extension(self, symbols):
         """bind a HIP-only extension when the library exports all of it; False otherwise"""

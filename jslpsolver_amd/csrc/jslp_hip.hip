@@ -17,6 +17,7 @@
 #include "../../include/jslpm_many.h"
 #include "../../include/jslpf_f32.h"
 #include "../../include/jslpr_mir.h"
+#include "../../include/jslpp_packed.h"
 #include "jslp_kernels.hip.h"
 #include "jslp_host_mem.h"
 
@@ -164,6 +165,13 @@ struct jslp_engine {
 
 static const long long WG_CELLS_SINGLE = 64 * 1024;         // one workgroup beats 2 launches/pivot below this
 static const long long WG_CELLS_BATCH = 4LL * 1024 * 1024;  // batches use one workgroup per node up to this
+// The pack of small LPs (include/jslpp_packed.h): an LP of at most this many cells (height x width) is solved by the one-wave build of
+// k_simplex_packed, a larger one by the 256-thread build.  A pivot's row update is cells / threads turns of a lane plus, in the 256-thread
+// build only, six workgroup barriers and three cross-wave reductions through LDS; one wave pays neither and leaves the CU's other
+// wave slots to other LPs.  At 2048 cells a lane's share of the update is 32 cells, about what those barriers and reductions cost, and
+// every fuzz root (<= 1260 cells) and every fixture but the few hundred-column ones stays on one wave.  Set from that reasoning and the
+// timing table (profiles/packed_lp_times.md), not from a sweep.
+static const long long PACK_CELLS_WAVE = 2048;
 #ifndef JSLP_SMALL_BATCH_1024_DEFAULT
 #define JSLP_SMALL_BATCH_1024_DEFAULT 256  // batches of at most this many nodes (one per CU) take the 1024-thread node kernel: 16 nodes 111 -> 102 us, 64 nodes 147 -> 132 us (r03_o); 0 = never
 #endif
@@ -850,8 +858,8 @@ static int state_error(const DevState& st) {
 }
 
 // fold a finished DevState into the ABI result (evaluation semantics: see jslp_simplex_result)
-static int fill_result(jslp_engine* e, const DevState& st, int slot, double prev_evaluation, jslp_simplex_result* out,
-                       double* evaluation_out) {
+// (decode_state: everything but the cycle message, which needs the history; shared with the pack of small LPs, jslpp_pack_simplex)
+static void decode_state(const DevState& st, double precision, double prev_evaluation, jslp_simplex_result* out, double* evaluation_out) {
     memset(out, 0, sizeof *out);
     out->feasible = st.feasible;
     out->bounded = st.bounded;
@@ -864,13 +872,17 @@ static int fill_result(jslp_engine* e, const DevState& st, int slot, double prev
     out->obj_cell = st.obj_cell;
     double ev = prev_evaluation;
     if (st.optimal) {  // setEvaluation (tableau.ts:420-426)
-        const double rc = js_round(1.0 / e->precision);
+        const double rc = js_round(1.0 / precision);
         ev = js_round((2.220446049250313e-16 + st.obj_cell) * rc) / rc;
     } else if (!st.bounded) {
         ev = -INFINITY;
     }
     out->evaluation = ev;
     if (evaluation_out) *evaluation_out = ev;
+}
+static int fill_result(jslp_engine* e, const DevState& st, int slot, double prev_evaluation, jslp_simplex_result* out,
+                       double* evaluation_out) {
+    decode_state(st, e->precision, prev_evaluation, out, evaluation_out);
     if (st.cycle_phase && st.hist_n > 0) {
         std::vector<int2> h(st.hist_n);
         if (hipMemcpy(h.data(), e->s.hist + (size_t)slot * e->s.hist_cap, sizeof(int2) * st.hist_n, hipMemcpyDeviceToHost) != hipSuccess)
@@ -3405,6 +3417,360 @@ extern "C" int jslpf_simplex_f32_sweep(jslp_engine* e, const double* precisions,
     return JSLP_OK;
 }
 
+// ---- a pack of small LPs solved in LDS (include/jslpp_packed.h) ---------------------------------------------------------------------
+// One object, one arena: [LP images | descriptor table | launch order | per-LP checkForCycles | histories | traces].  The images have a
+// pinned twin (the ONE H2D copy of upload); the result block [states | RHS columns | row maps] has another (the ONE D2H copy of simplex).
+// A pack call holds no jslp_engine and takes no g_many_mu.  The kernels live in jslp_tu_packed.hip (jslp_packed.hip.h).
+#include "jslp_packed.hip.h"
+#ifdef JSLP_SPLIT_TU
+extern "C" __attribute__((visibility("hidden"))) int jslpp_packed_launch_tu(int threads, unsigned grid, size_t lds, const void* args, void* stream);
+static int packed_launch(int threads, unsigned grid, size_t lds, const PackLaunch& a, hipStream_t s) { return jslpp_packed_launch_tu(threads, grid, lds, &a, s); }
+#else
+static int packed_launch_impl(int threads, unsigned grid, size_t lds, const void* bytes, hipStream_t s);  // (jslp_packed.hip.h, at the end of this file)
+static int packed_launch(int threads, unsigned grid, size_t lds, const PackLaunch& a, hipStream_t s) { return packed_launch_impl(threads, grid, lds, &a, s); }
+#endif
+
+struct jslpp_pack {
+    int device = 0;
+    int32_t n = 0, trace_cap = 0, hist_cap = 0;
+    // stream and events: a bundle of the resource pool when it had one (handed back intact at destroy), else the pack's own
+    PooledRes res;
+    bool pooled = false;
+    Stream own_stream;
+    Event own_begin, own_end;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev_begin = nullptr, ev_end = nullptr;
+    std::vector<int32_t> H, W;
+    std::vector<double> precision, evaluation;
+    std::vector<size_t> image_off;  // LP i's image in the arena / the pinned twin
+    std::vector<int64_t> offs;      // LP i's RHS column / row map in the result block, n + 1 entries
+    std::vector<uint8_t> is_set;
+    size_t image_bytes = 0;
+    DevBuf arena;
+    PinBuf h_image, h_cc;
+    StagePair result;
+    char* d_image = nullptr;
+    PackLp* d_lps = nullptr;
+    int32_t *d_order = nullptr, *d_cc = nullptr;
+    int2 *d_hist = nullptr, *d_trace = nullptr;
+    int32_t n_wave = 0, n_block = 0;  // LPs of the one-wave / the 256-thread build
+    size_t lds_wave = 0, lds_block = 0;
+    int uploaded = 0;
+    int32_t launches = 0;
+    DevState* h_states() const { return result.h.as<DevState>(); }
+    double* h_rhs() const { return reinterpret_cast<double*>(result.h.p + res_rhs_off()); }
+    int32_t* h_rows() const { return reinterpret_cast<int32_t*>(result.h.p + res_rows_off()); }
+    size_t res_rhs_off() const { return (sizeof(DevState) * (size_t)n + 255) & ~(size_t)255; }
+    size_t res_rows_off() const { return (res_rhs_off() + sizeof(double) * (size_t)offs[n] + 255) & ~(size_t)255; }
+    size_t res_bytes() const { return res_rows_off() + sizeof(int32_t) * (size_t)offs[n]; }
+};
+static int pack_fail(int code, const char* what, int32_t i, const char* why) {
+    snprintf(g_err, sizeof g_err, "%s: LP %d: %s", what, (int)i, why);
+    return code;
+}
+static size_t pack_image_bytes(int32_t H, int32_t W) { return sizeof(DevState) + 8 * (size_t)pk_image_doubles(H, W) + 4 * (size_t)pk_ints(H, W).total; }
+static_assert(sizeof(DevState) % 16 == 0, "an LP's matrix follows its DevState at a 16-byte boundary");
+
+extern "C" int64_t jslpp_lds_bytes(int32_t height, int32_t width) {
+    if (height < 2 || width < 2) return 0;
+    return (int64_t)pk_lds_bytes(height, width);
+}
+
+static void pack_carve(jslpp_pack* p, Carver& cv) {
+    p->d_image = cv.take<char>(p->image_bytes);
+    p->d_lps = cv.take<PackLp>((size_t)p->n);
+    p->d_order = cv.take<int32_t>((size_t)p->n);
+    p->d_cc = cv.take<int32_t>((size_t)p->n);
+    p->d_hist = cv.take<int2>((size_t)p->n * p->hist_cap);
+    p->d_trace = cv.take<int2>((size_t)p->n * p->trace_cap);
+}
+// the device side of create(): stream, events, the arena, the pinned twins, the descriptor table and the launch order (built ONCE)
+static int pack_init(jslpp_pack* p, int32_t max_pivots) {
+    p->pooled = pool_take(p->device, &p->res);
+    if (p->pooled) {
+        p->stream = p->res.stream; p->ev_begin = p->res.ev_begin; p->ev_end = p->res.ev_end;
+    } else {
+        HIPC(hipStreamCreateWithFlags(&p->own_stream.h, hipStreamNonBlocking));
+        HIPC(hipEventCreate(&p->own_begin.h));
+        HIPC(hipEventCreate(&p->own_end.h));
+        p->stream = p->own_stream; p->ev_begin = p->own_begin; p->ev_end = p->own_end;
+    }
+    const size_t n = (size_t)p->n;
+    HIPC_CARVE(p->arena, [&](Carver& cv) { pack_carve(p, cv); });
+    HIPC(p->h_image.reserve(std::max<size_t>(p->image_bytes, 256)));
+    memset(p->h_image.p, 0, p->image_bytes);
+    HIPC(p->h_cc.reserve(std::max<size_t>(sizeof(int32_t) * n, 256)));
+    HIPC(p->result.reserve(std::max<size_t>(p->res_bytes(), 256)));
+    std::vector<PackLp> lps(n);
+    std::vector<int32_t> order(n);
+    int32_t k = 0;
+    for (int pass = 0; pass < 2; pass++)  // the one-wave LPs first, then the 256-thread ones, each in pack order
+        for (size_t i = 0; i < n; i++) {
+            const bool wave = (long long)p->H[i] * p->W[i] <= PACK_CELLS_WAVE;
+            if (wave != (pass == 0)) continue;
+            order[k++] = (int32_t)i;
+            const size_t lds = (size_t)pk_lds_bytes(p->H[i], p->W[i]);
+            if (wave) { p->n_wave += 1; p->lds_wave = std::max(p->lds_wave, lds); }
+            else { p->n_block += 1; p->lds_block = std::max(p->lds_block, lds); }
+        }
+    for (size_t i = 0; i < n; i++) {
+        PackLp& m = lps[i];
+        m.image = p->d_image + p->image_off[i];
+        m.hist = p->d_hist + i * p->hist_cap;
+        m.trace = p->d_trace + i * p->trace_cap;
+        m.precision = p->precision[i];
+        m.out_off = p->offs[i];
+        m.H = p->H[i]; m.W = p->W[i];
+        m.hist_cap = p->hist_cap; m.trace_cap = p->trace_cap;
+        // the engine's iters_cap formula with row_capacity = height
+        m.iters_cap = max_pivots > 0 ? max_pivots : (int32_t)std::min<long long>(2000000LL + 200LL * ((long long)m.H + m.W), 2000000000LL);
+        // partial pricing parameters (simplex.ts:118-127), as jslp_engine_create derives them
+        const int32_t n_columns = m.W - 1;
+        m.batch = std::min(500, std::max(50, (int32_t)floor(sqrt((double)n_columns))));
+        m.use_partial = n_columns > m.batch * 2;
+        m.pad = 0;
+    }
+    if (n) {
+        HIPC(hipMemcpyAsync(p->d_lps, lps.data(), sizeof(PackLp) * n, hipMemcpyHostToDevice, p->stream));
+        HIPC(hipMemcpyAsync(p->d_order, order.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, p->stream));
+        HIPC(hipStreamSynchronize(p->stream));  // (both vectors die with this function)
+    }
+    return JSLP_OK;
+}
+
+extern "C" int jslpp_pack_create(jslpp_pack** out, int device, int32_t n, const int32_t* height, const int32_t* width, const double* precision,
+                                 int32_t trace_cap, int32_t max_pivots) {
+    if (!out || n < 0 || (n > 0 && (!height || !width || !precision))) return fail(JSLP_ERR_ARG, "pack_create: bad arguments");
+    if (trace_cap < 0 || max_pivots < 0) return fail(JSLP_ERR_ARG, "pack_create: negative trace_cap or max_pivots");
+    for (int32_t i = 0; i < n; i++) {
+        if (height[i] < 2 || width[i] < 2) return pack_fail(JSLP_ERR_ARG, "pack_create", i, "a tableau has at least 2 rows and 2 columns");
+        if (!(precision[i] == precision[i])) return pack_fail(JSLP_ERR_ARG, "pack_create", i, "precision is not a number");
+        // (cells beyond the limit first: the byte count of an absurd shape must not overflow before it is compared)
+        if ((long long)height[i] * width[i] > JSLPP_LDS_LIMIT / 8 || pk_lds_bytes(height[i], width[i]) > (long long)WGLDS_MAX_BYTES)
+            return pack_fail(JSLP_ERR_UNSUPPORTED, "pack_create", i, "the tableau's LDS image exceeds 64 KiB (jslpp_lds_bytes): solve it through a jslp_engine");
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
+        return fail(JSLP_ERR_DEVICE, "pack_create: no HIP device visible (this engine has no CPU fallback)");
+    if (device < 0 || device >= ndev) return fail(JSLP_ERR_ARG, "pack_create: device ordinal out of range");
+    HIPC(hipSetDevice(device));
+    jslpp_pack* p = new jslpp_pack();
+    p->device = device; p->n = n; p->trace_cap = trace_cap;
+    p->hist_cap = max_pivots > 0 ? std::min<int32_t>(max_pivots, JSLPP_HIST_CAP) : JSLPP_HIST_CAP;
+    p->H.assign(height, height + n); p->W.assign(width, width + n); p->precision.assign(precision, precision + n);
+    p->evaluation.assign((size_t)n, 0.0);
+    p->is_set.assign((size_t)n, 0);
+    p->image_off.resize((size_t)n);
+    p->offs.resize((size_t)n + 1);
+    p->offs[0] = 0;
+    for (int32_t i = 0; i < n; i++) {
+        p->image_off[i] = p->image_bytes;
+        p->image_bytes += pack_image_bytes(height[i], width[i]);
+        p->offs[i + 1] = p->offs[i] + height[i];
+    }
+    const int rc = pack_init(p, max_pivots);
+    if (rc) { jslpp_pack_destroy(p); return rc; }
+    *out = p;
+    return JSLP_OK;
+}
+
+extern "C" void jslpp_pack_destroy(jslpp_pack* p) {
+    if (!p) return;
+    hipSetDevice(p->device);
+    if (p->stream) hipStreamSynchronize(p->stream);
+    if (p->pooled && p->res.complete()) pool_give(std::move(p->res));  // the bundle goes back as it came
+    delete p;
+}
+
+extern "C" int32_t jslpp_pack_size(const jslpp_pack* p) { return p ? p->n : 0; }
+extern "C" int32_t jslpp_pack_launches(const jslpp_pack* p) { return p ? p->launches : 0; }
+
+extern "C" int jslpp_pack_host_matrix(jslpp_pack* p, int32_t i, double** matrix, int64_t* n_doubles) {
+    if (!p || !matrix) return fail(JSLP_ERR_ARG, "pack_host_matrix: null pointer");
+    if (i < 0 || i >= p->n) return fail(JSLP_ERR_ARG, "pack_host_matrix: no such LP");
+    double* m = reinterpret_cast<double*>(p->h_image.p + p->image_off[i] + sizeof(DevState));
+    memset(m, 0, sizeof(double) * (size_t)p->H[i] * p->W[i]);  // a fresh Float64Array is zero-filled (tableau.ts:304)
+    *matrix = m;
+    if (n_doubles) *n_doubles = (int64_t)p->H[i] * p->W[i];
+    return JSLP_OK;
+}
+
+extern "C" int jslpp_pack_set(jslpp_pack* p, int32_t i, const double* matrix, const int32_t* var_index_by_row, const int32_t* var_index_by_col,
+                              const int32_t* unrestricted_var_indexes, int32_t n_unrestricted) {
+    if (!p || !var_index_by_row || !var_index_by_col) return fail(JSLP_ERR_ARG, "pack_set: null pointer");
+    if (i < 0 || i >= p->n) return fail(JSLP_ERR_ARG, "pack_set: no such LP");
+    if (n_unrestricted < 0 || (n_unrestricted > 0 && !unrestricted_var_indexes)) return pack_fail(JSLP_ERR_ARG, "pack_set", i, "bad unrestricted list");
+    const int32_t H = p->H[i], W = p->W[i], n_idx = pk_n_idx(H, W);
+    for (int32_t r = 1; r < H; r++)
+        if (var_index_by_row[r] < 0 || var_index_by_row[r] >= n_idx) return pack_fail(JSLP_ERR_ARG, "pack_set", i, "row variable index out of range");
+    for (int32_t c = 1; c < W; c++)
+        if (var_index_by_col[c] < 0 || var_index_by_col[c] >= n_idx) return pack_fail(JSLP_ERR_ARG, "pack_set", i, "column variable index out of range");
+    for (int32_t k = 0; k < n_unrestricted; k++)
+        if (unrestricted_var_indexes[k] < 0 || unrestricted_var_indexes[k] >= n_idx)
+            return pack_fail(JSLP_ERR_ARG, "pack_set", i, "unrestricted variable index out of range");
+    char* img = p->h_image.p + p->image_off[i];
+    double* m = reinterpret_cast<double*>(img + sizeof(DevState));
+    if (matrix && matrix != m) memcpy(m, matrix, sizeof(double) * (size_t)H * W);
+    // the integer block, as k_upload_finish builds an engine's: the maps, their inverses, the unrestricted flags
+    const PackInts io = pk_ints(H, W);
+    int32_t* ints = reinterpret_cast<int32_t*>(img + sizeof(DevState) + 8 * (size_t)pk_image_doubles(H, W));
+    memset(ints, 0, 4 * (size_t)io.total);
+    int32_t *vibr = ints + io.vibr, *vibc = ints + io.vibc, *rbv = ints + io.rbv, *cbv = ints + io.cbv;
+    uint8_t* unr = reinterpret_cast<uint8_t*>(ints + io.unr);
+    for (int32_t k = 0; k < n_idx; k++) { rbv[k] = -1; cbv[k] = -1; }
+    vibr[0] = -1; vibc[0] = -1;
+    for (int32_t r = 1; r < H; r++) { vibr[r] = var_index_by_row[r]; rbv[vibr[r]] = r; }
+    for (int32_t c = 1; c < W; c++) { vibc[c] = var_index_by_col[c]; cbv[vibc[c]] = c; }
+    for (int32_t k = 0; k < n_unrestricted; k++) unr[unrestricted_var_indexes[k]] = 1;
+    p->is_set[i] = 1;
+    return JSLP_OK;
+}
+
+extern "C" int jslpp_pack_upload(jslpp_pack* p) {
+    if (!p) return fail(JSLP_ERR_ARG, "pack_upload: null pack");
+    for (int32_t i = 0; i < p->n; i++)
+        if (!p->is_set[i]) return pack_fail(JSLP_ERR_STATE, "pack_upload", i, "never set (jslpp_pack_set)");
+    HIPC(hipSetDevice(p->device));
+    for (int32_t i = 0; i < p->n; i++) {  // the state an upload leaves (k_upload_finish)
+        DevState st;
+        memset(&st, 0, sizeof st);
+        st.H = p->H[i];
+        st.last_element_index = p->W[i] + p->H[i] - 2;  // tableau.ts:312-316
+        st.status = ST_DONE;
+        st.phase = 1;
+        st.feasible = 1;
+        st.bounded = 1;
+        st.unbounded_var = -1;
+        memcpy(p->h_image.p + p->image_off[i], &st, sizeof st);
+        p->evaluation[i] = 0;
+    }
+    if (p->image_bytes) HIPC(hipMemcpyAsync(p->d_image, p->h_image.p, p->image_bytes, hipMemcpyHostToDevice, p->stream));
+    HIPC(hipStreamSynchronize(p->stream));
+    p->uploaded = 1;
+    return JSLP_OK;
+}
+
+extern "C" int jslpp_pack_simplex(jslpp_pack* p, const int32_t* check_cycles, jslp_simplex_result* out, int32_t* status, double* device_ms) {
+    if (!p || (p->n > 0 && !out)) return fail(JSLP_ERR_ARG, "pack_simplex: bad arguments");
+    if (!p->uploaded) return fail(JSLP_ERR_STATE, "pack_simplex before upload");
+    if (device_ms) *device_ms = 0;
+    p->launches = 0;
+    const int32_t n = p->n;
+    if (n == 0) return JSLP_OK;
+    HIPC(hipSetDevice(p->device));
+    hipStream_t s = p->stream;
+    PackLaunch a{};
+    a.lps = p->d_lps;
+    a.cc = nullptr;
+    a.cc_all = check_cycles ? (check_cycles[0] != 0) : 1;
+    if (check_cycles) {  // one flag for all is an argument; a mixed list is a small copy of its own
+        bool mixed = false;
+        for (int32_t i = 1; i < n && !mixed; i++) mixed = (check_cycles[i] != 0) != (a.cc_all != 0);
+        if (mixed) {
+            int32_t* h = p->h_cc.as<int32_t>();
+            for (int32_t i = 0; i < n; i++) h[i] = check_cycles[i] != 0;
+            HIPC(hipMemcpyAsync(p->d_cc, h, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, s));
+            a.cc = p->d_cc;
+        }
+    }
+    a.states = p->result.d.p;
+    a.rhs = reinterpret_cast<double*>(p->result.d.p + p->res_rhs_off());
+    a.rows = reinterpret_cast<int32_t*>(p->result.d.p + p->res_rows_off());
+    const bool dbg = debug_launch_on();
+    HIPC(hipEventRecord(p->ev_begin, s));
+    for (int build = 0; build < 2; build++) {
+        const int32_t cnt = build ? p->n_block : p->n_wave;
+        if (!cnt) continue;
+        const int threads = build ? 256 : 64;
+        const size_t lds = build ? p->lds_block : p->lds_wave;
+        a.order = p->d_order + (build ? p->n_wave : 0);
+        (void)packed_launch(threads, (unsigned)cnt, lds, a, s);
+        HIPC(hipGetLastError());
+        p->launches += 1;
+        if (dbg) fprintf(stderr, "[jslp] launch k_simplex_packed<%d> n %d lds %zu\n", threads, (int)cnt, lds);
+    }
+    HIPC(hipEventRecord(p->ev_end, s));
+    HIPC(hipMemcpyAsync(p->result.h.p, p->result.d.p, p->res_bytes(), hipMemcpyDeviceToHost, s));
+    HIPC(hipStreamSynchronize(s));
+    float ms = 0;
+    if (device_ms && hipEventElapsedTime(&ms, p->ev_begin, p->ev_end) == hipSuccess) *device_ms = ms;
+    if (status) for (int32_t i = 0; i < n; i++) status[i] = JSLP_OK;
+    int32_t first_bad = -1; int first_rc = JSLP_OK; char first_msg[sizeof g_err];
+    const DevState* sts = p->h_states();
+    for (int32_t i = 0; i < n; i++) {  // what jslp_engine_simplex does after its solve, per LP
+        const DevState& st = sts[i];
+        int rc = state_error(st);
+        if (!rc) {
+            decode_state(st, p->precision[i], p->evaluation[i], &out[i], &p->evaluation[i]);
+            if (st.cycle_phase && st.hist_n > 0) {  // the reference's [start, length] message from the LP's history (rare: one small copy)
+                std::vector<int2> h(st.hist_n);
+                if (hipMemcpy(h.data(), p->d_hist + (size_t)i * p->hist_cap, sizeof(int2) * st.hist_n, hipMemcpyDeviceToHost) != hipSuccess)
+                    rc = fail(JSLP_ERR_DEVICE, "cycle history read-back failed");
+                else
+                    cycle_message(h, &out[i].cycle_start, &out[i].cycle_length);
+            }
+        }
+        if (rc) {
+            if (status) status[i] = rc;
+            if (first_bad < 0) { first_bad = i; first_rc = rc; snprintf(first_msg, sizeof first_msg, "%s", g_err); }
+        }
+    }
+    if (first_bad >= 0) {
+        snprintf(g_err, sizeof g_err, "pack_simplex: LP %d: %s", (int)first_bad, first_msg);
+        return first_rc;
+    }
+    return JSLP_OK;
+}
+
+extern "C" int jslpp_pack_read_rhs(jslpp_pack* p, const double** rhs, const int32_t** var_index_by_row, const int64_t** offsets) {
+    if (!p) return fail(JSLP_ERR_ARG, "pack_read_rhs: null pack");
+    if (!p->uploaded) return fail(JSLP_ERR_STATE, "pack_read_rhs before upload");
+    if (rhs) *rhs = p->h_rhs();
+    if (var_index_by_row) *var_index_by_row = p->h_rows();
+    if (offsets) *offsets = p->offs.data();
+    return JSLP_OK;
+}
+
+extern "C" int jslpp_pack_download(jslpp_pack* p, int32_t i, double* matrix, int32_t* var_index_by_row, int32_t* var_index_by_col,
+                                   int32_t* row_by_var_index, int32_t* col_by_var_index) {
+    if (!p) return fail(JSLP_ERR_ARG, "pack_download: null pack");
+    if (i < 0 || i >= p->n) return fail(JSLP_ERR_ARG, "pack_download: no such LP");
+    if (!p->uploaded) return fail(JSLP_ERR_STATE, "pack_download before upload");
+    HIPC(hipSetDevice(p->device));
+    HIPC(hipStreamSynchronize(p->stream));
+    const int32_t H = p->H[i], W = p->W[i], n_idx = pk_n_idx(H, W);
+    std::vector<char> img(pack_image_bytes(H, W));
+    HIPC(hipMemcpy(img.data(), p->d_image + p->image_off[i], img.size(), hipMemcpyDeviceToHost));
+    const PackInts io = pk_ints(H, W);
+    const int32_t* ints = reinterpret_cast<const int32_t*>(img.data() + sizeof(DevState) + 8 * (size_t)pk_image_doubles(H, W));
+    if (matrix) memcpy(matrix, img.data() + sizeof(DevState), sizeof(double) * (size_t)H * W);
+    if (var_index_by_row) memcpy(var_index_by_row, ints + io.vibr, sizeof(int32_t) * (size_t)H);
+    if (var_index_by_col) memcpy(var_index_by_col, ints + io.vibc, sizeof(int32_t) * (size_t)W);
+    if (row_by_var_index) memcpy(row_by_var_index, ints + io.rbv, sizeof(int32_t) * (size_t)n_idx);
+    if (col_by_var_index) memcpy(col_by_var_index, ints + io.cbv, sizeof(int32_t) * (size_t)n_idx);
+    return JSLP_OK;
+}
+
+extern "C" int jslpp_pack_pivot_trace(jslpp_pack* p, int32_t i, int32_t* row_col, int64_t max_pairs, int64_t* n_pivots) {
+    if (!p || !n_pivots) return fail(JSLP_ERR_ARG, "pack_pivot_trace: null pointer");
+    if (i < 0 || i >= p->n) return fail(JSLP_ERR_ARG, "pack_pivot_trace: no such LP");
+    if (!p->uploaded) return fail(JSLP_ERR_STATE, "pack_pivot_trace before upload");
+    HIPC(hipSetDevice(p->device));
+    HIPC(hipStreamSynchronize(p->stream));
+    DevState st;
+    HIPC(hipMemcpy(&st, p->d_image + p->image_off[i], sizeof st, hipMemcpyDeviceToHost));
+    *n_pivots = st.trace_n;
+    if (row_col && max_pairs > 0 && st.trace_n > p->trace_cap)
+        return pack_fail(JSLP_ERR_CAPACITY, "pack_pivot_trace", i, "more pivots since upload than the pack's trace_cap: the recorded prefix is not handed out as if it were complete");
+    if (row_col && max_pairs > 0) {
+        const long long n = std::min<long long>(st.trace_n, max_pairs);
+        if (n > 0) HIPC(hipMemcpy(row_col, p->d_trace + (size_t)i * p->trace_cap, sizeof(int2) * n, hipMemcpyDeviceToHost));
+    }
+    return JSLP_OK;
+}
+
 #if !defined(JSLP_SPLIT_TU)
 #include "jslp_mir_kernels.hip.h"  // single-unit build: the MIR kernels behind everything else (the product: jslp_tu_mir.hip)
+#define JSLP_PACKED_KERNELS 1
+#include "jslp_packed.hip.h"       // ... and the pack's two (the product: jslp_tu_packed.hip)
 #endif

@@ -1,0 +1,342 @@
+// jslp_packed.hip.h -- the pack of small LPs (include/jslpp_packed.h): one workgroup per LP, the WHOLE tableau and its index maps in LDS.
+//
+// Two parts, each included once per unit (no #pragma once on purpose):
+//   * the layout (always): where the pieces of one LP lie in the arena image and in LDS, the per-LP descriptor and the launch arguments --
+//     host and device read the same functions, jslpp_lds_bytes is pk_lds_bytes;
+//   * the kernels and their launch function (-DJSLP_PACKED_KERNELS; needs jslp_kernels.hip.h in front: Cand / the orders / wave_reduce /
+//     block_reduce / eliminate / nonzero16 / suffix_is_square / begin_simplex / many_global).  The product compiles them in a unit of
+//     their own (jslp_tu_packed.hip); a single-unit build includes them at the end of jslp_hip.hip.
+//
+// Why a kernel of its own: k_simplex_lds_many keeps the selection state in LDS and the tableau in global memory, so every pivot of a
+// 3 x 3 LP pays a strided column gather, a row read and the gated rows' round trips through L2.  A tableau of a few thousand cells fits
+// in LDS whole: here a pivot touches global memory twice, with stores nobody waits for (the history pair and the trace pair).
+#ifndef JSLP_PACKED_LAYOUT
+#define JSLP_PACKED_LAYOUT
+
+// ---- layout ---------------------------------------------------------------------------------------------------------------------------
+// Arena image of one LP (what the ONE H2D copy brings, 16-byte aligned, a multiple of 16 bytes):
+//   [DevState | matrix H x W doubles, reference layout (stride W), padded to an even count | integer block]
+// Integer block, the same in the image and in LDS, every piece padded to 16 bytes so that the block moves as a run of 16-byte words:
+//   [varIndexByRow H | varIndexByCol W | rowByVarIndex n_idx | colByVarIndex n_idx | unrestricted flags, n_idx bytes]
+// with n_idx = W + 2 H + 2, as jslp_engine_create(height, width, row_capacity = height) sizes the maps.
+// LDS image: [tableau H x S doubles | pivot column H doubles | (pad to 16 bytes) | integer block], S = the row stride padded to an ODD
+// number of doubles: the pivot-column gather has lane r reading A[r][c], and with an odd stride 32 consecutive rows fall into 32
+// distinct pairs of the 64 four-byte banks -- conflict-free for ds_read_b64 (an even stride of 2^k doubles would be 2^k-way).
+struct PackInts { int32_t vibr, vibc, rbv, cbv, unr, total; };  // offsets / size in 4-byte words
+__host__ __device__ __forceinline__ int32_t pk_pad4(int32_t n) { return (n + 3) & ~3; }
+__host__ __device__ __forceinline__ int32_t pk_n_idx(int32_t H, int32_t W) { return W + 2 * H + 2; }
+__host__ __device__ __forceinline__ int32_t pk_stride(int32_t W) { return W | 1; }
+__host__ __device__ __forceinline__ PackInts pk_ints(int32_t H, int32_t W) {
+    const int32_t n = pk_n_idx(H, W);
+    PackInts o;
+    o.vibr = 0;
+    o.vibc = pk_pad4(H);
+    o.rbv = o.vibc + pk_pad4(W);
+    o.cbv = o.rbv + pk_pad4(n);
+    o.unr = o.cbv + pk_pad4(n);
+    o.total = o.unr + pk_pad4((n + 3) / 4);
+    return o;
+}
+__host__ __device__ __forceinline__ long long pk_image_doubles(int32_t H, int32_t W) { return ((long long)H * W + 1) & ~1LL; }  // the matrix in the image
+__host__ __device__ __forceinline__ long long pk_lds_doubles(int32_t H, int32_t W) { return ((long long)H * pk_stride(W) + H + 1) & ~1LL; }
+__host__ __device__ __forceinline__ long long pk_lds_bytes(int32_t H, int32_t W) { return 8 * pk_lds_doubles(H, W) + 4LL * pk_ints(H, W).total; }
+
+// One LP of a pack: built on the host ONCE, at create; one entry per workgroup.
+struct PackLp {
+    char* image;        // this LP's arena image (see above)
+    int2* hist;         // cycle-check history of the current phase, hist_cap pairs
+    int2* trace;        // pivot trace since the upload, trace_cap pairs
+    double precision;
+    long long out_off;  // first entry of this LP's RHS column / row map in the result block
+    int32_t H, W;
+    int32_t hist_cap, trace_cap;
+    int32_t iters_cap;
+    int32_t batch, use_partial;  // partial-pricing parameters (simplex.ts:118-127)
+    int32_t pad;
+};
+// arguments of one launch, travelling as bytes between the units (the same struct in every unit)
+struct PackLaunch {
+    const PackLp* lps;
+    const int32_t* order;  // blockIdx.x -> LP index (the LPs of this build)
+    const int32_t* cc;     // per-LP checkForCycles, or nullptr: cc_all for every LP
+    int32_t cc_all, pad;
+    void* states;          // result block: DevState per LP (LP order) ...
+    double* rhs;           // ... the RHS columns one after the other ...
+    int32_t* rows;         // ... and the row maps
+};
+#endif  // JSLP_PACKED_LAYOUT
+
+#if defined(JSLP_PACKED_KERNELS) && !defined(JSLP_PACKED_KERNELS_DONE)
+#define JSLP_PACKED_KERNELS_DONE
+
+#define PK_HIST 128  // first pairs of the cycle-check history kept in LDS: while the history fits, the suffix test runs on them
+struct PackSmem {
+    Smem g;              // cross-wave stage of block_reduce
+    int2 hist[PK_HIST];
+};
+
+// the winner of a selection in every thread: one wave reduces with shuffles alone, four waves meet in LDS (block_reduce)
+template <int THREADS, class Better>
+__device__ __forceinline__ Cand pk_reduce(Cand x, Better better, Smem& sm) {
+    if constexpr (THREADS == 64) {
+        x = wave_reduce(x, better);
+        Cand r;
+        r.v = __shfl(x.v, 0, 64);
+        r.i = __shfl(x.i, 0, 64);
+        r.b = __shfl(x.b, 0, 64);
+        return r;
+    } else {
+        return block_reduce(x, better, sm);
+    }
+}
+
+// simplex() of LP order[blockIdx.x] of a pack: load the LP into LDS, run phase 1 / phase 2 / pivot / checkForCycles there, write the
+// tableau, the maps, the state, the RHS column and the row map back once.  THREADS = 64: one wave -- the block barriers below degenerate
+// (the compiler drops s_barrier for a one-wave workgroup) and every reduction is wave_reduce alone; THREADS = 256: four waves.
+// The loop restates select_step / prepare_pivot / update_rows_wg (jslp_core.inc.h) over LDS with its scalars in registers, as
+// simplex_wg_lds does over global memory; arithmetic, orders and tie-breaks are the core's own functions.  Every loop is bounded by the
+// pivot cap; the kernel waits on nothing outside its workgroup.
+template <int THREADS>
+__global__ void __launch_bounds__(THREADS) k_simplex_packed(const PackLp* __restrict__ lps, const int32_t* __restrict__ order, const int32_t* __restrict__ cc,
+                                                            int cc_all, DevState* __restrict__ out_states, double* __restrict__ out_rhs,
+                                                            int32_t* __restrict__ out_rows) {
+    extern __shared__ __attribute__((aligned(16))) double pk_lds[];
+    __shared__ PackSmem sm;
+    const int idx = order[blockIdx.x];
+    const PackLp m = lps[idx];  // one uniform copy at entry
+    const int tid = threadIdx.x;
+    const int H = m.H, W = m.W, S = pk_stride(W);
+    const PackInts io = pk_ints(H, W);
+    const double precision = m.precision;
+    const int check_cycles = cc ? cc[idx] : cc_all;
+    // LDS, indexed from the extern base: ds_read / ds_write, never flat
+    double* A = pk_lds;
+    double* pcol = pk_lds + H * S;
+    int32_t* ints = reinterpret_cast<int32_t*>(pk_lds + pk_lds_doubles(H, W));
+    int32_t* vibr = ints + io.vibr;
+    int32_t* vibc = ints + io.vibc;
+    int32_t* rbv = ints + io.rbv;
+    int32_t* cbv = ints + io.cbv;
+    const uint8_t* unr = reinterpret_cast<const uint8_t*>(ints + io.unr);
+    // global memory (the descriptor's pointers were loaded from memory: say where they point, see many_global)
+    char* image = many_global(m.image);
+    DevState* st = reinterpret_cast<DevState*>(image);
+    double2* gA = reinterpret_cast<double2*>(image + sizeof(DevState));
+    int4* gI = reinterpret_cast<int4*>(image + sizeof(DevState) + 8 * pk_image_doubles(H, W));
+    int2* ghist = many_global(m.hist);
+    int2* gtrace = many_global(m.trace);
+
+    // ---- load: the matrix as 16-byte words (stride W -> stride S), the integer block verbatim --------------------------------------
+    const int cells = H * W, pairs = (cells + 1) >> 1, words = io.total >> 2;
+    for (int q = tid; q < pairs; q += THREADS) {
+        const double2 v = gA[q];
+        const int e = 2 * q, r = e / W, c = e - r * W;
+        A[r * S + c] = v.x;
+        if (e + 1 < cells) {
+            const bool wrap = c + 1 == W;
+            A[(wrap ? r + 1 : r) * S + (wrap ? 0 : c + 1)] = v.y;
+        }
+    }
+    for (int q = tid; q < words; q += THREADS) reinterpret_cast<int4*>(ints)[q] = gI[q];
+    if (tid == 0) begin_simplex(st, m.iters_cap);  // simplex.ts:14-23
+    long long trace_n = st->trace_n;
+    __syncthreads();
+
+    // the row update's thread grid: CW columns (a power of two covering the width, at most the workgroup) x RP rows at a time
+    int cshift = 0;
+    while ((1 << cshift) < W && (1 << cshift) < THREADS) cshift++;
+    const int CW = 1 << cshift, RP = THREADS >> cshift, col0 = tid & (CW - 1), rsub = tid >> cshift;
+
+    int phase = 1, it1 = 0, it2 = 0, hist_n = 0, iters_left = m.iters_cap, entered2 = 0;
+    // outcome: 0 running, 1 optimal, 2 unbounded, 3 cycle, 4 infeasible, 5 iteration cap, 6 history full
+    int outcome = 0, unbounded_col = 0;
+    while (outcome == 0) {
+        if (iters_left <= 0) { outcome = 5; break; }
+        int pr = 0, pc = 0;
+        if (phase == 1) {
+            // leaving row: most negative RHS below -precision, first index on ties (simplex.ts:39-49)
+            Cand best; best.v = -precision; best.i = 0; best.b = 0;
+            for (int r = 1 + tid; r < H; r += THREADS) {
+                const double v = A[r * S];
+                if (v < best.v) { best.v = v; best.i = r; }
+            }
+            best = pk_reduce<THREADS>(best, MinFirst(), sm.g);
+            if (best.i == 0) {  // :51-54 feasible: phase 2 starts in this same iteration with a fresh history (:102)
+                phase = 2; entered2 = 1; hist_n = 0;
+            } else {
+                pr = best.i;
+                // entering column: max -cost/coef over unrestricted or coef < -precision (simplex.ts:56-71)
+                const double* row = A + pr * S;
+                Cand q; q.v = -INFINITY; q.i = 0; q.b = 0;
+                for (int col = 1 + tid; col < W; col += THREADS) {
+                    const double coef = row[col];
+                    const bool un = unr[vibc[col]] != 0;
+                    if (un || coef < -precision) {
+                        const double quo = -A[col] / coef;
+                        if (q.v < quo) { q.v = quo; q.i = col; }
+                    }
+                }
+                q = pk_reduce<THREADS>(q, MaxFirst(), sm.g);
+                if (q.i == 0) { outcome = 4; break; }  // :73-76 infeasible
+                pc = q.i;
+            }
+        }
+        if (phase == 2) {
+            // Dantzig pricing with the reference's batch rule (simplex.ts:118-219): the first batch holding a candidate
+            // wins; inside it the largest value, first index on ties
+            Cand e; e.v = precision; e.i = 0; e.b = 0;
+            for (int col = 1 + tid; col < W; col += THREADS) {
+                const double rc = A[col];
+                const bool un = unr[vibc[col]] != 0;
+                const int b = m.use_partial ? (col - 1) / m.batch : 0;
+                const double val = (un && rc < 0) ? -rc : rc;
+                if (val > precision) {
+                    Cand cand; cand.v = val; cand.i = col; cand.b = b;
+                    const bool take = PriceFirst()(cand, e);
+                    e.v = take ? cand.v : e.v;
+                    e.i = take ? cand.i : e.i;
+                    e.b = take ? cand.b : e.b;
+                }
+            }
+            e = pk_reduce<THREADS>(e, PriceFirst(), sm.g);
+            if (e.i == 0) { outcome = 1; break; }  // optimal (simplex.ts:265-269)
+            pc = e.i;
+            int neg_flag;
+            {   // isReducedCostNegative of the winner
+                const double rc = A[pc];
+                neg_flag = (unr[vibc[pc]] != 0 && rc < 0) ? 1 : 0;
+            }
+            // ratio test (simplex.ts:271-296) in its order-free form: the first row passing the degenerate test wins
+            // outright, otherwise the first-index argmin of the accepted quotients.  One reduction: an accepted quotient is above
+            // precision > 0, so a degenerate row enters as -Infinity and MinFirst breaks the ties among them by the first index.
+            Cand mq; mq.v = INFINITY; mq.i = 0; mq.b = 0;
+            int rdeg = 0;
+            for (int r = 1 + tid; r < H; r += THREADS) {
+                const double colv = A[r * S + pc];
+                const double rhs = A[r * S];
+                if (-precision < colv && colv < precision) continue;
+                if (colv > 0 && precision > rhs && rhs > -precision) {
+                    if (rdeg == 0) rdeg = r;  // (my rows ascend)
+                    continue;
+                }
+                const double quo = neg_flag ? -rhs / colv : rhs / colv;
+                if (quo > precision && mq.v > quo) { mq.v = quo; mq.i = r; }
+            }
+            if (rdeg != 0) { mq.v = -INFINITY; mq.i = rdeg; }
+            mq = pk_reduce<THREADS>(mq, MinFirst(), sm.g);
+            if (mq.i == 0) { outcome = 2; unbounded_col = pc; break; }  // unbounded (simplex.ts:298-303)
+            pr = mq.i;
+        }
+        const int leaving = vibr[pr], entering = vibc[pc];
+        // cycle check (simplex.ts:78-93 / 305-320): append first, test, stop WITHOUT pivoting on a hit.  The host rebuilds the
+        // reference's [start, length] message from the global copy.
+        if (check_cycles) {
+            if (hist_n >= m.hist_cap) { outcome = 6; break; }
+            if (tid == 0) {
+                const int2 pair = make_int2(leaving, entering);
+                ghist[hist_n] = pair;
+                if (hist_n < PK_HIST) sm.hist[hist_n] = pair;
+            }
+            __syncthreads();
+            hist_n += 1;
+            const bool cycle = hist_n <= PK_HIST ? suffix_is_square(sm.hist, hist_n, sm.g) : suffix_is_square(ghist, hist_n, sm.g);
+            if (cycle) { outcome = 3; break; }
+        }
+        // ---- pivot(pr, pc) (simplex.ts:330-391) ------------------------------------------------------------------------------------
+        const double quot = A[pr * S + pc];  // :335
+        int any = 0;
+        for (int r = tid; r < H; r += THREADS) {  // the pivot column: lane r reads A[r][pc], conflict-free with the odd stride
+            const double k = A[r * S + pc];
+            pcol[r] = k;
+            any |= (r != pr && nonzero16(k)) ? 1 : 0;
+        }
+        // any row that will execute the inner loop of :367-391 lazily zeroes the tiny pivot-row entries
+        const int anyrow = __syncthreads_or(any);  // (also orders the quot read above against the row write below)
+        double* prow = A + pr * S;
+        for (int col = tid; col < W; col += THREADS) {
+            const double val = prow[col];
+            const bool innz = nonzero16(val);                          // :356
+            double v = innz ? val / quot : 0.0;                        // :357 / :361  (IEEE division)
+            if (col == pc) v = 1.0 / quot;                             // :364
+            if (innz && anyrow && !nonzero16(v) && v != 0.0) v = 0.0;  // :381-383
+            prow[col] = v;
+        }
+        if (tid == 0) {  // :339-349
+            vibr[pr] = entering;
+            vibc[pc] = leaving;
+            rbv[entering] = pr;
+            rbv[leaving] = -1;
+            cbv[entering] = -1;
+            cbv[leaving] = pc;
+            if (trace_n < m.trace_cap) gtrace[trace_n] = make_int2(pr, pc);
+        }
+        trace_n += 1;
+        if (phase == 1) it1 += 1; else it2 += 1;
+        iters_left -= 1;
+        __syncthreads();  // the normalised pivot row and the pivot column are complete
+        for (int r = rsub; r < H; r += RP) {
+            const double k = pcol[r];
+            if (r == pr || !nonzero16(k)) continue;  // the row gate, :370-375
+            double* row = A + r * S;
+            for (int col = col0; col < W; col += CW) {
+                if (col == pc) { row[col] = -k / quot; continue; }  // :387 overwrites whatever the loop did to column pc
+                const double p = prow[col];
+                if (nonzero16(p)) row[col] = eliminate(row[col], k, p);  // :376-386, both roundings
+            }
+        }
+        __syncthreads();
+    }
+    // ---- epilogue: everything back once -------------------------------------------------------------------------------------------
+    __syncthreads();
+    for (int q = tid; q < pairs; q += THREADS) {
+        const int e = 2 * q, r = e / W, c = e - r * W;
+        const bool wrap = c + 1 == W;
+        double2 v;
+        v.x = A[r * S + c];
+        v.y = e + 1 < cells ? A[(wrap ? r + 1 : r) * S + (wrap ? 0 : c + 1)] : 0.0;
+        gA[q] = v;
+    }
+    for (int q = tid; q < words; q += THREADS) gI[q] = reinterpret_cast<const int4*>(ints)[q];
+    for (int r = tid; r < H; r += THREADS) {
+        out_rhs[m.out_off + r] = A[r * S];
+        out_rows[m.out_off + r] = vibr[r];
+    }
+    if (tid == 0) {
+        st->phase = phase;
+        st->it1 = it1;
+        st->it2 = it2;
+        st->hist_n = hist_n;
+        st->iters_left = iters_left;
+        st->trace_n = trace_n;
+        st->entered_phase2 = entered2;
+        if (entered2) st->feasible = 1;
+        if (outcome == 1) st->optimal = 1;
+        if (outcome == 2) { st->bounded = 0; st->unbounded_var = vibc[unbounded_col]; }
+        if (outcome == 3) { st->cycle_phase = phase; st->feasible = 0; }
+        if (outcome == 4) st->feasible = 0;
+        if (outcome == 5) st->err = ERR_ITER_LIMIT;
+        if (outcome == 6) st->err = ERR_HIST_FULL;
+        st->status = ST_DONE;
+        st->do_pivot = 0;
+        st->obj_cell = A[0];
+    }
+    __syncthreads();
+    static_assert(sizeof(DevState) % 8 == 0 && sizeof(DevState) / 8 <= 64, "DevState is copied by one wave, a word per lane");
+    if (tid < (int)(sizeof(DevState) / 8))
+        reinterpret_cast<long long*>(out_states + idx)[tid] = reinterpret_cast<const long long*>(st)[tid];
+}
+
+// launches the build for `threads` (64 or 256); returns the hipError_t of the launch, or -1 for an unknown build.  The error is PEEKED
+// at, not taken: the caller's hipGetLastError still sees it and reports it
+static int packed_launch_impl(int threads, unsigned grid, size_t lds, const void* bytes, hipStream_t s) {
+    const PackLaunch a = *static_cast<const PackLaunch*>(bytes);
+    DevState* states = static_cast<DevState*>(a.states);
+    if (threads == 64)
+        hipLaunchKernelGGL(k_simplex_packed<64>, dim3(grid), dim3(64), lds, s, a.lps, a.order, a.cc, a.cc_all, states, a.rhs, a.rows);
+    else if (threads == 256)
+        hipLaunchKernelGGL(k_simplex_packed<256>, dim3(grid), dim3(256), lds, s, a.lps, a.order, a.cc, a.cc_all, states, a.rhs, a.rows);
+    else
+        return -1;
+    return (int)hipPeekAtLastError();
+}
+#endif  // JSLP_PACKED_KERNELS

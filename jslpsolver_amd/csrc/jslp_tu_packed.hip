@@ -1,0 +1,21 @@
+// jslp_tu_packed.hip -- the two builds of k_simplex_packed (include/jslpp_packed.h) as a translation unit of their own.
+//
+// The product build compiles this file next to jslp_hip.hip (-DJSLP_SPLIT_TU), the two parts of jslp_tu_resident.hip and jslp_tu_mir.hip
+// (__graft_entry__.build()).  As there, the kernel headers are included inside a namespace of the unit's own, so every kernel and helper
+// has internal linkage and the units never meet at link time; the unit exports ONE hidden function that launches the build a thread count
+// names, its arguments travelling as bytes (PackLaunch, jslp_packed.hip.h: the same struct in every unit).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <math.h>
+#include <stddef.h>
+#include <string.h>
+
+namespace {
+#include "jslp_kernels.hip.h"
+#define JSLP_PACKED_KERNELS 1
+#include "jslp_packed.hip.h"
+}  // namespace
+
+extern "C" __attribute__((visibility("hidden"))) int jslpp_packed_launch_tu(int threads, unsigned grid, size_t lds, const void* args, void* stream) {
+    return packed_launch_impl(threads, grid, lds, args, static_cast<hipStream_t>(stream));
+}

@@ -883,3 +883,208 @@ def pivot_digest(pairs):
         h = ((h ^ int(r)) * 16777619) & 0xFFFFFFFF
         h = ((h ^ int(c)) * 16777619) & 0xFFFFFFFF
     return "%x" % h
+
+
+def pack_lds_bytes(height, width):
+    """jslpp_lds_bytes (include/jslpp_packed.h) restated: the dynamic LDS one LP of a pack needs -- the tableau with its row stride padded to
+    an odd number of doubles, the pivot column, and the integer block [vibr | vibc | rbv | cbv | unrestricted flags] with every piece padded
+    to 16 bytes.  What a library without the extension (the oracle) is asked instead; tests/test_packed_abi.py holds the two together."""
+    h, w = int(height), int(width)
+    if h < 2 or w < 2:
+        return 0
+    pad4 = lambda n: (n + 3) & ~3  # noqa: E731
+    n_idx = w + 2 * h + 2
+    doubles = (h * (w | 1) + h + 1) & ~1
+    ints = pad4(h) + pad4(w) + 2 * pad4(n_idx) + pad4((n_idx + 3) // 4)
+    return 8 * doubles + 4 * ints
+
+
+def pack_fits(height, width, lib=None):
+    """whether a tableau of this shape can join a TableauPack (its LDS image stays within the 64 KiB the pack kernels are launched with)"""
+    if lib is not None and getattr(lib, "has_pack", False):
+        b = int(lib.jslpp_lds_bytes(int(height), int(width)))
+    else:
+        b = pack_lds_bytes(height, width)
+    return 0 < b <= _capi.JSLPP_LDS_LIMIT
+
+
+class TableauPack:
+    """Many small independent LPs in one object (include/jslpp_packed.h): one arena, one upload, one launch per kernel build that solves
+    every LP with its whole tableau in LDS, one read-back.  `lps` is a list of (matrix, var_index_by_row, var_index_by_col, unrestricted);
+    `precision` one tolerance or one per LP.  trace_cap: pivot pairs recorded per LP; max_pivots > 0 caps the pivots per LP and call.
+
+    simplex() returns the results as ONE numpy structured array (_capi.RESULT_DTYPE, a field per jslp_simplex_result member) and keeps
+    `status` (per-LP engine codes), `evaluation`, `feasible` and `bounded` as arrays; result(i) is LP i's SimplexResult.
+
+    A library without the extension (the CPU oracle) gets a RESTATEMENT behind the same interface: one engine per LP, solved one after the
+    other (max_pivots is then the engine's own cap) -- the host logic stays testable without a GPU.  A HIP library without the extension is
+    an error, never a fallback."""
+
+    def __init__(self, lps, precision=1e-8, lib=None, device=0, trace_cap=0, max_pivots=0):
+        self.lib = lib if lib is not None else _capi.load_hip()
+        self._lps = []
+        for matrix, vibr, vibc, unr in lps:
+            m = _capi.as_f64(matrix)
+            if m.ndim != 2:
+                raise ValueError("matrix must be height x width")
+            vibr, vibc = _capi.as_i32(vibr), _capi.as_i32(vibc)
+            if vibr.shape[0] != m.shape[0] or vibc.shape[0] != m.shape[1]:
+                raise ValueError("index maps do not match the matrix shape")
+            self._lps.append((m, vibr, vibc, _capi.as_i32(list(unr))))
+        self.n = n = len(self._lps)
+        if isinstance(precision, (int, float)):
+            self.precision = np.full(n, float(precision), dtype=np.float64)
+        else:
+            self.precision = _capi.as_f64(list(precision))
+            if self.precision.shape[0] != n:
+                raise ValueError("TableauPack: %d precisions for %d LPs" % (self.precision.shape[0], n))
+        self.heights = _capi.as_i32([m.shape[0] for m, _, _, _ in self._lps])
+        self.widths = _capi.as_i32([m.shape[1] for m, _, _, _ in self._lps])
+        self.trace_cap, self.max_pivots, self.device = int(trace_cap), int(max_pivots), int(device)
+        self.results = np.zeros(n, dtype=_capi.RESULT_DTYPE)
+        self.status = np.zeros(n, dtype=np.int32)
+        self.evaluation = np.zeros(n, dtype=np.float64)
+        self.feasible = np.ones(n, dtype=bool)
+        self.bounded = np.ones(n, dtype=bool)
+        self.device_ms = 0.0
+        self._launches = 0
+        self._h = None
+        self._twins = None
+        if self.lib.has_pack:
+            self._h = _capi.C.c_void_p()
+            self.lib.check(self.lib.jslpp_pack_create(_capi.C.byref(self._h), self.device, n, _capi.ptr_i32(self.heights), _capi.ptr_i32(self.widths),
+                                                      _capi.ptr_f64(self.precision), self.trace_cap, self.max_pivots), "jslpp_pack_create")
+            try:
+                for i, (m, vibr, vibc, unr) in enumerate(self._lps):
+                    self.lib.check(self.lib.jslpp_pack_set(self._h, i, _capi.ptr_f64(m), _capi.ptr_i32(vibr), _capi.ptr_i32(vibc), _capi.ptr_i32(unr),
+                                                           int(unr.shape[0])), "jslpp_pack_set")
+                self._lps = None  # (the pack's pinned image holds the inputs from here on)
+                self.upload()
+            except Exception:
+                self.close()
+                raise
+        elif self.lib.backend == "oracle-c":
+            for h, w in zip(self.heights, self.widths):
+                if not pack_fits(h, w):
+                    raise _capi.EngineError("jslpp_pack_create failed (%d): the tableau's LDS image exceeds 64 KiB" % _capi.JSLP_ERR_UNSUPPORTED)
+            self._twins = [Tableau(m, vibr, vibc, unr, precision=float(p), device=self.device, lib=self.lib)
+                           for (m, vibr, vibc, unr), p in zip(self._lps, self.precision)]
+        else:
+            raise _capi.EngineError("TableauPack: %s does not export the pack extension (include/jslpp_packed.h)" % self.lib.path)
+
+    # ---- lifetime -------------------------------------------------------------------------------
+    def close(self):
+        if self._h is not None and self._h.value:
+            self.lib.jslpp_pack_destroy(self._h)
+        self._h = None
+        for t in self._twins or ():
+            t.close()
+        self._twins = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __len__(self):
+        return self.n
+
+    @property
+    def launches(self):
+        """kernel launches of the last simplex(): at most one per kernel build (0 for the restatement)"""
+        return self._launches
+
+    def upload(self):
+        """hand the LPs over again as they were given: one H2D copy; every LP's state, evaluation, counters and trace start afresh"""
+        if self._twins is not None:
+            for t, (m, vibr, vibc, unr) in zip(self._twins, self._lps):
+                t.upload(m, vibr, vibc, unr)
+                t.evaluation, t.feasible, t.bounded = 0.0, True, True
+        else:
+            self.lib.check(self.lib.jslpp_pack_upload(self._h), "jslpp_pack_upload")
+        self.evaluation[:] = 0.0
+        self.feasible[:] = True
+        self.bounded[:] = True
+
+    def _flags(self, check_cycles):
+        if isinstance(check_cycles, (bool, int, np.bool_)):
+            return np.full(self.n, int(bool(check_cycles)), dtype=np.int32)
+        flags = _capi.as_i32([int(bool(c)) for c in check_cycles])
+        if flags.shape[0] != self.n:
+            raise ValueError("TableauPack.simplex: %d check_cycles flags for %d LPs" % (flags.shape[0], self.n))
+        return flags
+
+    def simplex(self, check_cycles=True):
+        """Tableau.simplex() of every LP.  An LP whose solve fails (pivot cap, history capacity) keeps its earlier result and scalars and gets
+        the engine's code in `status`; the others are solved; the call then raises EngineError naming the first such LP."""
+        flags = self._flags(check_cycles)
+        out = self.results.copy()
+        status = np.zeros(self.n, dtype=np.int32)
+        if self._twins is not None:
+            rc, msg = _capi.JSLP_OK, ""
+            for i, (t, c) in enumerate(zip(self._twins, flags)):
+                res = SimplexResult()
+                st = self.lib.jslp_engine_simplex(t._h, int(c), _capi.C.byref(res))
+                status[i] = st
+                if st == _capi.JSLP_OK:
+                    t._absorb(res)
+                    out[i] = np.frombuffer(res, dtype=_capi.RESULT_DTYPE)[0]
+                elif rc == _capi.JSLP_OK:
+                    rc, msg = st, "pack_simplex: LP %d: %s" % (i, self.lib.jslp_last_error().decode())
+            self._launches = 0
+        else:
+            ms = _capi.C.c_double()
+            all_same = bool((flags == flags[0]).all()) if self.n else True
+            rc = self.lib.jslpp_pack_simplex(self._h, None if (all_same and self.n and flags[0]) else _capi.ptr_i32(flags), out.ctypes.data,
+                                             _capi.ptr_i32(status), _capi.C.byref(ms))
+            msg = self.lib.jslp_last_error().decode() if rc != _capi.JSLP_OK else ""
+            if rc != _capi.JSLP_OK and not status.any():  # refused before any work
+                raise _capi.EngineError("jslpp_pack_simplex failed (%d): %s" % (rc, msg))
+            self.device_ms = ms.value
+            self._launches = int(self.lib.jslpp_pack_launches(self._h))
+        ok = status == _capi.JSLP_OK  # (an LP that failed leaves its scalars alone, as simplex() does)
+        self.results = out
+        self.status = status
+        self.feasible[ok] = out["feasible"][ok] != 0
+        self.bounded[ok] = out["bounded"][ok] != 0
+        self.evaluation[ok] = out["evaluation"][ok]
+        if rc != _capi.JSLP_OK:
+            raise _capi.EngineError("jslpp_pack_simplex failed (%d): %s" % (rc, msg))
+        return out
+
+    def result(self, i):
+        """LP i's result of the last simplex() as a SimplexResult"""
+        return SimplexResult.from_buffer_copy(self.results[i].tobytes())
+
+    # ---- read-back --------------------------------------------------------------------------------
+    def read_rhs(self, i):
+        """RHS column and varIndexByRow of LP i after the last simplex() (copies; native: out of the pack's pinned result block)"""
+        if self._twins is not None:
+            return self._twins[i].read_rhs()
+        rhs, rows, offs = _capi._f64p(), _capi._i32p(), _capi._P(_capi.C.c_int64)()
+        self.lib.check(self.lib.jslpp_pack_read_rhs(self._h, _capi.C.byref(rhs), _capi.C.byref(rows), _capi.C.byref(offs)), "jslpp_pack_read_rhs")
+        a, b = int(offs[i]), int(offs[i + 1])
+        return (np.ctypeslib.as_array(rhs, shape=(int(offs[self.n]),))[a:b].copy(),
+                np.ctypeslib.as_array(rows, shape=(int(offs[self.n]),))[a:b].copy())
+
+    def download(self, i):
+        if self._twins is not None:
+            return self._twins[i].download()
+        h, w = int(self.heights[i]), int(self.widths[i])
+        n = w + 2 * h + 2
+        m = np.empty((h, w), dtype=np.float64)
+        vibr, vibc = np.empty(h, dtype=np.int32), np.empty(w, dtype=np.int32)
+        rbv, cbv = np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32)
+        self.lib.check(self.lib.jslpp_pack_download(self._h, int(i), _capi.ptr_f64(m), _capi.ptr_i32(vibr), _capi.ptr_i32(vibc), _capi.ptr_i32(rbv),
+                                                    _capi.ptr_i32(cbv)), "jslpp_pack_download")
+        return m, vibr, vibc, rbv, cbv
+
+    def pivot_trace(self, i):
+        if self._twins is not None:
+            return self._twins[i].pivot_trace()
+        n = _capi.C.c_int64()
+        self.lib.check(self.lib.jslpp_pack_pivot_trace(self._h, int(i), None, 0, _capi.C.byref(n)), "jslpp_pack_pivot_trace")
+        buf = np.empty(2 * max(n.value, 1), dtype=np.int32)
+        self.lib.check(self.lib.jslpp_pack_pivot_trace(self._h, int(i), _capi.ptr_i32(buf), n.value, _capi.C.byref(n)), "jslpp_pack_pivot_trace")
+        return buf[:2 * n.value].reshape(-1, 2)

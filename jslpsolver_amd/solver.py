@@ -7,7 +7,7 @@ import warnings
 
 from . import _capi
 from .branch_and_cut import branch_and_cut, js_round
-from .engine import Tableau, simplex_many
+from .engine import Tableau, TableauPack, pack_fits, simplex_many
 from .model import Model, js_keys
 
 EPSILON = 2.220446049250313e-16
@@ -61,8 +61,51 @@ def solve_many(models, precision=None, lib=None, device=0):
             t.close()
 
 
-def _prepare(model, precision, lib, device, row_capacity_extra):
-    """Solve's set-up: the parsed model, its engine with the tableau uploaded, the integer count and the service choice"""
+class _PackedLp:
+    """LP i of a solved TableauPack as _solve_on reads a Tableau: the scalars simplex() folds and the RHS read-back"""
+
+    def __init__(self, pack, i):
+        self._pack, self._i = pack, i
+        self.evaluation = float(pack.evaluation[i])
+        self.feasible = bool(pack.feasible[i])
+        self.bounded = bool(pack.bounded[i])
+
+    def read_rhs(self):
+        return self._pack.read_rhs(self._i)
+
+
+def solve_packed(models, precision=None, lib=None, device=0):
+    """[Solve(m, precision, lib=lib, device=device) for m in models], in order, for the workload of many SMALL models: every model without
+    integer variables and without optional objectives whose tableau fits the pack's LDS limit (engine.pack_fits) goes through ONE
+    engine.TableauPack -- one arena, one upload, one launch per kernel build, one read-back, no engine per model.  Every other model
+    (integer variables, optional objectives, a tableau beyond the limit) goes through Solve as it is.  A model Solve rejects raises the
+    same exception before anything is solved."""
+    lib = lib if lib is not None else _capi.load_hip()
+    models = list(models)
+    parsed = [_parse(model, precision, 4) for model in models]
+    packed = []  # positions of the models that go into the pack
+    for k, (m, matrix, _, _) in enumerate(parsed):
+        _priorities, optional_rows = m.optional_objectives()
+        if len(m.integerVariables) == 0 and (optional_rows is None or len(optional_rows) == 0) and pack_fits(*matrix.shape, lib=lib):
+            packed.append(k)
+    results = [None] * len(models)
+    if packed:
+        pack = TableauPack([(parsed[k][1], parsed[k][2], parsed[k][3], parsed[k][0].unrestricted) for k in packed],
+                           precision=[parsed[k][0].precision for k in packed], lib=lib, device=device)
+        try:
+            pack.simplex(check_cycles=[parsed[k][0].checkForCycles for k in packed])
+            for i, k in enumerate(packed):
+                results[k] = _solve_on(_PackedLp(pack, i), parsed[k][0], 0, False, 1, None, False, simplex_done=True)
+        finally:
+            pack.close()
+    for k, model in enumerate(models):
+        if results[k] is None:
+            results[k] = Solve(model, precision, lib=lib, device=device)
+    return results
+
+
+def _parse(model, precision, stacklevel):
+    """what Solve checks and builds before any engine exists: the parsed model and its tableau"""
     global _presolve_warned
     if model is None:
         raise ValueError("Solver requires a model to operate on")  # main.ts:110-112
@@ -74,8 +117,14 @@ def _prepare(model, precision, lib, device, row_capacity_extra):
         _presolve_warned = True
         warnings.warn("jslpsolver_amd.Solve does not run the reference's presolve pre-pass (src/tableau/presolve.ts): on models "
                       "where presolve fixes variables or proves infeasibility the result can differ from solver.Solve(); "
-                      "pass options.presolve = false to compare like with like, or use the reference host + binding", stacklevel=3)
+                      "pass options.presolve = false to compare like with like, or use the reference host + binding", stacklevel=stacklevel)
     matrix, vibr, vibc = m.build_tableau()
+    return m, matrix, vibr, vibc
+
+
+def _prepare(model, precision, lib, device, row_capacity_extra):
+    """Solve's set-up: the parsed model, its engine with the tableau uploaded, the integer count and the service choice"""
+    m, matrix, vibr, vibc = _parse(model, precision, 4)
     n_int = len(m.integerVariables)
     # cut rows: at most one "min" and one "max" cut per integer variable (branch-and-cut.ts:166-179)
     extra = 2 * n_int if row_capacity_extra is None else row_capacity_extra
