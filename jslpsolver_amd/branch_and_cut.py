@@ -71,6 +71,34 @@ class BranchMinHeap:
         return top
 
 
+class TreeCapacity(Exception):
+    """a bound of an instrumented tree walk was reached (CountingHeap, branch_and_cut(max_nodes=...)): `which` names it"""
+
+    def __init__(self, which):
+        Exception.__init__(self, "branch_and_cut: %s reached" % which)
+        self.which = which
+
+
+class CountingHeap(BranchMinHeap):
+    """BranchMinHeap that counts what a device-side tree has to hold (include/jslpt_tree.h): the pushes, the most entries at once and the
+    longest cut list pushed -- and enforces the same capacities, in the kernel's order (the cut list first, then the heap)."""
+
+    def __init__(self, heap_cap=None, cut_rows=None):
+        BranchMinHeap.__init__(self)
+        self.heap_cap, self.cut_rows = heap_cap, cut_rows
+        self.pushes = self.high_water = self.cuts_high_water = 0
+
+    def push(self, relaxed_evaluation, cuts):
+        if self.cut_rows is not None and len(cuts) > self.cut_rows:
+            raise TreeCapacity("cut_rows")
+        if self.heap_cap is not None and len(self.heap) >= self.heap_cap:
+            raise TreeCapacity("heap_cap")
+        BranchMinHeap.push(self, relaxed_evaluation, cuts)
+        self.pushes += 1
+        self.high_water = max(self.high_water, len(self.heap))
+        self.cuts_high_water = max(self.cuts_high_water, len(cuts))
+
+
 class _RowMap:
     """rowByVarIndex as the host tree reads it: variable index -> row of the final tableau (-1 = not basic)"""
     __slots__ = ("row_of",)
@@ -213,7 +241,7 @@ class _NodeEvalBranch:
 EVAL_STATS = {"seconds": 0.0, "batches": 0, "nodes": 0}  # speculative batches since the caller last zeroed it (bench.py)
 
 
-def branch_and_cut(tableau, model, speculate=1, evaluate_batch=None, read_back=None):
+def branch_and_cut(tableau, model, speculate=1, evaluate_batch=None, read_back=None, heap=None, max_nodes=None):
     """branch-and-cut.ts:54-199.  Leaves `tableau` holding the incumbent; returns the iteration count and
     whether an integral node was accepted (tableau.__isIntegral).
 
@@ -231,8 +259,10 @@ def branch_and_cut(tableau, model, speculate=1, evaluate_batch=None, read_back=N
     options.useMIRCuts: a speculative batch evaluates every node WITH its MIR loop (Tableau.applyCutsBatchMIR, include/jslpr_mir.h) and reads
     whole columns back (read_back is ignored); the root, before save(), and the final re-evaluation of the incumbent keep the round-by-round
     loop.  Without speculation JSLP_TREE_MIR=1 makes every node after the root one Tableau.applyCutsMIR call.
+
+    heap: the BranchMinHeap to use (a CountingHeap instruments the walk); max_nodes: raise TreeCapacity before evaluating one node more.
     """
-    branches = BranchMinHeap()
+    branches = heap if heap is not None else BranchMinHeap()
     iterations = 0
     tolerance = model.tolerance or 0
     tolerance_flag = True
@@ -314,6 +344,8 @@ def branch_and_cut(tableau, model, speculate=1, evaluate_batch=None, read_back=N
         relaxed, seq, cuts = branches.pop()
         if relaxed > best_evaluation:
             continue
+        if max_nodes is not None and iterations >= max_nodes:
+            raise TreeCapacity("max_nodes")
         if speculate > 1 and saved:
             if seq not in cache:
                 # this node + the entries the heap would hand out next (best first, LIFO ties); nodes already

@@ -18,6 +18,7 @@
 #include "../../include/jslpf_f32.h"
 #include "../../include/jslpr_mir.h"
 #include "../../include/jslpp_packed.h"
+#include "../../include/jslpt_tree.h"
 #include "jslp_kernels.hip.h"
 #include "jslp_host_mem.h"
 
@@ -3422,12 +3423,16 @@ extern "C" int jslpf_simplex_f32_sweep(jslp_engine* e, const double* precisions,
 // pinned twin (the ONE H2D copy of upload); the result block [states | RHS columns | row maps] has another (the ONE D2H copy of simplex).
 // A pack call holds no jslp_engine and takes no g_many_mu.  The kernels live in jslp_tu_packed.hip (jslp_packed.hip.h).
 #include "jslp_packed.hip.h"
+#include "jslp_tree.hip.h"  // (the layout of a pack with cut rows and a heap per LP, include/jslpt_tree.h)
 #ifdef JSLP_SPLIT_TU
 extern "C" __attribute__((visibility("hidden"))) int jslpp_packed_launch_tu(int threads, unsigned grid, size_t lds, const void* args, void* stream);
 static int packed_launch(int threads, unsigned grid, size_t lds, const PackLaunch& a, hipStream_t s) { return jslpp_packed_launch_tu(threads, grid, lds, &a, s); }
 #else
 static int packed_launch_impl(int threads, unsigned grid, size_t lds, const void* bytes, hipStream_t s);  // (jslp_packed.hip.h, at the end of this file)
-static int packed_launch(int threads, unsigned grid, size_t lds, const PackLaunch& a, hipStream_t s) { return packed_launch_impl(threads, grid, lds, &a, s); }
+static int tree_launch_impl(int threads, unsigned grid, size_t lds, const void* bytes, hipStream_t s);    // (jslp_tree.hip.h, there too)
+static int packed_launch(int threads, unsigned grid, size_t lds, const PackLaunch& a, hipStream_t s) {
+    return a.kind == 1 ? tree_launch_impl(threads, grid, lds, &a, s) : packed_launch_impl(threads, grid, lds, &a, s);
+}
 #endif
 
 struct jslpp_pack {
@@ -3441,6 +3446,14 @@ struct jslpp_pack {
     hipStream_t stream = nullptr;
     hipEvent_t ev_begin = nullptr, ev_end = nullptr;
     std::vector<int32_t> H, W;
+    std::vector<int32_t> RC;        // rows LP i's image, LDS layout and result block are sized for: H[i], or H[i] + cut_rows[i] (jslpt_pack_create)
+    // a pack made by jslpt_pack_create: per LP a heap and a pool of cut lists (jslp_tree.hip.h); tree_ran: the arena holds saved roots
+    bool tree = false, tree_ran = false;
+    int32_t max_nodes = 0;
+    std::vector<int32_t> cut_rows, heap_cap;
+    TreeLp* d_trees = nullptr;
+    char* d_tree_mem = nullptr;
+    size_t tree_mem_bytes = 0;
     std::vector<double> precision, evaluation;
     std::vector<size_t> image_off;  // LP i's image in the arena / the pinned twin
     std::vector<int64_t> offs;      // LP i's RHS column / row map in the result block, n + 1 entries
@@ -3462,12 +3475,16 @@ struct jslpp_pack {
     int32_t* h_rows() const { return reinterpret_cast<int32_t*>(result.h.p + res_rows_off()); }
     size_t res_rhs_off() const { return (sizeof(DevState) * (size_t)n + 255) & ~(size_t)255; }
     size_t res_rows_off() const { return (res_rhs_off() + sizeof(double) * (size_t)offs[n] + 255) & ~(size_t)255; }
-    size_t res_bytes() const { return res_rows_off() + sizeof(int32_t) * (size_t)offs[n]; }
+    size_t res_tree_off() const { return (res_rows_off() + sizeof(int32_t) * (size_t)offs[n] + 255) & ~(size_t)255; }
+    size_t res_bytes() const { return tree ? res_tree_off() + sizeof(TreeRec) * (size_t)n : res_rows_off() + sizeof(int32_t) * (size_t)offs[n]; }
+    TreeRec* h_tree() const { return reinterpret_cast<TreeRec*>(result.h.p + res_tree_off()); }
+    size_t ivars_off(int32_t i) const { return sizeof(DevState) + 8 * (size_t)pk_image_doubles(RC[i], W[i]) + 4 * (size_t)pk_ints(RC[i], W[i]).total; }
 };
 static int pack_fail(int code, const char* what, int32_t i, const char* why) {
     snprintf(g_err, sizeof g_err, "%s: LP %d: %s", what, (int)i, why);
     return code;
 }
+// (H: the rows the image is sized for -- an LP's row capacity)
 static size_t pack_image_bytes(int32_t H, int32_t W) { return sizeof(DevState) + 8 * (size_t)pk_image_doubles(H, W) + 4 * (size_t)pk_ints(H, W).total; }
 static_assert(sizeof(DevState) % 16 == 0, "an LP's matrix follows its DevState at a 16-byte boundary");
 
@@ -3483,6 +3500,10 @@ static void pack_carve(jslpp_pack* p, Carver& cv) {
     p->d_cc = cv.take<int32_t>((size_t)p->n);
     p->d_hist = cv.take<int2>((size_t)p->n * p->hist_cap);
     p->d_trace = cv.take<int2>((size_t)p->n * p->trace_cap);
+    if (p->tree) {
+        p->d_trees = cv.take<TreeLp>((size_t)p->n);
+        p->d_tree_mem = cv.take<char>(p->tree_mem_bytes);
+    }
 }
 // the device side of create(): stream, events, the arena, the pinned twins, the descriptor table and the launch order (built ONCE)
 static int pack_init(jslpp_pack* p, int32_t max_pivots) {
@@ -3506,10 +3527,10 @@ static int pack_init(jslpp_pack* p, int32_t max_pivots) {
     int32_t k = 0;
     for (int pass = 0; pass < 2; pass++)  // the one-wave LPs first, then the 256-thread ones, each in pack order
         for (size_t i = 0; i < n; i++) {
-            const bool wave = (long long)p->H[i] * p->W[i] <= PACK_CELLS_WAVE;
+            const bool wave = (long long)p->RC[i] * p->W[i] <= PACK_CELLS_WAVE;
             if (wave != (pass == 0)) continue;
             order[k++] = (int32_t)i;
-            const size_t lds = (size_t)pk_lds_bytes(p->H[i], p->W[i]);
+            const size_t lds = (size_t)pk_lds_bytes(p->RC[i], p->W[i]);
             if (wave) { p->n_wave += 1; p->lds_wave = std::max(p->lds_wave, lds); }
             else { p->n_block += 1; p->lds_block = std::max(p->lds_block, lds); }
         }
@@ -3522,13 +3543,31 @@ static int pack_init(jslpp_pack* p, int32_t max_pivots) {
         m.out_off = p->offs[i];
         m.H = p->H[i]; m.W = p->W[i];
         m.hist_cap = p->hist_cap; m.trace_cap = p->trace_cap;
-        // the engine's iters_cap formula with row_capacity = height
-        m.iters_cap = max_pivots > 0 ? max_pivots : (int32_t)std::min<long long>(2000000LL + 200LL * ((long long)m.H + m.W), 2000000000LL);
+        // the engine's iters_cap formula with its row_capacity
+        m.iters_cap = max_pivots > 0 ? max_pivots : (int32_t)std::min<long long>(2000000LL + 200LL * ((long long)p->RC[i] + m.W), 2000000000LL);
         // partial pricing parameters (simplex.ts:118-127), as jslp_engine_create derives them
         const int32_t n_columns = m.W - 1;
         m.batch = std::min(500, std::max(50, (int32_t)floor(sqrt((double)n_columns))));
         m.use_partial = n_columns > m.batch * 2;
-        m.pad = 0;
+        m.RC = p->RC[i];
+    }
+    if (p->tree && n) {  // every LP's heap, cut-list pool and free stack, carved out of one block
+        std::vector<TreeLp> trees(n);
+        size_t off = 0;
+        for (size_t i = 0; i < n; i++) {
+            TreeLp& t = trees[i];
+            const size_t slots = (size_t)p->heap_cap[i] + 3;
+            t.heap = reinterpret_cast<TreeEntry*>(p->d_tree_mem + off);
+            off += sizeof(TreeEntry) * (size_t)p->heap_cap[i];
+            t.pool = p->d_tree_mem + off;
+            off += (size_t)tree_slot_bytes(p->cut_rows[i]) * slots;
+            t.free_list = reinterpret_cast<int32_t*>(p->d_tree_mem + off);
+            off += (sizeof(int32_t) * slots + 15) & ~(size_t)15;
+            t.rcoef = js_round(1.0 / p->precision[i]);
+            t.cut_rows = p->cut_rows[i]; t.heap_cap = p->heap_cap[i]; t.max_nodes = p->max_nodes; t.pad = 0;
+        }
+        HIPC(hipMemcpyAsync(p->d_trees, trees.data(), sizeof(TreeLp) * n, hipMemcpyHostToDevice, p->stream));
+        HIPC(hipStreamSynchronize(p->stream));
     }
     if (n) {
         HIPC(hipMemcpyAsync(p->d_lps, lps.data(), sizeof(PackLp) * n, hipMemcpyHostToDevice, p->stream));
@@ -3538,16 +3577,23 @@ static int pack_init(jslpp_pack* p, int32_t max_pivots) {
     return JSLP_OK;
 }
 
-extern "C" int jslpp_pack_create(jslpp_pack** out, int device, int32_t n, const int32_t* height, const int32_t* width, const double* precision,
-                                 int32_t trace_cap, int32_t max_pivots) {
+// jslpp_pack_create and jslpt_pack_create (cut_rows / heap_cap: null for a pack without trees)
+static int pack_create(jslpp_pack** out, int device, int32_t n, const int32_t* height, const int32_t* width, const double* precision,
+                       const int32_t* cut_rows, const int32_t* heap_cap, int32_t trace_cap, int32_t max_pivots, int32_t max_nodes) {
+    const bool tree = cut_rows != nullptr;
     if (!out || n < 0 || (n > 0 && (!height || !width || !precision))) return fail(JSLP_ERR_ARG, "pack_create: bad arguments");
-    if (trace_cap < 0 || max_pivots < 0) return fail(JSLP_ERR_ARG, "pack_create: negative trace_cap or max_pivots");
+    if (trace_cap < 0 || max_pivots < 0 || max_nodes < 0) return fail(JSLP_ERR_ARG, "pack_create: negative trace_cap, max_pivots or max_nodes");
     for (int32_t i = 0; i < n; i++) {
         if (height[i] < 2 || width[i] < 2) return pack_fail(JSLP_ERR_ARG, "pack_create", i, "a tableau has at least 2 rows and 2 columns");
         if (!(precision[i] == precision[i])) return pack_fail(JSLP_ERR_ARG, "pack_create", i, "precision is not a number");
+        if (tree && (cut_rows[i] < 0 || heap_cap[i] < 1 || heap_cap[i] > (1 << 24)))
+            return pack_fail(JSLP_ERR_ARG, "pack_create", i, "cut_rows is at least 0 and heap_cap between 1 and 2^24");
+        const long long rc = (long long)height[i] + (tree ? cut_rows[i] : 0);
         // (cells beyond the limit first: the byte count of an absurd shape must not overflow before it is compared)
-        if ((long long)height[i] * width[i] > JSLPP_LDS_LIMIT / 8 || pk_lds_bytes(height[i], width[i]) > (long long)WGLDS_MAX_BYTES)
-            return pack_fail(JSLP_ERR_UNSUPPORTED, "pack_create", i, "the tableau's LDS image exceeds 64 KiB (jslpp_lds_bytes): solve it through a jslp_engine");
+        if (rc * width[i] > JSLPP_LDS_LIMIT / 8 || pk_lds_bytes((int32_t)rc, width[i]) > (long long)WGLDS_MAX_BYTES)
+            return pack_fail(JSLP_ERR_UNSUPPORTED, "pack_create", i,
+                             tree ? "the tableau's LDS image at its row capacity exceeds 64 KiB (jslpt_lds_bytes): fewer cut rows, or solve it through a jslp_engine"
+                                  : "the tableau's LDS image exceeds 64 KiB (jslpp_lds_bytes): solve it through a jslp_engine");
     }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
@@ -3558,6 +3604,17 @@ extern "C" int jslpp_pack_create(jslpp_pack** out, int device, int32_t n, const 
     p->device = device; p->n = n; p->trace_cap = trace_cap;
     p->hist_cap = max_pivots > 0 ? std::min<int32_t>(max_pivots, JSLPP_HIST_CAP) : JSLPP_HIST_CAP;
     p->H.assign(height, height + n); p->W.assign(width, width + n); p->precision.assign(precision, precision + n);
+    p->RC = p->H;
+    p->tree = tree;
+    if (tree) {
+        p->cut_rows.assign(cut_rows, cut_rows + n); p->heap_cap.assign(heap_cap, heap_cap + n);
+        p->max_nodes = max_nodes > 0 ? max_nodes : JSLPT_MAX_NODES_DEFAULT;
+        for (int32_t i = 0; i < n; i++) {
+            p->RC[i] = height[i] + cut_rows[i];
+            const size_t slots = (size_t)heap_cap[i] + 3;
+            p->tree_mem_bytes += sizeof(TreeEntry) * (size_t)heap_cap[i] + (size_t)tree_slot_bytes(cut_rows[i]) * slots + ((sizeof(int32_t) * slots + 15) & ~(size_t)15);
+        }
+    }
     p->evaluation.assign((size_t)n, 0.0);
     p->is_set.assign((size_t)n, 0);
     p->image_off.resize((size_t)n);
@@ -3565,12 +3622,41 @@ extern "C" int jslpp_pack_create(jslpp_pack** out, int device, int32_t n, const 
     p->offs[0] = 0;
     for (int32_t i = 0; i < n; i++) {
         p->image_off[i] = p->image_bytes;
-        p->image_bytes += pack_image_bytes(height[i], width[i]);
-        p->offs[i + 1] = p->offs[i] + height[i];
+        p->image_bytes += pack_image_bytes(p->RC[i], width[i]) + (tree ? (size_t)tree_ivars_bytes(p->RC[i], width[i]) : 0);
+        p->offs[i + 1] = p->offs[i] + p->RC[i];
     }
     const int rc = pack_init(p, max_pivots);
     if (rc) { jslpp_pack_destroy(p); return rc; }
     *out = p;
+    return JSLP_OK;
+}
+extern "C" int jslpp_pack_create(jslpp_pack** out, int device, int32_t n, const int32_t* height, const int32_t* width, const double* precision,
+                                 int32_t trace_cap, int32_t max_pivots) {
+    return pack_create(out, device, n, height, width, precision, nullptr, nullptr, trace_cap, max_pivots, 0);
+}
+extern "C" int jslpt_pack_create(jslpp_pack** out, int device, int32_t n, const int32_t* height, const int32_t* width, const double* precision,
+                                 const int32_t* cut_rows, const int32_t* heap_cap, int32_t trace_cap, int32_t max_pivots, int32_t max_nodes) {
+    if (n > 0 && (!cut_rows || !heap_cap)) return fail(JSLP_ERR_ARG, "pack_create: bad arguments");
+    static const int32_t none = 0;
+    return pack_create(out, device, n, height, width, precision, cut_rows ? cut_rows : &none, heap_cap ? heap_cap : &none, trace_cap, max_pivots, max_nodes);
+}
+extern "C" int64_t jslpt_lds_bytes(int32_t height, int32_t width, int32_t row_capacity) {
+    if (height < 2 || width < 2 || row_capacity < height) return 0;
+    return (int64_t)pk_lds_bytes(row_capacity, width);
+}
+extern "C" int jslpt_pack_set_integers(jslpp_pack* p, int32_t i, const int32_t* var_indexes, int32_t n) {
+    if (!p) return fail(JSLP_ERR_ARG, "pack_set_integers: null pack");
+    if (!p->tree) return fail(JSLP_ERR_STATE, "pack_set_integers: not a pack made by jslpt_pack_create");
+    if (i < 0 || i >= p->n) return fail(JSLP_ERR_ARG, "pack_set_integers: no such LP");
+    const int32_t n_idx = pk_n_idx(p->RC[i], p->W[i]);
+    if (n < 0 || n > n_idx || (n > 0 && !var_indexes)) return pack_fail(JSLP_ERR_ARG, "pack_set_integers", i, "bad integer variable list");
+    for (int32_t k = 0; k < n; k++)
+        if (var_indexes[k] < 0 || var_indexes[k] >= n_idx) return pack_fail(JSLP_ERR_ARG, "pack_set_integers", i, "integer variable index out of range");
+    int32_t* v = reinterpret_cast<int32_t*>(p->h_image.p + p->image_off[i] + p->ivars_off(i));
+    memset(v, 0, (size_t)tree_ivars_bytes(p->RC[i], p->W[i]));
+    v[0] = n;
+    if (n) memcpy(v + 4, var_indexes, sizeof(int32_t) * (size_t)n);
+    p->uploaded = 0;  // (the device copy is stale until the next upload)
     return JSLP_OK;
 }
 
@@ -3600,7 +3686,7 @@ extern "C" int jslpp_pack_set(jslpp_pack* p, int32_t i, const double* matrix, co
     if (!p || !var_index_by_row || !var_index_by_col) return fail(JSLP_ERR_ARG, "pack_set: null pointer");
     if (i < 0 || i >= p->n) return fail(JSLP_ERR_ARG, "pack_set: no such LP");
     if (n_unrestricted < 0 || (n_unrestricted > 0 && !unrestricted_var_indexes)) return pack_fail(JSLP_ERR_ARG, "pack_set", i, "bad unrestricted list");
-    const int32_t H = p->H[i], W = p->W[i], n_idx = pk_n_idx(H, W);
+    const int32_t H = p->H[i], W = p->W[i], RC = p->RC[i], n_idx = pk_n_idx(RC, W);
     for (int32_t r = 1; r < H; r++)
         if (var_index_by_row[r] < 0 || var_index_by_row[r] >= n_idx) return pack_fail(JSLP_ERR_ARG, "pack_set", i, "row variable index out of range");
     for (int32_t c = 1; c < W; c++)
@@ -3612,8 +3698,8 @@ extern "C" int jslpp_pack_set(jslpp_pack* p, int32_t i, const double* matrix, co
     double* m = reinterpret_cast<double*>(img + sizeof(DevState));
     if (matrix && matrix != m) memcpy(m, matrix, sizeof(double) * (size_t)H * W);
     // the integer block, as k_upload_finish builds an engine's: the maps, their inverses, the unrestricted flags
-    const PackInts io = pk_ints(H, W);
-    int32_t* ints = reinterpret_cast<int32_t*>(img + sizeof(DevState) + 8 * (size_t)pk_image_doubles(H, W));
+    const PackInts io = pk_ints(RC, W);
+    int32_t* ints = reinterpret_cast<int32_t*>(img + sizeof(DevState) + 8 * (size_t)pk_image_doubles(RC, W));
     memset(ints, 0, 4 * (size_t)io.total);
     int32_t *vibr = ints + io.vibr, *vibc = ints + io.vibc, *rbv = ints + io.rbv, *cbv = ints + io.cbv;
     uint8_t* unr = reinterpret_cast<uint8_t*>(ints + io.unr);
@@ -3647,12 +3733,14 @@ extern "C" int jslpp_pack_upload(jslpp_pack* p) {
     if (p->image_bytes) HIPC(hipMemcpyAsync(p->d_image, p->h_image.p, p->image_bytes, hipMemcpyHostToDevice, p->stream));
     HIPC(hipStreamSynchronize(p->stream));
     p->uploaded = 1;
+    p->tree_ran = false;
     return JSLP_OK;
 }
 
 extern "C" int jslpp_pack_simplex(jslpp_pack* p, const int32_t* check_cycles, jslp_simplex_result* out, int32_t* status, double* device_ms) {
     if (!p || (p->n > 0 && !out)) return fail(JSLP_ERR_ARG, "pack_simplex: bad arguments");
     if (!p->uploaded) return fail(JSLP_ERR_STATE, "pack_simplex before upload");
+    if (p->tree_ran) return fail(JSLP_ERR_STATE, "pack_simplex: after jslpt_pack_branch_and_cut the arena holds the saved roots; upload first");
     if (device_ms) *device_ms = 0;
     p->launches = 0;
     const int32_t n = p->n;
@@ -3736,13 +3824,14 @@ extern "C" int jslpp_pack_download(jslpp_pack* p, int32_t i, double* matrix, int
     if (!p) return fail(JSLP_ERR_ARG, "pack_download: null pack");
     if (i < 0 || i >= p->n) return fail(JSLP_ERR_ARG, "pack_download: no such LP");
     if (!p->uploaded) return fail(JSLP_ERR_STATE, "pack_download before upload");
+    if (p->tree_ran) return fail(JSLP_ERR_STATE, "pack_download: after jslpt_pack_branch_and_cut the arena holds the saved roots, not the final tableaus");
     HIPC(hipSetDevice(p->device));
     HIPC(hipStreamSynchronize(p->stream));
-    const int32_t H = p->H[i], W = p->W[i], n_idx = pk_n_idx(H, W);
-    std::vector<char> img(pack_image_bytes(H, W));
+    const int32_t H = p->H[i], W = p->W[i], RC = p->RC[i], n_idx = pk_n_idx(RC, W);
+    std::vector<char> img(pack_image_bytes(RC, W));
     HIPC(hipMemcpy(img.data(), p->d_image + p->image_off[i], img.size(), hipMemcpyDeviceToHost));
-    const PackInts io = pk_ints(H, W);
-    const int32_t* ints = reinterpret_cast<const int32_t*>(img.data() + sizeof(DevState) + 8 * (size_t)pk_image_doubles(H, W));
+    const PackInts io = pk_ints(RC, W);
+    const int32_t* ints = reinterpret_cast<const int32_t*>(img.data() + sizeof(DevState) + 8 * (size_t)pk_image_doubles(RC, W));
     if (matrix) memcpy(matrix, img.data() + sizeof(DevState), sizeof(double) * (size_t)H * W);
     if (var_index_by_row) memcpy(var_index_by_row, ints + io.vibr, sizeof(int32_t) * (size_t)H);
     if (var_index_by_col) memcpy(var_index_by_col, ints + io.vibc, sizeof(int32_t) * (size_t)W);
@@ -3769,8 +3858,116 @@ extern "C" int jslpp_pack_pivot_trace(jslpp_pack* p, int32_t i, int32_t* row_col
     return JSLP_OK;
 }
 
+// ---- the trees of a pack, each walked by its LP's workgroup (include/jslpt_tree.h) ---------------------------------------------------
+static int tree_error(const TreeRec& r) {
+    switch (r.err) {
+        case TREE_OK: return JSLP_OK;
+        case TREE_ERR_NODES: return fail(JSLP_ERR_CAPACITY, "branch_and_cut: max_nodes reached before the tree was done");
+        case TREE_ERR_HEAP: return fail(JSLP_ERR_CAPACITY, "branch_and_cut: heap_cap reached (the heap is full)");
+        case TREE_ERR_CUTS: return fail(JSLP_ERR_CAPACITY, "branch_and_cut: cut_rows reached (a node's cut list is longer)");
+        case TREE_ERR_BRANCH: return fail(JSLP_ERR_ARG, "branch_and_cut: a node is not integral and has no fractional variable (negative precision?)");
+    }
+    return fail(JSLP_ERR_DEVICE, "unknown tree error code");
+}
+
+extern "C" int jslpt_pack_branch_and_cut(jslpp_pack* p, const int32_t* check_cycles, jslp_simplex_result* out, jslpt_tree_result* tree_out,
+                                         int32_t* status, double* device_ms) {
+    if (!p || (p->n > 0 && !out)) return fail(JSLP_ERR_ARG, "pack_branch_and_cut: bad arguments");
+    if (!p->tree) return fail(JSLP_ERR_STATE, "pack_branch_and_cut: not a pack made by jslpt_pack_create");
+    if (!p->uploaded) return fail(JSLP_ERR_STATE, "pack_branch_and_cut before upload");
+    if (p->tree_ran) return fail(JSLP_ERR_STATE, "pack_branch_and_cut: the arena holds the saved roots of an earlier call; upload first");
+    if (device_ms) *device_ms = 0;
+    p->launches = 0;
+    const int32_t n = p->n;
+    if (n == 0) return JSLP_OK;
+    HIPC(hipSetDevice(p->device));
+    hipStream_t s = p->stream;
+    PackLaunch a{};
+    a.kind = 1;
+    a.lps = p->d_lps;
+    a.trees = p->d_trees;
+    a.cc = nullptr;
+    a.cc_all = check_cycles ? (check_cycles[0] != 0) : 1;
+    if (check_cycles) {
+        bool mixed = false;
+        for (int32_t i = 1; i < n && !mixed; i++) mixed = (check_cycles[i] != 0) != (a.cc_all != 0);
+        if (mixed) {
+            int32_t* h = p->h_cc.as<int32_t>();
+            for (int32_t i = 0; i < n; i++) h[i] = check_cycles[i] != 0;
+            HIPC(hipMemcpyAsync(p->d_cc, h, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, s));
+            a.cc = p->d_cc;
+        }
+    }
+    a.states = p->result.d.p;
+    a.rhs = reinterpret_cast<double*>(p->result.d.p + p->res_rhs_off());
+    a.rows = reinterpret_cast<int32_t*>(p->result.d.p + p->res_rows_off());
+    a.tree_out = p->result.d.p + p->res_tree_off();
+    const bool dbg = debug_launch_on();
+    p->tree_ran = true;
+    HIPC(hipEventRecord(p->ev_begin, s));
+    for (int build = 0; build < 2; build++) {
+        const int32_t cnt = build ? p->n_block : p->n_wave;
+        if (!cnt) continue;
+        const int threads = build ? 256 : 64;
+        const size_t lds = build ? p->lds_block : p->lds_wave;
+        a.order = p->d_order + (build ? p->n_wave : 0);
+        (void)packed_launch(threads, (unsigned)cnt, lds, a, s);
+        HIPC(hipGetLastError());
+        p->launches += 1;
+        if (dbg) fprintf(stderr, "[jslp] launch k_tree_packed<%d> n %d lds %zu\n", threads, (int)cnt, lds);
+    }
+    HIPC(hipEventRecord(p->ev_end, s));
+    HIPC(hipMemcpyAsync(p->result.h.p, p->result.d.p, p->res_bytes(), hipMemcpyDeviceToHost, s));
+    HIPC(hipStreamSynchronize(s));
+    float ms = 0;
+    if (device_ms && hipEventElapsedTime(&ms, p->ev_begin, p->ev_end) == hipSuccess) *device_ms = ms;
+    if (status) for (int32_t i = 0; i < n; i++) status[i] = JSLP_OK;
+    int32_t first_bad = -1; int first_rc = JSLP_OK; char first_msg[sizeof g_err];
+    const DevState* sts = p->h_states();
+    const TreeRec* recs = p->h_tree();
+    for (int32_t i = 0; i < n; i++) {
+        const DevState& st = sts[i];
+        const TreeRec& r = recs[i];
+        int rc = state_error(st);
+        if (!rc) rc = tree_error(r);
+        if (!rc) {
+            decode_state(st, p->precision[i], r.evaluation, &out[i], nullptr);
+            out[i].evaluation = r.evaluation;  // folded on the device, node after node (a node without an optimum keeps the one before)
+            p->evaluation[i] = r.evaluation;
+            if (st.cycle_phase && st.hist_n > 0) {
+                std::vector<int2> h(st.hist_n);
+                if (hipMemcpy(h.data(), p->d_hist + (size_t)i * p->hist_cap, sizeof(int2) * st.hist_n, hipMemcpyDeviceToHost) != hipSuccess)
+                    rc = fail(JSLP_ERR_DEVICE, "cycle history read-back failed");
+                else
+                    cycle_message(h, &out[i].cycle_start, &out[i].cycle_length);
+            }
+            if (!rc && tree_out) {
+                jslpt_tree_result& o = tree_out[i];
+                o.iterations = r.iterations; o.is_integral = r.is_integral; o.final_height = r.final_height;
+                o.nodes_pushed = r.nodes_pushed; o.heap_high_water = r.heap_high_water; o.cuts_high_water = r.cuts_high_water;
+            }
+        }
+        if (rc) {
+            if (status) status[i] = rc;
+            if (first_bad < 0) { first_bad = i; first_rc = rc; snprintf(first_msg, sizeof first_msg, "%s", g_err); }
+        }
+    }
+    if (first_bad >= 0) {
+        snprintf(g_err, sizeof g_err, "pack_branch_and_cut: LP %d: %s", (int)first_bad, first_msg);
+        return first_rc;
+    }
+    return JSLP_OK;
+}
+
+extern "C" int jslpt_pack_read_rhs(jslpp_pack* p, const double** rhs, const int32_t** var_index_by_row, const int64_t** offsets) {
+    if (!p) return fail(JSLP_ERR_ARG, "pack_read_rhs: null pack");
+    if (!p->tree) return fail(JSLP_ERR_STATE, "pack_read_rhs: not a pack made by jslpt_pack_create");
+    return jslpp_pack_read_rhs(p, rhs, var_index_by_row, offsets);
+}
+
 #if !defined(JSLP_SPLIT_TU)
 #include "jslp_mir_kernels.hip.h"  // single-unit build: the MIR kernels behind everything else (the product: jslp_tu_mir.hip)
 #define JSLP_PACKED_KERNELS 1
 #include "jslp_packed.hip.h"       // ... and the pack's two (the product: jslp_tu_packed.hip)
+#include "jslp_tree.hip.h"         // ... with the tree kernels behind them
 #endif

@@ -18,7 +18,8 @@
 //   [DevState | matrix H x W doubles, reference layout (stride W), padded to an even count | integer block]
 // Integer block, the same in the image and in LDS, every piece padded to 16 bytes so that the block moves as a run of 16-byte words:
 //   [varIndexByRow H | varIndexByCol W | rowByVarIndex n_idx | colByVarIndex n_idx | unrestricted flags, n_idx bytes]
-// with n_idx = W + 2 H + 2, as jslp_engine_create(height, width, row_capacity = height) sizes the maps.
+// with n_idx = W + 2 H + 2, as jslp_engine_create(height, width, row_capacity = height) sizes the maps.  In a pack with cut rows
+// (include/jslpt_tree.h) every H of this layout is the LP's row capacity RC, of which the first `height` rows hold the tableau.
 // LDS image: [tableau H x S doubles | pivot column H doubles | (pad to 16 bytes) | integer block], S = the row stride padded to an ODD
 // number of doubles: the pivot-column gather has lane r reading A[r][c], and with an odd stride 32 consecutive rows fall into 32
 // distinct pairs of the 64 four-byte banks -- conflict-free for ds_read_b64 (an even stride of 2^k doubles would be 2^k-way).
@@ -52,17 +53,19 @@ struct PackLp {
     int32_t hist_cap, trace_cap;
     int32_t iters_cap;
     int32_t batch, use_partial;  // partial-pricing parameters (simplex.ts:118-127)
-    int32_t pad;
+    int32_t RC;         // rows the image and the LDS layout are sized for: H, or H + cut rows in a pack made by jslpt_pack_create
 };
 // arguments of one launch, travelling as bytes between the units (the same struct in every unit)
 struct PackLaunch {
     const PackLp* lps;
     const int32_t* order;  // blockIdx.x -> LP index (the LPs of this build)
     const int32_t* cc;     // per-LP checkForCycles, or nullptr: cc_all for every LP
-    int32_t cc_all, pad;
+    int32_t cc_all, kind;  // kind 0: k_simplex_packed, 1: k_tree_packed (jslp_tree.hip.h)
     void* states;          // result block: DevState per LP (LP order) ...
     double* rhs;           // ... the RHS columns one after the other ...
     int32_t* rows;         // ... and the row maps
+    const void* trees;     // kind 1: the TreeLp table ...
+    void* tree_out;        // ... and the TreeRec per LP
 };
 #endif  // JSLP_PACKED_LAYOUT
 
@@ -90,12 +93,173 @@ __device__ __forceinline__ Cand pk_reduce(Cand x, Better better, Smem& sm) {
     }
 }
 
-// simplex() of LP order[blockIdx.x] of a pack: load the LP into LDS, run phase 1 / phase 2 / pivot / checkForCycles there, write the
-// tableau, the maps, the state, the RHS column and the row map back once.  THREADS = 64: one wave -- the block barriers below degenerate
-// (the compiler drops s_barrier for a one-wave workgroup) and every reduction is wave_reduce alone; THREADS = 256: four waves.
-// The loop restates select_step / prepare_pivot / update_rows_wg (jslp_core.inc.h) over LDS with its scalars in registers, as
-// simplex_wg_lds does over global memory; arithmetic, orders and tie-breaks are the core's own functions.  Every loop is bounded by the
-// pivot cap; the kernel waits on nothing outside its workgroup.
+// what one simplex() leaves in registers.  outcome: 0 running, 1 optimal, 2 unbounded, 3 cycle, 4 infeasible, 5 iteration cap, 6 history full
+struct PkRun { int phase, it1, it2, hist_n, entered2, outcome, unbounded_col; };
+
+// simplex() of the H x W tableau that LDS holds (row stride S, its maps and flags next to it), for k_tree_packed (jslp_tree.hip.h), which
+// runs it once per node: phase 1 / phase 2 / pivot / checkForCycles.  The loop restates select_step / prepare_pivot / update_rows_wg
+// (jslp_core.inc.h) over LDS with its scalars in registers, as simplex_wg_lds does over global memory; arithmetic, orders and tie-breaks
+// are the core's own functions.  Bounded by iters_left.  The caller puts a barrier in front (LDS complete) and one behind.
+// A SECOND COPY of k_simplex_packed's loop below, line for line, on purpose: with the kernel calling this function its 256-thread build
+// took 59 VGPRs instead of 57 (profiles/packed_tree_kernel_resources.md), so the kernel keeps its own text.  Change both together.
+template <int THREADS>
+__device__ __forceinline__ PkRun pk_simplex(double* A, double* pcol, const int H, const int W, const int S, int32_t* vibr, int32_t* vibc, int32_t* rbv,
+                                            int32_t* cbv, const uint8_t* unr, const double precision, const int check_cycles, const PackLp& m, int2* ghist,
+                                            int2* gtrace, PackSmem& sm, int& iters_left, long long& trace_n) {
+    const int tid = threadIdx.x;
+    // the row update's thread grid: CW columns (a power of two covering the width, at most the workgroup) x RP rows at a time
+    int cshift = 0;
+    while ((1 << cshift) < W && (1 << cshift) < THREADS) cshift++;
+    const int CW = 1 << cshift, RP = THREADS >> cshift, col0 = tid & (CW - 1), rsub = tid >> cshift;
+
+    int phase = 1, it1 = 0, it2 = 0, hist_n = 0, entered2 = 0;
+    int outcome = 0, unbounded_col = 0;
+    while (outcome == 0) {
+        if (iters_left <= 0) { outcome = 5; break; }
+        int pr = 0, pc = 0;
+        if (phase == 1) {
+            // leaving row: most negative RHS below -precision, first index on ties (simplex.ts:39-49)
+            Cand best; best.v = -precision; best.i = 0; best.b = 0;
+            for (int r = 1 + tid; r < H; r += THREADS) {
+                const double v = A[r * S];
+                if (v < best.v) { best.v = v; best.i = r; }
+            }
+            best = pk_reduce<THREADS>(best, MinFirst(), sm.g);
+            if (best.i == 0) {  // :51-54 feasible: phase 2 starts in this same iteration with a fresh history (:102)
+                phase = 2; entered2 = 1; hist_n = 0;
+            } else {
+                pr = best.i;
+                // entering column: max -cost/coef over unrestricted or coef < -precision (simplex.ts:56-71)
+                const double* row = A + pr * S;
+                Cand q; q.v = -INFINITY; q.i = 0; q.b = 0;
+                for (int col = 1 + tid; col < W; col += THREADS) {
+                    const double coef = row[col];
+                    const bool un = unr[vibc[col]] != 0;
+                    if (un || coef < -precision) {
+                        const double quo = -A[col] / coef;
+                        if (q.v < quo) { q.v = quo; q.i = col; }
+                    }
+                }
+                q = pk_reduce<THREADS>(q, MaxFirst(), sm.g);
+                if (q.i == 0) { outcome = 4; break; }  // :73-76 infeasible
+                pc = q.i;
+            }
+        }
+        if (phase == 2) {
+            // Dantzig pricing with the reference's batch rule (simplex.ts:118-219): the first batch holding a candidate
+            // wins; inside it the largest value, first index on ties
+            Cand e; e.v = precision; e.i = 0; e.b = 0;
+            for (int col = 1 + tid; col < W; col += THREADS) {
+                const double rc = A[col];
+                const bool un = unr[vibc[col]] != 0;
+                const int b = m.use_partial ? (col - 1) / m.batch : 0;
+                const double val = (un && rc < 0) ? -rc : rc;
+                if (val > precision) {
+                    Cand cand; cand.v = val; cand.i = col; cand.b = b;
+                    const bool take = PriceFirst()(cand, e);
+                    e.v = take ? cand.v : e.v;
+                    e.i = take ? cand.i : e.i;
+                    e.b = take ? cand.b : e.b;
+                }
+            }
+            e = pk_reduce<THREADS>(e, PriceFirst(), sm.g);
+            if (e.i == 0) { outcome = 1; break; }  // optimal (simplex.ts:265-269)
+            pc = e.i;
+            int neg_flag;
+            {   // isReducedCostNegative of the winner
+                const double rc = A[pc];
+                neg_flag = (unr[vibc[pc]] != 0 && rc < 0) ? 1 : 0;
+            }
+            // ratio test (simplex.ts:271-296) in its order-free form: the first row passing the degenerate test wins
+            // outright, otherwise the first-index argmin of the accepted quotients.  One reduction: an accepted quotient is above
+            // precision > 0, so a degenerate row enters as -Infinity and MinFirst breaks the ties among them by the first index.
+            Cand mq; mq.v = INFINITY; mq.i = 0; mq.b = 0;
+            int rdeg = 0;
+            for (int r = 1 + tid; r < H; r += THREADS) {
+                const double colv = A[r * S + pc];
+                const double rhs = A[r * S];
+                if (-precision < colv && colv < precision) continue;
+                if (colv > 0 && precision > rhs && rhs > -precision) {
+                    if (rdeg == 0) rdeg = r;  // (my rows ascend)
+                    continue;
+                }
+                const double quo = neg_flag ? -rhs / colv : rhs / colv;
+                if (quo > precision && mq.v > quo) { mq.v = quo; mq.i = r; }
+            }
+            if (rdeg != 0) { mq.v = -INFINITY; mq.i = rdeg; }
+            mq = pk_reduce<THREADS>(mq, MinFirst(), sm.g);
+            if (mq.i == 0) { outcome = 2; unbounded_col = pc; break; }  // unbounded (simplex.ts:298-303)
+            pr = mq.i;
+        }
+        const int leaving = vibr[pr], entering = vibc[pc];
+        // cycle check (simplex.ts:78-93 / 305-320): append first, test, stop WITHOUT pivoting on a hit.  The host rebuilds the
+        // reference's [start, length] message from the global copy.
+        if (check_cycles) {
+            if (hist_n >= m.hist_cap) { outcome = 6; break; }
+            if (tid == 0) {
+                const int2 pair = make_int2(leaving, entering);
+                ghist[hist_n] = pair;
+                if (hist_n < PK_HIST) sm.hist[hist_n] = pair;
+            }
+            __syncthreads();
+            hist_n += 1;
+            const bool cycle = hist_n <= PK_HIST ? suffix_is_square(sm.hist, hist_n, sm.g) : suffix_is_square(ghist, hist_n, sm.g);
+            if (cycle) { outcome = 3; break; }
+        }
+        // ---- pivot(pr, pc) (simplex.ts:330-391) ------------------------------------------------------------------------------------
+        const double quot = A[pr * S + pc];  // :335
+        int any = 0;
+        for (int r = tid; r < H; r += THREADS) {  // the pivot column: lane r reads A[r][pc], conflict-free with the odd stride
+            const double k = A[r * S + pc];
+            pcol[r] = k;
+            any |= (r != pr && nonzero16(k)) ? 1 : 0;
+        }
+        // any row that will execute the inner loop of :367-391 lazily zeroes the tiny pivot-row entries
+        const int anyrow = __syncthreads_or(any);  // (also orders the quot read above against the row write below)
+        double* prow = A + pr * S;
+        for (int col = tid; col < W; col += THREADS) {
+            const double val = prow[col];
+            const bool innz = nonzero16(val);                          // :356
+            double v = innz ? val / quot : 0.0;                        // :357 / :361  (IEEE division)
+            if (col == pc) v = 1.0 / quot;                             // :364
+            if (innz && anyrow && !nonzero16(v) && v != 0.0) v = 0.0;  // :381-383
+            prow[col] = v;
+        }
+        if (tid == 0) {  // :339-349
+            vibr[pr] = entering;
+            vibc[pc] = leaving;
+            rbv[entering] = pr;
+            rbv[leaving] = -1;
+            cbv[entering] = -1;
+            cbv[leaving] = pc;
+            if (trace_n < m.trace_cap) gtrace[trace_n] = make_int2(pr, pc);
+        }
+        trace_n += 1;
+        if (phase == 1) it1 += 1; else it2 += 1;
+        iters_left -= 1;
+        __syncthreads();  // the normalised pivot row and the pivot column are complete
+        for (int r = rsub; r < H; r += RP) {
+            const double k = pcol[r];
+            if (r == pr || !nonzero16(k)) continue;  // the row gate, :370-375
+            double* row = A + r * S;
+            for (int col = col0; col < W; col += CW) {
+                if (col == pc) { row[col] = -k / quot; continue; }  // :387 overwrites whatever the loop did to column pc
+                const double p = prow[col];
+                if (nonzero16(p)) row[col] = eliminate(row[col], k, p);  // :376-386, both roundings
+            }
+        }
+        __syncthreads();
+    }
+    PkRun o;
+    o.phase = phase; o.it1 = it1; o.it2 = it2; o.hist_n = hist_n; o.entered2 = entered2; o.outcome = outcome; o.unbounded_col = unbounded_col;
+    return o;
+}
+
+// simplex() of LP order[blockIdx.x] of a pack: load the LP into LDS, run phase 1 / phase 2 / pivot / checkForCycles there (the loop of
+// pk_simplex above, in a copy of the kernel's own), write the tableau, the maps, the state, the RHS column and the row map back once.  THREADS = 64: one wave -- the block barriers degenerate (the compiler drops s_barrier for a
+// one-wave workgroup) and every reduction is wave_reduce alone; THREADS = 256: four waves.  Every loop is bounded by the pivot cap; the
+// kernel waits on nothing outside its workgroup.  The image and the LDS layout are those of RC rows (RC = H but in a pack with cut rows,
+// include/jslpt_tree.h), of which H hold the tableau.
 template <int THREADS>
 __global__ void __launch_bounds__(THREADS) k_simplex_packed(const PackLp* __restrict__ lps, const int32_t* __restrict__ order, const int32_t* __restrict__ cc,
                                                             int cc_all, DevState* __restrict__ out_states, double* __restrict__ out_rhs,
@@ -105,14 +269,14 @@ __global__ void __launch_bounds__(THREADS) k_simplex_packed(const PackLp* __rest
     const int idx = order[blockIdx.x];
     const PackLp m = lps[idx];  // one uniform copy at entry
     const int tid = threadIdx.x;
-    const int H = m.H, W = m.W, S = pk_stride(W);
-    const PackInts io = pk_ints(H, W);
+    const int H = m.H, W = m.W, RC = m.RC, S = pk_stride(W);
+    const PackInts io = pk_ints(RC, W);
     const double precision = m.precision;
     const int check_cycles = cc ? cc[idx] : cc_all;
     // LDS, indexed from the extern base: ds_read / ds_write, never flat
     double* A = pk_lds;
-    double* pcol = pk_lds + H * S;
-    int32_t* ints = reinterpret_cast<int32_t*>(pk_lds + pk_lds_doubles(H, W));
+    double* pcol = pk_lds + RC * S;
+    int32_t* ints = reinterpret_cast<int32_t*>(pk_lds + pk_lds_doubles(RC, W));
     int32_t* vibr = ints + io.vibr;
     int32_t* vibc = ints + io.vibc;
     int32_t* rbv = ints + io.rbv;
@@ -122,7 +286,7 @@ __global__ void __launch_bounds__(THREADS) k_simplex_packed(const PackLp* __rest
     char* image = many_global(m.image);
     DevState* st = reinterpret_cast<DevState*>(image);
     double2* gA = reinterpret_cast<double2*>(image + sizeof(DevState));
-    int4* gI = reinterpret_cast<int4*>(image + sizeof(DevState) + 8 * pk_image_doubles(H, W));
+    int4* gI = reinterpret_cast<int4*>(image + sizeof(DevState) + 8 * pk_image_doubles(RC, W));
     int2* ghist = many_global(m.hist);
     int2* gtrace = many_global(m.trace);
 

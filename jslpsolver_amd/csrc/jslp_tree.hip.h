@@ -1,0 +1,396 @@
+// jslp_tree.hip.h -- the branch-and-bound tree of every LP of a pack, walked inside ONE launch (include/jslpt_tree.h): one workgroup per
+// LP holds the tableau at its ROW CAPACITY in LDS (jslp_packed.hip.h's layout with RC rows) and runs the default service's loop
+// (branch-and-cut.ts:54-199) itself: pop, prune, restore + addCutConstraints + simplex, isIntegral / getMostFractionalVar, the two pushes.
+//
+// Two parts like jslp_packed.hip.h (included behind it, once per unit): the layout (always) and the kernels (-DJSLP_PACKED_KERNELS).
+//
+// Memory of one LP:
+//   LDS     the tableau RC x S doubles, the pivot column, the integer block sized for RC rows -- jslpt_lds_bytes;
+//   image   [DevState | matrix | integer block | n_int, the integer variables' indexes]: the upload, and from iteration 1 on the SAVED
+//           ROOT (written once, read by every later node: an L2-resident restore; the tableau is never written back);
+//   heap    heap_cap entries of 16 bytes {relaxedEvaluation, seq, slot} -- min-heap.ts as it is, executed by thread 0;
+//   pool    heap_cap + 3 cut lists of cut_rows cuts (16 bytes each) behind a 16-byte header: one per heap entry, the node under
+//           evaluation, the incumbent, and the list being built; a free stack hands the slots out.
+// Every scalar of the tree (the incumbent's evaluation, the counters, the heap size) is computed by every thread alike and lives in
+// registers; thread 0 alone touches the heap and the pool and publishes what the others need through LDS.
+#ifndef JSLP_TREE_LAYOUT
+#define JSLP_TREE_LAYOUT
+
+struct TreeCut { double value; int32_t var; int32_t type; };    // type 0 = "min" (x >= value), 1 = "max" (x <= value), as Cuts::type
+struct TreeEntry { double key; int32_t seq; int32_t slot; };    // slot -1: the empty cut list of the root
+struct TreeLp {
+    TreeEntry* heap;
+    char* pool;
+    int32_t* free_list;
+    double rcoef;  // Math.round(1 / precision), computed on the host like decode_state's
+    int32_t cut_rows, heap_cap, max_nodes, pad;
+};
+enum { TREE_OK = 0, TREE_ERR_NODES = 1, TREE_ERR_HEAP = 2, TREE_ERR_CUTS = 3, TREE_ERR_BRANCH = 4 };
+struct TreeRec {  // what the kernel reports per LP next to its DevState
+    double evaluation;
+    int32_t iterations, is_integral, final_height, nodes_pushed, heap_high_water, cuts_high_water, err, pad;
+};
+__host__ __device__ __forceinline__ long long tree_slot_bytes(int32_t cut_rows) { return 16LL * (1 + cut_rows); }
+__host__ __device__ __forceinline__ long long tree_ivars_bytes(int32_t RC, int32_t W) { return 16 + 4LL * pk_pad4(pk_n_idx(RC, W)); }
+#endif  // JSLP_TREE_LAYOUT
+
+#if defined(JSLP_PACKED_KERNELS) && !defined(JSLP_TREE_KERNELS_DONE)
+#define JSLP_TREE_KERNELS_DONE
+
+struct TreeSmem {
+    PackSmem ps;
+    double key;                // the popped entry's relaxedEvaluation
+    int32_t slot, code, n_high, n_low;
+};
+
+// min-heap.ts:43-49
+__device__ __forceinline__ bool tree_before(const TreeEntry& a, const TreeEntry& b) {
+    if (a.key != b.key) return a.key < b.key;
+    return a.seq > b.seq;
+}
+// min-heap.ts push (thread 0): the bubble-up loop with a hole
+__device__ __forceinline__ void tree_push(TreeEntry* h, int n, TreeEntry e) {
+    int i = n;
+    while (i > 0) {
+        const int p = (i - 1) >> 1;
+        const TreeEntry pe = h[p];
+        if (!tree_before(e, pe)) break;
+        h[i] = pe;
+        i = p;
+    }
+    h[i] = e;
+}
+// min-heap.ts pop (thread 0): n = entries before the pop
+__device__ __forceinline__ TreeEntry tree_pop(TreeEntry* h, int n) {
+    const TreeEntry top = h[0];
+    const TreeEntry last = h[n - 1];
+    n -= 1;
+    if (n == 0) return top;
+    int i = 0;
+    const int half = n >> 1;
+    while (i < half) {
+        int c = 2 * i + 1;
+        TreeEntry ce = h[c];
+        if (c + 1 < n) {
+            const TreeEntry re = h[c + 1];
+            if (tree_before(re, ce)) { c += 1; ce = re; }
+        }
+        if (!tree_before(ce, last)) break;
+        h[i] = ce;
+        i = c;
+    }
+    h[i] = last;
+    return top;
+}
+// Math.round (ties toward +Infinity; the subtraction is exact), as branch_acc_add's
+__device__ __forceinline__ double tree_round(double x) {
+    if (!(fabs(x) < INFINITY)) return x;
+    const double f = floor(x);
+    return (x - f >= 0.5) ? f + 1.0 : f;
+}
+
+// Tableau.solve() of LP order[blockIdx.x] under the default branch-and-cut service.  THREADS as k_simplex_packed.  Bounded: every
+// simplex by the pivot cap, the node loop by max_nodes evaluations and by the heap (each iteration pops one entry; pushes are
+// bounded by heap_cap); the kernel waits on nothing outside its workgroup.
+template <int THREADS>
+__global__ void __launch_bounds__(THREADS) k_tree_packed(const PackLp* __restrict__ lps, const TreeLp* __restrict__ trees, const int32_t* __restrict__ order,
+                                                         const int32_t* __restrict__ cc, int cc_all, DevState* __restrict__ out_states,
+                                                         double* __restrict__ out_rhs, int32_t* __restrict__ out_rows, TreeRec* __restrict__ out_tree) {
+    extern __shared__ __attribute__((aligned(16))) double pk_lds[];
+    __shared__ TreeSmem sm;
+    const int idx = order[blockIdx.x];
+    const PackLp m = lps[idx];
+    const TreeLp t = trees[idx];
+    const int tid = threadIdx.x;
+    const int H0 = m.H, W = m.W, RC = m.RC, S = pk_stride(W);
+    const PackInts io = pk_ints(RC, W);
+    const double precision = m.precision;
+    const int check_cycles = cc ? cc[idx] : cc_all;
+    double* A = pk_lds;
+    double* pcol = pk_lds + RC * S;
+    int32_t* ints = reinterpret_cast<int32_t*>(pk_lds + pk_lds_doubles(RC, W));
+    int32_t* vibr = ints + io.vibr;
+    int32_t* vibc = ints + io.vibc;
+    int32_t* rbv = ints + io.rbv;
+    int32_t* cbv = ints + io.cbv;
+    const uint8_t* unr = reinterpret_cast<const uint8_t*>(ints + io.unr);
+    char* image = many_global(m.image);
+    DevState* st = reinterpret_cast<DevState*>(image);
+    double2* gA = reinterpret_cast<double2*>(image + sizeof(DevState));
+    int4* gI = reinterpret_cast<int4*>(image + sizeof(DevState) + 8 * pk_image_doubles(RC, W));
+    const int32_t* gV = reinterpret_cast<const int32_t*>(image + sizeof(DevState) + 8 * pk_image_doubles(RC, W) + 4LL * io.total);
+    const int n_int = gV[0];
+    const int32_t* ivars = gV + 4;
+    int2* ghist = many_global(m.hist);
+    int2* gtrace = many_global(m.trace);
+    TreeEntry* heap = many_global(t.heap);
+    char* pool = many_global(t.pool);
+    int32_t* free_list = many_global(t.free_list);
+    const long long slot_bytes = tree_slot_bytes(t.cut_rows);
+
+    // the saved root's rows and the whole integer block: image <-> LDS, 16-byte words (stride W <-> stride S)
+    const int cells = H0 * W, pairs = (cells + 1) >> 1, words = io.total >> 2;
+    auto restore = [&]() {
+        for (int q = tid; q < pairs; q += THREADS) {
+            const double2 v = gA[q];
+            const int e = 2 * q, r = e / W, c = e - r * W;
+            A[r * S + c] = v.x;
+            if (e + 1 < cells) {
+                const bool wrap = c + 1 == W;
+                A[(wrap ? r + 1 : r) * S + (wrap ? 0 : c + 1)] = v.y;
+            }
+        }
+        for (int q = tid; q < words; q += THREADS) reinterpret_cast<int4*>(ints)[q] = gI[q];
+    };
+    auto save = [&]() {
+        for (int q = tid; q < pairs; q += THREADS) {
+            const int e = 2 * q, r = e / W, c = e - r * W;
+            const bool wrap = c + 1 == W;
+            double2 v;
+            v.x = A[r * S + c];
+            v.y = e + 1 < cells ? A[(wrap ? r + 1 : r) * S + (wrap ? 0 : c + 1)] : 0.0;
+            gA[q] = v;
+        }
+        for (int q = tid; q < words; q += THREADS) gI[q] = reinterpret_cast<const int4*>(ints)[q];
+    };
+    // addCutConstraints (cutting-strategies.ts:16-72) of the list in `slot` on the restored root: every cut row reads rows below H0
+    // and the restored maps only, so the rows are built side by side, one (cut, column) cell per thread and step; returns the height
+    auto add_cuts = [&](int slot) -> int {
+        if (slot < 0) return H0;
+        const char* sp = pool + slot * slot_bytes;
+        const int n = *reinterpret_cast<const int32_t*>(sp);
+        const TreeCut* cuts = reinterpret_cast<const TreeCut*>(sp + 16);
+        for (int q = tid; q < n * W; q += THREADS) {
+            const int h = q / W, col = q - h * W;
+            const TreeCut c = cuts[h];
+            const double sign = c.type == 0 ? -1.0 : 1.0;  // "min" -> -1 (:41)
+            const int var_row = rbv[c.var], var_col = cbv[c.var];
+            double v = 0.0;
+            if (var_row == -1) {  // non-basic variable: unit row (:46-53)
+                if (col == 0) v = sign * c.value;
+                else if (col == var_col) v = sign;
+            } else {              // basic variable: negated copy of its row (:54-62)
+                const double s = A[var_row * S + col];
+                v = col == 0 ? sign * (c.value - s) : -sign * s;
+            }
+            A[(H0 + h) * S + col] = v;
+        }
+        __syncthreads();  // (the maps read above are written below)
+        for (int h = tid; h < n; h += THREADS) {  // getNewElementIndex + map updates (:64-69)
+            const int slack = W + H0 - 2 + h;
+            vibr[H0 + h] = slack;
+            rbv[slack] = H0 + h;
+            cbv[slack] = -1;
+        }
+        return H0 + n;
+    };
+
+    restore();
+    long long trace_n = st->trace_n;
+    __syncthreads();
+
+    int H = H0, feasible = 1, unb_var = -1, iters_left = m.iters_cap;
+    PkRun o;
+    double evaluation = 0.0, best_eval = INFINITY;
+    int iterations = 0, found = 0, best_slot = -1, have_best = 0, cur_slot = -1;
+    int heap_n = 0, seq = 1, free_n = 0, fresh_n = 0, pushes = 1, heap_hw = 1, cuts_hw = 0;  // (the root's push and pop are not executed)
+    int terr = (n_int > 0 && t.heap_cap < 1) ? (int)TREE_ERR_HEAP : (int)TREE_OK, serr = ERR_NONE;
+    bool root = true, done = false;
+    auto release = [&](int slot) {  // a cut list nobody refers to any more goes back on the free stack
+        if (slot < 0) return;
+        if (tid == 0) free_list[free_n] = slot;
+        free_n += 1;
+    };
+
+    while (terr == TREE_OK && !done) {
+        if (!root) {
+            if (heap_n == 0) break;
+            if (tid == 0) {
+                const TreeEntry e = tree_pop(heap, heap_n);
+                sm.key = e.key;
+                sm.slot = e.slot;
+            }
+            __syncthreads();
+            const double key = sm.key;
+            cur_slot = sm.slot;
+            heap_n -= 1;
+            __syncthreads();  // (sm.key / sm.slot may be written again)
+            if (key > best_eval) { release(cur_slot); continue; }  // :89-92
+        }
+        if (iterations >= t.max_nodes) { terr = TREE_ERR_NODES; break; }
+        if (!root) {  // applyCuts: restore + addCutConstraints (:33-37)
+            restore();
+            __syncthreads();
+            H = add_cuts(cur_slot);
+            __syncthreads();
+        }
+        root = false;
+        iters_left = m.iters_cap;
+        o = pk_simplex<THREADS>(A, pcol, H, W, S, vibr, vibc, rbv, cbv, unr, precision, check_cycles, m, ghist, gtrace, sm.ps, iters_left, trace_n);
+        __syncthreads();
+        if (o.outcome >= 5) { serr = o.outcome == 5 ? (int)ERR_ITER_LIMIT : (int)ERR_HIST_FULL; break; }
+        iterations += 1;
+        feasible = (o.outcome == 3 || o.outcome == 4) ? 0 : 1;
+        unb_var = o.outcome == 2 ? vibc[o.unbounded_col] : -1;
+        if (o.outcome == 1)  // setEvaluation (tableau.ts:420-430); a node that reaches no optimum keeps the previous node's
+            evaluation = __ddiv_rn(tree_round(__dmul_rn(__dadd_rn(2.220446049250313e-16, A[0]), t.rcoef)), t.rcoef);
+        else if (o.outcome == 2)
+            evaluation = -INFINITY;
+        if (n_int == 0) break;  // no integer variables: a plain simplex() (tableau.ts:250-258)
+        if (!feasible || evaluation > best_eval || evaluation == best_eval) { release(cur_slot); continue; }  // :99-127
+        // isIntegral + getMostFractionalVar (mip-utils.ts:43-61, 100-126) over the integer variables in model order
+        Cand b; b.v = -1.0; b.i = 0; b.b = 0;
+        int nonint = 0;
+        for (int k = tid; k < n_int; k += THREADS) {
+            const int r = rbv[ivars[k]];
+            if (r > 0) {
+                const double v = A[r * S];
+                const double frac = fabs(v - tree_round(v));
+                nonint |= frac > precision ? 1 : 0;           // (NaN: false)
+                const double fkey = frac == frac ? frac : -1.0;  // `fraction > biggest` is false for NaN
+                if (fkey > b.v) { b.v = fkey; b.i = k + 1; }
+            }
+        }
+        b = pk_reduce<THREADS>(b, MaxFirst(), sm.ps.g);
+        nonint = __syncthreads_or(nonint);
+        if (!nonint) {
+            found = 1;
+            if (iterations == 1) { done = true; break; }  // :132-135: no save, no final re-evaluation
+            release(best_slot);
+            best_slot = cur_slot;  // (the list changes owner: not released)
+            have_best = 1;
+            best_eval = evaluation;
+            continue;
+        }
+        if (!(b.v > 0.0)) { terr = TREE_ERR_BRANCH; break; }
+        if (iterations == 1) { save(); __syncthreads(); }  // :155-157
+        if (tid == 0) {  // :160-191: the two children's cut lists and their pushes, the high child first
+            const int var = ivars[b.i - 1];
+            const double value = A[rbv[var] * S];
+            const int src_n = cur_slot < 0 ? 0 : *reinterpret_cast<const int32_t*>(pool + cur_slot * slot_bytes);
+            const TreeCut* src = reinterpret_cast<const TreeCut*>(pool + (cur_slot < 0 ? 0 : cur_slot) * slot_bytes + 16);
+            int code = TREE_OK, fn = free_n, fr = fresh_n, hn = heap_n, sq = seq, len[2] = {0, 0};
+            for (int child = 0; child < 2 && code == TREE_OK; child++) {  // 0: high ("min" cut, ceil), 1: low ("max" cut, floor)
+                const int slot = fn > 0 ? free_list[--fn] : fr++;
+                char* dp = pool + slot * slot_bytes;
+                TreeCut* dst = reinterpret_cast<TreeCut*>(dp + 16);
+                int n = 0;
+                for (int k = 0; k <= src_n && code == TREE_OK; k++) {
+                    TreeCut c;
+                    if (k < src_n) {
+                        c = src[k];
+                        // a cut on the branching variable survives only in the child of its own type (:166-179)
+                        if (c.var == var && (c.type == 0) != (child == 1)) continue;
+                    } else {
+                        c.value = child == 0 ? ceil(value) : floor(value);
+                        c.var = var;
+                        c.type = child;
+                    }
+                    if (n >= t.cut_rows) { code = TREE_ERR_CUTS; break; }
+                    dst[n++] = c;
+                }
+                if (code != TREE_OK) break;
+                *reinterpret_cast<int32_t*>(dp) = n;
+                len[child] = n;
+                if (hn >= t.heap_cap) { code = TREE_ERR_HEAP; break; }
+                TreeEntry e; e.key = evaluation; e.seq = sq++; e.slot = slot;
+                tree_push(heap, hn, e);
+                hn += 1;
+            }
+            sm.code = code;
+            sm.n_high = len[0];
+            sm.n_low = len[1];
+        }
+        __syncthreads();
+        terr = sm.code;
+        cuts_hw = max(cuts_hw, max(sm.n_high, sm.n_low));
+        __syncthreads();
+        if (terr != TREE_OK) break;
+        // what thread 0 did to the free stack, the heap and the counters, in every thread
+        for (int child = 0; child < 2; child++) {
+            if (free_n > 0) free_n -= 1; else fresh_n += 1;
+        }
+        heap_n += 2;
+        seq += 2;
+        pushes += 2;
+        heap_hw = max(heap_hw, heap_n);
+        release(cur_slot);
+    }
+    // :195-197: the incumbent's cut list is evaluated once more -- the final tableau, and its pivots join the trace
+    if (terr == TREE_OK && serr == ERR_NONE && !done && have_best) {
+        restore();
+        __syncthreads();
+        H = add_cuts(best_slot);
+        __syncthreads();
+        iters_left = m.iters_cap;
+        o = pk_simplex<THREADS>(A, pcol, H, W, S, vibr, vibc, rbv, cbv, unr, precision, check_cycles, m, ghist, gtrace, sm.ps, iters_left, trace_n);
+        __syncthreads();
+        if (o.outcome >= 5) serr = o.outcome == 5 ? (int)ERR_ITER_LIMIT : (int)ERR_HIST_FULL;
+        feasible = (o.outcome == 3 || o.outcome == 4) ? 0 : 1;
+        unb_var = o.outcome == 2 ? vibc[o.unbounded_col] : -1;
+        if (o.outcome == 1)
+            evaluation = __ddiv_rn(tree_round(__dmul_rn(__dadd_rn(2.220446049250313e-16, A[0]), t.rcoef)), t.rcoef);
+        else if (o.outcome == 2)
+            evaluation = -INFINITY;
+    }
+    // ---- epilogue: the state, the RHS column and the row map of whatever LDS holds now ----------------------------------------------------
+    __syncthreads();
+    const bool ok = terr == TREE_OK && serr == ERR_NONE && iterations > 0;
+    if (ok)
+        for (int r = tid; r < H; r += THREADS) {
+            out_rhs[m.out_off + r] = A[r * S];
+            out_rows[m.out_off + r] = vibr[r];
+        }
+    if (tid == 0) {
+        st->H = H;
+        st->last_element_index = W + H - 2;
+        st->status = ST_DONE;
+        st->do_pivot = 0;
+        st->err = serr;
+        st->trace_n = trace_n;
+        st->iters_left = iters_left;
+        if (ok) {
+            st->phase = o.phase;
+            st->it1 = o.it1;
+            st->it2 = o.it2;
+            st->hist_n = o.hist_n;
+            st->entered_phase2 = o.entered2;
+            st->feasible = feasible;
+            st->bounded = o.outcome == 2 ? 0 : 1;
+            st->optimal = o.outcome == 1 ? 1 : 0;
+            st->unbounded_var = unb_var;
+            st->cycle_phase = o.outcome == 3 ? o.phase : 0;
+            st->obj_cell = A[0];
+        }
+        TreeRec rec;
+        rec.evaluation = evaluation;
+        rec.iterations = n_int > 0 ? iterations : 0;
+        rec.is_integral = found;
+        rec.final_height = H;
+        rec.nodes_pushed = n_int > 0 ? pushes : 0;
+        rec.heap_high_water = n_int > 0 ? heap_hw : 0;
+        rec.cuts_high_water = cuts_hw;
+        rec.err = terr;
+        rec.pad = 0;
+        out_tree[idx] = rec;
+    }
+    __syncthreads();
+    if (tid < (int)(sizeof(DevState) / 8))
+        reinterpret_cast<long long*>(out_states + idx)[tid] = reinterpret_cast<const long long*>(st)[tid];
+}
+
+// as packed_launch_impl, for the tree kernels (PackLaunch::kind == 1)
+static int tree_launch_impl(int threads, unsigned grid, size_t lds, const void* bytes, hipStream_t s) {
+    const PackLaunch a = *static_cast<const PackLaunch*>(bytes);
+    DevState* states = static_cast<DevState*>(a.states);
+    const TreeLp* trees = static_cast<const TreeLp*>(a.trees);
+    TreeRec* recs = static_cast<TreeRec*>(a.tree_out);
+    if (threads == 64)
+        hipLaunchKernelGGL(k_tree_packed<64>, dim3(grid), dim3(64), lds, s, a.lps, trees, a.order, a.cc, a.cc_all, states, a.rhs, a.rows, recs);
+    else if (threads == 256)
+        hipLaunchKernelGGL(k_tree_packed<256>, dim3(grid), dim3(256), lds, s, a.lps, trees, a.order, a.cc, a.cc_all, states, a.rhs, a.rows, recs);
+    else
+        return -1;
+    return (int)hipPeekAtLastError();
+}
+#endif  // JSLP_PACKED_KERNELS

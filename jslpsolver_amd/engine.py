@@ -899,6 +899,45 @@ def pack_lds_bytes(height, width):
     return 8 * doubles + 4 * ints
 
 
+def tree_lds_bytes(height, width, row_capacity):
+    """jslpt_lds_bytes (include/jslpt_tree.h) restated: pack_lds_bytes with the tableau and the maps sized for row_capacity rows"""
+    h, w, rc = int(height), int(width), int(row_capacity)
+    if h < 2 or w < 2 or rc < h:
+        return 0
+    return pack_lds_bytes(rc, w)
+
+
+def tree_cut_rows(height, width, n_int, lib=None):
+    """the cut rows a model with n_int integer variables joins a tree pack with: 2 per integer variable -- the most a cut list can hold
+    (branch-and-cut.ts:166-179) -- or the most that fit the LDS limit; 0 when not even one fits"""
+    def fits(cut_rows):
+        if lib is not None and getattr(lib, "has_tree", False):
+            b = int(lib.jslpt_lds_bytes(int(height), int(width), int(height) + cut_rows))
+        else:
+            b = tree_lds_bytes(height, width, int(height) + cut_rows)
+        return 0 < b <= _capi.JSLPP_LDS_LIMIT
+    lo, hi = 0, 2 * int(n_int)
+    if fits(hi):
+        return hi
+    while lo < hi:  # (the byte count is monotone in the row capacity)
+        mid = (lo + hi + 1) // 2
+        lo, hi = (mid, hi) if fits(mid) else (lo, mid - 1)
+    return lo
+
+
+class _TreeModel:
+    """what branch_and_cut.branch_and_cut reads of a model, for an LP of a pack: the default service, no tolerance, no timeout"""
+    tolerance = 0
+    timeout = None
+    useMIRCuts = False
+    isMinimization = True
+
+    def __init__(self, integers, check_cycles):
+        self.integer_index_array = np.asarray(integers, dtype=np.int64)
+        self.integer_index_set = frozenset(int(i) for i in integers)
+        self.checkForCycles = bool(check_cycles)
+
+
 def pack_fits(height, width, lib=None):
     """whether a tableau of this shape can join a TableauPack (its LDS image stays within the 64 KiB the pack kernels are launched with)"""
     if lib is not None and getattr(lib, "has_pack", False):
@@ -920,7 +959,8 @@ class TableauPack:
     other (max_pivots is then the engine's own cap) -- the host logic stays testable without a GPU.  A HIP library without the extension is
     an error, never a fallback."""
 
-    def __init__(self, lps, precision=1e-8, lib=None, device=0, trace_cap=0, max_pivots=0):
+    def __init__(self, lps, precision=1e-8, lib=None, device=0, trace_cap=0, max_pivots=0, integers=None, cut_rows=None, heap_cap=None,
+                 max_nodes=0):
         self.lib = lib if lib is not None else _capi.load_hip()
         self._lps = []
         for matrix, vibr, vibc, unr in lps:
@@ -950,25 +990,54 @@ class TableauPack:
         self._launches = 0
         self._h = None
         self._twins = None
+        # a pack with trees (include/jslpt_tree.h): per LP its integer variables in model order, its cut rows and its heap
+        self.is_tree = integers is not None
+        self.tree = np.zeros(n, dtype=_capi.TREE_DTYPE)
+        if self.is_tree:
+            self.integers = [_capi.as_i32(list(iv)) for iv in integers]
+            if len(self.integers) != n:
+                raise ValueError("TableauPack: %d integer lists for %d LPs" % (len(self.integers), n))
+            per_lp = lambda v, default: _capi.as_i32(default if v is None else ([v] * n if isinstance(v, (int, np.integer)) else list(v)))  # noqa: E731
+            self.cut_rows = per_lp(cut_rows, [2 * iv.shape[0] for iv in self.integers])
+            self.heap_cap = per_lp(heap_cap, [128] * n)
+            if self.cut_rows.shape[0] != n or self.heap_cap.shape[0] != n:
+                raise ValueError("TableauPack: cut_rows / heap_cap are one number or one per LP")
+            self.max_nodes = int(max_nodes) if max_nodes else _capi.JSLPT_MAX_NODES_DEFAULT
+            self.row_capacity = self.heights + self.cut_rows
+        else:
+            self.row_capacity = self.heights
+        if self.is_tree and self.lib.has_pack and not getattr(self.lib, "has_tree", False):
+            raise _capi.EngineError("TableauPack: %s does not export the tree extension (include/jslpt_tree.h)" % self.lib.path)
         if self.lib.has_pack:
             self._h = _capi.C.c_void_p()
-            self.lib.check(self.lib.jslpp_pack_create(_capi.C.byref(self._h), self.device, n, _capi.ptr_i32(self.heights), _capi.ptr_i32(self.widths),
-                                                      _capi.ptr_f64(self.precision), self.trace_cap, self.max_pivots), "jslpp_pack_create")
+            if self.is_tree:
+                self.lib.check(self.lib.jslpt_pack_create(_capi.C.byref(self._h), self.device, n, _capi.ptr_i32(self.heights), _capi.ptr_i32(self.widths),
+                                                          _capi.ptr_f64(self.precision), _capi.ptr_i32(self.cut_rows), _capi.ptr_i32(self.heap_cap),
+                                                          self.trace_cap, self.max_pivots, self.max_nodes), "jslpt_pack_create")
+            else:
+                self.lib.check(self.lib.jslpp_pack_create(_capi.C.byref(self._h), self.device, n, _capi.ptr_i32(self.heights), _capi.ptr_i32(self.widths),
+                                                          _capi.ptr_f64(self.precision), self.trace_cap, self.max_pivots), "jslpp_pack_create")
             try:
                 for i, (m, vibr, vibc, unr) in enumerate(self._lps):
                     self.lib.check(self.lib.jslpp_pack_set(self._h, i, _capi.ptr_f64(m), _capi.ptr_i32(vibr), _capi.ptr_i32(vibc), _capi.ptr_i32(unr),
                                                            int(unr.shape[0])), "jslpp_pack_set")
+                    if self.is_tree:
+                        iv = self.integers[i]
+                        self.lib.check(self.lib.jslpt_pack_set_integers(self._h, i, _capi.ptr_i32(iv), int(iv.shape[0])), "jslpt_pack_set_integers")
                 self._lps = None  # (the pack's pinned image holds the inputs from here on)
                 self.upload()
             except Exception:
                 self.close()
                 raise
         elif self.lib.backend == "oracle-c":
-            for h, w in zip(self.heights, self.widths):
-                if not pack_fits(h, w):
+            for i, (h, w, rc) in enumerate(zip(self.heights, self.widths, self.row_capacity)):
+                if self.is_tree and not 0 < tree_lds_bytes(h, w, rc) <= _capi.JSLPP_LDS_LIMIT:
+                    raise _capi.EngineError("jslpt_pack_create failed (%d): pack_create: LP %d: the tableau's LDS image at its row capacity exceeds "
+                                            "64 KiB" % (_capi.JSLP_ERR_UNSUPPORTED, i))
+                if not self.is_tree and not pack_fits(h, w):
                     raise _capi.EngineError("jslpp_pack_create failed (%d): the tableau's LDS image exceeds 64 KiB" % _capi.JSLP_ERR_UNSUPPORTED)
-            self._twins = [Tableau(m, vibr, vibc, unr, precision=float(p), device=self.device, lib=self.lib)
-                           for (m, vibr, vibc, unr), p in zip(self._lps, self.precision)]
+            self._twins = [Tableau(m, vibr, vibc, unr, precision=float(p), row_capacity=int(rc), device=self.device, lib=self.lib)
+                           for (m, vibr, vibc, unr), p, rc in zip(self._lps, self.precision, self.row_capacity)]
         else:
             raise _capi.EngineError("TableauPack: %s does not export the pack extension (include/jslpp_packed.h)" % self.lib.path)
 
@@ -1053,6 +1122,61 @@ class TableauPack:
             raise _capi.EngineError("jslpp_pack_simplex failed (%d): %s" % (rc, msg))
         return out
 
+    def branch_and_cut(self, check_cycles=True):
+        """Tableau.solve() of every LP under the default branch-and-cut service, each tree walked by its LP's workgroup inside ONE launch per
+        kernel build (include/jslpt_tree.h).  Returns the results like simplex() -- per LP the last relaxation evaluated -- and keeps `tree`
+        (_capi.TREE_DTYPE: iterations, is_integral, final_height, nodes_pushed, heap_high_water, cuts_high_water), `status`, `evaluation`,
+        `feasible` and `bounded`.  An LP that reaches a capacity keeps its earlier entries and gets JSLP_ERR_CAPACITY in `status`; the others
+        are solved; the call then raises EngineError naming the first such LP.  The restatement walks branch_and_cut.branch_and_cut on one
+        engine per LP with the same capacities enforced (max_pivots excepted: the engine's own cap)."""
+        if not self.is_tree:
+            raise _capi.EngineError("TableauPack.branch_and_cut: the pack was made without `integers`")
+        flags = self._flags(check_cycles)
+        out = self.results.copy()
+        tree = self.tree.copy()
+        status = np.zeros(self.n, dtype=np.int32)
+        if self._twins is not None:
+            from . import branch_and_cut as bc
+            rc, msg = _capi.JSLP_OK, ""
+            for i, (t, c) in enumerate(zip(self._twins, flags)):
+                try:
+                    if self.integers[i].shape[0] == 0:
+                        t.simplex(check_cycles=bool(c))
+                        rec = (0, 0, t.last.height, 0, 0, 0)
+                    else:
+                        heap = bc.CountingHeap(heap_cap=int(self.heap_cap[i]), cut_rows=int(self.cut_rows[i]))
+                        iterations, integral = bc.branch_and_cut(t, _TreeModel(self.integers[i], c), heap=heap, max_nodes=self.max_nodes)
+                        rec = (iterations, int(integral), t.last.height, heap.pushes, heap.high_water, heap.cuts_high_water)
+                    res = SimplexResult.from_buffer_copy(bytes(t.last))
+                    res.evaluation = t.evaluation
+                    out[i] = np.frombuffer(res, dtype=_capi.RESULT_DTYPE)[0]
+                    tree[i] = rec
+                except (bc.TreeCapacity, _capi.EngineError) as e:
+                    status[i] = _capi.JSLP_ERR_CAPACITY if isinstance(e, bc.TreeCapacity) or "(%d)" % _capi.JSLP_ERR_CAPACITY in str(e) else _capi.JSLP_ERR_DEVICE
+                    if rc == _capi.JSLP_OK:
+                        rc, msg = int(status[i]), "pack_branch_and_cut: LP %d: %s" % (i, e)
+            self._launches = 0
+        else:
+            ms = _capi.C.c_double()
+            all_same = bool((flags == flags[0]).all()) if self.n else True
+            rc = self.lib.jslpt_pack_branch_and_cut(self._h, None if (all_same and self.n and flags[0]) else _capi.ptr_i32(flags), out.ctypes.data,
+                                                    tree.ctypes.data, _capi.ptr_i32(status), _capi.C.byref(ms))
+            msg = self.lib.jslp_last_error().decode() if rc != _capi.JSLP_OK else ""
+            if rc != _capi.JSLP_OK and not status.any():  # refused before any work
+                raise _capi.EngineError("jslpt_pack_branch_and_cut failed (%d): %s" % (rc, msg))
+            self.device_ms = ms.value
+            self._launches = int(self.lib.jslpp_pack_launches(self._h))
+        ok = status == _capi.JSLP_OK
+        self.results = out
+        self.tree = tree
+        self.status = status
+        self.feasible[ok] = out["feasible"][ok] != 0
+        self.bounded[ok] = out["bounded"][ok] != 0
+        self.evaluation[ok] = out["evaluation"][ok]
+        if rc != _capi.JSLP_OK:
+            raise _capi.EngineError("jslpt_pack_branch_and_cut failed (%d): %s" % (rc, msg))
+        return out
+
     def result(self, i):
         """LP i's result of the last simplex() as a SimplexResult"""
         return SimplexResult.from_buffer_copy(self.results[i].tobytes())
@@ -1065,6 +1189,8 @@ class TableauPack:
         rhs, rows, offs = _capi._f64p(), _capi._i32p(), _capi._P(_capi.C.c_int64)()
         self.lib.check(self.lib.jslpp_pack_read_rhs(self._h, _capi.C.byref(rhs), _capi.C.byref(rows), _capi.C.byref(offs)), "jslpp_pack_read_rhs")
         a, b = int(offs[i]), int(offs[i + 1])
+        if self.is_tree:  # (the LP's block is sized by its row capacity: the final tableau's rows are valid)
+            b = a + int(self.results[i]["height"])
         return (np.ctypeslib.as_array(rhs, shape=(int(offs[self.n]),))[a:b].copy(),
                 np.ctypeslib.as_array(rows, shape=(int(offs[self.n]),))[a:b].copy())
 
@@ -1072,7 +1198,7 @@ class TableauPack:
         if self._twins is not None:
             return self._twins[i].download()
         h, w = int(self.heights[i]), int(self.widths[i])
-        n = w + 2 * h + 2
+        n = w + 2 * int(self.row_capacity[i]) + 2  # (the maps are sized for the LP's row capacity)
         m = np.empty((h, w), dtype=np.float64)
         vibr, vibc = np.empty(h, dtype=np.int32), np.empty(w, dtype=np.int32)
         rbv, cbv = np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32)

@@ -5,13 +5,18 @@ import math
 import os
 import warnings
 
+import numpy as np
+
 from . import _capi
 from .branch_and_cut import branch_and_cut, js_round
-from .engine import Tableau, TableauPack, pack_fits, simplex_many
+from .engine import Tableau, TableauPack, pack_fits, simplex_many, tree_cut_rows
 from .model import Model, js_keys
 
 EPSILON = 2.220446049250313e-16
 _presolve_warned = False
+# solve_packed: the heap entries and the nodes a tree in the pack may use before it is handed to Solve (include/jslpt_tree.h)
+TREE_HEAP_CAP = 128
+TREE_MAX_NODES = 1 << 16
 
 
 def _round_value(v, rounding_coeff):
@@ -74,20 +79,40 @@ class _PackedLp:
         return self._pack.read_rhs(self._i)
 
 
+def _tree_in_scope(m):
+    """whether the default branch-and-cut service alone decides this model's result, with nothing that needs the host or a clock
+    (include/jslpt_tree.h)"""
+    o = m.options
+    return not (m.useMIRCuts or o.get("useIncremental") is True or o.get("nodeSelection") or o.get("branching") or m.tolerance or m.timeout
+                or m.keep_solutions)
+
+
 def solve_packed(models, precision=None, lib=None, device=0):
-    """[Solve(m, precision, lib=lib, device=device) for m in models], in order, for the workload of many SMALL models: every model without
-    integer variables and without optional objectives whose tableau fits the pack's LDS limit (engine.pack_fits) goes through ONE
-    engine.TableauPack -- one arena, one upload, one launch per kernel build, one read-back, no engine per model.  Every other model
-    (integer variables, optional objectives, a tableau beyond the limit) goes through Solve as it is.  A model Solve rejects raises the
-    same exception before anything is solved."""
+    """[Solve(m, precision, lib=lib, device=device) for m in models], in order, for the workload of many SMALL models.  Every model
+    without optional objectives whose tableau fits the pack's LDS limit goes through an engine.TableauPack -- one arena, one upload, one
+    launch per kernel build, one read-back, no engine per model:
+      * without integer variables (engine.pack_fits): its simplex();
+      * with integer variables, under the default branch-and-cut service with no tolerance and no timeout, when the tableau with
+        min(2 per integer variable, the most that fit) >= 1 cut rows fits (engine.tree_cut_rows): its whole tree, walked on the device
+        (TableauPack.branch_and_cut).  A tree that reaches a capacity of the pack (heap, cut rows, nodes) is solved again through Solve.
+    Every other model goes through Solve as it is.  A model Solve rejects raises the same exception before anything is solved."""
     lib = lib if lib is not None else _capi.load_hip()
     models = list(models)
     parsed = [_parse(model, precision, 4) for model in models]
-    packed = []  # positions of the models that go into the pack
+    packed = []  # positions of the models that go into the pack of plain LPs
+    trees = []   # (position, cut rows) of the models whose tree goes into the pack with trees
     for k, (m, matrix, _, _) in enumerate(parsed):
         _priorities, optional_rows = m.optional_objectives()
-        if len(m.integerVariables) == 0 and (optional_rows is None or len(optional_rows) == 0) and pack_fits(*matrix.shape, lib=lib):
-            packed.append(k)
+        if optional_rows is not None and len(optional_rows) > 0:
+            continue
+        n_int = len(m.integerVariables)
+        if n_int == 0:
+            if pack_fits(*matrix.shape, lib=lib):
+                packed.append(k)
+        elif _tree_in_scope(m):
+            cut_rows = tree_cut_rows(matrix.shape[0], matrix.shape[1], n_int, lib=lib)
+            if cut_rows >= 1:
+                trees.append((k, cut_rows))
     results = [None] * len(models)
     if packed:
         pack = TableauPack([(parsed[k][1], parsed[k][2], parsed[k][3], parsed[k][0].unrestricted) for k in packed],
@@ -96,6 +121,23 @@ def solve_packed(models, precision=None, lib=None, device=0):
             pack.simplex(check_cycles=[parsed[k][0].checkForCycles for k in packed])
             for i, k in enumerate(packed):
                 results[k] = _solve_on(_PackedLp(pack, i), parsed[k][0], 0, False, 1, None, False, simplex_done=True)
+        finally:
+            pack.close()
+    if trees:
+        pack = TableauPack([(parsed[k][1], parsed[k][2], parsed[k][3], parsed[k][0].unrestricted) for k, _ in trees],
+                           precision=[parsed[k][0].precision for k, _ in trees], lib=lib, device=device,
+                           integers=[[v["index"] for v in parsed[k][0].integerVariables] for k, _ in trees], cut_rows=[c for _, c in trees],
+                           heap_cap=TREE_HEAP_CAP, max_nodes=TREE_MAX_NODES)
+        try:
+            try:
+                pack.branch_and_cut(check_cycles=[parsed[k][0].checkForCycles for k, _ in trees])
+            except _capi.EngineError:
+                if not (pack.status == _capi.JSLP_ERR_CAPACITY).any() or not np.isin(pack.status, (_capi.JSLP_OK, _capi.JSLP_ERR_CAPACITY)).all():
+                    raise
+            for i, (k, _) in enumerate(trees):
+                if pack.status[i] == _capi.JSLP_OK:  # (an LP that reached a capacity stays None: Solve below)
+                    results[k] = _solve_on(_PackedLp(pack, i), parsed[k][0], 0, False, 1, None, False, simplex_done=True,
+                                           integral=bool(pack.tree[i]["is_integral"]))
         finally:
             pack.close()
     for k, model in enumerate(models):
@@ -146,9 +188,8 @@ def _prepare(model, precision, lib, device, row_capacity_extra):
     return m, t, n_int, incremental
 
 
-def _solve_on(t, m, n_int, incremental, speculate, group, full, simplex_done=False):
+def _solve_on(t, m, n_int, incremental, speculate, group, full, simplex_done=False, integral=False):
     iterations = 0
-    integral = False
     if n_int > 0:  # tableau.ts:250-258
         evaluate = None
         if group is not None:

@@ -1,0 +1,99 @@
+"""The tree extension's boundary (runs without a GPU): include/jslpt_tree.h, the ctypes table TREE_SYMBOLS and the jslpt_ exports of the
+product and test libraries agree; the extension stays out of the other headers and out of the oracle; create refuses bad arguments and
+row capacities beyond the LDS limit before touching a device; jslpt_lds_bytes is a pure, monotone function that equals jslpp_lds_bytes at
+row_capacity == height."""
+import ctypes
+import os
+
+import numpy as np
+
+from jslpsolver_amd import _capi
+from jslpsolver_amd.engine import tree_cut_rows, tree_lds_bytes
+from test_many_abi import built, declared_in_header, exported
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEADER = os.path.join(ROOT, "include", "jslpt_tree.h")
+CHAOS = os.path.join(ROOT, "jslpsolver_amd", "csrc", "libjslp_hip_chaos.so")
+PREFIX = "jslpt_"
+
+
+def _hip():
+    return _capi.Library(built(_capi.HIP_LIB_PATH))
+
+
+def test_header_and_binding_declare_the_same_extension():
+    declared = declared_in_header(HEADER, PREFIX)
+    assert declared == set(_capi.TREE_SYMBOLS) and len(declared) == 5
+    for other in ("jslp_engine.h", "jslpp_packed.h", "jslpm_many.h", "jslpx_branch.h", "jslpr_mir.h", "jslpf_f32.h"):
+        assert not declared_in_header(os.path.join(ROOT, "include", other), PREFIX)
+    for other in (_capi.SYMBOLS, _capi.MANY_SYMBOLS, _capi.BRANCH_SYMBOLS, _capi.F32_SYMBOLS, _capi.MIR_SYMBOLS, _capi.PACK_SYMBOLS):
+        assert not set(_capi.TREE_SYMBOLS) & set(other)
+    assert ctypes.sizeof(ctypes.c_int32) * 6 == _capi.TREE_DTYPE.itemsize == 24
+
+
+def test_product_and_test_libraries_export_the_extension():
+    assert exported(built(_capi.HIP_LIB_PATH), PREFIX) == declared_in_header(HEADER, PREFIX)
+    assert exported(built(CHAOS), PREFIX) == declared_in_header(HEADER, PREFIX)
+    assert _hip().has_tree
+
+
+def test_oracle_does_not_export_the_extension(oracle_lib):
+    assert exported(oracle_lib.path, PREFIX) == set()
+    assert not oracle_lib.has_tree
+
+
+def _create(lib, n, heights, widths, cut_rows, heap_cap, trace_cap=0, max_pivots=0, max_nodes=0):
+    h = ctypes.c_void_p()
+    arr = lambda a: None if a is None else _capi.ptr_i32(_capi.as_i32(a))  # noqa: E731
+    ps = _capi.ptr_f64(_capi.as_f64([1e-8] * max(n, 1)))
+    rc = lib.jslpt_pack_create(ctypes.byref(h), 0, n, arr(heights), arr(widths), ps, arr(cut_rows), arr(heap_cap), trace_cap, max_pivots, max_nodes)
+    return rc, h
+
+
+def test_argument_errors_without_a_device():
+    """refused before any device call: this host has no GPU, and a call that reached the device would answer JSLP_ERR_DEVICE"""
+    lib = _hip()
+    assert _create(lib, 1, [3], [3], None, [4])[0] == _capi.JSLP_ERR_ARG
+    assert _create(lib, 1, [3], [3], [2], None)[0] == _capi.JSLP_ERR_ARG
+    assert _create(lib, 2, [3, 3], [3, 3], [2, -1], [4, 4])[0] == _capi.JSLP_ERR_ARG
+    assert b"LP 1" in lib.jslp_last_error()
+    assert _create(lib, 2, [3, 3], [3, 3], [2, 2], [0, 4])[0] == _capi.JSLP_ERR_ARG
+    assert b"LP 0" in lib.jslp_last_error()
+    assert _create(lib, 1, [3], [3], [2], [4], max_nodes=-1)[0] == _capi.JSLP_ERR_ARG
+    # Knapsack_1 (52 x 51, 50 integer variables) misses the limit at 100 cut rows and fits with fewer
+    assert lib.jslpt_lds_bytes(52, 51, 152) - 65536 == 1760
+    rc, h = _create(lib, 2, [3, 52], [3, 51], [4, 100], [8, 8])
+    assert rc == _capi.JSLP_ERR_UNSUPPORTED and not h.value
+    assert b"LP 1" in lib.jslp_last_error() and b"64 KiB" in lib.jslp_last_error()
+    assert tree_cut_rows(52, 51, 50, lib=lib) == tree_cut_rows(52, 51, 50) == 96
+    assert lib.jslpt_lds_bytes(52, 51, 52 + 96) <= 65536 < lib.jslpt_lds_bytes(52, 51, 52 + 97)
+    rc, h = _create(lib, 1, [2 ** 20], [2 ** 20], [2 ** 20], [1])  # (a byte count that would not fit 32 bits)
+    assert rc == _capi.JSLP_ERR_UNSUPPORTED and b"LP 0" in lib.jslp_last_error()
+    # the other entry points refuse a null pack
+    assert lib.jslpt_pack_set_integers(None, 0, None, 0) == _capi.JSLP_ERR_ARG
+    assert lib.jslpt_pack_branch_and_cut(None, None, None, None, None, None) == _capi.JSLP_ERR_ARG
+    assert lib.jslpt_pack_read_rhs(None, None, None, None) == _capi.JSLP_ERR_ARG
+
+
+def test_lds_bytes_against_its_restatement():
+    lib = _hip()
+    sizes = [2, 3, 4, 5, 7, 8, 16, 31, 32, 33, 51, 52, 63, 64, 65, 66, 87, 88, 100, 128, 129, 257]
+    extra = [0, 1, 2, 3, 4, 7, 8, 20, 63, 64, 65, 100]
+    table = np.array([[[lib.jslpt_lds_bytes(h, w, h + e) for e in extra] for w in sizes] for h in sizes], dtype=np.int64)
+    assert (table > 0).all() and (table % 16 == 0).all()
+    assert (np.diff(table, axis=0) > 0).all()   # a row more always costs
+    assert (np.diff(table, axis=1) >= 0).all()  # a column more never saves
+    assert (np.diff(table, axis=2) > 0).all()   # a cut row more always costs
+    for i, h in enumerate(sizes):
+        for j, w in enumerate(sizes):
+            assert table[i, j, 0] == lib.jslpp_lds_bytes(h, w)  # row_capacity == height: the pack's own image
+            for k, e in enumerate(extra):
+                assert table[i, j, k] == tree_lds_bytes(h, w, h + e) == lib.jslpp_lds_bytes(h + e, w)
+    assert lib.jslpt_lds_bytes(1, 5, 5) == 0 and lib.jslpt_lds_bytes(5, 1, 5) == 0 and lib.jslpt_lds_bytes(5, 5, 4) == 0
+    assert tree_lds_bytes(1, 5, 5) == 0 and tree_lds_bytes(5, 1, 5) == 0 and tree_lds_bytes(5, 5, 4) == 0
+    # the routing rule: 2 per integer variable, or the most that fit, or nothing
+    assert tree_cut_rows(3, 3, 2, lib=lib) == 4 and tree_cut_rows(88, 88, 3, lib=lib) == 0 and tree_cut_rows(193, 65, 64, lib=lib) == 0
+    for h, w, n_int in ((52, 51, 50), (60, 65, 40), (80, 80, 10)):
+        c = tree_cut_rows(h, w, n_int, lib=lib)
+        assert c == tree_cut_rows(h, w, n_int) and 0 < c < 2 * n_int
+        assert lib.jslpt_lds_bytes(h, w, h + c) <= 65536 < lib.jslpt_lds_bytes(h, w, h + c + 1)

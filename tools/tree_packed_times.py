@@ -1,0 +1,114 @@
+#!/usr/bin/env python3
+"""solve_packed on n small MILPs, on this tree and on another checkout of the project (the parent commit), in ONE session.
+  python tools/tree_packed_times.py [--parent DIR] [--ns 1,8,64,512,4096] [--reps 3] [--rounds 3] [--out profiles/packed_tree_times.md]
+Workload: the reference's default-policy fuzz MILPs that need no presolve pre-pass (tests/golden/fuzz_services.jsonl.gz), round robin up
+to n models.  On this tree solve_packed walks every tree on the device, one launch for the whole batch (include/jslpt_tree.h); on a tree
+without the extension (--parent: a built checkout of the parent commit) the same call walks each tree on the host through Solve.
+Each tree runs in a worker process of its own (this file with --worker, importing the package from --root), and the two alternate
+round by round, so both see the same machine in the same minutes.  A worker verifies EVERY result of every repetition against the
+reference's recorded result (the rule of tests/test_fuzz_services.py::replay) before it reports a time.  Wall time is a host clock
+around solve_packed, which ends in its own synchronisation and read-back; one warm-up call per n, then --reps timed calls; the table
+reports the best and the median over all rounds.  Nothing is asserted about the ratio: the file records what was measured."""
+import argparse
+import gzip
+import json
+import os
+import statistics
+import subprocess
+import sys
+import time
+import warnings
+
+HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def cases(root):
+    with gzip.open(os.path.join(root, "tests", "golden", "fuzz_services.jsonl.gz"), "rt") as fh:
+        cs = [json.loads(line) for line in fh if line.startswith("{")]
+    return [c for c in cs if not c["model"].get("options") and c["fixed"] == 0 and not c["infeasPre"]]
+
+
+def worker(a):
+    sys.path.insert(0, a.root)
+    sys.path.insert(0, os.path.join(a.root, "tests"))
+    import numpy as np
+    import golden_util as G
+    from jslpsolver_amd import _capi
+    from jslpsolver_amd.solver import solve_packed
+    warnings.simplefilter("ignore")
+    lib = _capi.Library(os.path.join(a.root, a.lib)) if a.lib else _capi.load_hip()
+    cs = cases(a.root)
+
+    def verify(results, n):
+        for k in range(n):
+            c, res = cs[k % len(cs)], results[k]
+            assert list(res.keys()) == c["keys"], (k, c["gen"], c["seed"])
+            for key, v in c["result"].items():
+                ref = v if isinstance(v, bool) else G.num(v)
+                assert res[key] == ref or (isinstance(ref, float) and np.isnan(ref) and np.isnan(res[key])), (k, key)
+
+    for n in [int(x) for x in a.ns.split(",")]:
+        models = [cs[k % len(cs)]["model"] for k in range(n)]
+        verify(solve_packed(models, lib=lib), n)  # warm-up: code objects, pooled streams, the allocator
+        for _ in range(a.reps):
+            t0 = time.perf_counter()
+            results = solve_packed(models, lib=lib)
+            dt = time.perf_counter() - t0
+            verify(results, n)
+            print(json.dumps({"n": n, "wall_ms": 1e3 * dt, "device_tree": bool(getattr(lib, "has_tree", False))}), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--parent", default=None, help="a built checkout of the parent commit")
+    ap.add_argument("--ns", default="1,8,64,512,4096")
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--worker", action="store_true")
+    ap.add_argument("--root", default=HERE)
+    ap.add_argument("--lib", default=None, help="engine library, relative to each checkout (default: the HIP product library); "
+                    "oracle/libjslp_oracle.so rehearses the tool without a GPU -- its times say nothing")
+    a = ap.parse_args()
+    if a.worker:
+        return worker(a)
+    trees = [("this commit", HERE)] + ([("parent commit", os.path.abspath(a.parent))] if a.parent else [])
+    times = {name: {} for name, _ in trees}
+    flags = {}
+    for _ in range(a.rounds):
+        for name, root in trees:  # (the two alternate, round by round)
+            out = subprocess.run([sys.executable, os.path.abspath(__file__), "--worker", "--root", root, "--ns", a.ns, "--reps", str(a.reps)] + (["--lib", a.lib] if a.lib else []),
+                                 check=True, capture_output=True, text=True, timeout=900).stdout
+            print("round done: %s" % name, file=sys.stderr, flush=True)
+            for line in out.splitlines():
+                if line.startswith("{"):
+                    r = json.loads(line)
+                    times[name].setdefault(r["n"], []).append(r["wall_ms"])
+                    flags[name] = r["device_tree"]
+    n_models = len(cases(HERE))
+    lines = ["# `solve_packed` on small MILPs: trees walked on the device against trees walked on the host (MI355X)", "",
+             "`python tools/tree_packed_times.py --parent <checkout of the parent commit> --out profiles/packed_tree_times.md`: one session, one "
+             "device, %d rounds alternating between the two checkouts, each in a process of its own; per round one warm-up call and %d timed "
+             "calls per n; wall time of `solve_packed(models)` on n models taken round robin from the %d default-policy fuzz MILPs; every result "
+             "of every call verified against the reference's recorded result before its time was kept." % (a.rounds, a.reps, n_models), "",
+             "| n | " + " | ".join("%s: best ms | median ms | trees/s (best)" % name for name, _ in trees) + (" | parent / this (best) |" if a.parent else " |"),
+             "|---|" + "---|---|---|" * len(trees) + ("---|" if a.parent else "")]
+    for n in [int(x) for x in a.ns.split(",")]:
+        row, best = ["%d" % n], {}
+        for name, _ in trees:
+            ts = times[name][n]
+            best[name] = min(ts)
+            row += ["%.3f" % min(ts), "%.3f" % statistics.median(ts), "%.0f" % (n / (1e-3 * min(ts)))]
+        if a.parent:
+            row.append("%.2fx" % (best["parent commit"] / best["this commit"]))
+        lines.append("| " + " | ".join(row) + " |")
+    lines += ["", "- device-side trees: " + ", ".join("%s: %s" % (name, "yes" if flags.get(name) else "no (each tree through `Solve`)") for name, _ in trees) + "."]
+    text = "\n".join(lines) + "\n"
+    print(text)
+    if a.out:
+        with open(a.out, "w") as fh:
+            fh.write(text)
+
+
+if __name__ == "__main__":
+    main()
