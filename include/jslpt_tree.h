@@ -12,8 +12,9 @@
  * there is one, the last node's otherwise), the final RHS column and row map, the iteration count, and the pivot trace of EVERY node
  * in order, the final re-evaluation included.  A node that reaches no optimum keeps the evaluation of the node before it.
  *
- * Out of scope, by design (such models go through a jslp_engine): optional objectives, MIR cuts, the incremental and enhanced
- * services, tolerance, timeout, keep_solutions, and an LP whose LDS image at its row capacity exceeds JSLPP_LDS_LIMIT.
+ * Out of scope, by design (such models go through a jslp_engine): MIR cuts, the incremental and enhanced services, tolerance,
+ * timeout, keep_solutions, and an LP whose LDS image at its row capacity exceeds JSLPP_LDS_LIMIT.  Optional objectives come
+ * through jslps_soft.h.
  *
  * jslpp_pack_set, jslpp_pack_host_matrix, jslpp_pack_upload, jslpp_pack_simplex, jslpp_pack_destroy, jslpp_pack_size and
  * jslpp_pack_pivot_trace work on such a pack as on any other.  The arena keeps the SAVED ROOT, not the final tableau: after

@@ -239,6 +239,9 @@ class _NodeEvalBranch:
 
 
 EVAL_STATS = {"seconds": 0.0, "batches": 0, "nodes": 0}  # speculative batches since the caller last zeroed it (bench.py)
+# nodes whose evaluation equalled the incumbent's on a tableau with optional objectives (branch-and-cut.ts:107-127), and how many of them won
+# the tie on an objective, since the caller last zeroed it (the tests show with it that their inputs reach that code)
+TIE_STATS = {"ties": 0, "won": 0}
 
 
 def branch_and_cut(tableau, model, speculate=1, evaluate_batch=None, read_back=None, heap=None, max_nodes=None):
@@ -389,6 +392,9 @@ def branch_and_cut(tableau, model, speculate=1, evaluate_batch=None, read_back=N
                     if optional_cells[o] < best_optional[o]:
                         worse = False
                         break
+            if n_opt > 0:
+                TIE_STATS["ties"] += 1
+                TIE_STATS["won"] += 0 if worse else 1
             if worse:
                 continue
         rows = vibr if isinstance(vibr, (_WatchedRows, _NodeEvalBranch)) else _rows_by_var(vibr)

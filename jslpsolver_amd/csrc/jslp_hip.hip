@@ -19,6 +19,7 @@
 #include "../../include/jslpr_mir.h"
 #include "../../include/jslpp_packed.h"
 #include "../../include/jslpt_tree.h"
+#include "../../include/jslps_soft.h"
 #include "jslp_kernels.hip.h"
 #include "jslp_host_mem.h"
 
@@ -3420,7 +3421,9 @@ extern "C" int jslpf_simplex_f32_sweep(jslp_engine* e, const double* precisions,
 
 // ---- a pack of small LPs solved in LDS (include/jslpp_packed.h) ---------------------------------------------------------------------
 // One object, one arena: [LP images | descriptor table | launch order | per-LP checkForCycles | histories | traces].  The images have a
-// pinned twin (the ONE H2D copy of upload); the result block [states | RHS columns | row maps] has another (the ONE D2H copy of simplex).
+// pinned twin (the ONE H2D copy of upload); the result block [states | RHS columns | row maps | (tree records) | optional rows] has another
+// (the ONE D2H copy of simplex).  An LP with optional objectives (include/jslps_soft.h) carries their rows in its image behind the matrix and
+// runs in the OPT build of its kernel: up to four launches per call, 64 or 256 threads, each with or without OPT.
 // A pack call holds no jslp_engine and takes no g_many_mu.  The kernels live in jslp_tu_packed.hip (jslp_packed.hip.h).
 #include "jslp_packed.hip.h"
 #include "jslp_tree.hip.h"  // (the layout of a pack with cut rows and a heap per LP, include/jslpt_tree.h)
@@ -3466,8 +3469,14 @@ struct jslpp_pack {
     PackLp* d_lps = nullptr;
     int32_t *d_order = nullptr, *d_cc = nullptr;
     int2 *d_hist = nullptr, *d_trace = nullptr;
-    int32_t n_wave = 0, n_block = 0;  // LPs of the one-wave / the 256-thread build
-    size_t lds_wave = 0, lds_block = 0;
+    // the launch groups, in launch order: [0] one wave, [1] 256 threads, [2] one wave with OPT, [3] 256 threads with OPT
+    int32_t n_group[4] = {0, 0, 0, 0};
+    size_t lds_group[4] = {0, 0, 0, 0};
+    // optional objectives (include/jslps_soft.h): rows per LP, whether they were set, and where they lie in the result block (in doubles)
+    std::vector<int32_t> n_opt;
+    std::vector<uint8_t> opt_set;
+    std::vector<int64_t> opt_offs;  // n + 1 entries
+    bool solved = false;            // a solve since the last upload: the result block holds its rows
     int uploaded = 0;
     int32_t launches = 0;
     DevState* h_states() const { return result.h.as<DevState>(); }
@@ -3476,21 +3485,31 @@ struct jslpp_pack {
     size_t res_rhs_off() const { return (sizeof(DevState) * (size_t)n + 255) & ~(size_t)255; }
     size_t res_rows_off() const { return (res_rhs_off() + sizeof(double) * (size_t)offs[n] + 255) & ~(size_t)255; }
     size_t res_tree_off() const { return (res_rows_off() + sizeof(int32_t) * (size_t)offs[n] + 255) & ~(size_t)255; }
-    size_t res_bytes() const { return tree ? res_tree_off() + sizeof(TreeRec) * (size_t)n : res_rows_off() + sizeof(int32_t) * (size_t)offs[n]; }
+    size_t res_plain_bytes() const { return tree ? res_tree_off() + sizeof(TreeRec) * (size_t)n : res_rows_off() + sizeof(int32_t) * (size_t)offs[n]; }
+    size_t res_opt_off() const { return (res_plain_bytes() + 255) & ~(size_t)255; }
+    size_t res_bytes() const { return opt_offs[n] ? res_opt_off() + sizeof(double) * (size_t)opt_offs[n] : res_plain_bytes(); }
     TreeRec* h_tree() const { return reinterpret_cast<TreeRec*>(result.h.p + res_tree_off()); }
-    size_t ivars_off(int32_t i) const { return sizeof(DevState) + 8 * (size_t)pk_image_doubles(RC[i], W[i]) + 4 * (size_t)pk_ints(RC[i], W[i]).total; }
+    size_t ints_off(int32_t i) const { return sizeof(DevState) + 8 * (size_t)pk_image_doubles(RC[i], W[i], n_opt[i]); }
+    size_t opt_rows_off(int32_t i) const { return sizeof(DevState) + 8 * (size_t)pk_opt_image_off(RC[i], W[i]); }
+    size_t ivars_off(int32_t i) const { return ints_off(i) + 4 * (size_t)pk_ints(RC[i], W[i]).total; }
 };
 static int pack_fail(int code, const char* what, int32_t i, const char* why) {
     snprintf(g_err, sizeof g_err, "%s: LP %d: %s", what, (int)i, why);
     return code;
 }
 // (H: the rows the image is sized for -- an LP's row capacity)
-static size_t pack_image_bytes(int32_t H, int32_t W) { return sizeof(DevState) + 8 * (size_t)pk_image_doubles(H, W) + 4 * (size_t)pk_ints(H, W).total; }
+static size_t pack_image_bytes(int32_t H, int32_t W, int32_t n_opt) {
+    return sizeof(DevState) + 8 * (size_t)pk_image_doubles(H, W, n_opt) + 4 * (size_t)pk_ints(H, W).total;
+}
 static_assert(sizeof(DevState) % 16 == 0, "an LP's matrix follows its DevState at a 16-byte boundary");
 
 extern "C" int64_t jslpp_lds_bytes(int32_t height, int32_t width) {
     if (height < 2 || width < 2) return 0;
     return (int64_t)pk_lds_bytes(height, width);
+}
+extern "C" int64_t jslps_lds_bytes(int32_t height, int32_t width, int32_t n_optional) {
+    if (height < 2 || width < 2 || n_optional < 0) return 0;
+    return (int64_t)pk_lds_bytes(height, width, n_optional);
 }
 
 static void pack_carve(jslpp_pack* p, Carver& cv) {
@@ -3525,14 +3544,13 @@ static int pack_init(jslpp_pack* p, int32_t max_pivots) {
     std::vector<PackLp> lps(n);
     std::vector<int32_t> order(n);
     int32_t k = 0;
-    for (int pass = 0; pass < 2; pass++)  // the one-wave LPs first, then the 256-thread ones, each in pack order
+    for (int g = 0; g < 4; g++)  // the one-wave LPs first, then the 256-thread ones, then the same two with optional objectives, each in pack order
         for (size_t i = 0; i < n; i++) {
-            const bool wave = (long long)p->RC[i] * p->W[i] <= PACK_CELLS_WAVE;
-            if (wave != (pass == 0)) continue;
+            const bool wave = (long long)p->RC[i] * p->W[i] <= PACK_CELLS_WAVE;  // (tableau cells at the row capacity, optional rows or not)
+            if ((wave ? 0 : 1) + (p->n_opt[i] > 0 ? 2 : 0) != g) continue;
             order[k++] = (int32_t)i;
-            const size_t lds = (size_t)pk_lds_bytes(p->RC[i], p->W[i]);
-            if (wave) { p->n_wave += 1; p->lds_wave = std::max(p->lds_wave, lds); }
-            else { p->n_block += 1; p->lds_block = std::max(p->lds_block, lds); }
+            p->n_group[g] += 1;
+            p->lds_group[g] = std::max(p->lds_group[g], (size_t)pk_lds_bytes(p->RC[i], p->W[i], p->n_opt[i]));
         }
     for (size_t i = 0; i < n; i++) {
         PackLp& m = lps[i];
@@ -3550,6 +3568,8 @@ static int pack_init(jslpp_pack* p, int32_t max_pivots) {
         m.batch = std::min(500, std::max(50, (int32_t)floor(sqrt((double)n_columns))));
         m.use_partial = n_columns > m.batch * 2;
         m.RC = p->RC[i];
+        m.n_opt = p->n_opt[i];
+        m.opt_out = p->n_opt[i] ? reinterpret_cast<double*>(p->result.d.p + p->res_opt_off()) + p->opt_offs[i] : nullptr;
     }
     if (p->tree && n) {  // every LP's heap, cut-list pool and free stack, carved out of one block
         std::vector<TreeLp> trees(n);
@@ -3563,6 +3583,8 @@ static int pack_init(jslpp_pack* p, int32_t max_pivots) {
             off += (size_t)tree_slot_bytes(p->cut_rows[i]) * slots;
             t.free_list = reinterpret_cast<int32_t*>(p->d_tree_mem + off);
             off += (sizeof(int32_t) * slots + 15) & ~(size_t)15;
+            t.best_opt = reinterpret_cast<double*>(p->d_tree_mem + off);
+            off += (sizeof(double) * (size_t)p->n_opt[i] + 15) & ~(size_t)15;
             t.rcoef = js_round(1.0 / p->precision[i]);
             t.cut_rows = p->cut_rows[i]; t.heap_cap = p->heap_cap[i]; t.max_nodes = p->max_nodes; t.pad = 0;
         }
@@ -3577,9 +3599,10 @@ static int pack_init(jslpp_pack* p, int32_t max_pivots) {
     return JSLP_OK;
 }
 
-// jslpp_pack_create and jslpt_pack_create (cut_rows / heap_cap: null for a pack without trees)
+// jslps_pack_create and jslps_tree_pack_create (cut_rows / heap_cap: null for a pack without trees; n_optional: null for none)
 static int pack_create(jslpp_pack** out, int device, int32_t n, const int32_t* height, const int32_t* width, const double* precision,
-                       const int32_t* cut_rows, const int32_t* heap_cap, int32_t trace_cap, int32_t max_pivots, int32_t max_nodes) {
+                       const int32_t* cut_rows, const int32_t* heap_cap, const int32_t* n_optional, int32_t trace_cap, int32_t max_pivots,
+                       int32_t max_nodes) {
     const bool tree = cut_rows != nullptr;
     if (!out || n < 0 || (n > 0 && (!height || !width || !precision))) return fail(JSLP_ERR_ARG, "pack_create: bad arguments");
     if (trace_cap < 0 || max_pivots < 0 || max_nodes < 0) return fail(JSLP_ERR_ARG, "pack_create: negative trace_cap, max_pivots or max_nodes");
@@ -3588,9 +3611,11 @@ static int pack_create(jslpp_pack** out, int device, int32_t n, const int32_t* h
         if (!(precision[i] == precision[i])) return pack_fail(JSLP_ERR_ARG, "pack_create", i, "precision is not a number");
         if (tree && (cut_rows[i] < 0 || heap_cap[i] < 1 || heap_cap[i] > (1 << 24)))
             return pack_fail(JSLP_ERR_ARG, "pack_create", i, "cut_rows is at least 0 and heap_cap between 1 and 2^24");
+        if (n_optional && n_optional[i] < 0) return pack_fail(JSLP_ERR_ARG, "pack_create", i, "n_optional is at least 0");
         const long long rc = (long long)height[i] + (tree ? cut_rows[i] : 0);
+        const long long no = n_optional ? n_optional[i] : 0;
         // (cells beyond the limit first: the byte count of an absurd shape must not overflow before it is compared)
-        if (rc * width[i] > JSLPP_LDS_LIMIT / 8 || pk_lds_bytes((int32_t)rc, width[i]) > (long long)WGLDS_MAX_BYTES)
+        if ((rc + no) * width[i] > JSLPP_LDS_LIMIT / 8 || pk_lds_bytes((int32_t)rc, width[i], (int32_t)no) > (long long)WGLDS_MAX_BYTES)
             return pack_fail(JSLP_ERR_UNSUPPORTED, "pack_create", i,
                              tree ? "the tableau's LDS image at its row capacity exceeds 64 KiB (jslpt_lds_bytes): fewer cut rows, or solve it through a jslp_engine"
                                   : "the tableau's LDS image exceeds 64 KiB (jslpp_lds_bytes): solve it through a jslp_engine");
@@ -3606,13 +3631,18 @@ static int pack_create(jslpp_pack** out, int device, int32_t n, const int32_t* h
     p->H.assign(height, height + n); p->W.assign(width, width + n); p->precision.assign(precision, precision + n);
     p->RC = p->H;
     p->tree = tree;
+    if (n_optional) p->n_opt.assign(n_optional, n_optional + n); else p->n_opt.assign((size_t)n, 0);
+    p->opt_set.assign((size_t)n, 0);
+    p->opt_offs.assign((size_t)n + 1, 0);
+    for (int32_t i = 0; i < n; i++) p->opt_offs[i + 1] = p->opt_offs[i] + (int64_t)p->n_opt[i] * width[i];
     if (tree) {
         p->cut_rows.assign(cut_rows, cut_rows + n); p->heap_cap.assign(heap_cap, heap_cap + n);
         p->max_nodes = max_nodes > 0 ? max_nodes : JSLPT_MAX_NODES_DEFAULT;
         for (int32_t i = 0; i < n; i++) {
             p->RC[i] = height[i] + cut_rows[i];
             const size_t slots = (size_t)heap_cap[i] + 3;
-            p->tree_mem_bytes += sizeof(TreeEntry) * (size_t)heap_cap[i] + (size_t)tree_slot_bytes(cut_rows[i]) * slots + ((sizeof(int32_t) * slots + 15) & ~(size_t)15);
+            p->tree_mem_bytes += sizeof(TreeEntry) * (size_t)heap_cap[i] + (size_t)tree_slot_bytes(cut_rows[i]) * slots + ((sizeof(int32_t) * slots + 15) & ~(size_t)15) +
+                                 ((sizeof(double) * (size_t)p->n_opt[i] + 15) & ~(size_t)15);
         }
     }
     p->evaluation.assign((size_t)n, 0.0);
@@ -3622,7 +3652,7 @@ static int pack_create(jslpp_pack** out, int device, int32_t n, const int32_t* h
     p->offs[0] = 0;
     for (int32_t i = 0; i < n; i++) {
         p->image_off[i] = p->image_bytes;
-        p->image_bytes += pack_image_bytes(p->RC[i], width[i]) + (tree ? (size_t)tree_ivars_bytes(p->RC[i], width[i]) : 0);
+        p->image_bytes += pack_image_bytes(p->RC[i], width[i], p->n_opt[i]) + (tree ? (size_t)tree_ivars_bytes(p->RC[i], width[i]) : 0);
         p->offs[i + 1] = p->offs[i] + p->RC[i];
     }
     const int rc = pack_init(p, max_pivots);
@@ -3632,17 +3662,50 @@ static int pack_create(jslpp_pack** out, int device, int32_t n, const int32_t* h
 }
 extern "C" int jslpp_pack_create(jslpp_pack** out, int device, int32_t n, const int32_t* height, const int32_t* width, const double* precision,
                                  int32_t trace_cap, int32_t max_pivots) {
-    return pack_create(out, device, n, height, width, precision, nullptr, nullptr, trace_cap, max_pivots, 0);
+    return jslps_pack_create(out, device, n, height, width, precision, nullptr, trace_cap, max_pivots);
+}
+extern "C" int jslps_pack_create(jslpp_pack** out, int device, int32_t n, const int32_t* height, const int32_t* width, const double* precision,
+                                 const int32_t* n_optional, int32_t trace_cap, int32_t max_pivots) {
+    return pack_create(out, device, n, height, width, precision, nullptr, nullptr, n_optional, trace_cap, max_pivots, 0);
 }
 extern "C" int jslpt_pack_create(jslpp_pack** out, int device, int32_t n, const int32_t* height, const int32_t* width, const double* precision,
                                  const int32_t* cut_rows, const int32_t* heap_cap, int32_t trace_cap, int32_t max_pivots, int32_t max_nodes) {
+    return jslps_tree_pack_create(out, device, n, height, width, precision, cut_rows, heap_cap, nullptr, trace_cap, max_pivots, max_nodes);
+}
+extern "C" int jslps_tree_pack_create(jslpp_pack** out, int device, int32_t n, const int32_t* height, const int32_t* width, const double* precision,
+                                      const int32_t* cut_rows, const int32_t* heap_cap, const int32_t* n_optional, int32_t trace_cap,
+                                      int32_t max_pivots, int32_t max_nodes) {
     if (n > 0 && (!cut_rows || !heap_cap)) return fail(JSLP_ERR_ARG, "pack_create: bad arguments");
     static const int32_t none = 0;
-    return pack_create(out, device, n, height, width, precision, cut_rows ? cut_rows : &none, heap_cap ? heap_cap : &none, trace_cap, max_pivots, max_nodes);
+    return pack_create(out, device, n, height, width, precision, cut_rows ? cut_rows : &none, heap_cap ? heap_cap : &none, n_optional, trace_cap,
+                       max_pivots, max_nodes);
 }
 extern "C" int64_t jslpt_lds_bytes(int32_t height, int32_t width, int32_t row_capacity) {
     if (height < 2 || width < 2 || row_capacity < height) return 0;
     return (int64_t)pk_lds_bytes(row_capacity, width);
+}
+extern "C" int64_t jslps_tree_lds_bytes(int32_t height, int32_t width, int32_t row_capacity, int32_t n_optional) {
+    if (height < 2 || width < 2 || row_capacity < height || n_optional < 0) return 0;
+    return (int64_t)pk_lds_bytes(row_capacity, width, n_optional);
+}
+extern "C" int jslps_pack_set_optional_objectives(jslpp_pack* p, int32_t i, const double* rows) {
+    if (!p) return fail(JSLP_ERR_ARG, "pack_set_optional_objectives: null pack");
+    if (i < 0 || i >= p->n) return fail(JSLP_ERR_ARG, "pack_set_optional_objectives: no such LP");
+    if (p->n_opt[i] == 0) return pack_fail(JSLP_ERR_ARG, "pack_set_optional_objectives", i, "created without optional objectives (n_optional)");
+    if (!rows) return pack_fail(JSLP_ERR_ARG, "pack_set_optional_objectives", i, "null rows");
+    memcpy(p->h_image.p + p->image_off[i] + p->opt_rows_off(i), rows, sizeof(double) * (size_t)p->n_opt[i] * p->W[i]);
+    p->opt_set[i] = 1;
+    p->uploaded = 0;  // (the device copy is stale until the next upload)
+    return JSLP_OK;
+}
+extern "C" int jslps_pack_get_optional_objectives(jslpp_pack* p, int32_t i, double* rows, int32_t* n_out) {
+    if (!p) return fail(JSLP_ERR_ARG, "pack_get_optional_objectives: null pack");
+    if (i < 0 || i >= p->n) return fail(JSLP_ERR_ARG, "pack_get_optional_objectives: no such LP");
+    if (!p->uploaded || !p->solved) return fail(JSLP_ERR_STATE, "pack_get_optional_objectives before a solve: the result block holds no rows yet");
+    if (n_out) *n_out = p->n_opt[i];
+    if (rows && p->n_opt[i])
+        memcpy(rows, reinterpret_cast<const double*>(p->result.h.p + p->res_opt_off()) + p->opt_offs[i], sizeof(double) * (size_t)p->n_opt[i] * p->W[i]);
+    return JSLP_OK;
 }
 extern "C" int jslpt_pack_set_integers(jslpp_pack* p, int32_t i, const int32_t* var_indexes, int32_t n) {
     if (!p) return fail(JSLP_ERR_ARG, "pack_set_integers: null pack");
@@ -3699,7 +3762,7 @@ extern "C" int jslpp_pack_set(jslpp_pack* p, int32_t i, const double* matrix, co
     if (matrix && matrix != m) memcpy(m, matrix, sizeof(double) * (size_t)H * W);
     // the integer block, as k_upload_finish builds an engine's: the maps, their inverses, the unrestricted flags
     const PackInts io = pk_ints(RC, W);
-    int32_t* ints = reinterpret_cast<int32_t*>(img + sizeof(DevState) + 8 * (size_t)pk_image_doubles(RC, W));
+    int32_t* ints = reinterpret_cast<int32_t*>(img + p->ints_off(i));
     memset(ints, 0, 4 * (size_t)io.total);
     int32_t *vibr = ints + io.vibr, *vibc = ints + io.vibc, *rbv = ints + io.rbv, *cbv = ints + io.cbv;
     uint8_t* unr = reinterpret_cast<uint8_t*>(ints + io.unr);
@@ -3716,6 +3779,9 @@ extern "C" int jslpp_pack_upload(jslpp_pack* p) {
     if (!p) return fail(JSLP_ERR_ARG, "pack_upload: null pack");
     for (int32_t i = 0; i < p->n; i++)
         if (!p->is_set[i]) return pack_fail(JSLP_ERR_STATE, "pack_upload", i, "never set (jslpp_pack_set)");
+    for (int32_t i = 0; i < p->n; i++)
+        if (p->n_opt[i] && !p->opt_set[i])
+            return pack_fail(JSLP_ERR_STATE, "pack_upload", i, "optional objectives reserved and never set (jslps_pack_set_optional_objectives)");
     HIPC(hipSetDevice(p->device));
     for (int32_t i = 0; i < p->n; i++) {  // the state an upload leaves (k_upload_finish)
         DevState st;
@@ -3734,6 +3800,7 @@ extern "C" int jslpp_pack_upload(jslpp_pack* p) {
     HIPC(hipStreamSynchronize(p->stream));
     p->uploaded = 1;
     p->tree_ran = false;
+    p->solved = false;
     return JSLP_OK;
 }
 
@@ -3766,20 +3833,24 @@ extern "C" int jslpp_pack_simplex(jslpp_pack* p, const int32_t* check_cycles, js
     a.rows = reinterpret_cast<int32_t*>(p->result.d.p + p->res_rows_off());
     const bool dbg = debug_launch_on();
     HIPC(hipEventRecord(p->ev_begin, s));
-    for (int build = 0; build < 2; build++) {
-        const int32_t cnt = build ? p->n_block : p->n_wave;
+    int32_t first = 0;
+    for (int g = 0; g < 4; first += p->n_group[g], g++) {  // one launch per kernel build that has LPs
+        const int32_t cnt = p->n_group[g];
         if (!cnt) continue;
-        const int threads = build ? 256 : 64;
-        const size_t lds = build ? p->lds_block : p->lds_wave;
-        a.order = p->d_order + (build ? p->n_wave : 0);
+        const int threads = (g & 1) ? 256 : 64;
+        const size_t lds = p->lds_group[g];
+        a.order = p->d_order + first;
+        a.opt = g >> 1;
         (void)packed_launch(threads, (unsigned)cnt, lds, a, s);
         HIPC(hipGetLastError());
         p->launches += 1;
-        if (dbg) fprintf(stderr, "[jslp] launch k_simplex_packed<%d> n %d lds %zu\n", threads, (int)cnt, lds);
+        if (dbg && a.opt) fprintf(stderr, "[jslp] launch k_simplex_packed<%d,opt 1> n %d lds %zu\n", threads, (int)cnt, lds);
+        else if (dbg) fprintf(stderr, "[jslp] launch k_simplex_packed<%d> n %d lds %zu\n", threads, (int)cnt, lds);
     }
     HIPC(hipEventRecord(p->ev_end, s));
     HIPC(hipMemcpyAsync(p->result.h.p, p->result.d.p, p->res_bytes(), hipMemcpyDeviceToHost, s));
     HIPC(hipStreamSynchronize(s));
+    p->solved = true;
     float ms = 0;
     if (device_ms && hipEventElapsedTime(&ms, p->ev_begin, p->ev_end) == hipSuccess) *device_ms = ms;
     if (status) for (int32_t i = 0; i < n; i++) status[i] = JSLP_OK;
@@ -3828,10 +3899,10 @@ extern "C" int jslpp_pack_download(jslpp_pack* p, int32_t i, double* matrix, int
     HIPC(hipSetDevice(p->device));
     HIPC(hipStreamSynchronize(p->stream));
     const int32_t H = p->H[i], W = p->W[i], RC = p->RC[i], n_idx = pk_n_idx(RC, W);
-    std::vector<char> img(pack_image_bytes(RC, W));
+    std::vector<char> img(pack_image_bytes(RC, W, p->n_opt[i]));
     HIPC(hipMemcpy(img.data(), p->d_image + p->image_off[i], img.size(), hipMemcpyDeviceToHost));
     const PackInts io = pk_ints(RC, W);
-    const int32_t* ints = reinterpret_cast<const int32_t*>(img.data() + sizeof(DevState) + 8 * (size_t)pk_image_doubles(RC, W));
+    const int32_t* ints = reinterpret_cast<const int32_t*>(img.data() + p->ints_off(i));
     if (matrix) memcpy(matrix, img.data() + sizeof(DevState), sizeof(double) * (size_t)H * W);
     if (var_index_by_row) memcpy(var_index_by_row, ints + io.vibr, sizeof(int32_t) * (size_t)H);
     if (var_index_by_col) memcpy(var_index_by_col, ints + io.vibc, sizeof(int32_t) * (size_t)W);
@@ -3905,20 +3976,24 @@ extern "C" int jslpt_pack_branch_and_cut(jslpp_pack* p, const int32_t* check_cyc
     const bool dbg = debug_launch_on();
     p->tree_ran = true;
     HIPC(hipEventRecord(p->ev_begin, s));
-    for (int build = 0; build < 2; build++) {
-        const int32_t cnt = build ? p->n_block : p->n_wave;
+    int32_t first = 0;
+    for (int g = 0; g < 4; first += p->n_group[g], g++) {  // one launch per kernel build that has LPs
+        const int32_t cnt = p->n_group[g];
         if (!cnt) continue;
-        const int threads = build ? 256 : 64;
-        const size_t lds = build ? p->lds_block : p->lds_wave;
-        a.order = p->d_order + (build ? p->n_wave : 0);
+        const int threads = (g & 1) ? 256 : 64;
+        const size_t lds = p->lds_group[g];
+        a.order = p->d_order + first;
+        a.opt = g >> 1;
         (void)packed_launch(threads, (unsigned)cnt, lds, a, s);
         HIPC(hipGetLastError());
         p->launches += 1;
-        if (dbg) fprintf(stderr, "[jslp] launch k_tree_packed<%d> n %d lds %zu\n", threads, (int)cnt, lds);
+        if (dbg && a.opt) fprintf(stderr, "[jslp] launch k_tree_packed<%d,opt 1> n %d lds %zu\n", threads, (int)cnt, lds);
+        else if (dbg) fprintf(stderr, "[jslp] launch k_tree_packed<%d> n %d lds %zu\n", threads, (int)cnt, lds);
     }
     HIPC(hipEventRecord(p->ev_end, s));
     HIPC(hipMemcpyAsync(p->result.h.p, p->result.d.p, p->res_bytes(), hipMemcpyDeviceToHost, s));
     HIPC(hipStreamSynchronize(s));
+    p->solved = true;
     float ms = 0;
     if (device_ms && hipEventElapsedTime(&ms, p->ev_begin, p->ev_end) == hipSuccess) *device_ms = ms;
     if (status) for (int32_t i = 0; i < n; i++) status[i] = JSLP_OK;

@@ -38,9 +38,19 @@ __host__ __device__ __forceinline__ PackInts pk_ints(int32_t H, int32_t W) {
     o.total = o.unr + pk_pad4((n + 3) / 4);
     return o;
 }
-__host__ __device__ __forceinline__ long long pk_image_doubles(int32_t H, int32_t W) { return ((long long)H * W + 1) & ~1LL; }  // the matrix in the image
-__host__ __device__ __forceinline__ long long pk_lds_doubles(int32_t H, int32_t W) { return ((long long)H * pk_stride(W) + H + 1) & ~1LL; }
-__host__ __device__ __forceinline__ long long pk_lds_bytes(int32_t H, int32_t W) { return 8 * pk_lds_doubles(H, W) + 4LL * pk_ints(H, W).total; }
+// An LP with n_opt >= 1 optional objectives (include/jslps_soft.h) carries their rows in both places: in the image n_opt x W doubles
+// (stride W) directly behind the matrix, at pk_opt_image_off; in LDS n_opt x S doubles directly behind the pivot column, with the same odd
+// stride S.  With n_opt == 0 every offset and byte count below is what it was before there were such rows.
+__host__ __device__ __forceinline__ long long pk_opt_image_off(int32_t H, int32_t W) { return ((long long)H * W + 1) & ~1LL; }  // in doubles, behind the matrix
+__host__ __device__ __forceinline__ long long pk_image_doubles(int32_t H, int32_t W, int32_t n_opt = 0) {  // the matrix (and the optional rows) in the image
+    return (pk_opt_image_off(H, W) + (long long)n_opt * W + 1) & ~1LL;
+}
+__host__ __device__ __forceinline__ long long pk_lds_doubles(int32_t H, int32_t W, int32_t n_opt = 0) {
+    return ((long long)H * pk_stride(W) + H + (long long)n_opt * pk_stride(W) + 1) & ~1LL;
+}
+__host__ __device__ __forceinline__ long long pk_lds_bytes(int32_t H, int32_t W, int32_t n_opt = 0) {
+    return 8 * pk_lds_doubles(H, W, n_opt) + 4LL * pk_ints(H, W).total;
+}
 
 // One LP of a pack: built on the host ONCE, at create; one entry per workgroup.
 struct PackLp {
@@ -54,6 +64,8 @@ struct PackLp {
     int32_t iters_cap;
     int32_t batch, use_partial;  // partial-pricing parameters (simplex.ts:118-127)
     int32_t RC;         // rows the image and the LDS layout are sized for: H, or H + cut rows in a pack made by jslpt_pack_create
+    int32_t n_opt;      // optional objectives (0: the LP runs in an OPT = false build)
+    double* opt_out;    // this LP's n_opt x W optional rows in the result block
 };
 // arguments of one launch, travelling as bytes between the units (the same struct in every unit)
 struct PackLaunch {
@@ -61,6 +73,7 @@ struct PackLaunch {
     const int32_t* order;  // blockIdx.x -> LP index (the LPs of this build)
     const int32_t* cc;     // per-LP checkForCycles, or nullptr: cc_all for every LP
     int32_t cc_all, kind;  // kind 0: k_simplex_packed, 1: k_tree_packed (jslp_tree.hip.h)
+    int32_t opt, pad;      // 1: the OPT = true build (every LP of `order` has optional objectives)
     void* states;          // result block: DevState per LP (LP order) ...
     double* rhs;           // ... the RHS columns one after the other ...
     int32_t* rows;         // ... and the row maps
@@ -102,10 +115,11 @@ struct PkRun { int phase, it1, it2, hist_n, entered2, outcome, unbounded_col; };
 // are the core's own functions.  Bounded by iters_left.  The caller puts a barrier in front (LDS complete) and one behind.
 // A SECOND COPY of k_simplex_packed's loop below, line for line, on purpose: with the kernel calling this function its 256-thread build
 // took 59 VGPRs instead of 57 (profiles/packed_tree_kernel_resources.md), so the kernel keeps its own text.  Change both together.
-template <int THREADS>
+// OPT: the LP has n_opt >= 1 optional objectives, their rows at oo (stride S); every line of theirs sits under `if constexpr (OPT)`.
+template <int THREADS, bool OPT>
 __device__ __forceinline__ PkRun pk_simplex(double* A, double* pcol, const int H, const int W, const int S, int32_t* vibr, int32_t* vibc, int32_t* rbv,
                                             int32_t* cbv, const uint8_t* unr, const double precision, const int check_cycles, const PackLp& m, int2* ghist,
-                                            int2* gtrace, PackSmem& sm, int& iters_left, long long& trace_n) {
+                                            int2* gtrace, PackSmem& sm, int& iters_left, long long& trace_n, double* oo, const int n_opt) {
     const int tid = threadIdx.x;
     // the row update's thread grid: CW columns (a power of two covering the width, at most the workgroup) x RP rows at a time
     int cshift = 0;
@@ -163,11 +177,39 @@ __device__ __forceinline__ PkRun pk_simplex(double* A, double* pcol, const int H
                 }
             }
             e = pk_reduce<THREADS>(e, PriceFirst(), sm.g);
+            int opt_row = -1;  // which optional objective named the entering column (-1: the cost row)
+            if constexpr (OPT) {
+                // simplex.ts:221-263 as select_step restates it: no column prices out on the cost row -> objective by objective in priority
+                // order, among the columns within +-precision on the cost row and on every earlier objective (every batch was scanned
+                // without a winner, so the deferred set spans all of them): the largest value above precision, first index on ties
+                for (int o = 0; e.i == 0 && o < n_opt; o++) {
+                    Cand x; x.v = precision; x.i = 0; x.b = 0;
+                    for (int col = 1 + tid; col < W; col += THREADS) {
+                        const double rc0 = A[col];
+                        bool deferred = -precision < rc0 && rc0 < precision;
+                        for (int q = 0; deferred && q < o; q++) {
+                            const double rq = oo[q * S + col];
+                            deferred = -precision < rq && rq < precision;
+                        }
+                        if (!deferred) continue;
+                        const double rc = oo[o * S + col];
+                        if (-precision < rc && rc < precision) continue;
+                        const bool un = unr[vibc[col]] != 0;
+                        const double val = (un && rc < 0) ? -rc : rc;
+                        const bool take = val > x.v;  // strict: the first index wins ties inside a thread (my columns ascend)
+                        x.v = take ? val : x.v;
+                        x.i = take ? col : x.i;
+                    }
+                    e = pk_reduce<THREADS>(x, PriceFirst(), sm.g);
+                    if (e.i != 0) opt_row = o;
+                }
+            }
             if (e.i == 0) { outcome = 1; break; }  // optimal (simplex.ts:265-269)
             pc = e.i;
             int neg_flag;
-            {   // isReducedCostNegative of the winner
-                const double rc = A[pc];
+            {   // isReducedCostNegative of the winner, from the row that named it
+                double rc = A[pc];
+                if constexpr (OPT) { if (opt_row >= 0) rc = oo[opt_row * S + pc]; }
                 neg_flag = (unr[vibc[pc]] != 0 && rc < 0) ? 1 : 0;
             }
             // ratio test (simplex.ts:271-296) in its order-free form: the first row passing the degenerate test wins
@@ -248,6 +290,26 @@ __device__ __forceinline__ PkRun pk_simplex(double* A, double* pcol, const int H
                 if (nonzero16(p)) row[col] = eliminate(row[col], k, p);  // :376-386, both roundings
             }
         }
+        if constexpr (OPT) {
+            // the optional objectives (simplex.ts:394-412) as prepare_pivot restates them: the same elimination with EXACT `!= 0` tests, on the
+            // final pivot row (lazy zeroing included), one (objective, column) cell per thread and step.  Column pc waits for the barrier:
+            // every thread has read an objective's coefficient before its owner overwrites it
+            for (int q = tid; q < n_opt * W; q += THREADS) {
+                const int o = q / W, col = q - o * W;
+                if (col == pc) continue;
+                double* rc = oo + o * S;
+                const double coefficient = rc[pc];
+                if (coefficient != 0.0) {
+                    const double v0 = prow[col];
+                    if (v0 != 0.0) rc[col] = eliminate(rc[col], coefficient, v0);
+                }
+            }
+            __syncthreads();
+            for (int o = tid; o < n_opt; o += THREADS) {
+                const double coefficient = oo[o * S + pc];
+                if (coefficient != 0.0) oo[o * S + pc] = -coefficient / quot;  // :410
+            }
+        }
         __syncthreads();
     }
     PkRun o;
@@ -260,7 +322,9 @@ __device__ __forceinline__ PkRun pk_simplex(double* A, double* pcol, const int H
 // one-wave workgroup) and every reduction is wave_reduce alone; THREADS = 256: four waves.  Every loop is bounded by the pivot cap; the
 // kernel waits on nothing outside its workgroup.  The image and the LDS layout are those of RC rows (RC = H but in a pack with cut rows,
 // include/jslpt_tree.h), of which H hold the tableau.
-template <int THREADS>
+// OPT = true: the LPs with optional objectives (include/jslps_soft.h): their rows come with the image, live in LDS behind the pivot column,
+// and go back into the image and into the result block with everything else.
+template <int THREADS, bool OPT>
 __global__ void __launch_bounds__(THREADS) k_simplex_packed(const PackLp* __restrict__ lps, const int32_t* __restrict__ order, const int32_t* __restrict__ cc,
                                                             int cc_all, DevState* __restrict__ out_states, double* __restrict__ out_rhs,
                                                             int32_t* __restrict__ out_rows) {
@@ -273,10 +337,13 @@ __global__ void __launch_bounds__(THREADS) k_simplex_packed(const PackLp* __rest
     const PackInts io = pk_ints(RC, W);
     const double precision = m.precision;
     const int check_cycles = cc ? cc[idx] : cc_all;
+    int n_opt = 0;
+    if constexpr (OPT) n_opt = m.n_opt;
     // LDS, indexed from the extern base: ds_read / ds_write, never flat
     double* A = pk_lds;
     double* pcol = pk_lds + RC * S;
-    int32_t* ints = reinterpret_cast<int32_t*>(pk_lds + pk_lds_doubles(RC, W));
+    double* oo = pcol + RC;  // (OPT) the optional rows, stride S
+    int32_t* ints = reinterpret_cast<int32_t*>(pk_lds + pk_lds_doubles(RC, W, n_opt));
     int32_t* vibr = ints + io.vibr;
     int32_t* vibc = ints + io.vibc;
     int32_t* rbv = ints + io.rbv;
@@ -286,7 +353,8 @@ __global__ void __launch_bounds__(THREADS) k_simplex_packed(const PackLp* __rest
     char* image = many_global(m.image);
     DevState* st = reinterpret_cast<DevState*>(image);
     double2* gA = reinterpret_cast<double2*>(image + sizeof(DevState));
-    int4* gI = reinterpret_cast<int4*>(image + sizeof(DevState) + 8 * pk_image_doubles(RC, W));
+    int4* gI = reinterpret_cast<int4*>(image + sizeof(DevState) + 8 * pk_image_doubles(RC, W, n_opt));
+    double* gO = reinterpret_cast<double*>(image + sizeof(DevState)) + pk_opt_image_off(RC, W);  // (OPT) the optional rows, stride W
     int2* ghist = many_global(m.hist);
     int2* gtrace = many_global(m.trace);
 
@@ -302,6 +370,11 @@ __global__ void __launch_bounds__(THREADS) k_simplex_packed(const PackLp* __rest
         }
     }
     for (int q = tid; q < words; q += THREADS) reinterpret_cast<int4*>(ints)[q] = gI[q];
+    if constexpr (OPT)
+        for (int q = tid; q < n_opt * W; q += THREADS) {
+            const int o = q / W;
+            oo[o * S + (q - o * W)] = gO[q];
+        }
     if (tid == 0) begin_simplex(st, m.iters_cap);  // simplex.ts:14-23
     long long trace_n = st->trace_n;
     __syncthreads();
@@ -363,11 +436,39 @@ __global__ void __launch_bounds__(THREADS) k_simplex_packed(const PackLp* __rest
                 }
             }
             e = pk_reduce<THREADS>(e, PriceFirst(), sm.g);
+            int opt_row = -1;  // which optional objective named the entering column (-1: the cost row)
+            if constexpr (OPT) {
+                // simplex.ts:221-263 as select_step restates it: no column prices out on the cost row -> objective by objective in priority
+                // order, among the columns within +-precision on the cost row and on every earlier objective (every batch was scanned
+                // without a winner, so the deferred set spans all of them): the largest value above precision, first index on ties
+                for (int o = 0; e.i == 0 && o < n_opt; o++) {
+                    Cand x; x.v = precision; x.i = 0; x.b = 0;
+                    for (int col = 1 + tid; col < W; col += THREADS) {
+                        const double rc0 = A[col];
+                        bool deferred = -precision < rc0 && rc0 < precision;
+                        for (int q = 0; deferred && q < o; q++) {
+                            const double rq = oo[q * S + col];
+                            deferred = -precision < rq && rq < precision;
+                        }
+                        if (!deferred) continue;
+                        const double rc = oo[o * S + col];
+                        if (-precision < rc && rc < precision) continue;
+                        const bool un = unr[vibc[col]] != 0;
+                        const double val = (un && rc < 0) ? -rc : rc;
+                        const bool take = val > x.v;  // strict: the first index wins ties inside a thread (my columns ascend)
+                        x.v = take ? val : x.v;
+                        x.i = take ? col : x.i;
+                    }
+                    e = pk_reduce<THREADS>(x, PriceFirst(), sm.g);
+                    if (e.i != 0) opt_row = o;
+                }
+            }
             if (e.i == 0) { outcome = 1; break; }  // optimal (simplex.ts:265-269)
             pc = e.i;
             int neg_flag;
-            {   // isReducedCostNegative of the winner
-                const double rc = A[pc];
+            {   // isReducedCostNegative of the winner, from the row that named it
+                double rc = A[pc];
+                if constexpr (OPT) { if (opt_row >= 0) rc = oo[opt_row * S + pc]; }
                 neg_flag = (unr[vibc[pc]] != 0 && rc < 0) ? 1 : 0;
             }
             // ratio test (simplex.ts:271-296) in its order-free form: the first row passing the degenerate test wins
@@ -448,6 +549,26 @@ __global__ void __launch_bounds__(THREADS) k_simplex_packed(const PackLp* __rest
                 if (nonzero16(p)) row[col] = eliminate(row[col], k, p);  // :376-386, both roundings
             }
         }
+        if constexpr (OPT) {
+            // the optional objectives (simplex.ts:394-412) as prepare_pivot restates them: the same elimination with EXACT `!= 0` tests, on the
+            // final pivot row (lazy zeroing included), one (objective, column) cell per thread and step.  Column pc waits for the barrier:
+            // every thread has read an objective's coefficient before its owner overwrites it
+            for (int q = tid; q < n_opt * W; q += THREADS) {
+                const int o = q / W, col = q - o * W;
+                if (col == pc) continue;
+                double* rc = oo + o * S;
+                const double coefficient = rc[pc];
+                if (coefficient != 0.0) {
+                    const double v0 = prow[col];
+                    if (v0 != 0.0) rc[col] = eliminate(rc[col], coefficient, v0);
+                }
+            }
+            __syncthreads();
+            for (int o = tid; o < n_opt; o += THREADS) {
+                const double coefficient = oo[o * S + pc];
+                if (coefficient != 0.0) oo[o * S + pc] = -coefficient / quot;  // :410
+            }
+        }
         __syncthreads();
     }
     // ---- epilogue: everything back once -------------------------------------------------------------------------------------------
@@ -464,6 +585,15 @@ __global__ void __launch_bounds__(THREADS) k_simplex_packed(const PackLp* __rest
     for (int r = tid; r < H; r += THREADS) {
         out_rhs[m.out_off + r] = A[r * S];
         out_rows[m.out_off + r] = vibr[r];
+    }
+    if constexpr (OPT) {  // the final rows: into the image (a second call continues from them) and home with the result block
+        double* out_opt = many_global(m.opt_out);
+        for (int q = tid; q < n_opt * W; q += THREADS) {
+            const int o = q / W;
+            const double v = oo[o * S + (q - o * W)];
+            gO[q] = v;
+            out_opt[q] = v;
+        }
     }
     if (tid == 0) {
         st->phase = phase;
@@ -495,10 +625,14 @@ __global__ void __launch_bounds__(THREADS) k_simplex_packed(const PackLp* __rest
 static int packed_launch_impl(int threads, unsigned grid, size_t lds, const void* bytes, hipStream_t s) {
     const PackLaunch a = *static_cast<const PackLaunch*>(bytes);
     DevState* states = static_cast<DevState*>(a.states);
-    if (threads == 64)
-        hipLaunchKernelGGL(k_simplex_packed<64>, dim3(grid), dim3(64), lds, s, a.lps, a.order, a.cc, a.cc_all, states, a.rhs, a.rows);
+    if (threads == 64 && !a.opt)
+        hipLaunchKernelGGL((k_simplex_packed<64, false>), dim3(grid), dim3(64), lds, s, a.lps, a.order, a.cc, a.cc_all, states, a.rhs, a.rows);
+    else if (threads == 256 && !a.opt)
+        hipLaunchKernelGGL((k_simplex_packed<256, false>), dim3(grid), dim3(256), lds, s, a.lps, a.order, a.cc, a.cc_all, states, a.rhs, a.rows);
+    else if (threads == 64)
+        hipLaunchKernelGGL((k_simplex_packed<64, true>), dim3(grid), dim3(64), lds, s, a.lps, a.order, a.cc, a.cc_all, states, a.rhs, a.rows);
     else if (threads == 256)
-        hipLaunchKernelGGL(k_simplex_packed<256>, dim3(grid), dim3(256), lds, s, a.lps, a.order, a.cc, a.cc_all, states, a.rhs, a.rows);
+        hipLaunchKernelGGL((k_simplex_packed<256, true>), dim3(grid), dim3(256), lds, s, a.lps, a.order, a.cc, a.cc_all, states, a.rhs, a.rows);
     else
         return -1;
     return (int)hipPeekAtLastError();

@@ -5,7 +5,8 @@
 // Two parts like jslp_packed.hip.h (included behind it, once per unit): the layout (always) and the kernels (-DJSLP_PACKED_KERNELS).
 //
 // Memory of one LP:
-//   LDS     the tableau RC x S doubles, the pivot column, the integer block sized for RC rows -- jslpt_lds_bytes;
+//   LDS     the tableau RC x S doubles, the pivot column, (the optional rows, n_opt x S,) the integer block sized for RC rows --
+//           jslpt_lds_bytes / jslps_tree_lds_bytes;
 //   image   [DevState | matrix | integer block | n_int, the integer variables' indexes]: the upload, and from iteration 1 on the SAVED
 //           ROOT (written once, read by every later node: an L2-resident restore; the tableau is never written back);
 //   heap    heap_cap entries of 16 bytes {relaxedEvaluation, seq, slot} -- min-heap.ts as it is, executed by thread 0;
@@ -24,6 +25,7 @@ struct TreeLp {
     int32_t* free_list;
     double rcoef;  // Math.round(1 / precision), computed on the host like decode_state's
     int32_t cut_rows, heap_cap, max_nodes, pad;
+    double* best_opt;  // n_opt doubles next to the heap: column 0 of the incumbent's optional rows (thread 0 alone reads and writes them)
 };
 enum { TREE_OK = 0, TREE_ERR_NODES = 1, TREE_ERR_HEAP = 2, TREE_ERR_CUTS = 3, TREE_ERR_BRANCH = 4 };
 struct TreeRec {  // what the kernel reports per LP next to its DevState
@@ -92,7 +94,10 @@ __device__ __forceinline__ double tree_round(double x) {
 // Tableau.solve() of LP order[blockIdx.x] under the default branch-and-cut service.  THREADS as k_simplex_packed.  Bounded: every
 // simplex by the pivot cap, the node loop by max_nodes evaluations and by the heap (each iteration pops one entry; pushes are
 // bounded by heap_cap); the kernel waits on nothing outside its workgroup.
-template <int THREADS>
+// OPT = true: the LPs with optional objectives (include/jslps_soft.h).  Their rows are saved with the root and come back with every restore
+// (backup.ts:35-43, 94-104), addCutConstraints leaves them alone, and a node whose evaluation EQUALS the incumbent's is compared with it
+// objective by objective on column 0 of the rows (branch-and-cut.ts:107-127).
+template <int THREADS, bool OPT>
 __global__ void __launch_bounds__(THREADS) k_tree_packed(const PackLp* __restrict__ lps, const TreeLp* __restrict__ trees, const int32_t* __restrict__ order,
                                                          const int32_t* __restrict__ cc, int cc_all, DevState* __restrict__ out_states,
                                                          double* __restrict__ out_rhs, int32_t* __restrict__ out_rows, TreeRec* __restrict__ out_tree) {
@@ -106,9 +111,12 @@ __global__ void __launch_bounds__(THREADS) k_tree_packed(const PackLp* __restric
     const PackInts io = pk_ints(RC, W);
     const double precision = m.precision;
     const int check_cycles = cc ? cc[idx] : cc_all;
+    int n_opt = 0;
+    if constexpr (OPT) n_opt = m.n_opt;
     double* A = pk_lds;
     double* pcol = pk_lds + RC * S;
-    int32_t* ints = reinterpret_cast<int32_t*>(pk_lds + pk_lds_doubles(RC, W));
+    double* oo = pcol + RC;  // (OPT) the optional rows, stride S
+    int32_t* ints = reinterpret_cast<int32_t*>(pk_lds + pk_lds_doubles(RC, W, n_opt));
     int32_t* vibr = ints + io.vibr;
     int32_t* vibc = ints + io.vibc;
     int32_t* rbv = ints + io.rbv;
@@ -117,8 +125,10 @@ __global__ void __launch_bounds__(THREADS) k_tree_packed(const PackLp* __restric
     char* image = many_global(m.image);
     DevState* st = reinterpret_cast<DevState*>(image);
     double2* gA = reinterpret_cast<double2*>(image + sizeof(DevState));
-    int4* gI = reinterpret_cast<int4*>(image + sizeof(DevState) + 8 * pk_image_doubles(RC, W));
-    const int32_t* gV = reinterpret_cast<const int32_t*>(image + sizeof(DevState) + 8 * pk_image_doubles(RC, W) + 4LL * io.total);
+    int4* gI = reinterpret_cast<int4*>(image + sizeof(DevState) + 8 * pk_image_doubles(RC, W, n_opt));
+    const int32_t* gV = reinterpret_cast<const int32_t*>(image + sizeof(DevState) + 8 * pk_image_doubles(RC, W, n_opt) + 4LL * io.total);
+    double* gO = reinterpret_cast<double*>(image + sizeof(DevState)) + pk_opt_image_off(RC, W);  // (OPT) the optional rows, stride W
+    double* best_opt = many_global(t.best_opt);
     const int n_int = gV[0];
     const int32_t* ivars = gV + 4;
     int2* ghist = many_global(m.hist);
@@ -141,6 +151,11 @@ __global__ void __launch_bounds__(THREADS) k_tree_packed(const PackLp* __restric
             }
         }
         for (int q = tid; q < words; q += THREADS) reinterpret_cast<int4*>(ints)[q] = gI[q];
+        if constexpr (OPT)
+            for (int q = tid; q < n_opt * W; q += THREADS) {
+                const int o = q / W;
+                oo[o * S + (q - o * W)] = gO[q];
+            }
     };
     auto save = [&]() {
         for (int q = tid; q < pairs; q += THREADS) {
@@ -152,6 +167,11 @@ __global__ void __launch_bounds__(THREADS) k_tree_packed(const PackLp* __restric
             gA[q] = v;
         }
         for (int q = tid; q < words; q += THREADS) gI[q] = reinterpret_cast<const int4*>(ints)[q];
+        if constexpr (OPT)
+            for (int q = tid; q < n_opt * W; q += THREADS) {
+                const int o = q / W;
+                gO[q] = oo[o * S + (q - o * W)];
+            }
     };
     // addCutConstraints (cutting-strategies.ts:16-72) of the list in `slot` on the restored root: every cut row reads rows below H0
     // and the restored maps only, so the rows are built side by side, one (cut, column) cell per thread and step; returns the height
@@ -187,6 +207,9 @@ __global__ void __launch_bounds__(THREADS) k_tree_packed(const PackLp* __restric
 
     restore();
     long long trace_n = st->trace_n;
+    if constexpr (OPT)  // bestOptionalObjectivesEvaluations (:66-69)
+        if (tid == 0)
+            for (int o = 0; o < n_opt; o++) best_opt[o] = INFINITY;
     __syncthreads();
 
     int H = H0, feasible = 1, unb_var = -1, iters_left = m.iters_cap;
@@ -226,7 +249,7 @@ __global__ void __launch_bounds__(THREADS) k_tree_packed(const PackLp* __restric
         }
         root = false;
         iters_left = m.iters_cap;
-        o = pk_simplex<THREADS>(A, pcol, H, W, S, vibr, vibc, rbv, cbv, unr, precision, check_cycles, m, ghist, gtrace, sm.ps, iters_left, trace_n);
+        o = pk_simplex<THREADS, OPT>(A, pcol, H, W, S, vibr, vibc, rbv, cbv, unr, precision, check_cycles, m, ghist, gtrace, sm.ps, iters_left, trace_n, oo, n_opt);
         __syncthreads();
         if (o.outcome >= 5) { serr = o.outcome == 5 ? (int)ERR_ITER_LIMIT : (int)ERR_HIST_FULL; break; }
         iterations += 1;
@@ -237,7 +260,26 @@ __global__ void __launch_bounds__(THREADS) k_tree_packed(const PackLp* __restric
         else if (o.outcome == 2)
             evaluation = -INFINITY;
         if (n_int == 0) break;  // no integer variables: a plain simplex() (tableau.ts:250-258)
-        if (!feasible || evaluation > best_eval || evaluation == best_eval) { release(cur_slot); continue; }  // :99-127
+        if constexpr (OPT) {
+            if (!feasible || evaluation > best_eval) { release(cur_slot); continue; }  // :99-105
+            if (evaluation == best_eval) {  // :107-127: the tie is broken on the optional objectives, in priority order (NaN decides nothing)
+                if (tid == 0) {
+                    int worse = 1;
+                    for (int k = 0; k < n_opt; k++) {
+                        const double mine = oo[k * S], best = best_opt[k];
+                        if (mine > best) break;
+                        if (mine < best) { worse = 0; break; }
+                    }
+                    sm.code = worse;
+                }
+                __syncthreads();
+                const int worse = sm.code;
+                __syncthreads();  // (sm.code may be written again)
+                if (worse) { release(cur_slot); continue; }
+            }
+        } else {
+            if (!feasible || evaluation > best_eval || evaluation == best_eval) { release(cur_slot); continue; }  // :99-127
+        }
         // isIntegral + getMostFractionalVar (mip-utils.ts:43-61, 100-126) over the integer variables in model order
         Cand b; b.v = -1.0; b.i = 0; b.b = 0;
         int nonint = 0;
@@ -260,6 +302,9 @@ __global__ void __launch_bounds__(THREADS) k_tree_packed(const PackLp* __restric
             best_slot = cur_slot;  // (the list changes owner: not released)
             have_best = 1;
             best_eval = evaluation;
+            if constexpr (OPT)  // :138-141 (the next restore waits behind the barrier of the pop)
+                if (tid == 0)
+                    for (int k = 0; k < n_opt; k++) best_opt[k] = oo[k * S];
             continue;
         }
         if (!(b.v > 0.0)) { terr = TREE_ERR_BRANCH; break; }
@@ -323,7 +368,7 @@ __global__ void __launch_bounds__(THREADS) k_tree_packed(const PackLp* __restric
         H = add_cuts(best_slot);
         __syncthreads();
         iters_left = m.iters_cap;
-        o = pk_simplex<THREADS>(A, pcol, H, W, S, vibr, vibc, rbv, cbv, unr, precision, check_cycles, m, ghist, gtrace, sm.ps, iters_left, trace_n);
+        o = pk_simplex<THREADS, OPT>(A, pcol, H, W, S, vibr, vibc, rbv, cbv, unr, precision, check_cycles, m, ghist, gtrace, sm.ps, iters_left, trace_n, oo, n_opt);
         __syncthreads();
         if (o.outcome >= 5) serr = o.outcome == 5 ? (int)ERR_ITER_LIMIT : (int)ERR_HIST_FULL;
         feasible = (o.outcome == 3 || o.outcome == 4) ? 0 : 1;
@@ -336,11 +381,19 @@ __global__ void __launch_bounds__(THREADS) k_tree_packed(const PackLp* __restric
     // ---- epilogue: the state, the RHS column and the row map of whatever LDS holds now ----------------------------------------------------
     __syncthreads();
     const bool ok = terr == TREE_OK && serr == ERR_NONE && iterations > 0;
-    if (ok)
+    if (ok) {
         for (int r = tid; r < H; r += THREADS) {
             out_rhs[m.out_off + r] = A[r * S];
             out_rows[m.out_off + r] = vibr[r];
         }
+        if constexpr (OPT) {  // the rows of whatever LDS holds: the incumbent's after the final re-evaluation
+            double* out_opt = many_global(m.opt_out);
+            for (int q = tid; q < n_opt * W; q += THREADS) {
+                const int k = q / W;
+                out_opt[q] = oo[k * S + (q - k * W)];
+            }
+        }
+    }
     if (tid == 0) {
         st->H = H;
         st->last_element_index = W + H - 2;
@@ -385,10 +438,14 @@ static int tree_launch_impl(int threads, unsigned grid, size_t lds, const void* 
     DevState* states = static_cast<DevState*>(a.states);
     const TreeLp* trees = static_cast<const TreeLp*>(a.trees);
     TreeRec* recs = static_cast<TreeRec*>(a.tree_out);
-    if (threads == 64)
-        hipLaunchKernelGGL(k_tree_packed<64>, dim3(grid), dim3(64), lds, s, a.lps, trees, a.order, a.cc, a.cc_all, states, a.rhs, a.rows, recs);
+    if (threads == 64 && !a.opt)
+        hipLaunchKernelGGL((k_tree_packed<64, false>), dim3(grid), dim3(64), lds, s, a.lps, trees, a.order, a.cc, a.cc_all, states, a.rhs, a.rows, recs);
+    else if (threads == 256 && !a.opt)
+        hipLaunchKernelGGL((k_tree_packed<256, false>), dim3(grid), dim3(256), lds, s, a.lps, trees, a.order, a.cc, a.cc_all, states, a.rhs, a.rows, recs);
+    else if (threads == 64)
+        hipLaunchKernelGGL((k_tree_packed<64, true>), dim3(grid), dim3(64), lds, s, a.lps, trees, a.order, a.cc, a.cc_all, states, a.rhs, a.rows, recs);
     else if (threads == 256)
-        hipLaunchKernelGGL(k_tree_packed<256>, dim3(grid), dim3(256), lds, s, a.lps, trees, a.order, a.cc, a.cc_all, states, a.rhs, a.rows, recs);
+        hipLaunchKernelGGL((k_tree_packed<256, true>), dim3(grid), dim3(256), lds, s, a.lps, trees, a.order, a.cc, a.cc_all, states, a.rhs, a.rows, recs);
     else
         return -1;
     return (int)hipPeekAtLastError();

@@ -1,4 +1,5 @@
-// jslp_tu_packed.hip -- the two builds of k_simplex_packed (include/jslpp_packed.h) as a translation unit of their own.
+// jslp_tu_packed.hip -- the builds of k_simplex_packed and k_tree_packed (include/jslpp_packed.h, jslpt_tree.h, jslps_soft.h: 64 or 256
+// threads, each with or without optional objectives) as a translation unit of their own.
 //
 // The product build compiles this file next to jslp_hip.hip (-DJSLP_SPLIT_TU), the two parts of jslp_tu_resident.hip and jslp_tu_mir.hip
 // (__graft_entry__.build()).  As there, the kernel headers are included inside a namespace of the unit's own, so every kernel and helper

@@ -885,36 +885,41 @@ def pivot_digest(pairs):
     return "%x" % h
 
 
-def pack_lds_bytes(height, width):
+def pack_lds_bytes(height, width, n_optional=0):
     """jslpp_lds_bytes (include/jslpp_packed.h) restated: the dynamic LDS one LP of a pack needs -- the tableau with its row stride padded to
     an odd number of doubles, the pivot column, and the integer block [vibr | vibc | rbv | cbv | unrestricted flags] with every piece padded
-    to 16 bytes.  What a library without the extension (the oracle) is asked instead; tests/test_packed_abi.py holds the two together."""
-    h, w = int(height), int(width)
-    if h < 2 or w < 2:
+    to 16 bytes.  What a library without the extension (the oracle) is asked instead; tests/test_packed_abi.py holds the two together.
+    n_optional: the LP's optional objectives, one row of the same stride each behind the pivot column (jslps_lds_bytes,
+    include/jslps_soft.h; tests/test_packed_soft_abi.py)."""
+    h, w, no = int(height), int(width), int(n_optional)
+    if h < 2 or w < 2 or no < 0:
         return 0
     pad4 = lambda n: (n + 3) & ~3  # noqa: E731
     n_idx = w + 2 * h + 2
-    doubles = (h * (w | 1) + h + 1) & ~1
+    doubles = (h * (w | 1) + h + no * (w | 1) + 1) & ~1
     ints = pad4(h) + pad4(w) + 2 * pad4(n_idx) + pad4((n_idx + 3) // 4)
     return 8 * doubles + 4 * ints
 
 
-def tree_lds_bytes(height, width, row_capacity):
-    """jslpt_lds_bytes (include/jslpt_tree.h) restated: pack_lds_bytes with the tableau and the maps sized for row_capacity rows"""
+def tree_lds_bytes(height, width, row_capacity, n_optional=0):
+    """jslpt_lds_bytes (include/jslpt_tree.h) restated: pack_lds_bytes with the tableau and the maps sized for row_capacity rows
+    (n_optional: jslps_tree_lds_bytes)"""
     h, w, rc = int(height), int(width), int(row_capacity)
     if h < 2 or w < 2 or rc < h:
         return 0
-    return pack_lds_bytes(rc, w)
+    return pack_lds_bytes(rc, w, n_optional)
 
 
-def tree_cut_rows(height, width, n_int, lib=None):
-    """the cut rows a model with n_int integer variables joins a tree pack with: 2 per integer variable -- the most a cut list can hold
-    (branch-and-cut.ts:166-179) -- or the most that fit the LDS limit; 0 when not even one fits"""
+def tree_cut_rows(height, width, n_int, lib=None, n_optional=0):
+    """the cut rows a model with n_int integer variables (and n_optional optional objectives) joins a tree pack with: 2 per integer variable
+    -- the most a cut list can hold (branch-and-cut.ts:166-179) -- or the most that fit the LDS limit; 0 when not even one fits"""
     def fits(cut_rows):
-        if lib is not None and getattr(lib, "has_tree", False):
+        if n_optional and lib is not None and getattr(lib, "has_soft", False):
+            b = int(lib.jslps_tree_lds_bytes(int(height), int(width), int(height) + cut_rows, int(n_optional)))
+        elif not n_optional and lib is not None and getattr(lib, "has_tree", False):
             b = int(lib.jslpt_lds_bytes(int(height), int(width), int(height) + cut_rows))
         else:
-            b = tree_lds_bytes(height, width, int(height) + cut_rows)
+            b = tree_lds_bytes(height, width, int(height) + cut_rows, n_optional)
         return 0 < b <= _capi.JSLPP_LDS_LIMIT
     lo, hi = 0, 2 * int(n_int)
     if fits(hi):
@@ -938,12 +943,15 @@ class _TreeModel:
         self.checkForCycles = bool(check_cycles)
 
 
-def pack_fits(height, width, lib=None):
-    """whether a tableau of this shape can join a TableauPack (its LDS image stays within the 64 KiB the pack kernels are launched with)"""
-    if lib is not None and getattr(lib, "has_pack", False):
+def pack_fits(height, width, lib=None, n_optional=0):
+    """whether a tableau of this shape (with n_optional optional objectives) can join a TableauPack: its LDS image stays within the 64 KiB
+    the pack kernels are launched with"""
+    if n_optional and lib is not None and getattr(lib, "has_soft", False):
+        b = int(lib.jslps_lds_bytes(int(height), int(width), int(n_optional)))
+    elif not n_optional and lib is not None and getattr(lib, "has_pack", False):
         b = int(lib.jslpp_lds_bytes(int(height), int(width)))
     else:
-        b = pack_lds_bytes(height, width)
+        b = pack_lds_bytes(height, width, n_optional)
     return 0 < b <= _capi.JSLPP_LDS_LIMIT
 
 
@@ -957,10 +965,13 @@ class TableauPack:
 
     A library without the extension (the CPU oracle) gets a RESTATEMENT behind the same interface: one engine per LP, solved one after the
     other (max_pivots is then the engine's own cap) -- the host logic stays testable without a GPU.  A HIP library without the extension is
-    an error, never a fallback."""
+    an error, never a fallback.
+
+    optional_objectives: one entry per LP, None or that LP's n x width optional objectives (include/jslps_soft.h), as Tableau takes them;
+    optional_objectives(i) reads LP i's rows back after a solve."""
 
     def __init__(self, lps, precision=1e-8, lib=None, device=0, trace_cap=0, max_pivots=0, integers=None, cut_rows=None, heap_cap=None,
-                 max_nodes=0):
+                 max_nodes=0, optional_objectives=None):
         self.lib = lib if lib is not None else _capi.load_hip()
         self._lps = []
         for matrix, vibr, vibc, unr in lps:
@@ -981,6 +992,20 @@ class TableauPack:
         self.heights = _capi.as_i32([m.shape[0] for m, _, _, _ in self._lps])
         self.widths = _capi.as_i32([m.shape[1] for m, _, _, _ in self._lps])
         self.trace_cap, self.max_pivots, self.device = int(trace_cap), int(max_pivots), int(device)
+        # per LP its optional objectives (None: none), n_optional x width
+        self._optional = [None] * n
+        if optional_objectives is not None:
+            if len(optional_objectives) != n:
+                raise ValueError("TableauPack: %d optional-objective entries for %d LPs" % (len(optional_objectives), n))
+            for i, oo in enumerate(optional_objectives):
+                if oo is None or len(oo) == 0:
+                    continue
+                oo = _capi.as_f64(oo)
+                if oo.ndim != 2 or oo.shape[1] != self.widths[i]:
+                    raise ValueError("TableauPack: LP %d: optional objectives must be n x width" % i)
+                self._optional[i] = oo
+        self.n_optional = _capi.as_i32([0 if oo is None else oo.shape[0] for oo in self._optional])
+        self.has_optional = bool(self.n_optional.any())
         self.results = np.zeros(n, dtype=_capi.RESULT_DTYPE)
         self.status = np.zeros(n, dtype=np.int32)
         self.evaluation = np.zeros(n, dtype=np.float64)
@@ -1008,9 +1033,20 @@ class TableauPack:
             self.row_capacity = self.heights
         if self.is_tree and self.lib.has_pack and not getattr(self.lib, "has_tree", False):
             raise _capi.EngineError("TableauPack: %s does not export the tree extension (include/jslpt_tree.h)" % self.lib.path)
+        if self.has_optional and self.lib.has_pack and not getattr(self.lib, "has_soft", False):
+            raise _capi.EngineError("TableauPack: %s does not export the optional-objective extension (include/jslps_soft.h)" % self.lib.path)
         if self.lib.has_pack:
             self._h = _capi.C.c_void_p()
-            if self.is_tree:
+            if self.has_optional and self.is_tree:
+                self.lib.check(self.lib.jslps_tree_pack_create(_capi.C.byref(self._h), self.device, n, _capi.ptr_i32(self.heights),
+                                                               _capi.ptr_i32(self.widths), _capi.ptr_f64(self.precision), _capi.ptr_i32(self.cut_rows),
+                                                               _capi.ptr_i32(self.heap_cap), _capi.ptr_i32(self.n_optional), self.trace_cap,
+                                                               self.max_pivots, self.max_nodes), "jslps_tree_pack_create")
+            elif self.has_optional:
+                self.lib.check(self.lib.jslps_pack_create(_capi.C.byref(self._h), self.device, n, _capi.ptr_i32(self.heights), _capi.ptr_i32(self.widths),
+                                                          _capi.ptr_f64(self.precision), _capi.ptr_i32(self.n_optional), self.trace_cap,
+                                                          self.max_pivots), "jslps_pack_create")
+            elif self.is_tree:
                 self.lib.check(self.lib.jslpt_pack_create(_capi.C.byref(self._h), self.device, n, _capi.ptr_i32(self.heights), _capi.ptr_i32(self.widths),
                                                           _capi.ptr_f64(self.precision), _capi.ptr_i32(self.cut_rows), _capi.ptr_i32(self.heap_cap),
                                                           self.trace_cap, self.max_pivots, self.max_nodes), "jslpt_pack_create")
@@ -1024,20 +1060,25 @@ class TableauPack:
                     if self.is_tree:
                         iv = self.integers[i]
                         self.lib.check(self.lib.jslpt_pack_set_integers(self._h, i, _capi.ptr_i32(iv), int(iv.shape[0])), "jslpt_pack_set_integers")
+                    if self._optional[i] is not None:
+                        self.lib.check(self.lib.jslps_pack_set_optional_objectives(self._h, i, _capi.ptr_f64(self._optional[i])),
+                                       "jslps_pack_set_optional_objectives")
                 self._lps = None  # (the pack's pinned image holds the inputs from here on)
                 self.upload()
             except Exception:
                 self.close()
                 raise
         elif self.lib.backend == "oracle-c":
-            for i, (h, w, rc) in enumerate(zip(self.heights, self.widths, self.row_capacity)):
-                if self.is_tree and not 0 < tree_lds_bytes(h, w, rc) <= _capi.JSLPP_LDS_LIMIT:
+            for i, (h, w, rc, no) in enumerate(zip(self.heights, self.widths, self.row_capacity, self.n_optional)):
+                if self.is_tree and not 0 < tree_lds_bytes(h, w, rc, no) <= _capi.JSLPP_LDS_LIMIT:
                     raise _capi.EngineError("jslpt_pack_create failed (%d): pack_create: LP %d: the tableau's LDS image at its row capacity exceeds "
                                             "64 KiB" % (_capi.JSLP_ERR_UNSUPPORTED, i))
-                if not self.is_tree and not pack_fits(h, w):
-                    raise _capi.EngineError("jslpp_pack_create failed (%d): the tableau's LDS image exceeds 64 KiB" % _capi.JSLP_ERR_UNSUPPORTED)
-            self._twins = [Tableau(m, vibr, vibc, unr, precision=float(p), row_capacity=int(rc), device=self.device, lib=self.lib)
-                           for (m, vibr, vibc, unr), p, rc in zip(self._lps, self.precision, self.row_capacity)]
+                if not self.is_tree and not pack_fits(h, w, n_optional=no):
+                    raise _capi.EngineError("jslpp_pack_create failed (%d): pack_create: LP %d: the tableau's LDS image exceeds 64 KiB"
+                                            % (_capi.JSLP_ERR_UNSUPPORTED, i))
+            self._twins = [Tableau(m, vibr, vibc, unr, precision=float(p), row_capacity=int(rc), device=self.device, lib=self.lib,
+                                   optional_objectives=oo)
+                           for (m, vibr, vibc, unr), p, rc, oo in zip(self._lps, self.precision, self.row_capacity, self._optional)]
         else:
             raise _capi.EngineError("TableauPack: %s does not export the pack extension (include/jslpp_packed.h)" % self.lib.path)
 
@@ -1067,8 +1108,11 @@ class TableauPack:
     def upload(self):
         """hand the LPs over again as they were given: one H2D copy; every LP's state, evaluation, counters and trace start afresh"""
         if self._twins is not None:
-            for t, (m, vibr, vibc, unr) in zip(self._twins, self._lps):
+            for t, (m, vibr, vibc, unr), oo in zip(self._twins, self._lps, self._optional):
                 t.upload(m, vibr, vibc, unr)
+                if oo is not None:  # (an engine's upload keeps the rows it has: hand the LP's own over again)
+                    self.lib.check(self.lib.jslp_engine_set_optional_objectives(t._h, int(oo.shape[0]), _capi.ptr_f64(oo)),
+                                   "jslp_engine_set_optional_objectives")
                 t.evaluation, t.feasible, t.bounded = 0.0, True, True
         else:
             self.lib.check(self.lib.jslpp_pack_upload(self._h), "jslpp_pack_upload")
@@ -1193,6 +1237,18 @@ class TableauPack:
             b = a + int(self.results[i]["height"])
         return (np.ctypeslib.as_array(rhs, shape=(int(offs[self.n]),))[a:b].copy(),
                 np.ctypeslib.as_array(rows, shape=(int(offs[self.n]),))[a:b].copy())
+
+    def optional_objectives(self, i):
+        """LP i's optional objectives after the last solve (n_optional x width; native: out of the pack's pinned result block)"""
+        no, w = int(self.n_optional[i]), int(self.widths[i])
+        if self._twins is not None:
+            return self._twins[i].optional_objectives()[:no].copy()
+        rows = np.zeros((no, w), dtype=np.float64)
+        if self.has_optional:
+            n = _capi.C.c_int32()
+            self.lib.check(self.lib.jslps_pack_get_optional_objectives(self._h, int(i), _capi.ptr_f64(rows) if no else None, _capi.C.byref(n)),
+                           "jslps_pack_get_optional_objectives")
+        return rows
 
     def download(self, i):
         if self._twins is not None:

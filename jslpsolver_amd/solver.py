@@ -89,8 +89,9 @@ def _tree_in_scope(m):
 
 def solve_packed(models, precision=None, lib=None, device=0):
     """[Solve(m, precision, lib=lib, device=device) for m in models], in order, for the workload of many SMALL models.  Every model
-    without optional objectives whose tableau fits the pack's LDS limit goes through an engine.TableauPack -- one arena, one upload, one
-    launch per kernel build, one read-back, no engine per model:
+    whose tableau -- with its optional objectives, one row per soft constraint priority, when it has any (include/jslps_soft.h) -- fits the
+    pack's LDS limit goes through an engine.TableauPack -- one arena, one upload, one launch per kernel build (64 or 256 threads, each with
+    or without optional objectives), one read-back, no engine per model:
       * without integer variables (engine.pack_fits): its simplex();
       * with integer variables, under the default branch-and-cut service with no tolerance and no timeout, when the tableau with
         min(2 per integer variable, the most that fit) >= 1 cut rows fits (engine.tree_cut_rows): its whole tree, walked on the device
@@ -101,22 +102,26 @@ def solve_packed(models, precision=None, lib=None, device=0):
     parsed = [_parse(model, precision, 4) for model in models]
     packed = []  # positions of the models that go into the pack of plain LPs
     trees = []   # (position, cut rows) of the models whose tree goes into the pack with trees
+    optional = [None] * len(models)  # per model its optional objectives (None: none)
     for k, (m, matrix, _, _) in enumerate(parsed):
         _priorities, optional_rows = m.optional_objectives()
+        n_opt = 0
         if optional_rows is not None and len(optional_rows) > 0:
-            continue
+            optional[k] = optional_rows
+            n_opt = len(optional_rows)
         n_int = len(m.integerVariables)
         if n_int == 0:
-            if pack_fits(*matrix.shape, lib=lib):
+            if pack_fits(*matrix.shape, lib=lib, n_optional=n_opt):
                 packed.append(k)
         elif _tree_in_scope(m):
-            cut_rows = tree_cut_rows(matrix.shape[0], matrix.shape[1], n_int, lib=lib)
+            cut_rows = tree_cut_rows(matrix.shape[0], matrix.shape[1], n_int, lib=lib, n_optional=n_opt)
             if cut_rows >= 1:
                 trees.append((k, cut_rows))
     results = [None] * len(models)
     if packed:
         pack = TableauPack([(parsed[k][1], parsed[k][2], parsed[k][3], parsed[k][0].unrestricted) for k in packed],
-                           precision=[parsed[k][0].precision for k in packed], lib=lib, device=device)
+                           precision=[parsed[k][0].precision for k in packed], lib=lib, device=device,
+                           optional_objectives=[optional[k] for k in packed])
         try:
             pack.simplex(check_cycles=[parsed[k][0].checkForCycles for k in packed])
             for i, k in enumerate(packed):
@@ -127,7 +132,7 @@ def solve_packed(models, precision=None, lib=None, device=0):
         pack = TableauPack([(parsed[k][1], parsed[k][2], parsed[k][3], parsed[k][0].unrestricted) for k, _ in trees],
                            precision=[parsed[k][0].precision for k, _ in trees], lib=lib, device=device,
                            integers=[[v["index"] for v in parsed[k][0].integerVariables] for k, _ in trees], cut_rows=[c for _, c in trees],
-                           heap_cap=TREE_HEAP_CAP, max_nodes=TREE_MAX_NODES)
+                           heap_cap=TREE_HEAP_CAP, max_nodes=TREE_MAX_NODES, optional_objectives=[optional[k] for k, _ in trees])
         try:
             try:
                 pack.branch_and_cut(check_cycles=[parsed[k][0].checkForCycles for k, _ in trees])

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """n small independent LPs: ONE simplex_many call over n engines (include/jslpm_many.h) against ONE TableauPack (include/jslpp_packed.h).
-  python tools/packed_lp_times.py [--reps R] [--ns 1,8,64,256,1024,16384] [--workloads small,farm] [--out profiles/packed_lp_times.md]
+  python tools/packed_lp_times.py [--reps R] [--ns 1,8,64,256,1024,16384] [--workloads small,farm] [--soft] [--out profiles/packed_lp_times.md]
 Workloads: the small reference fixtures without optional objectives, round robin (the workload of tools/many_lp_times.py); copies of the
 LargeFarmMIP root (36 x 101: the 256-thread build).  simplex_many is the yardstick: its code is what the parent commit runs, in the same
 process; it is run for n <= 1024 (an engine per LP beyond that is minutes of set-up).  At n = 1 a single Tableau.simplex() is timed too.
@@ -8,7 +8,10 @@ Every result is checked against the first single-engine result of its fixture (r
 BEFORE a number is printed.  Wall time is a host clock around calls that end in their own synchronisation (the pack's: launch + the one
 read-back + decode); device time comes from HIP events (the engines' around the batch launch, the pack's around its launches on its own
 stream).  One warm-up, then the best of R repetitions; the two paths alternate; tableaus are re-uploaded before each repetition (untimed
-for simplex_many; timed separately for the pack: `pack wall incl. upload`)."""
+for simplex_many; timed separately for the pack: `pack wall incl. upload`).
+--soft adds the workload `soft`: the fixtures WITH optional objectives (Relaxed, Fertilizer), round robin, in a pack made with
+optional_objectives= (include/jslps_soft.h: the OPT build of the pack kernel).  simplex_many takes no such engines, so the yardstick of
+that workload is one Tableau.simplex() per LP, one after the other; the check also covers the optional rows after the solve."""
 import argparse
 import hashlib
 import os
@@ -18,25 +21,36 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+import numpy as np  # noqa: E402
 import golden_util as G  # noqa: E402
 from jslpsolver_amd import _capi  # noqa: E402
 from jslpsolver_amd.engine import Tableau, TableauPack, pivot_digest, simplex_many  # noqa: E402
 
 SMALL = ["Berlin_Air_Lift_Problem", "Chocolate_Problem", "Coffe_Problem", "Computer_Problem", "Wiki_1", "Shift_Work_Problem",
          "Cycling_Fletcher", "Generic_Business_Problem", "Stigler_Diet", "TacoParty", "Chevalier_1", "Wood_Shop_Problem"]
+SOFT = ["Relaxed", "Fertilizer"]
 MANY_MAX = 1024
 
 
-def tableau_of(name):
+def tableau_of(name, soft=False):
     g = G.load(os.path.join(G.GOLDEN, "fixtures", name + ".json.gz"))
     tab = g["tableau"]
-    assert not tab["optionalObjectives"]
+    assert bool(tab["optionalObjectives"]) == soft
     m, vibr, vibc = G.dense_tableau(tab)
-    return dict(m=m, vibr=vibr, vibc=vibc, unr=tab["unrestricted"], precision=tab["precision"], check=bool(tab["checkForCycles"]))
+    oo = np.array([[G.num(v) for v in o["reducedCosts"]] for o in tab["optionalObjectives"]], dtype=np.float64) if soft else None
+    return dict(m=m, vibr=vibr, vibc=vibc, unr=tab["unrestricted"], precision=tab["precision"], check=bool(tab["checkForCycles"]), oo=oo)
 
 
-def signature(res, trace, matrix):
-    return (tuple(sorted(res.as_dict().items())), pivot_digest(trace), hashlib.sha256(matrix.tobytes()).hexdigest())
+def signature(res, trace, matrix, optional=None):
+    return (tuple(sorted(res.as_dict().items())), pivot_digest(trace), hashlib.sha256(matrix.tobytes()).hexdigest(),
+            None if optional is None else hashlib.sha256(optional.tobytes()).hexdigest())
+
+
+def upload(t, x):
+    """the tableau again, and its optional rows as they were given"""
+    t.upload(x["m"], x["vibr"], x["vibc"], x["unr"])
+    if x["oo"] is not None:
+        t.lib.check(t.lib.jslp_engine_set_optional_objectives(t._h, int(x["oo"].shape[0]), _capi.ptr_f64(x["oo"])), "jslp_engine_set_optional_objectives")
 
 
 def main():
@@ -45,6 +59,7 @@ def main():
     ap.add_argument("--ns", default="1,8,64,256,1024,16384")
     ap.add_argument("--workloads", default="small,farm")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--soft", action="store_true", help="add the workload of the fixtures with optional objectives")
     a = ap.parse_args()
     lib = _capi.load_hip()
     ns = [int(x) for x in a.ns.split(",")]
@@ -57,22 +72,23 @@ def main():
         print(s, flush=True)
 
     print("\n".join(lines), flush=True)
-    for wl in a.workloads.split(","):
-        names = ["LargeFarmMIP"] if wl == "farm" else SMALL
-        label = "LargeFarmMIP root 36 x 101" if wl == "farm" else "small fixtures"
-        tabs = {n: tableau_of(n) for n in names}
+    for wl in a.workloads.split(",") + (["soft"] if a.soft else []):
+        soft = wl == "soft"
+        names = ["LargeFarmMIP"] if wl == "farm" else SOFT if soft else SMALL
+        label = "LargeFarmMIP root 36 x 101" if wl == "farm" else "soft fixtures (yardstick: one `Tableau.simplex()` per LP)" if soft else "small fixtures"
+        tabs = {n: tableau_of(n, soft) for n in names}
         expect = {}
         for n in names:  # the yardstick of every check: a single engine that never saw a batch or a pack
             x = tabs[n]
-            t = Tableau(x["m"], x["vibr"], x["vibc"], x["unr"], precision=x["precision"], lib=lib)
+            t = Tableau(x["m"], x["vibr"], x["vibc"], x["unr"], precision=x["precision"], lib=lib, optional_objectives=x["oo"])
             r = t.simplex(check_cycles=x["check"])
-            expect[n] = signature(r, t.pivot_trace(), t.download()[0])
+            expect[n] = signature(r, t.pivot_trace(), t.download()[0], t.optional_objectives() if soft else None)
             t.close()
         n_eng = min(max(ns), MANY_MAX)
         which_all = [names[i % len(names)] for i in range(max(ns))]
         t0 = time.perf_counter()
-        engines = [Tableau(tabs[w]["m"], tabs[w]["vibr"], tabs[w]["vibc"], tabs[w]["unr"], precision=tabs[w]["precision"], lib=lib)
-                   for w in which_all[:n_eng]]
+        engines = [Tableau(tabs[w]["m"], tabs[w]["vibr"], tabs[w]["vibc"], tabs[w]["unr"], precision=tabs[w]["precision"], lib=lib,
+                           optional_objectives=tabs[w]["oo"]) for w in which_all[:n_eng]]
         sys.stderr.write("%s: %d engines created in %.1f s\n" % (wl, n_eng, time.perf_counter() - t0))
         for t in engines:
             t.set_timing(True)
@@ -81,7 +97,8 @@ def main():
             checks = [tabs[w]["check"] for w in which]
             t0 = time.perf_counter()
             pack = TableauPack([(tabs[w]["m"], tabs[w]["vibr"], tabs[w]["vibc"], tabs[w]["unr"]) for w in which],
-                               precision=[tabs[w]["precision"] for w in which], lib=lib, trace_cap=1024)
+                               precision=[tabs[w]["precision"] for w in which], lib=lib, trace_cap=1024,
+                               **({"optional_objectives": [tabs[w]["oo"] for w in which]} if soft else {}))
             create_s = time.perf_counter() - t0
             best = {}
             for rep in range(a.reps + 1):  # (repetition 0 warms up)
@@ -103,23 +120,25 @@ def main():
                         for i, w in enumerate(which):
                             assert tuple(sorted(pack.result(i).as_dict().items())) == expect[w][0], (wl, n, i, w)
                             if full:
-                                assert signature(pack.result(i), pack.pivot_trace(i), pack.download(i)[0]) == expect[w], (wl, n, i, w)
+                                assert signature(pack.result(i), pack.pivot_trace(i), pack.download(i)[0],
+                                                 pack.optional_objectives(i) if soft else None) == expect[w], (wl, n, i, w)
                     else:
                         for t, w in zip(engines[:n], which):
-                            x = tabs[w]
-                            t.upload(x["m"], x["vibr"], x["vibc"], x["unr"])
+                            upload(t, tabs[w])
                         for t in engines[:n]:
                             t.read_rhs()  # (an upload is asynchronous: this waits for it)
                         dev0 = engines[0].get_timing()[2]
                         w0 = time.perf_counter()
                         if mode == "single":
                             res = [engines[0].simplex(check_cycles=checks[0])]
+                        elif soft:
+                            res = [t.simplex(check_cycles=c) for t, c in zip(engines[:n], checks)]
                         else:
                             res = simplex_many(engines[:n], check_cycles=checks)
                         wall = time.perf_counter() - w0
                         wall_up, dev = wall, engines[0].get_timing()[2] - dev0
                         for t, r, w in zip(engines[:n], res, which):
-                            assert signature(r, t.pivot_trace(), t.download()[0]) == expect[w], (wl, n, mode, w)
+                            assert signature(r, t.pivot_trace(), t.download()[0], t.optional_objectives() if soft else None) == expect[w], (wl, n, mode, w)
                     if rep and (mode not in best or wall < best[mode][0]):
                         best[mode] = (wall, wall_up, dev)
                     if rep and mode == "pack":
