@@ -1,6 +1,7 @@
 """ctypes binding of the C ABI declared in include/jslp_engine.h (SYMBOLS) and of its HIP-only extensions include/jslpx_branch.h
 (BRANCH_SYMBOLS), include/jslpm_many.h (MANY_SYMBOLS), include/jslpf_f32.h (F32_SYMBOLS), include/jslpr_mir.h (MIR_SYMBOLS) and
-include/jslpp_packed.h (PACK_SYMBOLS) with include/jslpt_tree.h (TREE_SYMBOLS) and include/jslps_soft.h (SOFT_SYMBOLS).
+include/jslpp_packed.h (PACK_SYMBOLS) with include/jslpt_tree.h (TREE_SYMBOLS), include/jslps_soft.h (SOFT_SYMBOLS) and
+include/jslpc_tree_mir.h (TREE_MIR_SYMBOLS).
 
 The same binding class serves two libraries that export identical symbols:
   * jslpsolver_amd/csrc/libjslp_hip.so -- the product (hand-written HIP kernels, gfx950)
@@ -238,6 +239,15 @@ SOFT_SYMBOLS = {
     "jslps_pack_set_optional_objectives": (C.c_int, [C.c_void_p, C.c_int32, _f64p]),
     "jslps_pack_get_optional_objectives": (C.c_int, [C.c_void_p, C.c_int32, _f64p, _i32p]),
 }
+# name -> (restype, argtypes); must list EVERY symbol include/jslpc_tree_mir.h declares.  HIP library only (Library.has_tree_mir).
+TREE_MIR_SYMBOLS = {
+    "jslpc_tree_lds_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    "jslpc_tree_pack_create": (C.c_int, [_P(C.c_void_p), C.c_int, C.c_int32, _i32p, _i32p, _f64p, _i32p, _i32p, _i32p, C.c_int32, C.c_int32,
+                                         C.c_int32]),
+    "jslpc_pack_read_mir": (C.c_int, [C.c_void_p, C.c_void_p]),
+}
+# numpy twin of struct jslpc_mir_result
+MIR_TREE_DTYPE = np.dtype([(name, np.int32) for name in ("rounds", "rows_added", "simplexes", "root_rows", "rows_high_water")])
 # numpy twin of struct jslpt_tree_result
 TREE_DTYPE = np.dtype([(name, np.int32) for name in ("iterations", "is_integral", "final_height", "nodes_pushed", "heap_high_water",
                                                      "cuts_high_water")])
@@ -268,6 +278,7 @@ class Library:
         self.has_pack = self._bind_extension(PACK_SYMBOLS)
         self.has_tree = self.has_pack and self._bind_extension(TREE_SYMBOLS)
         self.has_soft = self.has_tree and self._bind_extension(SOFT_SYMBOLS)
+        self.has_tree_mir = self.has_tree and self._bind_extension(TREE_MIR_SYMBOLS)
 
     def _bind_extension(self, symbols):
         """bind a HIP-only extension when the library exports all of it; False otherwise"""

@@ -20,6 +20,7 @@
 #include "../../include/jslpp_packed.h"
 #include "../../include/jslpt_tree.h"
 #include "../../include/jslps_soft.h"
+#include "../../include/jslpc_tree_mir.h"
 #include "jslp_kernels.hip.h"
 #include "jslp_host_mem.h"
 
@@ -3429,11 +3430,17 @@ extern "C" int jslpf_simplex_f32_sweep(jslp_engine* e, const double* precisions,
 #include "jslp_tree.hip.h"  // (the layout of a pack with cut rows and a heap per LP, include/jslpt_tree.h)
 #ifdef JSLP_SPLIT_TU
 extern "C" __attribute__((visibility("hidden"))) int jslpp_packed_launch_tu(int threads, unsigned grid, size_t lds, const void* args, void* stream);
-static int packed_launch(int threads, unsigned grid, size_t lds, const PackLaunch& a, hipStream_t s) { return jslpp_packed_launch_tu(threads, grid, lds, &a, s); }
+extern "C" __attribute__((visibility("hidden"))) int jslpc_tree_mir_launch_tu(int threads, unsigned grid, size_t lds, const void* args, void* stream);
+static int packed_launch(int threads, unsigned grid, size_t lds, const PackLaunch& a, hipStream_t s) {
+    if (a.kind == 1 && a.mir) return jslpc_tree_mir_launch_tu(threads, grid, lds, &a, s);  // (the MIR builds of k_tree_packed: jslp_tu_tree_mir.hip)
+    return jslpp_packed_launch_tu(threads, grid, lds, &a, s);
+}
 #else
 static int packed_launch_impl(int threads, unsigned grid, size_t lds, const void* bytes, hipStream_t s);  // (jslp_packed.hip.h, at the end of this file)
 static int tree_launch_impl(int threads, unsigned grid, size_t lds, const void* bytes, hipStream_t s);    // (jslp_tree.hip.h, there too)
+static int tree_mir_launch_impl(int threads, unsigned grid, size_t lds, const void* bytes, hipStream_t s);  // (its MIR builds)
 static int packed_launch(int threads, unsigned grid, size_t lds, const PackLaunch& a, hipStream_t s) {
+    if (a.kind == 1 && a.mir) return tree_mir_launch_impl(threads, grid, lds, &a, s);
     return a.kind == 1 ? tree_launch_impl(threads, grid, lds, &a, s) : packed_launch_impl(threads, grid, lds, &a, s);
 }
 #endif
@@ -3454,6 +3461,11 @@ struct jslpp_pack {
     bool tree = false, tree_ran = false;
     int32_t max_nodes = 0;
     std::vector<int32_t> cut_rows, heap_cap;
+    // a pack made by jslpc_tree_pack_create (include/jslpc_tree_mir.h): which LPs are MIR LPs (row capacity height + row_extra, a MIR build of
+    // the tree kernel, a TreeMirRec in the result block), and the status of every LP after the last tree call (jslpc_pack_read_mir)
+    bool has_mir = false;
+    std::vector<uint8_t> mir;
+    std::vector<int32_t> tree_status;
     TreeLp* d_trees = nullptr;
     char* d_tree_mem = nullptr;
     size_t tree_mem_bytes = 0;
@@ -3469,9 +3481,10 @@ struct jslpp_pack {
     PackLp* d_lps = nullptr;
     int32_t *d_order = nullptr, *d_cc = nullptr;
     int2 *d_hist = nullptr, *d_trace = nullptr;
-    // the launch groups, in launch order: [0] one wave, [1] 256 threads, [2] one wave with OPT, [3] 256 threads with OPT
-    int32_t n_group[4] = {0, 0, 0, 0};
-    size_t lds_group[4] = {0, 0, 0, 0};
+    // the launch groups, in launch order: [0] one wave, [1] 256 threads, [2] one wave with OPT, [3] 256 threads with OPT, [4] one wave
+    // with MIR, [5] 256 threads with MIR (a plain simplex of a MIR LP runs in the build of group & 3)
+    int32_t n_group[6] = {0, 0, 0, 0, 0, 0};
+    size_t lds_group[6] = {0, 0, 0, 0, 0, 0};
     // optional objectives (include/jslps_soft.h): rows per LP, whether they were set, and where they lie in the result block (in doubles)
     std::vector<int32_t> n_opt;
     std::vector<uint8_t> opt_set;
@@ -3485,10 +3498,17 @@ struct jslpp_pack {
     size_t res_rhs_off() const { return (sizeof(DevState) * (size_t)n + 255) & ~(size_t)255; }
     size_t res_rows_off() const { return (res_rhs_off() + sizeof(double) * (size_t)offs[n] + 255) & ~(size_t)255; }
     size_t res_tree_off() const { return (res_rows_off() + sizeof(int32_t) * (size_t)offs[n] + 255) & ~(size_t)255; }
-    size_t res_plain_bytes() const { return tree ? res_tree_off() + sizeof(TreeRec) * (size_t)n : res_rows_off() + sizeof(int32_t) * (size_t)offs[n]; }
+    size_t res_mir_off() const { return (res_tree_off() + sizeof(TreeRec) * (size_t)n + 255) & ~(size_t)255; }  // (has_mir: a TreeMirRec per LP)
+    size_t res_plain_bytes() const {
+        if (has_mir) return res_mir_off() + sizeof(TreeMirRec) * (size_t)n;
+        return tree ? res_tree_off() + sizeof(TreeRec) * (size_t)n : res_rows_off() + sizeof(int32_t) * (size_t)offs[n];
+    }
     size_t res_opt_off() const { return (res_plain_bytes() + 255) & ~(size_t)255; }
     size_t res_bytes() const { return opt_offs[n] ? res_opt_off() + sizeof(double) * (size_t)opt_offs[n] : res_plain_bytes(); }
     TreeRec* h_tree() const { return reinterpret_cast<TreeRec*>(result.h.p + res_tree_off()); }
+    TreeMirRec* h_mir() const { return reinterpret_cast<TreeMirRec*>(result.h.p + res_mir_off()); }
+    bool is_mir(size_t i) const { return has_mir && mir[i]; }
+    size_t lds_bytes(size_t i) const { return is_mir(i) ? (size_t)tree_mir_lds_bytes(RC[i], W[i]) : (size_t)pk_lds_bytes(RC[i], W[i], n_opt[i]); }
     size_t ints_off(int32_t i) const { return sizeof(DevState) + 8 * (size_t)pk_image_doubles(RC[i], W[i], n_opt[i]); }
     size_t opt_rows_off(int32_t i) const { return sizeof(DevState) + 8 * (size_t)pk_opt_image_off(RC[i], W[i]); }
     size_t ivars_off(int32_t i) const { return ints_off(i) + 4 * (size_t)pk_ints(RC[i], W[i]).total; }
@@ -3544,13 +3564,13 @@ static int pack_init(jslpp_pack* p, int32_t max_pivots) {
     std::vector<PackLp> lps(n);
     std::vector<int32_t> order(n);
     int32_t k = 0;
-    for (int g = 0; g < 4; g++)  // the one-wave LPs first, then the 256-thread ones, then the same two with optional objectives, each in pack order
+    for (int g = 0; g < 6; g++)  // the one-wave LPs first, then the 256-thread ones, then the same two with optional objectives, then with MIR, each in pack order
         for (size_t i = 0; i < n; i++) {
             const bool wave = (long long)p->RC[i] * p->W[i] <= PACK_CELLS_WAVE;  // (tableau cells at the row capacity, optional rows or not)
-            if ((wave ? 0 : 1) + (p->n_opt[i] > 0 ? 2 : 0) != g) continue;
+            if ((wave ? 0 : 1) + (p->n_opt[i] > 0 ? 2 : 0) + (p->is_mir(i) ? 4 : 0) != g) continue;
             order[k++] = (int32_t)i;
             p->n_group[g] += 1;
-            p->lds_group[g] = std::max(p->lds_group[g], (size_t)pk_lds_bytes(p->RC[i], p->W[i], p->n_opt[i]));
+            p->lds_group[g] = std::max(p->lds_group[g], p->lds_bytes(i));
         }
     for (size_t i = 0; i < n; i++) {
         PackLp& m = lps[i];
@@ -3585,6 +3605,7 @@ static int pack_init(jslpp_pack* p, int32_t max_pivots) {
             off += (sizeof(int32_t) * slots + 15) & ~(size_t)15;
             t.best_opt = reinterpret_cast<double*>(p->d_tree_mem + off);
             off += (sizeof(double) * (size_t)p->n_opt[i] + 15) & ~(size_t)15;
+            if (p->is_mir(i)) t.mir_out = reinterpret_cast<TreeMirRec*>(p->result.d.p + p->res_mir_off()) + i;  // (never with optional objectives)
             t.rcoef = js_round(1.0 / p->precision[i]);
             t.cut_rows = p->cut_rows[i]; t.heap_cap = p->heap_cap[i]; t.max_nodes = p->max_nodes; t.pad = 0;
         }
@@ -3599,10 +3620,11 @@ static int pack_init(jslpp_pack* p, int32_t max_pivots) {
     return JSLP_OK;
 }
 
-// jslps_pack_create and jslps_tree_pack_create (cut_rows / heap_cap: null for a pack without trees; n_optional: null for none)
+// jslps_pack_create, jslps_tree_pack_create and jslpc_tree_pack_create (cut_rows / heap_cap: null for a pack without trees; n_optional: null
+// for none; row_extra: null for a pack without MIR LPs -- never with n_optional)
 static int pack_create(jslpp_pack** out, int device, int32_t n, const int32_t* height, const int32_t* width, const double* precision,
                        const int32_t* cut_rows, const int32_t* heap_cap, const int32_t* n_optional, int32_t trace_cap, int32_t max_pivots,
-                       int32_t max_nodes) {
+                       int32_t max_nodes, const int32_t* row_extra = nullptr) {
     const bool tree = cut_rows != nullptr;
     if (!out || n < 0 || (n > 0 && (!height || !width || !precision))) return fail(JSLP_ERR_ARG, "pack_create: bad arguments");
     if (trace_cap < 0 || max_pivots < 0 || max_nodes < 0) return fail(JSLP_ERR_ARG, "pack_create: negative trace_cap, max_pivots or max_nodes");
@@ -3612,9 +3634,15 @@ static int pack_create(jslpp_pack** out, int device, int32_t n, const int32_t* h
         if (tree && (cut_rows[i] < 0 || heap_cap[i] < 1 || heap_cap[i] > (1 << 24)))
             return pack_fail(JSLP_ERR_ARG, "pack_create", i, "cut_rows is at least 0 and heap_cap between 1 and 2^24");
         if (n_optional && n_optional[i] < 0) return pack_fail(JSLP_ERR_ARG, "pack_create", i, "n_optional is at least 0");
-        const long long rc = (long long)height[i] + (tree ? cut_rows[i] : 0);
+        const bool mir = row_extra && row_extra[i] >= 0;
+        if (mir && row_extra[i] < cut_rows[i])
+            return pack_fail(JSLP_ERR_ARG, "pack_create", i, "row_extra of a MIR LP is at least its cut_rows (a negative one makes a plain tree LP)");
+        const long long rc = (long long)height[i] + (mir ? row_extra[i] : tree ? cut_rows[i] : 0);
         const long long no = n_optional ? n_optional[i] : 0;
         // (cells beyond the limit first: the byte count of an absurd shape must not overflow before it is compared)
+        if (mir && ((rc + no) * width[i] > JSLPP_LDS_LIMIT / 8 || tree_mir_lds_bytes((int32_t)rc, width[i]) > (long long)WGLDS_MAX_BYTES))
+            return pack_fail(JSLP_ERR_UNSUPPORTED, "pack_create", i,
+                             "the MIR LP's LDS image at its row capacity exceeds 64 KiB (jslpc_tree_lds_bytes): a smaller row_extra, or solve it through a jslp_engine");
         if ((rc + no) * width[i] > JSLPP_LDS_LIMIT / 8 || pk_lds_bytes((int32_t)rc, width[i], (int32_t)no) > (long long)WGLDS_MAX_BYTES)
             return pack_fail(JSLP_ERR_UNSUPPORTED, "pack_create", i,
                              tree ? "the tableau's LDS image at its row capacity exceeds 64 KiB (jslpt_lds_bytes): fewer cut rows, or solve it through a jslp_engine"
@@ -3638,8 +3666,13 @@ static int pack_create(jslpp_pack** out, int device, int32_t n, const int32_t* h
     if (tree) {
         p->cut_rows.assign(cut_rows, cut_rows + n); p->heap_cap.assign(heap_cap, heap_cap + n);
         p->max_nodes = max_nodes > 0 ? max_nodes : JSLPT_MAX_NODES_DEFAULT;
+        if (row_extra) {
+            p->mir.resize((size_t)n);
+            for (int32_t i = 0; i < n; i++) p->mir[i] = row_extra[i] >= 0;
+            p->has_mir = true;
+        }
         for (int32_t i = 0; i < n; i++) {
-            p->RC[i] = height[i] + cut_rows[i];
+            p->RC[i] = height[i] + (p->is_mir(i) ? row_extra[i] : cut_rows[i]);
             const size_t slots = (size_t)heap_cap[i] + 3;
             p->tree_mem_bytes += sizeof(TreeEntry) * (size_t)heap_cap[i] + (size_t)tree_slot_bytes(cut_rows[i]) * slots + ((sizeof(int32_t) * slots + 15) & ~(size_t)15) +
                                  ((sizeof(double) * (size_t)p->n_opt[i] + 15) & ~(size_t)15);
@@ -3679,6 +3712,32 @@ extern "C" int jslps_tree_pack_create(jslpp_pack** out, int device, int32_t n, c
     static const int32_t none = 0;
     return pack_create(out, device, n, height, width, precision, cut_rows ? cut_rows : &none, heap_cap ? heap_cap : &none, n_optional, trace_cap,
                        max_pivots, max_nodes);
+}
+extern "C" int jslpc_tree_pack_create(jslpp_pack** out, int device, int32_t n, const int32_t* height, const int32_t* width, const double* precision,
+                                      const int32_t* cut_rows, const int32_t* heap_cap, const int32_t* row_extra, int32_t trace_cap,
+                                      int32_t max_pivots, int32_t max_nodes) {
+    if (n > 0 && (!cut_rows || !heap_cap || !row_extra)) return fail(JSLP_ERR_ARG, "pack_create: bad arguments");
+    static const int32_t none = 0;
+    return pack_create(out, device, n, height, width, precision, cut_rows ? cut_rows : &none, heap_cap ? heap_cap : &none, nullptr, trace_cap,
+                       max_pivots, max_nodes, row_extra ? row_extra : &none);
+}
+extern "C" int64_t jslpc_tree_lds_bytes(int32_t height, int32_t width, int32_t row_capacity) {
+    if (height < 2 || width < 2 || row_capacity < height) return 0;
+    return (int64_t)tree_mir_lds_bytes(row_capacity, width);
+}
+extern "C" int jslpc_pack_read_mir(jslpp_pack* p, jslpc_mir_result* out) {
+    if (!p || (p->n > 0 && !out)) return fail(JSLP_ERR_ARG, "pack_read_mir: bad arguments");
+    if (!p->tree) return fail(JSLP_ERR_STATE, "pack_read_mir: not a pack made by jslpc_tree_pack_create or jslpt_pack_create");
+    if (!p->uploaded || !p->tree_ran) return fail(JSLP_ERR_STATE, "pack_read_mir before jslpt_pack_branch_and_cut");
+    if ((int32_t)p->tree_status.size() != p->n) return fail(JSLP_ERR_STATE, "pack_read_mir: the last jslpt_pack_branch_and_cut did not finish");
+    static_assert(sizeof(jslpc_mir_result) == 20 && sizeof(TreeMirRec) == 32, "jslpc_mir_result is the head of a TreeMirRec");
+    static_assert(TMIR_MAX_ROUNDS == JSLPR_MAX_ROUNDS, "include/jslpr_mir.h and jslp_tree.hip.h agree");
+    for (int32_t i = 0; i < p->n; i++) {
+        if (p->tree_status[(size_t)i] != JSLP_OK) continue;  // (left as it was)
+        memset(&out[i], 0, sizeof out[i]);
+        if (p->is_mir((size_t)i)) memcpy(&out[i], &p->h_mir()[i], sizeof out[i]);
+    }
+    return JSLP_OK;
 }
 extern "C" int64_t jslpt_lds_bytes(int32_t height, int32_t width, int32_t row_capacity) {
     if (height < 2 || width < 2 || row_capacity < height) return 0;
@@ -3834,13 +3893,13 @@ extern "C" int jslpp_pack_simplex(jslpp_pack* p, const int32_t* check_cycles, js
     const bool dbg = debug_launch_on();
     HIPC(hipEventRecord(p->ev_begin, s));
     int32_t first = 0;
-    for (int g = 0; g < 4; first += p->n_group[g], g++) {  // one launch per kernel build that has LPs
+    for (int g = 0; g < 6; first += p->n_group[g], g++) {  // one launch per kernel build that has LPs (and one per group of MIR LPs, in the plain build)
         const int32_t cnt = p->n_group[g];
         if (!cnt) continue;
         const int threads = (g & 1) ? 256 : 64;
         const size_t lds = p->lds_group[g];
         a.order = p->d_order + first;
-        a.opt = g >> 1;
+        a.opt = (g >> 1) & 1;
         (void)packed_launch(threads, (unsigned)cnt, lds, a, s);
         HIPC(hipGetLastError());
         p->launches += 1;
@@ -3937,6 +3996,8 @@ static int tree_error(const TreeRec& r) {
         case TREE_ERR_HEAP: return fail(JSLP_ERR_CAPACITY, "branch_and_cut: heap_cap reached (the heap is full)");
         case TREE_ERR_CUTS: return fail(JSLP_ERR_CAPACITY, "branch_and_cut: cut_rows reached (a node's cut list is longer)");
         case TREE_ERR_BRANCH: return fail(JSLP_ERR_ARG, "branch_and_cut: a node is not integral and has no fractional variable (negative precision?)");
+        case TREE_ERR_MIR_ROWS: return fail(JSLP_ERR_CAPACITY, "branch_and_cut: row_extra reached (the rows of a MIR round or of a cut list do not fit the row capacity)");
+        case TREE_ERR_MIR_ROUNDS: return fail(JSLP_ERR_CAPACITY, "branch_and_cut: mir rounds: JSLPR_MAX_ROUNDS rounds of one node without a stop");
     }
     return fail(JSLP_ERR_DEVICE, "unknown tree error code");
 }
@@ -3977,17 +4038,19 @@ extern "C" int jslpt_pack_branch_and_cut(jslpp_pack* p, const int32_t* check_cyc
     p->tree_ran = true;
     HIPC(hipEventRecord(p->ev_begin, s));
     int32_t first = 0;
-    for (int g = 0; g < 4; first += p->n_group[g], g++) {  // one launch per kernel build that has LPs
+    for (int g = 0; g < 6; first += p->n_group[g], g++) {  // one launch per kernel build that has LPs
         const int32_t cnt = p->n_group[g];
         if (!cnt) continue;
         const int threads = (g & 1) ? 256 : 64;
         const size_t lds = p->lds_group[g];
         a.order = p->d_order + first;
-        a.opt = g >> 1;
+        a.opt = (g >> 1) & 1;
+        a.mir = g >> 2;
         (void)packed_launch(threads, (unsigned)cnt, lds, a, s);
         HIPC(hipGetLastError());
         p->launches += 1;
-        if (dbg && a.opt) fprintf(stderr, "[jslp] launch k_tree_packed<%d,opt 1> n %d lds %zu\n", threads, (int)cnt, lds);
+        if (dbg && a.mir) fprintf(stderr, "[jslp] launch k_tree_packed<%d,mir 1> n %d lds %zu\n", threads, (int)cnt, lds);
+        else if (dbg && a.opt) fprintf(stderr, "[jslp] launch k_tree_packed<%d,opt 1> n %d lds %zu\n", threads, (int)cnt, lds);
         else if (dbg) fprintf(stderr, "[jslp] launch k_tree_packed<%d> n %d lds %zu\n", threads, (int)cnt, lds);
     }
     HIPC(hipEventRecord(p->ev_end, s));
@@ -4000,6 +4063,7 @@ extern "C" int jslpt_pack_branch_and_cut(jslpp_pack* p, const int32_t* check_cyc
     int32_t first_bad = -1; int first_rc = JSLP_OK; char first_msg[sizeof g_err];
     const DevState* sts = p->h_states();
     const TreeRec* recs = p->h_tree();
+    p->tree_status.assign((size_t)n, JSLP_OK);
     for (int32_t i = 0; i < n; i++) {
         const DevState& st = sts[i];
         const TreeRec& r = recs[i];
@@ -4023,6 +4087,7 @@ extern "C" int jslpt_pack_branch_and_cut(jslpp_pack* p, const int32_t* check_cyc
             }
         }
         if (rc) {
+            p->tree_status[(size_t)i] = rc;
             if (status) status[i] = rc;
             if (first_bad < 0) { first_bad = i; first_rc = rc; snprintf(first_msg, sizeof first_msg, "%s", g_err); }
         }

@@ -73,7 +73,8 @@ struct PackLaunch {
     const int32_t* order;  // blockIdx.x -> LP index (the LPs of this build)
     const int32_t* cc;     // per-LP checkForCycles, or nullptr: cc_all for every LP
     int32_t cc_all, kind;  // kind 0: k_simplex_packed, 1: k_tree_packed (jslp_tree.hip.h)
-    int32_t opt, pad;      // 1: the OPT = true build (every LP of `order` has optional objectives)
+    int32_t opt, mir;      // opt 1: the OPT = true build (every LP of `order` has optional objectives); mir 1: the MIR = true build of
+                           // k_tree_packed (every LP of `order` is a MIR LP, include/jslpc_tree_mir.h)
     void* states;          // result block: DevState per LP (LP order) ...
     double* rhs;           // ... the RHS columns one after the other ...
     int32_t* rows;         // ... and the row maps
@@ -620,6 +621,7 @@ __global__ void __launch_bounds__(THREADS) k_simplex_packed(const PackLp* __rest
         reinterpret_cast<long long*>(out_states + idx)[tid] = reinterpret_cast<const long long*>(st)[tid];
 }
 
+#ifndef JSLP_PACKED_NO_LAUNCH  // (a unit that wants pk_simplex alone: jslp_tu_tree_mir.hip)
 // launches the build for `threads` (64 or 256); returns the hipError_t of the launch, or -1 for an unknown build.  The error is PEEKED
 // at, not taken: the caller's hipGetLastError still sees it and reports it
 static int packed_launch_impl(int threads, unsigned grid, size_t lds, const void* bytes, hipStream_t s) {
@@ -637,4 +639,5 @@ static int packed_launch_impl(int threads, unsigned grid, size_t lds, const void
         return -1;
     return (int)hipPeekAtLastError();
 }
+#endif  // JSLP_PACKED_NO_LAUNCH
 #endif  // JSLP_PACKED_KERNELS

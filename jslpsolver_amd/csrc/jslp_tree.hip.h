@@ -6,7 +6,8 @@
 //
 // Memory of one LP:
 //   LDS     the tableau RC x S doubles, the pivot column, (the optional rows, n_opt x S,) the integer block sized for RC rows --
-//           jslpt_lds_bytes / jslps_tree_lds_bytes;
+//           jslpt_lds_bytes / jslps_tree_lds_bytes; (a MIR LP, include/jslpc_tree_mir.h: one isInteger byte per variable index behind it --
+//           jslpc_tree_lds_bytes;)
 //   image   [DevState | matrix | integer block | n_int, the integer variables' indexes]: the upload, and from iteration 1 on the SAVED
 //           ROOT (written once, read by every later node: an L2-resident restore; the tableau is never written back);
 //   heap    heap_cap entries of 16 bytes {relaxedEvaluation, seq, slot} -- min-heap.ts as it is, executed by thread 0;
@@ -19,25 +20,36 @@
 
 struct TreeCut { double value; int32_t var; int32_t type; };    // type 0 = "min" (x >= value), 1 = "max" (x <= value), as Cuts::type
 struct TreeEntry { double key; int32_t seq; int32_t slot; };    // slot -1: the empty cut list of the root
+struct TreeMirRec { int32_t rounds, rows_added, simplexes, root_rows, rows_high_water, pad[3]; };  // what a MIR build reports per LP: jslpc_mir_result field for field
 struct TreeLp {
     TreeEntry* heap;
     char* pool;
     int32_t* free_list;
     double rcoef;  // Math.round(1 / precision), computed on the host like decode_state's
     int32_t cut_rows, heap_cap, max_nodes, pad;
-    double* best_opt;  // n_opt doubles next to the heap: column 0 of the incumbent's optional rows (thread 0 alone reads and writes them)
+    union {
+        double* best_opt;     // n_opt doubles next to the heap: column 0 of the incumbent's optional rows (thread 0 alone reads and writes them)
+        TreeMirRec* mir_out;  // a MIR LP (include/jslpc_tree_mir.h; never one with optional objectives): its record in the result block
+    };
 };
-enum { TREE_OK = 0, TREE_ERR_NODES = 1, TREE_ERR_HEAP = 2, TREE_ERR_CUTS = 3, TREE_ERR_BRANCH = 4 };
+enum { TREE_OK = 0, TREE_ERR_NODES = 1, TREE_ERR_HEAP = 2, TREE_ERR_CUTS = 3, TREE_ERR_BRANCH = 4, TREE_ERR_MIR_ROWS = 5, TREE_ERR_MIR_ROUNDS = 6 };
 struct TreeRec {  // what the kernel reports per LP next to its DevState
     double evaluation;
     int32_t iterations, is_integral, final_height, nodes_pushed, heap_high_water, cuts_high_water, err, pad;
 };
 __host__ __device__ __forceinline__ long long tree_slot_bytes(int32_t cut_rows) { return 16LL * (1 + cut_rows); }
 __host__ __device__ __forceinline__ long long tree_ivars_bytes(int32_t RC, int32_t W) { return 16 + 4LL * pk_pad4(pk_n_idx(RC, W)); }
+// A MIR LP (include/jslpc_tree_mir.h) runs in a MIR build of the kernel.  Its LDS image is the tree LP's at its row capacity with
+// variable.isInteger per variable index behind the integer block: n_idx bytes padded to 16, built by the kernel from the image's list of
+// integer variables (the image itself is a tree LP's).  jslpc_tree_lds_bytes is tree_mir_lds_bytes.
+#define TMIR_MAX_ROUNDS 64  // rounds of ONE node: JSLPR_MAX_ROUNDS of include/jslpr_mir.h (static_assert in jslp_hip.hip)
+__host__ __device__ __forceinline__ int32_t tree_mir_flag_words(int32_t RC, int32_t W) { return pk_pad4((pk_n_idx(RC, W) + 3) / 4); }
+__host__ __device__ __forceinline__ long long tree_mir_lds_bytes(int32_t RC, int32_t W) { return pk_lds_bytes(RC, W) + 4LL * tree_mir_flag_words(RC, W); }
 #endif  // JSLP_TREE_LAYOUT
 
 #if defined(JSLP_PACKED_KERNELS) && !defined(JSLP_TREE_KERNELS_DONE)
 #define JSLP_TREE_KERNELS_DONE
+#include "jslp_tree_mir.hip.h"  // the device functions of the MIR builds
 
 struct TreeSmem {
     PackSmem ps;
@@ -97,12 +109,21 @@ __device__ __forceinline__ double tree_round(double x) {
 // OPT = true: the LPs with optional objectives (include/jslps_soft.h).  Their rows are saved with the root and come back with every restore
 // (backup.ts:35-43, 94-104), addCutConstraints leaves them alone, and a node whose evaluation EQUALS the incumbent's is compared with it
 // objective by objective on column 0 of the rows (branch-and-cut.ts:107-127).
-template <int THREADS, bool OPT>
+// MIR = true: the LPs of a model with options.useMIRCuts (include/jslpc_tree_mir.h; never with OPT).  Every node's simplex -- the root's, a
+// later node's, the final re-evaluation's -- is followed by the loop of branch-and-cut.ts:38-52: computeFractionalVolume(true), applyMIRCuts,
+// simplex again, the volume again, until it shrinks by less than 10 % (jslp_tree_mir.hip.h).  The root's MIR rows are appended before
+// save(): the saved root is Hs >= H0 rows tall and every later node starts from it.  Each simplex of the loop has the pivot cap and the
+// cycle-check history of a call of its own, and folds feasible / bounded / evaluation as a node's does.  Bounded like everything else: a
+// round whose rows exceed the row capacity, and TMIR_MAX_ROUNDS rounds of one node without a stop, end the LP with an error of its own.
+// MIR = false instantiates the kernel as it was before there was such a build.
+template <int THREADS, bool OPT, bool MIR = false>
 __global__ void __launch_bounds__(THREADS) k_tree_packed(const PackLp* __restrict__ lps, const TreeLp* __restrict__ trees, const int32_t* __restrict__ order,
                                                          const int32_t* __restrict__ cc, int cc_all, DevState* __restrict__ out_states,
                                                          double* __restrict__ out_rhs, int32_t* __restrict__ out_rows, TreeRec* __restrict__ out_tree) {
     extern __shared__ __attribute__((aligned(16))) double pk_lds[];
     __shared__ TreeSmem sm;
+    __shared__ TreeMirSm ms;  // (MIR; no other build refers to it)
+    static_assert(!(MIR && OPT), "a MIR LP has no optional objectives (include/jslpc_tree_mir.h)");
     const int idx = order[blockIdx.x];
     const PackLp m = lps[idx];
     const TreeLp t = trees[idx];
@@ -122,6 +143,7 @@ __global__ void __launch_bounds__(THREADS) k_tree_packed(const PackLp* __restric
     int32_t* rbv = ints + io.rbv;
     int32_t* cbv = ints + io.cbv;
     const uint8_t* unr = reinterpret_cast<const uint8_t*>(ints + io.unr);
+    uint8_t* is_int = reinterpret_cast<uint8_t*>(ints + io.total);  // (MIR) variable.isInteger per variable index, behind the integer block
     char* image = many_global(m.image);
     DevState* st = reinterpret_cast<DevState*>(image);
     double2* gA = reinterpret_cast<double2*>(image + sizeof(DevState));
@@ -139,8 +161,10 @@ __global__ void __launch_bounds__(THREADS) k_tree_packed(const PackLp* __restric
     const long long slot_bytes = tree_slot_bytes(t.cut_rows);
 
     // the saved root's rows and the whole integer block: image <-> LDS, 16-byte words (stride W <-> stride S)
-    const int cells = H0 * W, pairs = (cells + 1) >> 1, words = io.total >> 2;
+    int Hs = H0;  // rows of the saved root: the LP's own, (MIR) with the root's MIR rows from save() on
+    const int words = io.total >> 2;
     auto restore = [&]() {
+        const int cells = Hs * W, pairs = (cells + 1) >> 1;
         for (int q = tid; q < pairs; q += THREADS) {
             const double2 v = gA[q];
             const int e = 2 * q, r = e / W, c = e - r * W;
@@ -158,6 +182,7 @@ __global__ void __launch_bounds__(THREADS) k_tree_packed(const PackLp* __restric
             }
     };
     auto save = [&]() {
+        const int cells = Hs * W, pairs = (cells + 1) >> 1;
         for (int q = tid; q < pairs; q += THREADS) {
             const int e = 2 * q, r = e / W, c = e - r * W;
             const bool wrap = c + 1 == W;
@@ -173,12 +198,15 @@ __global__ void __launch_bounds__(THREADS) k_tree_packed(const PackLp* __restric
                 gO[q] = oo[o * S + (q - o * W)];
             }
     };
-    // addCutConstraints (cutting-strategies.ts:16-72) of the list in `slot` on the restored root: every cut row reads rows below H0
+    // addCutConstraints (cutting-strategies.ts:16-72) of the list in `slot` on the restored root: every cut row reads rows below Hs
     // and the restored maps only, so the rows are built side by side, one (cut, column) cell per thread and step; returns the height
+    // ((MIR) or -1 with nothing written: the root's MIR rows have left the list no room below the row capacity)
     auto add_cuts = [&](int slot) -> int {
-        if (slot < 0) return H0;
+        if (slot < 0) return Hs;
         const char* sp = pool + slot * slot_bytes;
         const int n = *reinterpret_cast<const int32_t*>(sp);
+        if constexpr (MIR)
+            if (Hs + n > RC) return -1;
         const TreeCut* cuts = reinterpret_cast<const TreeCut*>(sp + 16);
         for (int q = tid; q < n * W; q += THREADS) {
             const int h = q / W, col = q - h * W;
@@ -193,18 +221,23 @@ __global__ void __launch_bounds__(THREADS) k_tree_packed(const PackLp* __restric
                 const double s = A[var_row * S + col];
                 v = col == 0 ? sign * (c.value - s) : -sign * s;
             }
-            A[(H0 + h) * S + col] = v;
+            A[(Hs + h) * S + col] = v;
         }
         __syncthreads();  // (the maps read above are written below)
         for (int h = tid; h < n; h += THREADS) {  // getNewElementIndex + map updates (:64-69)
-            const int slack = W + H0 - 2 + h;
-            vibr[H0 + h] = slack;
-            rbv[slack] = H0 + h;
+            const int slack = W + Hs - 2 + h;
+            vibr[Hs + h] = slack;
+            rbv[slack] = Hs + h;
             cbv[slack] = -1;
         }
-        return H0 + n;
+        return Hs + n;
     };
 
+    if constexpr (MIR) {  // variable.isInteger, from the image's list (restore() below moves the integer block in front of it only)
+        for (int q = tid; q < tree_mir_flag_words(RC, W); q += THREADS) reinterpret_cast<int32_t*>(is_int)[q] = 0;
+        __syncthreads();
+        for (int k = tid; k < n_int; k += THREADS) is_int[ivars[k]] = 1;
+    }
     restore();
     long long trace_n = st->trace_n;
     if constexpr (OPT)  // bestOptionalObjectivesEvaluations (:66-69)
@@ -223,6 +256,37 @@ __global__ void __launch_bounds__(THREADS) k_tree_packed(const PackLp* __restric
         if (slot < 0) return;
         if (tid == 0) free_list[free_n] = slot;
         free_n += 1;
+    };
+    // (MIR) the loop behind a node's simplex (branch-and-cut.ts:38-52); false: the LP has ended with terr or serr set
+    int mir_rounds = 0, mir_rows = 0, mir_simplexes = 0, mir_tallest = H0;
+    auto mir_loop = [&]() -> bool {
+        if constexpr (MIR) {
+            double before = tmir_volume<THREADS>(A, S, vibr, H, is_int, precision, pcol, ms);
+            for (int round = 0;; round++) {
+                if (round >= TMIR_MAX_ROUNDS) { terr = TREE_ERR_MIR_ROUNDS; return false; }
+                const int n = tmir_append<THREADS>(A, S, W, H, RC, vibr, vibc, rbv, cbv, is_int, precision, ms);
+                if (n < 0) { terr = TREE_ERR_MIR_ROWS; return false; }
+                H += n;
+                mir_rounds += 1;
+                mir_rows += n;
+                mir_simplexes += 1;
+                mir_tallest = max(mir_tallest, H);
+                iters_left = m.iters_cap;
+                o = pk_simplex<THREADS, OPT>(A, pcol, H, W, S, vibr, vibc, rbv, cbv, unr, precision, check_cycles, m, ghist, gtrace, sm.ps, iters_left, trace_n, oo, n_opt);
+                __syncthreads();
+                if (o.outcome >= 5) { serr = o.outcome == 5 ? (int)ERR_ITER_LIMIT : (int)ERR_HIST_FULL; return false; }
+                feasible = (o.outcome == 3 || o.outcome == 4) ? 0 : 1;
+                unb_var = o.outcome == 2 ? vibc[o.unbounded_col] : -1;
+                if (o.outcome == 1)
+                    evaluation = __ddiv_rn(tree_round(__dmul_rn(__dadd_rn(2.220446049250313e-16, A[0]), t.rcoef)), t.rcoef);
+                else if (o.outcome == 2)
+                    evaluation = -INFINITY;
+                const double after = tmir_volume<THREADS>(A, S, vibr, H, is_int, precision, pcol, ms);
+                if (after >= 0.9 * before) return true;  // (false for NaN: the loop goes on, as the reference's does)
+                before = after;
+            }
+        }
+        return true;
     };
 
     while (terr == TREE_OK && !done) {
@@ -246,6 +310,8 @@ __global__ void __launch_bounds__(THREADS) k_tree_packed(const PackLp* __restric
             __syncthreads();
             H = add_cuts(cur_slot);
             __syncthreads();
+            if constexpr (MIR)
+                if (H < 0) { H = Hs; terr = TREE_ERR_MIR_ROWS; break; }
         }
         root = false;
         iters_left = m.iters_cap;
@@ -259,6 +325,11 @@ __global__ void __launch_bounds__(THREADS) k_tree_packed(const PackLp* __restric
             evaluation = __ddiv_rn(tree_round(__dmul_rn(__dadd_rn(2.220446049250313e-16, A[0]), t.rcoef)), t.rcoef);
         else if (o.outcome == 2)
             evaluation = -INFINITY;
+        if constexpr (MIR) {
+            mir_simplexes += 1;
+            mir_tallest = max(mir_tallest, H);
+            if (n_int > 0 && !mir_loop()) break;
+        }
         if (n_int == 0) break;  // no integer variables: a plain simplex() (tableau.ts:250-258)
         if constexpr (OPT) {
             if (!feasible || evaluation > best_eval) { release(cur_slot); continue; }  // :99-105
@@ -308,7 +379,11 @@ __global__ void __launch_bounds__(THREADS) k_tree_packed(const PackLp* __restric
             continue;
         }
         if (!(b.v > 0.0)) { terr = TREE_ERR_BRANCH; break; }
-        if (iterations == 1) { save(); __syncthreads(); }  // :155-157
+        if (iterations == 1) {  // :155-157 ((MIR) with the root's MIR rows)
+            if constexpr (MIR) Hs = H;
+            save();
+            __syncthreads();
+        }
         if (tid == 0) {  // :160-191: the two children's cut lists and their pushes, the high child first
             const int var = ivars[b.i - 1];
             const double value = A[rbv[var] * S];
@@ -367,16 +442,25 @@ __global__ void __launch_bounds__(THREADS) k_tree_packed(const PackLp* __restric
         __syncthreads();
         H = add_cuts(best_slot);
         __syncthreads();
-        iters_left = m.iters_cap;
-        o = pk_simplex<THREADS, OPT>(A, pcol, H, W, S, vibr, vibc, rbv, cbv, unr, precision, check_cycles, m, ghist, gtrace, sm.ps, iters_left, trace_n, oo, n_opt);
-        __syncthreads();
-        if (o.outcome >= 5) serr = o.outcome == 5 ? (int)ERR_ITER_LIMIT : (int)ERR_HIST_FULL;
-        feasible = (o.outcome == 3 || o.outcome == 4) ? 0 : 1;
-        unb_var = o.outcome == 2 ? vibc[o.unbounded_col] : -1;
-        if (o.outcome == 1)
-            evaluation = __ddiv_rn(tree_round(__dmul_rn(__dadd_rn(2.220446049250313e-16, A[0]), t.rcoef)), t.rcoef);
-        else if (o.outcome == 2)
-            evaluation = -INFINITY;
+        if constexpr (MIR)
+            if (H < 0) { H = Hs; terr = TREE_ERR_MIR_ROWS; }
+        if (!MIR || terr == TREE_OK) {
+            iters_left = m.iters_cap;
+            o = pk_simplex<THREADS, OPT>(A, pcol, H, W, S, vibr, vibc, rbv, cbv, unr, precision, check_cycles, m, ghist, gtrace, sm.ps, iters_left, trace_n, oo, n_opt);
+            __syncthreads();
+            if (o.outcome >= 5) serr = o.outcome == 5 ? (int)ERR_ITER_LIMIT : (int)ERR_HIST_FULL;
+            feasible = (o.outcome == 3 || o.outcome == 4) ? 0 : 1;
+            unb_var = o.outcome == 2 ? vibc[o.unbounded_col] : -1;
+            if (o.outcome == 1)
+                evaluation = __ddiv_rn(tree_round(__dmul_rn(__dadd_rn(2.220446049250313e-16, A[0]), t.rcoef)), t.rcoef);
+            else if (o.outcome == 2)
+                evaluation = -INFINITY;
+            if constexpr (MIR) {
+                mir_simplexes += 1;
+                mir_tallest = max(mir_tallest, H);
+                if (serr == ERR_NONE) (void)mir_loop();
+            }
+        }
     }
     // ---- epilogue: the state, the RHS column and the row map of whatever LDS holds now ----------------------------------------------------
     __syncthreads();
@@ -426,13 +510,23 @@ __global__ void __launch_bounds__(THREADS) k_tree_packed(const PackLp* __restric
         rec.err = terr;
         rec.pad = 0;
         out_tree[idx] = rec;
+        if constexpr (MIR) {
+            TreeMirRec mr;
+            mr.rounds = mir_rounds; mr.rows_added = mir_rows; mr.simplexes = mir_simplexes;
+            mr.root_rows = Hs - H0; mr.rows_high_water = mir_tallest - H0;
+            mr.pad[0] = mr.pad[1] = mr.pad[2] = 0;
+            *many_global(t.mir_out) = mr;
+        }
     }
     __syncthreads();
     if (tid < (int)(sizeof(DevState) / 8))
         reinterpret_cast<long long*>(out_states + idx)[tid] = reinterpret_cast<const long long*>(st)[tid];
 }
 
-// as packed_launch_impl, for the tree kernels (PackLaunch::kind == 1)
+// as packed_launch_impl, for the tree kernels (PackLaunch::kind == 1).  The plain and OPT builds and the MIR builds have a launch function
+// each, so that a unit can hold one set without the other (-DJSLP_TREE_NO_MIR_BUILDS: jslp_tu_packed.hip; -DJSLP_TREE_NO_PLAIN_BUILDS:
+// jslp_tu_tree_mir.hip)
+#ifndef JSLP_TREE_NO_PLAIN_BUILDS
 static int tree_launch_impl(int threads, unsigned grid, size_t lds, const void* bytes, hipStream_t s) {
     const PackLaunch a = *static_cast<const PackLaunch*>(bytes);
     DevState* states = static_cast<DevState*>(a.states);
@@ -450,4 +544,21 @@ static int tree_launch_impl(int threads, unsigned grid, size_t lds, const void* 
         return -1;
     return (int)hipPeekAtLastError();
 }
+#endif
+#ifndef JSLP_TREE_NO_MIR_BUILDS
+// the MIR builds (PackLaunch::mir == 1; MIR with OPT is not built)
+static int tree_mir_launch_impl(int threads, unsigned grid, size_t lds, const void* bytes, hipStream_t s) {
+    const PackLaunch a = *static_cast<const PackLaunch*>(bytes);
+    DevState* states = static_cast<DevState*>(a.states);
+    const TreeLp* trees = static_cast<const TreeLp*>(a.trees);
+    TreeRec* recs = static_cast<TreeRec*>(a.tree_out);
+    if (threads == 64 && !a.opt)
+        hipLaunchKernelGGL((k_tree_packed<64, false, true>), dim3(grid), dim3(64), lds, s, a.lps, trees, a.order, a.cc, a.cc_all, states, a.rhs, a.rows, recs);
+    else if (threads == 256 && !a.opt)
+        hipLaunchKernelGGL((k_tree_packed<256, false, true>), dim3(grid), dim3(256), lds, s, a.lps, trees, a.order, a.cc, a.cc_all, states, a.rhs, a.rows, recs);
+    else
+        return -1;
+    return (int)hipPeekAtLastError();
+}
+#endif
 #endif  // JSLP_PACKED_KERNELS

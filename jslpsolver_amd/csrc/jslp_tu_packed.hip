@@ -14,6 +14,7 @@
 namespace {
 #include "jslp_kernels.hip.h"
 #define JSLP_PACKED_KERNELS 1
+#define JSLP_TREE_NO_MIR_BUILDS 1  // (the MIR builds of k_tree_packed: jslp_tu_tree_mir.hip)
 #include "jslp_packed.hip.h"
 #include "jslp_tree.hip.h"  // k_tree_packed (include/jslpt_tree.h): the same LDS layout, the loop as pk_simplex
 }  // namespace

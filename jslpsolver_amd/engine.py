@@ -930,17 +930,93 @@ def tree_cut_rows(height, width, n_int, lib=None, n_optional=0):
     return lo
 
 
+def tree_mir_lds_bytes(height, width, row_capacity):
+    """jslpc_tree_lds_bytes (include/jslpc_tree_mir.h) restated: tree_lds_bytes with variable.isInteger per variable index (one byte each,
+    padded to 16) behind the integer block"""
+    b = tree_lds_bytes(height, width, row_capacity)
+    if b == 0:
+        return 0
+    n_idx = int(width) + 2 * int(row_capacity) + 2
+    return b + 4 * (((n_idx + 3) // 4 + 3) & ~3)
+
+
+MIR_ROW_HEADROOM = 320  # rows a MIR LP gets beyond its cut rows by default: 32 rounds of 10, as Solve gives an engine (solver._prepare)
+
+
+def tree_mir_rows(height, width, n_int, lib=None, cut_rows=None):
+    """(row_extra, cut_rows) a model with options.useMIRCuts and n_int integer variables joins a tree pack with (include/jslpc_tree_mir.h):
+    row_extra = min(cut rows + MIR_ROW_HEADROOM, the most rows that fit the LDS limit) and cut_rows = min(2 per integer variable,
+    row_extra); (0, 0) when not even one row fits.  cut_rows: the LP's own count instead of 2 per integer variable."""
+    def fits(extra):
+        if lib is not None and getattr(lib, "has_tree_mir", False):
+            b = int(lib.jslpc_tree_lds_bytes(int(height), int(width), int(height) + extra))
+        else:
+            b = tree_mir_lds_bytes(height, width, int(height) + extra)
+        return 0 < b <= _capi.JSLPP_LDS_LIMIT
+    cuts = 2 * int(n_int) if cut_rows is None else int(cut_rows)
+    lo, hi = 0, cuts + MIR_ROW_HEADROOM
+    if not fits(hi):
+        while lo < hi:  # (the byte count is monotone in the row capacity)
+            mid = (lo + hi + 1) // 2
+            lo, hi = (mid, hi) if fits(mid) else (lo, mid - 1)
+        hi = lo
+    return hi, min(cuts, hi)
+
+
 class _TreeModel:
     """what branch_and_cut.branch_and_cut reads of a model, for an LP of a pack: the default service, no tolerance, no timeout"""
     tolerance = 0
     timeout = None
-    useMIRCuts = False
     isMinimization = True
 
-    def __init__(self, integers, check_cycles):
+    def __init__(self, integers, check_cycles, mir=False):
         self.integer_index_array = np.asarray(integers, dtype=np.int64)
         self.integer_index_set = frozenset(int(i) for i in integers)
         self.checkForCycles = bool(check_cycles)
+        self.useMIRCuts = bool(mir)
+
+
+class _MirCounters:
+    """what jslpc_pack_read_mir reports of a MIR LP, gathered around the calls of the host tree on the LP's twin (applyCuts, mirRound, save),
+    with the kernel's bound on the rounds of one node enforced"""
+
+    def __init__(self, tableau):
+        from .branch_and_cut import TreeCapacity
+        self.t, self.height0 = tableau, tableau.height0
+        self.rounds = self.rows_added = self.simplexes = self.root_rows = self.node_rounds = 0
+        self.tallest = self.height0
+        apply_cuts, mir_round, save = tableau.applyCuts, tableau.mirRound, tableau.save
+
+        def applyCuts(cuts, check_cycles=True):
+            self.node_rounds = 0
+            out = apply_cuts(cuts, check_cycles=check_cycles)
+            self.simplexes += 1
+            self.tallest = max(self.tallest, out[0].height)
+            return out
+
+        def mirRound(check_cycles=True):
+            if self.node_rounds >= _capi.JSLPR_MAX_ROUNDS:
+                raise TreeCapacity("mir rounds")
+            out = mir_round(check_cycles=check_cycles)
+            self.node_rounds += 1
+            self.rounds += 1
+            self.rows_added += out[0]
+            self.simplexes += 1
+            self.tallest = max(self.tallest, out[1].height)
+            return out
+
+        def save_root():
+            save()
+            self.root_rows = tableau.last.height - self.height0
+
+        tableau.applyCuts, tableau.mirRound, tableau.save = applyCuts, mirRound, save_root
+
+    def detach(self):
+        for name in ("applyCuts", "mirRound", "save"):
+            self.t.__dict__.pop(name, None)
+
+    def record(self):
+        return (self.rounds, self.rows_added, self.simplexes, self.root_rows, self.tallest - self.height0)
 
 
 def pack_fits(height, width, lib=None, n_optional=0):
@@ -968,10 +1044,17 @@ class TableauPack:
     an error, never a fallback.
 
     optional_objectives: one entry per LP, None or that LP's n x width optional objectives (include/jslps_soft.h), as Tableau takes them;
-    optional_objectives(i) reads LP i's rows back after a solve."""
+    optional_objectives(i) reads LP i's rows back after a solve.
+
+    mir: one flag per LP of a pack with trees (include/jslpc_tree_mir.h): the LP's model has options.useMIRCuts, and every node of its tree
+    runs its MIR-cut loop.  Such an LP's rows -- the root's MIR rows, a node's cuts, the node's MIR rows -- come out of a row capacity of
+    height + row_extra (one number or one per LP; default: cut_rows + MIR_ROW_HEADROOM, capped by what fits the LDS limit), its cut lists
+    still hold at most cut_rows cuts, and its integer variables are also its variable.isInteger.  `mir` (_capi.MIR_TREE_DTYPE: rounds,
+    rows_added, simplexes, root_rows, rows_high_water) is the read-back of the last branch_and_cut(), zero for the other LPs; `is_mir` holds
+    the flags.  Not together with optional objectives."""
 
     def __init__(self, lps, precision=1e-8, lib=None, device=0, trace_cap=0, max_pivots=0, integers=None, cut_rows=None, heap_cap=None,
-                 max_nodes=0, optional_objectives=None):
+                 max_nodes=0, optional_objectives=None, mir=None, row_extra=None):
         self.lib = lib if lib is not None else _capi.load_hip()
         self._lps = []
         for matrix, vibr, vibc, unr in lps:
@@ -1031,6 +1114,29 @@ class TableauPack:
             self.row_capacity = self.heights + self.cut_rows
         else:
             self.row_capacity = self.heights
+        # MIR LPs (include/jslpc_tree_mir.h): the flags, and row_extra per LP (-1: a plain tree LP)
+        self.is_mir = np.zeros(n, dtype=bool)
+        self.mir = np.zeros(n, dtype=_capi.MIR_TREE_DTYPE)
+        self.row_extra = np.full(n, -1, dtype=np.int32)
+        if mir is not None and any(mir):
+            if not self.is_tree:
+                raise ValueError("TableauPack: `mir` needs `integers` (a pack with trees)")
+            if len(mir) != n:
+                raise ValueError("TableauPack: %d mir flags for %d LPs" % (len(mir), n))
+            if self.has_optional:
+                raise ValueError("TableauPack: MIR LPs and optional objectives do not share a pack (include/jslpc_tree_mir.h)")
+            self.is_mir = np.array([bool(f) for f in mir], dtype=bool)
+            if row_extra is None:
+                extra = [tree_mir_rows(h, w, 0, lib=self.lib, cut_rows=c)[0] for h, w, c in zip(self.heights, self.widths, self.cut_rows)]
+            else:
+                extra = per_lp(row_extra, None)
+                if extra.shape[0] != n:
+                    raise ValueError("TableauPack: row_extra is one number or one per LP")
+            self.row_extra = np.where(self.is_mir, _capi.as_i32(extra), -1).astype(np.int32)
+            self.row_capacity = np.where(self.is_mir, self.heights + self.row_extra, self.row_capacity).astype(np.int32)
+        self.has_mir = bool(self.is_mir.any())
+        if self.has_mir and self.lib.has_pack and not getattr(self.lib, "has_tree_mir", False):
+            raise _capi.EngineError("TableauPack: %s does not export the MIR tree extension (include/jslpc_tree_mir.h)" % self.lib.path)
         if self.is_tree and self.lib.has_pack and not getattr(self.lib, "has_tree", False):
             raise _capi.EngineError("TableauPack: %s does not export the tree extension (include/jslpt_tree.h)" % self.lib.path)
         if self.has_optional and self.lib.has_pack and not getattr(self.lib, "has_soft", False):
@@ -1046,6 +1152,11 @@ class TableauPack:
                 self.lib.check(self.lib.jslps_pack_create(_capi.C.byref(self._h), self.device, n, _capi.ptr_i32(self.heights), _capi.ptr_i32(self.widths),
                                                           _capi.ptr_f64(self.precision), _capi.ptr_i32(self.n_optional), self.trace_cap,
                                                           self.max_pivots), "jslps_pack_create")
+            elif self.has_mir:
+                self.lib.check(self.lib.jslpc_tree_pack_create(_capi.C.byref(self._h), self.device, n, _capi.ptr_i32(self.heights),
+                                                               _capi.ptr_i32(self.widths), _capi.ptr_f64(self.precision), _capi.ptr_i32(self.cut_rows),
+                                                               _capi.ptr_i32(self.heap_cap), _capi.ptr_i32(self.row_extra), self.trace_cap,
+                                                               self.max_pivots, self.max_nodes), "jslpc_tree_pack_create")
             elif self.is_tree:
                 self.lib.check(self.lib.jslpt_pack_create(_capi.C.byref(self._h), self.device, n, _capi.ptr_i32(self.heights), _capi.ptr_i32(self.widths),
                                                           _capi.ptr_f64(self.precision), _capi.ptr_i32(self.cut_rows), _capi.ptr_i32(self.heap_cap),
@@ -1070,6 +1181,12 @@ class TableauPack:
                 raise
         elif self.lib.backend == "oracle-c":
             for i, (h, w, rc, no) in enumerate(zip(self.heights, self.widths, self.row_capacity, self.n_optional)):
+                if self.is_mir[i] and self.row_extra[i] < self.cut_rows[i]:
+                    raise _capi.EngineError("jslpc_tree_pack_create failed (%d): pack_create: LP %d: row_extra of a MIR LP is at least its cut_rows"
+                                            % (_capi.JSLP_ERR_ARG, i))
+                if self.is_mir[i] and not 0 < tree_mir_lds_bytes(h, w, rc) <= _capi.JSLPP_LDS_LIMIT:
+                    raise _capi.EngineError("jslpc_tree_pack_create failed (%d): pack_create: LP %d: the MIR LP's LDS image at its row capacity "
+                                            "exceeds 64 KiB" % (_capi.JSLP_ERR_UNSUPPORTED, i))
                 if self.is_tree and not 0 < tree_lds_bytes(h, w, rc, no) <= _capi.JSLPP_LDS_LIMIT:
                     raise _capi.EngineError("jslpt_pack_create failed (%d): pack_create: LP %d: the tableau's LDS image at its row capacity exceeds "
                                             "64 KiB" % (_capi.JSLP_ERR_UNSUPPORTED, i))
@@ -1077,8 +1194,8 @@ class TableauPack:
                     raise _capi.EngineError("jslpp_pack_create failed (%d): pack_create: LP %d: the tableau's LDS image exceeds 64 KiB"
                                             % (_capi.JSLP_ERR_UNSUPPORTED, i))
             self._twins = [Tableau(m, vibr, vibc, unr, precision=float(p), row_capacity=int(rc), device=self.device, lib=self.lib,
-                                   optional_objectives=oo)
-                           for (m, vibr, vibc, unr), p, rc, oo in zip(self._lps, self.precision, self.row_capacity, self._optional)]
+                                   optional_objectives=oo, integer_variables=self.integers[i] if self.is_mir[i] else None)
+                           for i, ((m, vibr, vibc, unr), p, rc, oo) in enumerate(zip(self._lps, self.precision, self.row_capacity, self._optional))]
         else:
             raise _capi.EngineError("TableauPack: %s does not export the pack extension (include/jslpp_packed.h)" % self.lib.path)
 
@@ -1113,6 +1230,10 @@ class TableauPack:
                 if oo is not None:  # (an engine's upload keeps the rows it has: hand the LP's own over again)
                     self.lib.check(self.lib.jslp_engine_set_optional_objectives(t._h, int(oo.shape[0]), _capi.ptr_f64(oo)),
                                    "jslp_engine_set_optional_objectives")
+                if t.integer_variables:  # (a MIR LP's variable.isInteger: an engine's upload forgets it with the model it replaces)
+                    iv = _capi.as_i32(sorted(t.integer_variables))
+                    self.lib.check(self.lib.jslp_engine_set_integer_variables(t._h, _capi.ptr_i32(iv), int(iv.shape[0])),
+                                   "jslp_engine_set_integer_variables")
                 t.evaluation, t.feasible, t.bounded = 0.0, True, True
         else:
             self.lib.check(self.lib.jslpp_pack_upload(self._h), "jslpp_pack_upload")
@@ -1172,33 +1293,48 @@ class TableauPack:
         (_capi.TREE_DTYPE: iterations, is_integral, final_height, nodes_pushed, heap_high_water, cuts_high_water), `status`, `evaluation`,
         `feasible` and `bounded`.  An LP that reaches a capacity keeps its earlier entries and gets JSLP_ERR_CAPACITY in `status`; the others
         are solved; the call then raises EngineError naming the first such LP.  The restatement walks branch_and_cut.branch_and_cut on one
-        engine per LP with the same capacities enforced (max_pivots excepted: the engine's own cap)."""
+        engine per LP with the same capacities enforced (max_pivots excepted: the engine's own cap).
+        A MIR LP (`mir=`) runs every node's MIR loop, in the kernel as in the restatement (round by round, mirRound); `mir` keeps its
+        counters; its capacities are the row capacity (`row_extra` in the message) and JSLPR_MAX_ROUNDS rounds of one node (`mir rounds`)."""
         if not self.is_tree:
             raise _capi.EngineError("TableauPack.branch_and_cut: the pack was made without `integers`")
         flags = self._flags(check_cycles)
         out = self.results.copy()
         tree = self.tree.copy()
+        mir = self.mir.copy()
         status = np.zeros(self.n, dtype=np.int32)
         if self._twins is not None:
             from . import branch_and_cut as bc
             rc, msg = _capi.JSLP_OK, ""
             for i, (t, c) in enumerate(zip(self._twins, flags)):
+                counters = None
                 try:
                     if self.integers[i].shape[0] == 0:
                         t.simplex(check_cycles=bool(c))
                         rec = (0, 0, t.last.height, 0, 0, 0)
+                        mir_rec = (0, 0, 1, 0, 0) if self.is_mir[i] else (0, 0, 0, 0, 0)
                     else:
                         heap = bc.CountingHeap(heap_cap=int(self.heap_cap[i]), cut_rows=int(self.cut_rows[i]))
-                        iterations, integral = bc.branch_and_cut(t, _TreeModel(self.integers[i], c), heap=heap, max_nodes=self.max_nodes)
+                        if self.is_mir[i]:
+                            counters = _MirCounters(t)
+                        iterations, integral = bc.branch_and_cut(t, _TreeModel(self.integers[i], c, mir=self.is_mir[i]), heap=heap,
+                                                                 max_nodes=self.max_nodes)
                         rec = (iterations, int(integral), t.last.height, heap.pushes, heap.high_water, heap.cuts_high_water)
+                        mir_rec = counters.record() if counters is not None else (0, 0, 0, 0, 0)
                     res = SimplexResult.from_buffer_copy(bytes(t.last))
                     res.evaluation = t.evaluation
                     out[i] = np.frombuffer(res, dtype=_capi.RESULT_DTYPE)[0]
                     tree[i] = rec
+                    mir[i] = mir_rec
                 except (bc.TreeCapacity, _capi.EngineError) as e:
                     status[i] = _capi.JSLP_ERR_CAPACITY if isinstance(e, bc.TreeCapacity) or "(%d)" % _capi.JSLP_ERR_CAPACITY in str(e) else _capi.JSLP_ERR_DEVICE
+                    if self.is_mir[i] and "row capacity exceeded" in str(e):  # (an engine's refusal of a round's or a cut list's rows)
+                        e = "branch_and_cut: row_extra reached (%s)" % e
                     if rc == _capi.JSLP_OK:
                         rc, msg = int(status[i]), "pack_branch_and_cut: LP %d: %s" % (i, e)
+                finally:
+                    if counters is not None:
+                        counters.detach()
             self._launches = 0
         else:
             ms = _capi.C.c_double()
@@ -1210,9 +1346,12 @@ class TableauPack:
                 raise _capi.EngineError("jslpt_pack_branch_and_cut failed (%d): %s" % (rc, msg))
             self.device_ms = ms.value
             self._launches = int(self.lib.jslpp_pack_launches(self._h))
+            if self.has_mir:
+                self.lib.check(self.lib.jslpc_pack_read_mir(self._h, mir.ctypes.data), "jslpc_pack_read_mir")
         ok = status == _capi.JSLP_OK
         self.results = out
         self.tree = tree
+        self.mir = mir
         self.status = status
         self.feasible[ok] = out["feasible"][ok] != 0
         self.bounded[ok] = out["bounded"][ok] != 0

@@ -9,7 +9,7 @@ import numpy as np
 
 from . import _capi
 from .branch_and_cut import branch_and_cut, js_round
-from .engine import Tableau, TableauPack, pack_fits, simplex_many, tree_cut_rows
+from .engine import Tableau, TableauPack, pack_fits, simplex_many, tree_cut_rows, tree_mir_rows
 from .model import Model, js_keys
 
 EPSILON = 2.220446049250313e-16
@@ -82,9 +82,13 @@ class _PackedLp:
 def _tree_in_scope(m):
     """whether the default branch-and-cut service alone decides this model's result, with nothing that needs the host or a clock
     (include/jslpt_tree.h)"""
+    return not m.useMIRCuts and _mir_tree_in_scope(m)
+
+
+def _mir_tree_in_scope(m):
+    """_tree_in_scope whatever options.useMIRCuts says: the default service's MIR loop runs in the tree kernel too (include/jslpc_tree_mir.h)"""
     o = m.options
-    return not (m.useMIRCuts or o.get("useIncremental") is True or o.get("nodeSelection") or o.get("branching") or m.tolerance or m.timeout
-                or m.keep_solutions)
+    return not (o.get("useIncremental") is True or o.get("nodeSelection") or o.get("branching") or m.tolerance or m.timeout or m.keep_solutions)
 
 
 def solve_packed(models, precision=None, lib=None, device=0):
@@ -95,13 +99,17 @@ def solve_packed(models, precision=None, lib=None, device=0):
       * without integer variables (engine.pack_fits): its simplex();
       * with integer variables, under the default branch-and-cut service with no tolerance and no timeout, when the tableau with
         min(2 per integer variable, the most that fit) >= 1 cut rows fits (engine.tree_cut_rows): its whole tree, walked on the device
-        (TableauPack.branch_and_cut).  A tree that reaches a capacity of the pack (heap, cut rows, nodes) is solved again through Solve.
+        (TableauPack.branch_and_cut).  A tree that reaches a capacity of the pack (heap, cut rows, nodes) is solved again through Solve;
+      * the same with options.useMIRCuts and no optional objectives (include/jslpc_tree_mir.h), as a MIR LP of that pack, when
+        row_extra = min(2 per integer variable + 320, the most rows that fit) >= 1, with cut_rows = min(2 per integer variable, row_extra)
+        (engine.tree_mir_rows): every node's MIR loop runs in the kernel as well.  Its further capacities are the row capacity
+        height + row_extra, which the root's MIR rows, a node's cuts and the node's MIR rows share, and 64 MIR rounds of one node.
     Every other model goes through Solve as it is.  A model Solve rejects raises the same exception before anything is solved."""
     lib = lib if lib is not None else _capi.load_hip()
     models = list(models)
     parsed = [_parse(model, precision, 4) for model in models]
     packed = []  # positions of the models that go into the pack of plain LPs
-    trees = []   # (position, cut rows) of the models whose tree goes into the pack with trees
+    trees = []   # (position, cut rows, row_extra or -1) of the models whose tree goes into the pack with trees (row_extra >= 0: a MIR LP)
     optional = [None] * len(models)  # per model its optional objectives (None: none)
     for k, (m, matrix, _, _) in enumerate(parsed):
         _priorities, optional_rows = m.optional_objectives()
@@ -116,7 +124,11 @@ def solve_packed(models, precision=None, lib=None, device=0):
         elif _tree_in_scope(m):
             cut_rows = tree_cut_rows(matrix.shape[0], matrix.shape[1], n_int, lib=lib, n_optional=n_opt)
             if cut_rows >= 1:
-                trees.append((k, cut_rows))
+                trees.append((k, cut_rows, -1))
+        elif m.useMIRCuts and n_opt == 0 and _mir_tree_in_scope(m):
+            row_extra, cut_rows = tree_mir_rows(matrix.shape[0], matrix.shape[1], n_int, lib=lib)
+            if row_extra >= 1:
+                trees.append((k, cut_rows, row_extra))
     results = [None] * len(models)
     if packed:
         pack = TableauPack([(parsed[k][1], parsed[k][2], parsed[k][3], parsed[k][0].unrestricted) for k in packed],
@@ -128,27 +140,40 @@ def solve_packed(models, precision=None, lib=None, device=0):
                 results[k] = _solve_on(_PackedLp(pack, i), parsed[k][0], 0, False, 1, None, False, simplex_done=True)
         finally:
             pack.close()
-    if trees:
-        pack = TableauPack([(parsed[k][1], parsed[k][2], parsed[k][3], parsed[k][0].unrestricted) for k, _ in trees],
-                           precision=[parsed[k][0].precision for k, _ in trees], lib=lib, device=device,
-                           integers=[[v["index"] for v in parsed[k][0].integerVariables] for k, _ in trees], cut_rows=[c for _, c in trees],
-                           heap_cap=TREE_HEAP_CAP, max_nodes=TREE_MAX_NODES, optional_objectives=[optional[k] for k, _ in trees])
-        try:
-            try:
-                pack.branch_and_cut(check_cycles=[parsed[k][0].checkForCycles for k, _ in trees])
-            except _capi.EngineError:
-                if not (pack.status == _capi.JSLP_ERR_CAPACITY).any() or not np.isin(pack.status, (_capi.JSLP_OK, _capi.JSLP_ERR_CAPACITY)).all():
-                    raise
-            for i, (k, _) in enumerate(trees):
-                if pack.status[i] == _capi.JSLP_OK:  # (an LP that reached a capacity stays None: Solve below)
-                    results[k] = _solve_on(_PackedLp(pack, i), parsed[k][0], 0, False, 1, None, False, simplex_done=True,
-                                           integral=bool(pack.tree[i]["is_integral"]))
-        finally:
-            pack.close()
+    # (a pack holds MIR LPs or LPs with optional objectives, never both: when both kinds are there, the MIR LPs get a pack of their own)
+    mir_trees = [t for t in trees if t[2] >= 0]
+    if mir_trees and any(optional[k] is not None for k, _, _ in trees):
+        trees = [t for t in trees if t[2] < 0]
+        _solve_tree_pack(mir_trees, parsed, optional, lib, device, results)
+    _solve_tree_pack(trees, parsed, optional, lib, device, results)
     for k, model in enumerate(models):
         if results[k] is None:
             results[k] = Solve(model, precision, lib=lib, device=device)
     return results
+
+
+def _solve_tree_pack(trees, parsed, optional, lib, device, results):
+    """solve_packed's pack with trees: results[k] for every model of `trees` whose LP reached no capacity (the others stay None: Solve)"""
+    if trees:
+        with_mir = any(e >= 0 for _, _, e in trees)
+        pack = TableauPack([(parsed[k][1], parsed[k][2], parsed[k][3], parsed[k][0].unrestricted) for k, _, _ in trees],
+                           precision=[parsed[k][0].precision for k, _, _ in trees], lib=lib, device=device,
+                           integers=[[v["index"] for v in parsed[k][0].integerVariables] for k, _, _ in trees], cut_rows=[c for _, c, _ in trees],
+                           heap_cap=TREE_HEAP_CAP, max_nodes=TREE_MAX_NODES,
+                           optional_objectives=None if with_mir else [optional[k] for k, _, _ in trees],
+                           mir=[e >= 0 for _, _, e in trees] if with_mir else None, row_extra=[e for _, _, e in trees] if with_mir else None)
+        try:
+            try:
+                pack.branch_and_cut(check_cycles=[parsed[k][0].checkForCycles for k, _, _ in trees])
+            except _capi.EngineError:
+                if not (pack.status == _capi.JSLP_ERR_CAPACITY).any() or not np.isin(pack.status, (_capi.JSLP_OK, _capi.JSLP_ERR_CAPACITY)).all():
+                    raise
+            for i, (k, _, _) in enumerate(trees):
+                if pack.status[i] == _capi.JSLP_OK:  # (an LP that reached a capacity is left out: Solve)
+                    results[k] = _solve_on(_PackedLp(pack, i), parsed[k][0], 0, False, 1, None, False, simplex_done=True,
+                                           integral=bool(pack.tree[i]["is_integral"]))
+        finally:
+            pack.close()
 
 
 def _parse(model, precision, stacklevel):

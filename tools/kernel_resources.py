@@ -35,7 +35,7 @@ def demangle(n):
 print("| kernel | VGPRs | SGPRs | scratch B/lane | VGPR spills | SGPR spills | waves/SIMD | LDS B |")
 print("|---|---|---|---|---|---|---|---|")
 for r in rows:
-    name = re.sub(r"\(.*", "", demangle(r["name"]))
+    name = re.sub(r"\(.*", "", demangle(r["name"]).replace("(anonymous namespace)::", ""))  # (a unit keeps its kernels in a namespace of its own)
     if flt and flt not in name:
         continue
     print("| `%s` | %s | %s | %s | %s | %s | %s | %s |" % (name, r.get("VGPRs"), r.get("TotalSGPRs"), r.get("ScratchSize"), r.get("VGPRs Spill"),

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """solve_packed on n small MILPs, on this tree and on another checkout of the project (the parent commit), in ONE session.
-  python tools/tree_packed_times.py [--parent DIR] [--ns 1,8,64,512,4096] [--reps 3] [--rounds 3] [--soft milps|lps] [--out profiles/packed_tree_times.md]
+  python tools/tree_packed_times.py [--parent DIR] [--ns 1,8,64,512,4096] [--reps 3] [--rounds 3] [--soft milps|lps] [--mir] [--out profiles/packed_tree_times.md]
 Workload: the reference's default-policy fuzz MILPs that need no presolve pre-pass (tests/golden/fuzz_services.jsonl.gz), round robin up
 to n models.  On this tree solve_packed walks every tree on the device, one launch for the whole batch (include/jslpt_tree.h); on a tree
 without the extension (--parent: a built checkout of the parent commit) the same call walks each tree on the host through Solve.
@@ -11,7 +11,10 @@ around solve_packed, which ends in its own synchronisation and read-back; one wa
 reports the best and the median over all rounds.  Nothing is asserted about the ratio: the file records what was measured.
 --soft: the workload is the reference's recorded SOFT-constraint runs instead (tests/golden/fuzz_soft.jsonl.gz: no options, no presolve, at
 least one optional objective) -- `milps`: those with integer variables under the default service, `lps`: those without.  On a tree with
-include/jslps_soft.h they run in the OPT builds of the pack kernels; on one without, solve_packed sends every one of them through Solve."""
+include/jslps_soft.h they run in the OPT builds of the pack kernels; on one without, solve_packed sends every one of them through Solve.
+--mir: every fuzz model gets options.useMIRCuts -- the workload is the reference's recorded runs of the same models with exactly that option
+(the same file), so every result is still verified against a record.  On a tree with include/jslpc_tree_mir.h every node's MIR loop runs
+in the MIR builds of the tree kernel; on one without, solve_packed sends every one of them through Solve."""
 import argparse
 import gzip
 import json
@@ -25,10 +28,11 @@ import warnings
 HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def cases(root, soft=None):
+def cases(root, soft=None, mir=False):
     with gzip.open(os.path.join(root, "tests", "golden", "fuzz_soft.jsonl.gz" if soft else "fuzz_services.jsonl.gz"), "rt") as fh:
         cs = [json.loads(line) for line in fh if line.startswith("{")]
-    cs = [c for c in cs if not c["model"].get("options") and c["fixed"] == 0 and not c["infeasPre"]]
+    options = {"useMIRCuts": True} if mir else None
+    cs = [c for c in cs if (c["model"].get("options") or None) == options and c["fixed"] == 0 and not c["infeasPre"]]
     if soft:  # (the selection of tests/soft_pack_util.py::soft_records)
         if root not in sys.path:
             sys.path.insert(0, root)
@@ -52,7 +56,7 @@ def worker(a):
     from jslpsolver_amd.solver import solve_packed
     warnings.simplefilter("ignore")
     lib = _capi.Library(os.path.join(a.root, a.lib)) if a.lib else _capi.load_hip()
-    cs = cases(a.root, a.soft)
+    cs = cases(a.root, a.soft, a.mir)
 
     def verify(results, n):
         for k in range(n):
@@ -70,7 +74,7 @@ def worker(a):
             results = solve_packed(models, lib=lib)
             dt = time.perf_counter() - t0
             verify(results, n)
-            print(json.dumps({"n": n, "wall_ms": 1e3 * dt, "device_tree": bool(getattr(lib, "has_soft" if a.soft else "has_tree", False))}), flush=True)
+            print(json.dumps({"n": n, "wall_ms": 1e3 * dt, "device_tree": bool(getattr(lib, "has_tree_mir" if a.mir else "has_soft" if a.soft else "has_tree", False))}), flush=True)
 
 
 def main():
@@ -81,11 +85,14 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--out", default=None)
     ap.add_argument("--soft", default=None, choices=["milps", "lps"], help="the recorded soft-constraint runs: those with / without integer variables")
+    ap.add_argument("--mir", action="store_true", help="every fuzz model with options.useMIRCuts (the reference's recorded runs with that option)")
     ap.add_argument("--worker", action="store_true")
     ap.add_argument("--root", default=HERE)
     ap.add_argument("--lib", default=None, help="engine library, relative to each checkout (default: the HIP product library); "
                     "oracle/libjslp_oracle.so rehearses the tool without a GPU -- its times say nothing")
     a = ap.parse_args()
+    if a.mir and a.soft:
+        ap.error("--mir and --soft are two workloads")
     if a.worker:
         return worker(a)
     trees = [("this commit", HERE)] + ([("parent commit", os.path.abspath(a.parent))] if a.parent else [])
@@ -94,7 +101,7 @@ def main():
     for _ in range(a.rounds):
         for name, root in trees:  # (the two alternate, round by round)
             out = subprocess.run([sys.executable, os.path.abspath(__file__), "--worker", "--root", root, "--ns", a.ns, "--reps", str(a.reps)] + (["--lib", a.lib] if a.lib else []) +
-                                 (["--soft", a.soft] if a.soft else []),
+                                 (["--soft", a.soft] if a.soft else []) + (["--mir"] if a.mir else []),
                                  check=True, capture_output=True, text=True, timeout=900).stdout
             print("round done: %s" % name, file=sys.stderr, flush=True)
             for line in out.splitlines():
@@ -102,11 +109,14 @@ def main():
                     r = json.loads(line)
                     times[name].setdefault(r["n"], []).append(r["wall_ms"])
                     flags[name] = r["device_tree"]
-    n_models = len(cases(HERE, a.soft))
+    n_models = len(cases(HERE, a.soft, a.mir))
     what = {None: "default-policy fuzz MILPs", "milps": "recorded soft-constraint MILPs", "lps": "recorded soft-constraint LPs"}[a.soft]
-    lines = ["# `solve_packed` on small MILPs: trees walked on the device against trees walked on the host (MI355X)" if not a.soft else
+    if a.mir:
+        what = "fuzz MILPs with `options.useMIRCuts`"
+    lines = ["# `solve_packed` on small MILPs with MIR cuts: every node's MIR loop in the tree kernel against one engine per model (MI355X)" if a.mir else
+             "# `solve_packed` on small MILPs: trees walked on the device against trees walked on the host (MI355X)" if not a.soft else
              "# `solve_packed` on the %s: the pack's OPT builds against one engine per model (MI355X)" % what, "",
-             "`python tools/tree_packed_times.py --parent <checkout of the parent commit> --out profiles/packed_tree_times.md`: one session, one "
+             "`python tools/tree_packed_times.py --parent <checkout of the parent commit>%s --out %s`: one session, one " % (" --mir" if a.mir else "", "profiles/" + os.path.basename(a.out or "packed_tree_times.md")) +
              "device, %d rounds alternating between the two checkouts, each in a process of its own; per round one warm-up call and %d timed "
              "calls per n; wall time of `solve_packed(models)` on n models taken round robin from the %d %s; every result "
              "of every call verified against the reference's recorded result before its time was kept." % (a.rounds, a.reps, n_models, what), "",
