@@ -112,6 +112,7 @@ struct jslp_engine {
     int* d_done_count = nullptr;  // workgroups of a small batch that have delivered their outcome (k_node_lds: the last one raises the completion flag)
     unsigned long long* d_nnz = nullptr; long long nnz = -1;  // non-zero cells of the uploaded tableau (counted on the device)
     unsigned spin_limit = 0; int test_abort_epoch = -1; int test_late_wave0 = 0;
+    int test_iters_cap = 0;  // tests only (JSLP_TEST_ITERS_CAP): a lower iteration cap, 0 = none
     int resident_fallbacks = 0;  // solves that were rolled back and re-run through the streaming kernels
     int resident_handovers = 0;  // solves the lean resident kernel handed to the general one (cycle-check history beyond its LDS copy)
     int resident_launches = 0;   // cooperative launches of k_simplex_resident the runtime accepted
@@ -399,6 +400,8 @@ static int read_engine_policy(jslp_engine* e) {
     e->test_abort_epoch = ta ? atoi(ta) : -1;
     const char* tl = getenv("JSLP_TEST_RESIDENT_LATE_WAVE0");  // tests only: wave 0 of every workgroup reaches each row fetch late
     e->test_late_wave0 = tl ? atoi(tl) : 0;
+    const char* tc = getenv("JSLP_TEST_ITERS_CAP");  // tests only: the iteration cap (iters_cap) comes down to this many pivots per simplex call
+    e->test_iters_cap = tc ? std::max(0, atoi(tc)) : 0;
     return JSLP_OK;
 }
 // snapshot, unrestricted flags and pivot trace: one allocation
@@ -629,6 +632,7 @@ static int iters_cap(const jslp_engine* e) {
     // the reference has no iteration limit; this cap only turns an endless cycle (cycle check disabled) into
     // an error instead of a hung GPU
     long long cap = 2000000LL + 200LL * ((long long)e->cap_rows + e->W);
+    if (e->test_iters_cap > 0) cap = std::min<long long>(cap, e->test_iters_cap);  // (tests: the exit at the cap after a handful of pivots)
     return (int)std::min<long long>(cap, 2000000000LL);
 }
 

@@ -334,6 +334,20 @@ __device__ __forceinline__ int price_optional_regs(const double (&x)[CPT], const
 // (a chain `if (i == row) a[i][j] = ...` over the unrolled rows is what the optimizer likes to fold into ONE store at a[row][j] -- a
 //  dynamic index, which sends the whole register array to scratch: 456 bytes per lane, 1648 scratch instructions, 28-47 k cycles per
 //  update pass (r04_d).  An empty asm per iteration makes every comparison's operand its own opaque value.)
+// which instances get the update pass's gate-free arm (JSLP_XL_UPDATE_PASS) and the candidate row's pick as a tree (JSLP_PUBLISH_ROW_PLAIN), and the row masks
+// of that arm -- ONE definition for the phase-2 and the phase-1 loop.  The 8-row geometries with 2 / 4 columns per lane, chip-wide, no optional objectives: the
+// instances where both leave VGPRs, scratch and VGPR spills as they were (profiles/update_fast_path.md: config 3a 200.7 k -> 207.3 k -> 210.0 k pivots/s)
+template <int CPT, int ROWS, bool OPT, bool XL>
+struct PipeUpd {
+    static constexpr bool UFAST = !XL && !OPT && ROWS <= 8 && CPT <= 4;  // (all of them builds whose update pass is JSLP_XL_UPDATE_PASS: UPD_NEW of the two loops)
+    static constexpr bool PUBTREE = UFAST && ROWS == 8;
+    static constexpr unsigned ALL_ROWS = (unsigned)((1ull << ROWS) - 1ull);
+    // (uniform) my rows >= r_end: padding, +0 in every cell.  Row 0 of workgroup 0 -- the cost row's mirror, overwritten behind every pass -- is NOT counted as
+    // dead, though it could be: its entry of the pivot column is the entering column's reduced cost, above the precision and so above the gate at every pivot of
+    // phase 2; in phase 1 a column of cost zero sends workgroup 0 (alone) through the gated arm, the parent's code at the parent's speed.  Not built: the headline
+    // cannot gain from it, and 3b's phase 1 (546 pivots, 3.2 ms) was not worth another round of measurements
+    static __device__ __forceinline__ unsigned dead_rows(int live) { return ALL_ROWS & ~(unsigned)((1ull << max(0, min(ROWS, live))) - 1ull); }
+};
 #define JSLP_OPAQUE_SGPR(x) ({ int o_ = (x); asm volatile("" : "+s"(o_)); o_; })
 #define JSLP_XL_UPDATE_PASS()                                                                                                     \
     do {                                                                                                                          \
@@ -346,9 +360,37 @@ __device__ __forceinline__ int price_optional_regs(const double (&x)[CPT], const
         /* (measured, r04_e ... r04_g, XCD-local build: per-row LDS reads + per-cell SELECTS 5.4-6.9 k cycles per pass; readlane multipliers  \
             3.9-5.9 k; one pass over the rows with the column gate as an EXEC-masked branch per cell 5.1-8.5 k; a second, gate-free copy of \
             the loop for dense pivot rows costs the register allocator ~400 spills.  Round 6, JSLP_PIPE_K_BROADCAST: the multipliers of eight \
-            rows come as BROADCAST LDS reads (one address for the whole wave) into vector registers -- a cell is then scalar bit test,    \
-            branch, v_mul_f64, v_add_f64; the two v_readlane + s_nop per cell, which sixteen lock-step waves paid on the VALU port, are gone) */ \
-        if (JSLP_PIPE_K_BROADCAST) {                                                                                              \
+            rows come as BROADCAST LDS reads (one address for the whole wave) into vector registers -- a cell is then v_mul_f64, v_add_f64     \
+            and two v_cndmask_b32 on the row gate's mask (if-converted: no branch); the two v_readlane + s_nop per cell, which sixteen lock-step waves paid on the VALU port, are gone) */ \
+        if (UFAST) {                                                                                                              \
+            /* ONE uniform test per pass: is every row's gate open, or the row padding?  Then 2 x ROWS f64 instructions per column, in place --\
+               on a dense LP that is all but every pass (profiles/update_fast_path.md: config 3a, 99.9997 % of the workgroups' passes).\
+               Padding rows (>= r_end) hold +0 in every cell and +0 in sm.colb, and (+0) - (+0 * p) = +0 for every finite p; a non-finite p\
+               leaves NaN there, which nobody reads (the ratio test, the publication, column 0's mirror and the store-back all stop at\
+               r_end; a NaN multiplier of a padding row meets only that row) -- so the last workgroup takes this arm too and does not set\
+               the pace for the others.  A closed gate somewhere (a sparse pivot column, the rare |k| <= 1e-16) takes the gated arm below:\
+               the compiler turns its per-row test into 8 x (s_bitcmp0 + s_cselect_b64) per column and two v_cndmask_b32 per cell.\
+               Two `if`s, the second behind an opaque copy of the mask, not if / else: as ONE diamond the two arms' results meet in a\
+               second set of ROWS x CPT register pairs (105 -> 127 VGPRs); like this both update the cells where they are */      \
+            double kb_[ROWS];                                                                                                     \
+            _Pragma("unroll") for (int i = 0; i < ROWS; i++) kb_[i] = sm.colb[par_p][i];                                          \
+            const int om_ = (int)(km_ | dead_rows), full_ = (int)ALL_ROWS;                                                        \
+            if (om_ == full_) {                                                                                                   \
+                _Pragma("unroll") for (int j = 0; j < CPT; j++) {                                                                 \
+                    if ((nzm >> j) & 1u) {                                                                                        \
+                        _Pragma("unroll") for (int i = 0; i < ROWS; i++) a[i][j] = eliminate(a[i][j], kb_[i], p[j]);              \
+                    }                                                                                                             \
+                }                                                                                                                 \
+            }                                                                                                                     \
+            if (JSLP_OPAQUE_SGPR(om_) != full_) {                                                                                 \
+                _Pragma("unroll") for (int j = 0; j < CPT; j++) {                                                                 \
+                    if ((nzm >> j) & 1u) {                                                                                        \
+                        _Pragma("unroll") for (int i = 0; i < ROWS; i++)                                                          \
+                            if (km_ & (1u << i)) a[i][j] = eliminate(a[i][j], kb_[i], p[j]);                                      \
+                    }                                                                                                             \
+                }                                                                                                                 \
+            }                                                                                                                     \
+        } else if (JSLP_PIPE_K_BROADCAST) {                                                                                       \
             _Pragma("unroll") for (int i0 = 0; i0 < ROWS; i0 += 8) {                                                              \
                 double kb_[8];                                                                                                    \
                 _Pragma("unroll") for (int i = 0; i < 8; i++) kb_[i] = (i0 + i < ROWS) ? sm.colb[par_p][i0 + i] : 0.0;            \
@@ -405,6 +447,7 @@ __device__ __forceinline__ int price_optional_regs(const double (&x)[CPT], const
                 }                                                                                                                 \
         }                                                                                                                         \
     } while (0)
+#define JSLP_PUB_COPY(i) do { _Pragma("unroll") for (int j = 0; j < CPT; j++) { double t_ = a[i][j]; asm volatile("" : "+v"(t_)); cand_[j] = t_; } } while (0)
 // the chip-wide builds' candidate row (untagged: the winner's flag follows its release): the same compare chain, the slot layout of SLOT / PERM
 #define JSLP_PUBLISH_ROW_PLAIN(ROW)                                                                                               \
     do {                                                                                                                          \
@@ -419,6 +462,15 @@ __device__ __forceinline__ int price_optional_regs(const double (&x)[CPT], const
         u64_t ck_ = 0;                                                                                                            \
         double cand_[CPT]; /* my columns of the row that can win (the compare chain: see JSLP_OPAQUE_SGPR) */                     \
         _Pragma("unroll") for (int j = 0; j < CPT; j++) cand_[j] = 0.0;                                                           \
+        if (PUBTREE) { /* (three uniform compares to one of eight leaves instead of a walk past all eight; the same opaque copies) */ \
+            if (JSLP_OPAQUE_SGPR(ipub_) < 4) {                                                                                    \
+                if (JSLP_OPAQUE_SGPR(ipub_) < 2) { if (JSLP_OPAQUE_SGPR(ipub_) == 0) JSLP_PUB_COPY(0); else if (JSLP_OPAQUE_SGPR(ipub_) == 1) JSLP_PUB_COPY(1); } \
+                else { if (JSLP_OPAQUE_SGPR(ipub_) == 2) JSLP_PUB_COPY(2); else if (JSLP_OPAQUE_SGPR(ipub_) == 3) JSLP_PUB_COPY(3); } \
+            } else {                                                                                                              \
+                if (JSLP_OPAQUE_SGPR(ipub_) < 6) { if (JSLP_OPAQUE_SGPR(ipub_) == 4) JSLP_PUB_COPY(4); else if (JSLP_OPAQUE_SGPR(ipub_) == 5) JSLP_PUB_COPY(5); } \
+                else { if (JSLP_OPAQUE_SGPR(ipub_) == 6) JSLP_PUB_COPY(6); else if (JSLP_OPAQUE_SGPR(ipub_) == 7) JSLP_PUB_COPY(7); } \
+            }                                                                                                                     \
+        } else                                                                                                                    \
         _Pragma("unroll") for (int i = 0; i < ROWS; i++)                                                                          \
             if (i == JSLP_OPAQUE_SGPR(ipub_)) { /* (each copy behind an opaque barrier: as plain selects the optimizer folds the chain into ONE   \
                 dynamically indexed read of a[][] -- the whole register array went to scratch in the tall geometry, 600 B per lane, 23 k pivots/s) */ \
@@ -694,6 +746,11 @@ __device__ __forceinline__ void resident_phase2_pipe(const ResCtx& f, RSmem& sm,
     // the pending pivot's row update in the XCD-local build's form (JSLP_XL_UPDATE_PASS: one ballot for the row gate, readlane multipliers,
     // the special rows fixed up once per pivot) instead of JSLP_PIPE_UPDATE_ROW's ~55 instructions per row
     constexpr bool UPD_NEW = XL || (CPT <= 4 && !(OPT && ROWS > 8));  // (the 6- / 8-column geometries and the tall OPT build would spill 14-94 VGPRs with it)
+    // ... and in it ONE uniform test per pass -- is every row's gate open? -- in front of a gate-free arm, and the candidate row picked by a tree of branches (PipeUpd)
+    typedef PipeUpd<CPT, ROWS, OPT, XL> PU;
+    constexpr bool UFAST = PU::UFAST, PUBTREE = PU::PUBTREE;
+    static_assert(!UFAST || UPD_NEW, "the gate-free arm lives in JSLP_XL_UPDATE_PASS");
+    constexpr unsigned ALL_ROWS = PU::ALL_ROWS;
     // candidate rows in the publication buffer (chip-wide builds): pair j of lane t at ((j / 2) * THREADS + t) * 16 inside the
     // workgroup's slot -- a wave's store of one pair is 1 KB of whole lines (with lane t's CPT columns adjacent, as they sit in the
     // tableau, the 512-thread geometries wrote 16 bytes into each of 64 lines per instruction: the partial-line writers of round 3);
@@ -718,6 +775,8 @@ __device__ __forceinline__ void resident_phase2_pipe(const ResCtx& f, RSmem& sm,
     const int c0 = tid * CPT;
     const bool colok = c0 < ld;
     const int r_begin = b * f.rpb, r_end = min(f.H, r_begin + f.rpb);
+    const unsigned dead_rows = PU::dead_rows(r_end - r_begin);
+    (void)dead_rows; (void)ALL_ROWS;
     double (&a)[ROWS][CPT] = R.a;
     double (&r0)[CPT] = R.r0;
     typedef unsigned int v4u_t __attribute__((ext_vector_type(4)));
@@ -1332,6 +1391,10 @@ __device__ __forceinline__ void resident_phase1_pipe(const ResCtx& f, RSmem& sm,
     // the pending pivot's row update in the XCD-local build's form (JSLP_XL_UPDATE_PASS: one ballot for the row gate, readlane multipliers,
     // the special rows fixed up once per pivot) instead of JSLP_PIPE_UPDATE_ROW's ~55 instructions per row
     constexpr bool UPD_NEW = XL || (CPT <= 4 && !(OPT && ROWS > 8));  // (the 6- / 8-column geometries and the tall OPT build would spill 14-94 VGPRs with it)
+    typedef PipeUpd<CPT, ROWS, OPT, XL> PU;
+    constexpr bool UFAST = PU::UFAST, PUBTREE = PU::PUBTREE;
+    static_assert(!UFAST || UPD_NEW, "the gate-free arm lives in JSLP_XL_UPDATE_PASS");
+    constexpr unsigned ALL_ROWS = PU::ALL_ROWS;
     // candidate rows in the publication buffer (chip-wide builds): pair j of lane t at ((j / 2) * THREADS + t) * 16 inside the
     // workgroup's slot -- a wave's store of one pair is 1 KB of whole lines (with lane t's CPT columns adjacent, as they sit in the
     // tableau, the 512-thread geometries wrote 16 bytes into each of 64 lines per instruction: the partial-line writers of round 3);
@@ -1352,6 +1415,8 @@ __device__ __forceinline__ void resident_phase1_pipe(const ResCtx& f, RSmem& sm,
     const int c0 = tid * CPT;
     const bool colok = c0 < ld;
     const int r_begin = b * f.rpb, r_end = min(f.H, r_begin + f.rpb);
+    const unsigned dead_rows = PU::dead_rows(r_end - r_begin);
+    (void)dead_rows; (void)ALL_ROWS;
     double (&a)[ROWS][CPT] = R.a;
     double (&r0)[CPT] = R.r0;
     typedef unsigned int v4u_t __attribute__((ext_vector_type(4)));
@@ -1791,6 +1856,7 @@ __device__ __forceinline__ void resident_phase1_pipe(const ResCtx& f, RSmem& sm,
 #undef JSLP_XL_UPDATE_PASS
 #undef JSLP_XL_PUBLISH_ROW
 #undef JSLP_PUBLISH_ROW_PLAIN
+#undef JSLP_PUB_COPY
 #undef JSLP_XL_FETCH_ROW
 #undef JSLP_CKS_FETCH_ROW
 #undef JSLP_CKS_ISSUE_LOOK
