@@ -1,7 +1,7 @@
 """ctypes binding of the C ABI declared in include/jslp_engine.h (SYMBOLS) and of its HIP-only extensions include/jslpx_branch.h
 (BRANCH_SYMBOLS), include/jslpm_many.h (MANY_SYMBOLS), include/jslpf_f32.h (F32_SYMBOLS), include/jslpr_mir.h (MIR_SYMBOLS) and
 include/jslpp_packed.h (PACK_SYMBOLS) with include/jslpt_tree.h (TREE_SYMBOLS), include/jslps_soft.h (SOFT_SYMBOLS) and
-include/jslpc_tree_mir.h (TREE_MIR_SYMBOLS).
+include/jslpc_tree_mir.h (TREE_MIR_SYMBOLS) and include/jslpe_tree_enhanced.h (TREE_ENH_SYMBOLS).
 
 The same binding class serves two libraries that export identical symbols:
   * jslpsolver_amd/csrc/libjslp_hip.so -- the product (hand-written HIP kernels, gfx950)
@@ -246,6 +246,20 @@ TREE_MIR_SYMBOLS = {
                                          C.c_int32]),
     "jslpc_pack_read_mir": (C.c_int, [C.c_void_p, C.c_void_p]),
 }
+# name -> (restype, argtypes); must list EVERY symbol include/jslpe_tree_enhanced.h declares.  HIP library only (Library.has_tree_enh).
+TREE_ENH_SYMBOLS = {
+    "jslpe_tree_pack_create": (C.c_int, [_P(C.c_void_p), C.c_int, C.c_int32, _i32p, _i32p, _f64p, _i32p, _i32p, _i32p, _i32p, C.c_int32, C.c_int32,
+                                         C.c_int32]),
+    "jslpe_tree_pack_create_mixed": (C.c_int, [_P(C.c_void_p), C.c_int, C.c_int32, _i32p, _i32p, _f64p, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p,
+                                               C.c_int32, C.c_int32, C.c_int32]),
+    "jslpe_pack_read_enhanced": (C.c_int, [C.c_void_p, C.c_void_p]),
+}
+# numpy twin of struct jslpe_tree_result
+ENH_TREE_DTYPE = np.dtype([(name, np.int32) for name in ("solutions_found", "stack_high_water", "moved_to_heap", "pseudo_updates",
+                                                         "scored_by_pseudocost", "dropped_nodes", "reserved0", "reserved1")])
+# node_selection / branching of jslpe_tree_pack_create (0: the default service)
+ENH_NODE_SELECTION = {"best-first": 1, "depth-first": 2, "hybrid": 3}
+ENH_BRANCHING = {"most-fractional": 1, "pseudocost": 2, "strong": 3}
 # numpy twin of struct jslpc_mir_result
 MIR_TREE_DTYPE = np.dtype([(name, np.int32) for name in ("rounds", "rows_added", "simplexes", "root_rows", "rows_high_water")])
 # numpy twin of struct jslpt_tree_result
@@ -279,6 +293,7 @@ class Library:
         self.has_tree = self.has_pack and self._bind_extension(TREE_SYMBOLS)
         self.has_soft = self.has_tree and self._bind_extension(SOFT_SYMBOLS)
         self.has_tree_mir = self.has_tree and self._bind_extension(TREE_MIR_SYMBOLS)
+        self.has_tree_enh = self.has_tree_mir and self.has_soft and self._bind_extension(TREE_ENH_SYMBOLS)
 
     def _bind_extension(self, symbols):
         """bind a HIP-only extension when the library exports all of it; False otherwise"""

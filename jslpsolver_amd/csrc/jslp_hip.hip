@@ -21,6 +21,7 @@
 #include "../../include/jslpt_tree.h"
 #include "../../include/jslps_soft.h"
 #include "../../include/jslpc_tree_mir.h"
+#include "../../include/jslpe_tree_enhanced.h"
 #include "jslp_kernels.hip.h"
 #include "jslp_host_mem.h"
 
@@ -3435,7 +3436,9 @@ extern "C" int jslpf_simplex_f32_sweep(jslp_engine* e, const double* precisions,
 #ifdef JSLP_SPLIT_TU
 extern "C" __attribute__((visibility("hidden"))) int jslpp_packed_launch_tu(int threads, unsigned grid, size_t lds, const void* args, void* stream);
 extern "C" __attribute__((visibility("hidden"))) int jslpc_tree_mir_launch_tu(int threads, unsigned grid, size_t lds, const void* args, void* stream);
+extern "C" __attribute__((visibility("hidden"))) int jslpe_tree_enh_launch_tu(int threads, unsigned grid, size_t lds, const void* args, void* stream);
 static int packed_launch(int threads, unsigned grid, size_t lds, const PackLaunch& a, hipStream_t s) {
+    if (a.kind == 1 && a.enh) return jslpe_tree_enh_launch_tu(threads, grid, lds, &a, s);  // (the ENH builds of k_tree_packed: jslp_tu_tree_enh.hip)
     if (a.kind == 1 && a.mir) return jslpc_tree_mir_launch_tu(threads, grid, lds, &a, s);  // (the MIR builds of k_tree_packed: jslp_tu_tree_mir.hip)
     return jslpp_packed_launch_tu(threads, grid, lds, &a, s);
 }
@@ -3443,7 +3446,9 @@ static int packed_launch(int threads, unsigned grid, size_t lds, const PackLaunc
 static int packed_launch_impl(int threads, unsigned grid, size_t lds, const void* bytes, hipStream_t s);  // (jslp_packed.hip.h, at the end of this file)
 static int tree_launch_impl(int threads, unsigned grid, size_t lds, const void* bytes, hipStream_t s);    // (jslp_tree.hip.h, there too)
 static int tree_mir_launch_impl(int threads, unsigned grid, size_t lds, const void* bytes, hipStream_t s);  // (its MIR builds)
+static int tree_enh_launch_impl(int threads, unsigned grid, size_t lds, const void* bytes, hipStream_t s);  // (its ENH builds)
 static int packed_launch(int threads, unsigned grid, size_t lds, const PackLaunch& a, hipStream_t s) {
+    if (a.kind == 1 && a.enh) return tree_enh_launch_impl(threads, grid, lds, &a, s);
     if (a.kind == 1 && a.mir) return tree_mir_launch_impl(threads, grid, lds, &a, s);
     return a.kind == 1 ? tree_launch_impl(threads, grid, lds, &a, s) : packed_launch_impl(threads, grid, lds, &a, s);
 }
@@ -3470,6 +3475,10 @@ struct jslpp_pack {
     bool has_mir = false;
     std::vector<uint8_t> mir;
     std::vector<int32_t> tree_status;
+    // a pack made by jslpe_tree_pack_create (include/jslpe_tree_enhanced.h): per LP its tree policy (0: the default service; else node selection
+    // | branching << 4: an ENH build of the tree kernel, a pseudocost table behind its heap, a TreeEnhRec in the result block)
+    bool has_enh = false;
+    std::vector<int32_t> policy;
     TreeLp* d_trees = nullptr;
     char* d_tree_mem = nullptr;
     size_t tree_mem_bytes = 0;
@@ -3486,9 +3495,10 @@ struct jslpp_pack {
     int32_t *d_order = nullptr, *d_cc = nullptr;
     int2 *d_hist = nullptr, *d_trace = nullptr;
     // the launch groups, in launch order: [0] one wave, [1] 256 threads, [2] one wave with OPT, [3] 256 threads with OPT, [4] one wave
-    // with MIR, [5] 256 threads with MIR (a plain simplex of a MIR LP runs in the build of group & 3)
-    int32_t n_group[6] = {0, 0, 0, 0, 0, 0};
-    size_t lds_group[6] = {0, 0, 0, 0, 0, 0};
+    // with MIR, [5] 256 threads with MIR, [6] one wave with ENH, [7] 256 threads with ENH (a plain simplex of a MIR or an enhanced LP runs
+    // in the build of group & 1)
+    int32_t n_group[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    size_t lds_group[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     // optional objectives (include/jslps_soft.h): rows per LP, whether they were set, and where they lie in the result block (in doubles)
     std::vector<int32_t> n_opt;
     std::vector<uint8_t> opt_set;
@@ -3503,7 +3513,11 @@ struct jslpp_pack {
     size_t res_rows_off() const { return (res_rhs_off() + sizeof(double) * (size_t)offs[n] + 255) & ~(size_t)255; }
     size_t res_tree_off() const { return (res_rows_off() + sizeof(int32_t) * (size_t)offs[n] + 255) & ~(size_t)255; }
     size_t res_mir_off() const { return (res_tree_off() + sizeof(TreeRec) * (size_t)n + 255) & ~(size_t)255; }  // (has_mir: a TreeMirRec per LP)
+    size_t res_enh_off() const {  // (has_enh: a TreeEnhRec per LP, behind the MIR records when the pack has them)
+        return ((has_mir ? res_mir_off() + sizeof(TreeMirRec) * (size_t)n : res_tree_off() + sizeof(TreeRec) * (size_t)n) + 255) & ~(size_t)255;
+    }
     size_t res_plain_bytes() const {
+        if (has_enh) return res_enh_off() + sizeof(TreeEnhRec) * (size_t)n;
         if (has_mir) return res_mir_off() + sizeof(TreeMirRec) * (size_t)n;
         return tree ? res_tree_off() + sizeof(TreeRec) * (size_t)n : res_rows_off() + sizeof(int32_t) * (size_t)offs[n];
     }
@@ -3511,7 +3525,14 @@ struct jslpp_pack {
     size_t res_bytes() const { return opt_offs[n] ? res_opt_off() + sizeof(double) * (size_t)opt_offs[n] : res_plain_bytes(); }
     TreeRec* h_tree() const { return reinterpret_cast<TreeRec*>(result.h.p + res_tree_off()); }
     TreeMirRec* h_mir() const { return reinterpret_cast<TreeMirRec*>(result.h.p + res_mir_off()); }
+    TreeEnhRec* h_enh() const { return reinterpret_cast<TreeEnhRec*>(result.h.p + res_enh_off()); }
     bool is_mir(size_t i) const { return has_mir && mir[i]; }
+    bool is_enh(size_t i) const { return has_enh && policy[i] != 0; }
+    size_t tree_lp_bytes(size_t i) const {  // LP i's share of d_tree_mem: heap, (pseudocost table,) pool, free stack, best_opt
+        const size_t slots = (size_t)heap_cap[i] + 3;
+        return sizeof(TreeEntry) * (size_t)heap_cap[i] + (is_enh(i) ? (size_t)tree_pseudo_bytes(RC[i], W[i]) : 0) + (size_t)tree_slot_bytes(cut_rows[i]) * slots +
+               ((sizeof(int32_t) * slots + 15) & ~(size_t)15) + ((sizeof(double) * (size_t)n_opt[i] + 15) & ~(size_t)15);
+    }
     size_t lds_bytes(size_t i) const { return is_mir(i) ? (size_t)tree_mir_lds_bytes(RC[i], W[i]) : (size_t)pk_lds_bytes(RC[i], W[i], n_opt[i]); }
     size_t ints_off(int32_t i) const { return sizeof(DevState) + 8 * (size_t)pk_image_doubles(RC[i], W[i], n_opt[i]); }
     size_t opt_rows_off(int32_t i) const { return sizeof(DevState) + 8 * (size_t)pk_opt_image_off(RC[i], W[i]); }
@@ -3568,10 +3589,10 @@ static int pack_init(jslpp_pack* p, int32_t max_pivots) {
     std::vector<PackLp> lps(n);
     std::vector<int32_t> order(n);
     int32_t k = 0;
-    for (int g = 0; g < 6; g++)  // the one-wave LPs first, then the 256-thread ones, then the same two with optional objectives, then with MIR, each in pack order
+    for (int g = 0; g < 8; g++)  // the one-wave LPs first, then the 256-thread ones, then the same two with optional objectives, with MIR, with ENH, each in pack order
         for (size_t i = 0; i < n; i++) {
             const bool wave = (long long)p->RC[i] * p->W[i] <= PACK_CELLS_WAVE;  // (tableau cells at the row capacity, optional rows or not)
-            if ((wave ? 0 : 1) + (p->n_opt[i] > 0 ? 2 : 0) + (p->is_mir(i) ? 4 : 0) != g) continue;
+            if ((wave ? 0 : 1) + (p->n_opt[i] > 0 ? 2 : 0) + (p->is_mir(i) ? 4 : 0) + (p->is_enh(i) ? 6 : 0) != g) continue;
             order[k++] = (int32_t)i;
             p->n_group[g] += 1;
             p->lds_group[g] = std::max(p->lds_group[g], p->lds_bytes(i));
@@ -3603,6 +3624,7 @@ static int pack_init(jslpp_pack* p, int32_t max_pivots) {
             const size_t slots = (size_t)p->heap_cap[i] + 3;
             t.heap = reinterpret_cast<TreeEntry*>(p->d_tree_mem + off);
             off += sizeof(TreeEntry) * (size_t)p->heap_cap[i];
+            if (p->is_enh(i)) off += (size_t)tree_pseudo_bytes(p->RC[i], p->W[i]);  // (the pseudocost table: behind the heap array, where the kernel looks for it)
             t.pool = p->d_tree_mem + off;
             off += (size_t)tree_slot_bytes(p->cut_rows[i]) * slots;
             t.free_list = reinterpret_cast<int32_t*>(p->d_tree_mem + off);
@@ -3611,7 +3633,8 @@ static int pack_init(jslpp_pack* p, int32_t max_pivots) {
             off += (sizeof(double) * (size_t)p->n_opt[i] + 15) & ~(size_t)15;
             if (p->is_mir(i)) t.mir_out = reinterpret_cast<TreeMirRec*>(p->result.d.p + p->res_mir_off()) + i;  // (never with optional objectives)
             t.rcoef = js_round(1.0 / p->precision[i]);
-            t.cut_rows = p->cut_rows[i]; t.heap_cap = p->heap_cap[i]; t.max_nodes = p->max_nodes; t.pad = 0;
+            if (p->is_enh(i)) t.enh_out = reinterpret_cast<TreeEnhRec*>(p->result.d.p + p->res_enh_off()) + i;  // (never with optional objectives or MIR)
+            t.cut_rows = p->cut_rows[i]; t.heap_cap = p->heap_cap[i]; t.max_nodes = p->max_nodes; t.policy = p->is_enh(i) ? p->policy[i] : 0;
         }
         HIPC(hipMemcpyAsync(p->d_trees, trees.data(), sizeof(TreeLp) * n, hipMemcpyHostToDevice, p->stream));
         HIPC(hipStreamSynchronize(p->stream));
@@ -3625,10 +3648,12 @@ static int pack_init(jslpp_pack* p, int32_t max_pivots) {
 }
 
 // jslps_pack_create, jslps_tree_pack_create and jslpc_tree_pack_create (cut_rows / heap_cap: null for a pack without trees; n_optional: null
-// for none; row_extra: null for a pack without MIR LPs -- never with n_optional)
+// for none; row_extra: null for a pack without MIR LPs -- never with n_optional; node_selection / branching: null for a pack without
+// enhanced LPs, include/jslpe_tree_enhanced.h)
 static int pack_create(jslpp_pack** out, int device, int32_t n, const int32_t* height, const int32_t* width, const double* precision,
                        const int32_t* cut_rows, const int32_t* heap_cap, const int32_t* n_optional, int32_t trace_cap, int32_t max_pivots,
-                       int32_t max_nodes, const int32_t* row_extra = nullptr) {
+                       int32_t max_nodes, const int32_t* row_extra = nullptr, const int32_t* node_selection = nullptr,
+                       const int32_t* branching = nullptr) {
     const bool tree = cut_rows != nullptr;
     if (!out || n < 0 || (n > 0 && (!height || !width || !precision))) return fail(JSLP_ERR_ARG, "pack_create: bad arguments");
     if (trace_cap < 0 || max_pivots < 0 || max_nodes < 0) return fail(JSLP_ERR_ARG, "pack_create: negative trace_cap, max_pivots or max_nodes");
@@ -3639,6 +3664,12 @@ static int pack_create(jslpp_pack** out, int device, int32_t n, const int32_t* h
             return pack_fail(JSLP_ERR_ARG, "pack_create", i, "cut_rows is at least 0 and heap_cap between 1 and 2^24");
         if (n_optional && n_optional[i] < 0) return pack_fail(JSLP_ERR_ARG, "pack_create", i, "n_optional is at least 0");
         const bool mir = row_extra && row_extra[i] >= 0;
+        if (node_selection) {
+            if (node_selection[i] < 0 || node_selection[i] > 3) return pack_fail(JSLP_ERR_ARG, "pack_create", i, "node_selection is 0 (the default service), 1 best-first, 2 depth-first or 3 hybrid");
+            if (branching[i] < 0 || branching[i] > 3) return pack_fail(JSLP_ERR_ARG, "pack_create", i, "branching is 0 (the default service), 1 most-fractional, 2 pseudocost or 3 strong");
+            if ((node_selection[i] || branching[i]) && (mir || (n_optional && n_optional[i] > 0)))
+                return pack_fail(JSLP_ERR_ARG, "pack_create", i, "an enhanced LP (node_selection / branching) has neither MIR cuts (row_extra) nor optional objectives");
+        }
         if (mir && row_extra[i] < cut_rows[i])
             return pack_fail(JSLP_ERR_ARG, "pack_create", i, "row_extra of a MIR LP is at least its cut_rows (a negative one makes a plain tree LP)");
         const long long rc = (long long)height[i] + (mir ? row_extra[i] : tree ? cut_rows[i] : 0);
@@ -3675,11 +3706,17 @@ static int pack_create(jslpp_pack** out, int device, int32_t n, const int32_t* h
             for (int32_t i = 0; i < n; i++) p->mir[i] = row_extra[i] >= 0;
             p->has_mir = true;
         }
+        if (node_selection) {  // an LP with exactly one of the two set gets the other's default, hybrid / pseudocost (main.ts:76-77)
+            p->policy.resize((size_t)n);
+            for (int32_t i = 0; i < n; i++)
+                p->policy[i] = (node_selection[i] || branching[i]) ? (node_selection[i] ? node_selection[i] : (int32_t)ENH_HYBRID) |
+                                                                         (branching[i] ? branching[i] : (int32_t)ENH_PSEUDOCOST) << 4
+                                                                   : 0;
+            p->has_enh = true;
+        }
         for (int32_t i = 0; i < n; i++) {
             p->RC[i] = height[i] + (p->is_mir(i) ? row_extra[i] : cut_rows[i]);
-            const size_t slots = (size_t)heap_cap[i] + 3;
-            p->tree_mem_bytes += sizeof(TreeEntry) * (size_t)heap_cap[i] + (size_t)tree_slot_bytes(cut_rows[i]) * slots + ((sizeof(int32_t) * slots + 15) & ~(size_t)15) +
-                                 ((sizeof(double) * (size_t)p->n_opt[i] + 15) & ~(size_t)15);
+            p->tree_mem_bytes += p->tree_lp_bytes((size_t)i);
         }
     }
     p->evaluation.assign((size_t)n, 0.0);
@@ -3724,6 +3761,41 @@ extern "C" int jslpc_tree_pack_create(jslpp_pack** out, int device, int32_t n, c
     static const int32_t none = 0;
     return pack_create(out, device, n, height, width, precision, cut_rows ? cut_rows : &none, heap_cap ? heap_cap : &none, nullptr, trace_cap,
                        max_pivots, max_nodes, row_extra ? row_extra : &none);
+}
+// include/jslpe_tree_enhanced.h
+extern "C" int jslpe_tree_pack_create_mixed(jslpp_pack** out, int device, int32_t n, const int32_t* height, const int32_t* width, const double* precision,
+                                            const int32_t* cut_rows, const int32_t* heap_cap, const int32_t* n_optional, const int32_t* row_extra,
+                                            const int32_t* node_selection, const int32_t* branching, int32_t trace_cap, int32_t max_pivots,
+                                            int32_t max_nodes) {
+    if (n > 0 && (!cut_rows || !heap_cap || !node_selection || !branching)) return fail(JSLP_ERR_ARG, "pack_create: bad arguments");
+    if (n_optional && row_extra)
+        for (int32_t i = 0; i < n; i++)
+            if (row_extra[i] >= 0 && n_optional[i] > 0) return pack_fail(JSLP_ERR_ARG, "pack_create", i, "a MIR LP has no optional objectives");
+    static const int32_t none = 0;
+    return pack_create(out, device, n, height, width, precision, cut_rows ? cut_rows : &none, heap_cap ? heap_cap : &none, n_optional, trace_cap,
+                       max_pivots, max_nodes, row_extra, node_selection ? node_selection : &none, branching ? branching : &none);
+}
+extern "C" int jslpe_tree_pack_create(jslpp_pack** out, int device, int32_t n, const int32_t* height, const int32_t* width, const double* precision,
+                                      const int32_t* cut_rows, const int32_t* heap_cap, const int32_t* node_selection, const int32_t* branching,
+                                      int32_t trace_cap, int32_t max_pivots, int32_t max_nodes) {
+    return jslpe_tree_pack_create_mixed(out, device, n, height, width, precision, cut_rows, heap_cap, nullptr, nullptr, node_selection, branching, trace_cap,
+                                        max_pivots, max_nodes);
+}
+extern "C" int jslpe_pack_read_enhanced(jslpp_pack* p, jslpe_tree_result* out) {
+    if (!p || (p->n > 0 && !out)) return fail(JSLP_ERR_ARG, "pack_read_enhanced: bad arguments");
+    if (!p->tree) return fail(JSLP_ERR_STATE, "pack_read_enhanced: not a pack with trees (jslpe_tree_pack_create, jslpt_pack_create)");
+    if (!p->uploaded || !p->tree_ran) return fail(JSLP_ERR_STATE, "pack_read_enhanced before jslpt_pack_branch_and_cut");
+    if ((int32_t)p->tree_status.size() != p->n) return fail(JSLP_ERR_STATE, "pack_read_enhanced: the last jslpt_pack_branch_and_cut did not finish");
+    static_assert(sizeof(jslpe_tree_result) == 32 && sizeof(TreeEnhRec) == 32 && sizeof(TreePseudo) == 32, "jslpe_tree_result is a TreeEnhRec");
+    static_assert(JSLPE_BEST_FIRST == ENH_BEST_FIRST && JSLPE_DEPTH_FIRST == ENH_DEPTH_FIRST && JSLPE_HYBRID == ENH_HYBRID && JSLPE_MOST_FRACTIONAL == ENH_MOST_FRACTIONAL &&
+                      JSLPE_PSEUDOCOST == ENH_PSEUDOCOST && JSLPE_STRONG == ENH_STRONG,
+                  "include/jslpe_tree_enhanced.h and jslp_tree.hip.h agree");
+    for (int32_t i = 0; i < p->n; i++) {
+        if (p->tree_status[(size_t)i] != JSLP_OK) continue;  // (left as it was)
+        memset(&out[i], 0, sizeof out[i]);
+        if (p->is_enh((size_t)i)) memcpy(&out[i], &p->h_enh()[i], sizeof out[i]);
+    }
+    return JSLP_OK;
 }
 extern "C" int64_t jslpc_tree_lds_bytes(int32_t height, int32_t width, int32_t row_capacity) {
     if (height < 2 || width < 2 || row_capacity < height) return 0;
@@ -3778,6 +3850,12 @@ extern "C" int jslpt_pack_set_integers(jslpp_pack* p, int32_t i, const int32_t* 
     if (n < 0 || n > n_idx || (n > 0 && !var_indexes)) return pack_fail(JSLP_ERR_ARG, "pack_set_integers", i, "bad integer variable list");
     for (int32_t k = 0; k < n; k++)
         if (var_indexes[k] < 0 || var_indexes[k] >= n_idx) return pack_fail(JSLP_ERR_ARG, "pack_set_integers", i, "integer variable index out of range");
+    if (p->is_enh((size_t)i)) {  // (the pseudocost table has one entry per list position: the reference's has one per variable index)
+        std::vector<int32_t> sorted(var_indexes, var_indexes + n);
+        std::sort(sorted.begin(), sorted.end());
+        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end())
+            return pack_fail(JSLP_ERR_ARG, "pack_set_integers", i, "the integer variables of an enhanced LP are distinct");
+    }
     int32_t* v = reinterpret_cast<int32_t*>(p->h_image.p + p->image_off[i] + p->ivars_off(i));
     memset(v, 0, (size_t)tree_ivars_bytes(p->RC[i], p->W[i]));
     v[0] = n;
@@ -3897,13 +3975,13 @@ extern "C" int jslpp_pack_simplex(jslpp_pack* p, const int32_t* check_cycles, js
     const bool dbg = debug_launch_on();
     HIPC(hipEventRecord(p->ev_begin, s));
     int32_t first = 0;
-    for (int g = 0; g < 6; first += p->n_group[g], g++) {  // one launch per kernel build that has LPs (and one per group of MIR LPs, in the plain build)
+    for (int g = 0; g < 8; first += p->n_group[g], g++) {  // one launch per kernel build that has LPs (and one per group of MIR or enhanced LPs, in the plain build)
         const int32_t cnt = p->n_group[g];
         if (!cnt) continue;
         const int threads = (g & 1) ? 256 : 64;
         const size_t lds = p->lds_group[g];
         a.order = p->d_order + first;
-        a.opt = (g >> 1) & 1;
+        a.opt = (g >> 1) == 1;
         (void)packed_launch(threads, (unsigned)cnt, lds, a, s);
         HIPC(hipGetLastError());
         p->launches += 1;
@@ -4042,18 +4120,20 @@ extern "C" int jslpt_pack_branch_and_cut(jslpp_pack* p, const int32_t* check_cyc
     p->tree_ran = true;
     HIPC(hipEventRecord(p->ev_begin, s));
     int32_t first = 0;
-    for (int g = 0; g < 6; first += p->n_group[g], g++) {  // one launch per kernel build that has LPs
+    for (int g = 0; g < 8; first += p->n_group[g], g++) {  // one launch per kernel build that has LPs
         const int32_t cnt = p->n_group[g];
         if (!cnt) continue;
         const int threads = (g & 1) ? 256 : 64;
         const size_t lds = p->lds_group[g];
         a.order = p->d_order + first;
-        a.opt = (g >> 1) & 1;
-        a.mir = g >> 2;
+        a.opt = (g >> 1) == 1;
+        a.mir = (g >> 1) == 2;
+        a.enh = (g >> 1) == 3;
         (void)packed_launch(threads, (unsigned)cnt, lds, a, s);
         HIPC(hipGetLastError());
         p->launches += 1;
-        if (dbg && a.mir) fprintf(stderr, "[jslp] launch k_tree_packed<%d,mir 1> n %d lds %zu\n", threads, (int)cnt, lds);
+        if (dbg && a.enh) fprintf(stderr, "[jslp] launch k_tree_packed<%d,enh 1> n %d lds %zu\n", threads, (int)cnt, lds);
+        else if (dbg && a.mir) fprintf(stderr, "[jslp] launch k_tree_packed<%d,mir 1> n %d lds %zu\n", threads, (int)cnt, lds);
         else if (dbg && a.opt) fprintf(stderr, "[jslp] launch k_tree_packed<%d,opt 1> n %d lds %zu\n", threads, (int)cnt, lds);
         else if (dbg) fprintf(stderr, "[jslp] launch k_tree_packed<%d> n %d lds %zu\n", threads, (int)cnt, lds);
     }
@@ -4112,6 +4192,7 @@ extern "C" int jslpt_pack_read_rhs(jslpp_pack* p, const double** rhs, const int3
 #if !defined(JSLP_SPLIT_TU)
 #include "jslp_mir_kernels.hip.h"  // single-unit build: the MIR kernels behind everything else (the product: jslp_tu_mir.hip)
 #define JSLP_PACKED_KERNELS 1
+#define JSLP_TREE_ENH_BUILDS 1
 #include "jslp_packed.hip.h"       // ... and the pack's two (the product: jslp_tu_packed.hip)
 #include "jslp_tree.hip.h"         // ... with the tree kernels behind them
 #endif

@@ -21,15 +21,24 @@
 struct TreeCut { double value; int32_t var; int32_t type; };    // type 0 = "min" (x >= value), 1 = "max" (x <= value), as Cuts::type
 struct TreeEntry { double key; int32_t seq; int32_t slot; };    // slot -1: the empty cut list of the root
 struct TreeMirRec { int32_t rounds, rows_added, simplexes, root_rows, rows_high_water, pad[3]; };  // what a MIR build reports per LP: jslpc_mir_result field for field
+// An enhanced LP (include/jslpe_tree_enhanced.h) runs in the ENH build of the kernel.  Its LDS image is a tree LP's; what the enhanced service
+// adds lives in global memory and is thread 0's alone, like the heap: the depth-first stack grows DOWN from the top of the heap array (stack
+// and heap share its heap_cap entries), and behind the array lies the pseudocost table, one TreePseudo per integer variable in model order.
+// A cut of such an LP carries that position in its type: type = (position << 1) | ("max" ? 1 : 0).
+struct TreePseudo { double up_sum, down_sum; int32_t up_count, down_count, pad[2]; };
+struct TreeEnhRec { int32_t solutions_found, stack_high_water, moved_to_heap, pseudo_updates, scored_by_pseudocost, dropped_nodes, pad[2]; };  // jslpe_tree_result
+enum { ENH_BEST_FIRST = 1, ENH_DEPTH_FIRST = 2, ENH_HYBRID = 3, ENH_MOST_FRACTIONAL = 1, ENH_PSEUDOCOST = 2, ENH_STRONG = 3, ENH_STRONG_CANDIDATES = 5 };
 struct TreeLp {
     TreeEntry* heap;
     char* pool;
     int32_t* free_list;
     double rcoef;  // Math.round(1 / precision), computed on the host like decode_state's
-    int32_t cut_rows, heap_cap, max_nodes, pad;
+    int32_t cut_rows, heap_cap, max_nodes;
+    int32_t policy;  // 0: the default service; an enhanced LP: node selection | branching << 4 (ENH_*)
     union {
         double* best_opt;     // n_opt doubles next to the heap: column 0 of the incumbent's optional rows (thread 0 alone reads and writes them)
         TreeMirRec* mir_out;  // a MIR LP (include/jslpc_tree_mir.h; never one with optional objectives): its record in the result block
+        TreeEnhRec* enh_out;  // an enhanced LP (never one with optional objectives or MIR): its record in the result block
     };
 };
 enum { TREE_OK = 0, TREE_ERR_NODES = 1, TREE_ERR_HEAP = 2, TREE_ERR_CUTS = 3, TREE_ERR_BRANCH = 4, TREE_ERR_MIR_ROWS = 5, TREE_ERR_MIR_ROUNDS = 6 };
@@ -38,6 +47,7 @@ struct TreeRec {  // what the kernel reports per LP next to its DevState
     int32_t iterations, is_integral, final_height, nodes_pushed, heap_high_water, cuts_high_water, err, pad;
 };
 __host__ __device__ __forceinline__ long long tree_slot_bytes(int32_t cut_rows) { return 16LL * (1 + cut_rows); }
+__host__ __device__ __forceinline__ long long tree_pseudo_bytes(int32_t RC, int32_t W) { return (long long)sizeof(TreePseudo) * pk_n_idx(RC, W); }  // (an LP has at most n_idx integer variables)
 __host__ __device__ __forceinline__ long long tree_ivars_bytes(int32_t RC, int32_t W) { return 16 + 4LL * pk_pad4(pk_n_idx(RC, W)); }
 // A MIR LP (include/jslpc_tree_mir.h) runs in a MIR build of the kernel.  Its LDS image is the tree LP's at its row capacity with
 // variable.isInteger per variable index behind the integer block: n_idx bytes padded to 16, built by the kernel from the image's list of
@@ -116,7 +126,13 @@ __device__ __forceinline__ double tree_round(double x) {
 // cycle-check history of a call of its own, and folds feasible / bounded / evaluation as a node's does.  Bounded like everything else: a
 // round whose rows exceed the row capacity, and TMIR_MAX_ROUNDS rounds of one node without a stop, end the LP with an error of its own.
 // MIR = false instantiates the kernel as it was before there was such a build.
-template <int THREADS, bool OPT, bool MIR = false>
+// ENH = true: the LPs of a model with options.nodeSelection / options.branching (include/jslpe_tree_enhanced.h; never with OPT or MIR), under the
+// enhanced service (enhanced-branch-and-cut.ts:223-434).  The tableau, the saved root, the cut rows and the simplex are the default
+// service's; the tree policy differs: a depth-first stack beside the heap and the hybrid switch at the first incumbent, the pseudocost
+// table with its order-dependent update, and selectBranchingVariable (:112-196) scanned across the lanes.  Node selection and branching
+// rule are the LP's own (TreeLp::policy), uniform across its workgroup.  ENH = false instantiates the kernel, instruction for instruction,
+// as it was before there was such a build.
+template <int THREADS, bool OPT, bool MIR = false, bool ENH = false>
 __global__ void __launch_bounds__(THREADS) k_tree_packed(const PackLp* __restrict__ lps, const TreeLp* __restrict__ trees, const int32_t* __restrict__ order,
                                                          const int32_t* __restrict__ cc, int cc_all, DevState* __restrict__ out_states,
                                                          double* __restrict__ out_rhs, int32_t* __restrict__ out_rows, TreeRec* __restrict__ out_tree) {
@@ -124,6 +140,7 @@ __global__ void __launch_bounds__(THREADS) k_tree_packed(const PackLp* __restric
     __shared__ TreeSmem sm;
     __shared__ TreeMirSm ms;  // (MIR; no other build refers to it)
     static_assert(!(MIR && OPT), "a MIR LP has no optional objectives (include/jslpc_tree_mir.h)");
+    static_assert(!(ENH && (OPT || MIR)), "an enhanced LP has neither optional objectives nor MIR cuts (include/jslpe_tree_enhanced.h)");
     const int idx = order[blockIdx.x];
     const PackLp m = lps[idx];
     const TreeLp t = trees[idx];
@@ -210,7 +227,8 @@ __global__ void __launch_bounds__(THREADS) k_tree_packed(const PackLp* __restric
         const TreeCut* cuts = reinterpret_cast<const TreeCut*>(sp + 16);
         for (int q = tid; q < n * W; q += THREADS) {
             const int h = q / W, col = q - h * W;
-            const TreeCut c = cuts[h];
+            TreeCut c = cuts[h];
+            if constexpr (ENH) c.type &= 1;  // (the integer variable's position rides above bit 0)
             const double sign = c.type == 0 ? -1.0 : 1.0;  // "min" -> -1 (:41)
             const int var_row = rbv[c.var], var_col = cbv[c.var];
             double v = 0.0;
@@ -238,6 +256,13 @@ __global__ void __launch_bounds__(THREADS) k_tree_packed(const PackLp* __restric
         __syncthreads();
         for (int k = tid; k < n_int; k += THREADS) is_int[ivars[k]] = 1;
     }
+    // (ENH) the pseudocost table behind the heap array: every call starts with none (pseudoCosts = new Map(), :69)
+    TreePseudo* pseudo = reinterpret_cast<TreePseudo*>(heap + t.heap_cap);
+    if constexpr (ENH)
+        for (int k = tid; k < n_int; k += THREADS) {
+            TreePseudo z; z.up_sum = 0.0; z.down_sum = 0.0; z.up_count = 0; z.down_count = 0; z.pad[0] = z.pad[1] = 0;
+            pseudo[k] = z;
+        }
     restore();
     long long trace_n = st->trace_n;
     if constexpr (OPT)  // bestOptionalObjectivesEvaluations (:66-69)
@@ -252,6 +277,15 @@ __global__ void __launch_bounds__(THREADS) k_tree_packed(const PackLp* __restric
     int heap_n = 0, seq = 1, free_n = 0, fresh_n = 0, pushes = 1, heap_hw = 1, cuts_hw = 0;  // (the root's push and pop are not executed)
     int terr = (n_int > 0 && t.heap_cap < 1) ? (int)TREE_ERR_HEAP : (int)TREE_OK, serr = ERR_NONE;
     bool root = true, done = false;
+    // (ENH) the enhanced service's registers, uniform like the others: which container the next node comes from, the stack's size, and
+    // what the LP's TreeEnhRec reports.  The root starts on the stack unless the selection is best-first (:246-255); the heap's sequence
+    // numbers count its own pushes only.
+    const int node_sel = t.policy & 15, branching = t.policy >> 4;
+    bool use_df = ENH && node_sel != ENH_BEST_FIRST;
+    int stack_n = 0, stack_hw = use_df ? 1 : 0, solutions = 0, moved = 0, pseudo_updates = 0, scored = 0, dropped = 0;
+    if constexpr (ENH)
+        if (use_df) seq = 0;
+    double parent_eval = 0.0;  // (declared out here: a declaration inside the node loop changes the code of the other builds)
     auto release = [&](int slot) {  // a cut list nobody refers to any more goes back on the free stack
         if (slot < 0) return;
         if (tid == 0) free_list[free_n] = slot;
@@ -291,16 +325,29 @@ __global__ void __launch_bounds__(THREADS) k_tree_packed(const PackLp* __restric
 
     while (terr == TREE_OK && !done) {
         if (!root) {
-            if (heap_n == 0) break;
-            if (tid == 0) {
-                const TreeEntry e = tree_pop(heap, heap_n);
-                sm.key = e.key;
-                sm.slot = e.slot;
+            if constexpr (ENH) {  // :257-280: the stack's top while the walk is depth-first, the heap's best after
+                if ((use_df ? stack_n : heap_n) == 0) break;
+                if (tid == 0) {
+                    const TreeEntry e = use_df ? heap[t.heap_cap - stack_n] : tree_pop(heap, heap_n);
+                    sm.key = e.key;
+                    sm.slot = e.slot;
+                }
+            } else {
+                if (heap_n == 0) break;
+                if (tid == 0) {
+                    const TreeEntry e = tree_pop(heap, heap_n);
+                    sm.key = e.key;
+                    sm.slot = e.slot;
+                }
             }
             __syncthreads();
             const double key = sm.key;
             cur_slot = sm.slot;
-            heap_n -= 1;
+            if constexpr (ENH) {
+                if (use_df) stack_n -= 1; else heap_n -= 1;
+            } else {
+                heap_n -= 1;
+            }
             __syncthreads();  // (sm.key / sm.slot may be written again)
             if (key > best_eval) { release(cur_slot); continue; }  // :89-92
         }
@@ -314,6 +361,7 @@ __global__ void __launch_bounds__(THREADS) k_tree_packed(const PackLp* __restric
                 if (H < 0) { H = Hs; terr = TREE_ERR_MIR_ROWS; break; }
         }
         root = false;
+        if constexpr (ENH) parent_eval = evaluation;  // tableau.evaluation as the PREVIOUS node left it (:287)
         iters_left = m.iters_cap;
         o = pk_simplex<THREADS, OPT>(A, pcol, H, W, S, vibr, vibc, rbv, cbv, unr, precision, check_cycles, m, ghist, gtrace, sm.ps, iters_left, trace_n, oo, n_opt);
         __syncthreads();
@@ -331,6 +379,179 @@ __global__ void __launch_bounds__(THREADS) k_tree_packed(const PackLp* __restric
             if (n_int > 0 && !mir_loop()) break;
         }
         if (n_int == 0) break;  // no integer variables: a plain simplex() (tableau.ts:250-258)
+        if constexpr (ENH) {  // enhanced-branch-and-cut.ts:292-427; every path ends this iteration
+            if (!feasible || evaluation > best_eval) { release(cur_slot); continue; }  // :292-299
+            // :301-314: the pseudocost of the node's LAST cut, from the evaluation the previous node left (a node off the stack or the heap
+            // has at least one cut; NaN !== 0)
+            if (cur_slot >= 0 && parent_eval != 0.0) {
+                if (tid == 0) {
+                    const char* sp = pool + cur_slot * slot_bytes;
+                    const int n = *reinterpret_cast<const int32_t*>(sp);
+                    const TreeCut c = reinterpret_cast<const TreeCut*>(sp + 16)[n - 1];
+                    TreePseudo* d = pseudo + (c.type >> 1);
+                    const double normalized = __ddiv_rn(fabs(__dsub_rn(evaluation, parent_eval)), 0.5);  // (fraction = 0.5 either way, :307)
+                    if ((c.type & 1) == 0) { d->up_sum = __dadd_rn(d->up_sum, normalized); d->up_count += 1; }
+                    else { d->down_sum = __dadd_rn(d->down_sum, normalized); d->down_count += 1; }
+                }
+                pseudo_updates += 1;
+            }
+            if (evaluation == best_eval) { release(cur_slot); continue; }  // :316-336 without optional objectives
+            // isIntegral (mip-utils.ts:43-61), as the default build's scan decides it
+            int nonint = 0;
+            for (int k = tid; k < n_int; k += THREADS) {
+                const int r = rbv[ivars[k]];
+                if (r > 0) {
+                    const double v = A[r * S];
+                    nonint |= fabs(v - tree_round(v)) > precision ? 1 : 0;  // (NaN: false)
+                }
+            }
+            nonint = __syncthreads_or(nonint);  // (thread 0's pseudocost update is behind this barrier for every lane)
+            if (!nonint) {  // :338-376
+                found = 1;
+                solutions += 1;
+                if (iterations == 1) { done = true; break; }
+                release(best_slot);
+                best_slot = cur_slot;
+                have_best = 1;
+                best_eval = evaluation;
+                if (node_sel == ENH_HYBRID && use_df) {  // :366-376: the stack's entries, from the top, into the heap, each with a fresh seq
+                    if (tid == 0) {
+                        int hn = heap_n, sq = seq;
+                        for (int j = stack_n; j > 0; j--) {  // (heap[hn] is at or below the entry just read: stack and heap fit heap_cap together)
+                            TreeEntry e = heap[t.heap_cap - j];
+                            e.seq = sq++;
+                            tree_push(heap, hn, e);
+                            hn += 1;
+                        }
+                    }
+                    heap_n += stack_n;
+                    seq += stack_n;
+                    moved += stack_n;
+                    stack_n = 0;
+                    use_df = false;
+                }
+                continue;
+            }
+            if (iterations == 1) {  // :378-380, before the selection
+                save();
+                __syncthreads();
+            }
+            // selectBranchingVariable (:112-196).  A candidate is an integer variable, in model order, with a row and a fraction above
+            // precision (so a finite one); every rule is a first-wins maximum over the candidates, reduced across the lanes.
+            auto fraction_of = [&](int k) -> double {  // -1: no candidate
+                const int r = rbv[ivars[k]];
+                if (r == -1) return -1.0;
+                const double v = A[r * S];
+                const double f = fabs(v - tree_round(v));
+                return f > precision ? f : -1.0;
+            };
+            auto js_max = [](double x, double y) -> double { return x != x ? x : (x > y ? x : y); };  // Math.max(x, y) for a number y: NaN stays NaN
+            auto score_of = [&](int k, double f) -> double {  // getScore (:98-110)
+                const TreePseudo d = pseudo[k];
+                const double up = d.up_count > 0 ? __ddiv_rn(d.up_sum, (double)d.up_count) : 1.0;
+                const double down = d.down_count > 0 ? __ddiv_rn(d.down_sum, (double)d.down_count) : 1.0;
+                return __dmul_rn(js_max(__dmul_rn(up, __dsub_rn(1.0, f)), 1e-6), js_max(__dmul_rn(down, f), 1e-6));
+            };
+            Cand b; b.v = -2.0; b.i = 0; b.b = 0;
+            if (branching == ENH_STRONG) {
+                // :161-193: the five most fractional -- a stable descending sort keeps model order among equals, so five first-wins maxima,
+                // each over what the earlier ones left -- then the first strictly greatest score among them, from -Infinity on
+                int top[ENH_STRONG_CANDIDATES];
+#pragma unroll
+                for (int j = 0; j < ENH_STRONG_CANDIDATES; j++) top[j] = -1;
+#pragma unroll
+                for (int j = 0; j < ENH_STRONG_CANDIDATES; j++) {
+                    Cand x; x.v = -2.0; x.i = 0; x.b = 0;
+                    for (int k = tid; k < n_int; k += THREADS) {
+                        bool taken = false;
+#pragma unroll
+                        for (int q = 0; q < ENH_STRONG_CANDIDATES; q++) taken |= top[q] == k;
+                        const double f = taken ? -1.0 : fraction_of(k);
+                        if (f >= 0.0 && f > x.v) { x.v = f; x.i = k + 1; }
+                    }
+                    x = pk_reduce<THREADS>(x, MaxFirst(), sm.ps.g);
+                    top[j] = x.i - 1;  // (-1: the candidates have run out)
+                }
+                double best_score = -INFINITY;
+                b.i = top[0] + 1;
+#pragma unroll
+                for (int j = 0; j < ENH_STRONG_CANDIDATES; j++) {
+                    if (top[j] < 0) continue;
+                    const double f = fraction_of(top[j]);
+                    const TreePseudo d = pseudo[top[j]];
+                    const bool by_pseudo = d.up_count >= 2 && d.down_count >= 2;
+                    scored += by_pseudo ? 1 : 0;
+                    const double score = by_pseudo ? score_of(top[j], f) : __dmul_rn(f, __dsub_rn(1.0, f));
+                    if (score > best_score) { best_score = score; b.i = top[j] + 1; }
+                }
+            } else {
+                // most-fractional (:139-143): the first strictly largest fraction.  pseudocost (:145-159): the first strictly largest
+                // score from -Infinity on, candidate 0 when none compares greater -- a score is positive or NaN, and NaN ranks as -1
+                for (int k = tid; k < n_int; k += THREADS) {
+                    const double f = fraction_of(k);
+                    if (f < 0.0) continue;
+                    double key = f;
+                    if (branching == ENH_PSEUDOCOST) {
+                        const double score = score_of(k, f);
+                        key = score == score ? score : -1.0;
+                    }
+                    if (key > b.v) { b.v = key; b.i = k + 1; }
+                }
+                b = pk_reduce<THREADS>(b, MaxFirst(), sm.ps.g);
+            }
+            if (b.i == 0) { dropped += 1; release(cur_slot); continue; }  // :384: no candidate -- the node is dropped
+            if (tid == 0) {  // :386-426: the two children's cut lists, then the stack (low first, so that high is popped first) or the heap (high first)
+                const int pos = b.i - 1, var = ivars[pos];
+                const double value = A[rbv[var] * S];
+                const int src_n = cur_slot < 0 ? 0 : *reinterpret_cast<const int32_t*>(pool + cur_slot * slot_bytes);
+                const TreeCut* src = reinterpret_cast<const TreeCut*>(pool + (cur_slot < 0 ? 0 : cur_slot) * slot_bytes + 16);
+                int code = TREE_OK, fn = free_n, fr = fresh_n, hn = heap_n, sn = stack_n, sq = seq, len[2] = {0, 0};
+                for (int ord = 0; ord < 2 && code == TREE_OK; ord++) {
+                    const int child = use_df ? 1 - ord : ord;  // 0: high ("min" cut, ceil), 1: low ("max" cut, floor)
+                    const int slot = fn > 0 ? free_list[--fn] : fr++;
+                    char* dp = pool + slot * slot_bytes;
+                    TreeCut* dst = reinterpret_cast<TreeCut*>(dp + 16);
+                    int n = 0;
+                    for (int k = 0; k <= src_n && code == TREE_OK; k++) {
+                        TreeCut c;
+                        if (k < src_n) {
+                            c = src[k];
+                            if (c.var == var && ((c.type & 1) == 0) != (child == 1)) continue;  // :393-405
+                        } else {
+                            c.value = child == 0 ? ceil(value) : floor(value);
+                            c.var = var;
+                            c.type = (pos << 1) | child;
+                        }
+                        if (n >= t.cut_rows) { code = TREE_ERR_CUTS; break; }
+                        dst[n++] = c;
+                    }
+                    if (code != TREE_OK) break;
+                    *reinterpret_cast<int32_t*>(dp) = n;
+                    len[child] = n;
+                    if (sn + hn >= t.heap_cap) { code = TREE_ERR_HEAP; break; }  // (stack and heap share the array)
+                    TreeEntry e; e.key = evaluation; e.slot = slot;
+                    if (use_df) { e.seq = 0; heap[t.heap_cap - 1 - sn] = e; sn += 1; }
+                    else { e.seq = sq++; tree_push(heap, hn, e); hn += 1; }
+                }
+                sm.code = code;
+                sm.n_high = len[0];
+                sm.n_low = len[1];
+            }
+            __syncthreads();
+            terr = sm.code;
+            cuts_hw = max(cuts_hw, max(sm.n_high, sm.n_low));
+            __syncthreads();
+            if (terr != TREE_OK) break;
+            for (int child = 0; child < 2; child++) {
+                if (free_n > 0) free_n -= 1; else fresh_n += 1;
+            }
+            if (use_df) { stack_n += 2; stack_hw = max(stack_hw, stack_n); }
+            else { heap_n += 2; seq += 2; }
+            pushes += 2;
+            heap_hw = max(heap_hw, stack_n + heap_n);
+            release(cur_slot);
+            continue;
+        }
         if constexpr (OPT) {
             if (!feasible || evaluation > best_eval) { release(cur_slot); continue; }  // :99-105
             if (evaluation == best_eval) {  // :107-127: the tie is broken on the optional objectives, in priority order (NaN decides nothing)
@@ -517,6 +738,13 @@ __global__ void __launch_bounds__(THREADS) k_tree_packed(const PackLp* __restric
             mr.pad[0] = mr.pad[1] = mr.pad[2] = 0;
             *many_global(t.mir_out) = mr;
         }
+        if constexpr (ENH) {
+            TreeEnhRec er;
+            er.solutions_found = solutions; er.stack_high_water = n_int > 0 ? stack_hw : 0; er.moved_to_heap = moved;
+            er.pseudo_updates = pseudo_updates; er.scored_by_pseudocost = scored; er.dropped_nodes = dropped;
+            er.pad[0] = er.pad[1] = 0;
+            *many_global(t.enh_out) = er;
+        }
     }
     __syncthreads();
     if (tid < (int)(sizeof(DevState) / 8))
@@ -525,7 +753,7 @@ __global__ void __launch_bounds__(THREADS) k_tree_packed(const PackLp* __restric
 
 // as packed_launch_impl, for the tree kernels (PackLaunch::kind == 1).  The plain and OPT builds and the MIR builds have a launch function
 // each, so that a unit can hold one set without the other (-DJSLP_TREE_NO_MIR_BUILDS: jslp_tu_packed.hip; -DJSLP_TREE_NO_PLAIN_BUILDS:
-// jslp_tu_tree_mir.hip)
+// jslp_tu_tree_mir.hip), and so have the ENH builds (-DJSLP_TREE_ENH_BUILDS: jslp_tu_tree_enh.hip and the single-unit build)
 #ifndef JSLP_TREE_NO_PLAIN_BUILDS
 static int tree_launch_impl(int threads, unsigned grid, size_t lds, const void* bytes, hipStream_t s) {
     const PackLaunch a = *static_cast<const PackLaunch*>(bytes);
@@ -556,6 +784,22 @@ static int tree_mir_launch_impl(int threads, unsigned grid, size_t lds, const vo
         hipLaunchKernelGGL((k_tree_packed<64, false, true>), dim3(grid), dim3(64), lds, s, a.lps, trees, a.order, a.cc, a.cc_all, states, a.rhs, a.rows, recs);
     else if (threads == 256 && !a.opt)
         hipLaunchKernelGGL((k_tree_packed<256, false, true>), dim3(grid), dim3(256), lds, s, a.lps, trees, a.order, a.cc, a.cc_all, states, a.rhs, a.rows, recs);
+    else
+        return -1;
+    return (int)hipPeekAtLastError();
+}
+#endif
+#ifdef JSLP_TREE_ENH_BUILDS
+// the ENH builds (PackLaunch::enh == 1; never with opt or mir)
+static int tree_enh_launch_impl(int threads, unsigned grid, size_t lds, const void* bytes, hipStream_t s) {
+    const PackLaunch a = *static_cast<const PackLaunch*>(bytes);
+    DevState* states = static_cast<DevState*>(a.states);
+    const TreeLp* trees = static_cast<const TreeLp*>(a.trees);
+    TreeRec* recs = static_cast<TreeRec*>(a.tree_out);
+    if (threads == 64 && !a.opt && !a.mir)
+        hipLaunchKernelGGL((k_tree_packed<64, false, false, true>), dim3(grid), dim3(64), lds, s, a.lps, trees, a.order, a.cc, a.cc_all, states, a.rhs, a.rows, recs);
+    else if (threads == 256 && !a.opt && !a.mir)
+        hipLaunchKernelGGL((k_tree_packed<256, false, false, true>), dim3(grid), dim3(256), lds, s, a.lps, trees, a.order, a.cc, a.cc_all, states, a.rhs, a.rows, recs);
     else
         return -1;
     return (int)hipPeekAtLastError();

@@ -972,6 +972,7 @@ class _TreeModel:
     def __init__(self, integers, check_cycles, mir=False):
         self.integer_index_array = np.asarray(integers, dtype=np.int64)
         self.integer_index_set = frozenset(int(i) for i in integers)
+        self.integerVariables = [{"index": int(i)} for i in integers]  # (what the enhanced service's selectBranchingVariable reads)
         self.checkForCycles = bool(check_cycles)
         self.useMIRCuts = bool(mir)
 
@@ -1051,10 +1052,17 @@ class TableauPack:
     height + row_extra (one number or one per LP; default: cut_rows + MIR_ROW_HEADROOM, capped by what fits the LDS limit), its cut lists
     still hold at most cut_rows cuts, and its integer variables are also its variable.isInteger.  `mir` (_capi.MIR_TREE_DTYPE: rounds,
     rows_added, simplexes, root_rows, rows_high_water) is the read-back of the last branch_and_cut(), zero for the other LPs; `is_mir` holds
-    the flags.  Not together with optional objectives."""
+    the flags.  Not together with optional objectives.
+
+    node_selection / branching: one entry per LP of a pack with trees (include/jslpe_tree_enhanced.h): None, or the model's
+    options.nodeSelection ("best-first", "depth-first", "hybrid") / options.branching ("most-fractional", "pseudocost", "strong").  An LP
+    with either is an ENHANCED LP: its tree is walked under the enhanced service (one of the two left None gets its default, hybrid /
+    pseudocost); its depth-first stack and its heap share heap_cap.  `enhanced` (_capi.ENH_TREE_DTYPE: solutions_found, stack_high_water,
+    moved_to_heap, pseudo_updates, scored_by_pseudocost, dropped_nodes) is the read-back of the last branch_and_cut(), zero for the other
+    LPs; `is_enhanced` holds the flags.  Not for an LP with `mir` or with optional objectives."""
 
     def __init__(self, lps, precision=1e-8, lib=None, device=0, trace_cap=0, max_pivots=0, integers=None, cut_rows=None, heap_cap=None,
-                 max_nodes=0, optional_objectives=None, mir=None, row_extra=None):
+                 max_nodes=0, optional_objectives=None, mir=None, row_extra=None, node_selection=None, branching=None):
         self.lib = lib if lib is not None else _capi.load_hip()
         self._lps = []
         for matrix, vibr, vibc, unr in lps:
@@ -1135,6 +1143,30 @@ class TableauPack:
             self.row_extra = np.where(self.is_mir, _capi.as_i32(extra), -1).astype(np.int32)
             self.row_capacity = np.where(self.is_mir, self.heights + self.row_extra, self.row_capacity).astype(np.int32)
         self.has_mir = bool(self.is_mir.any())
+        # enhanced LPs (include/jslpe_tree_enhanced.h): the codes as the create takes them (0: not given)
+        self.node_selection = np.zeros(n, dtype=np.int32)
+        self.branching = np.zeros(n, dtype=np.int32)
+        self.enhanced = np.zeros(n, dtype=_capi.ENH_TREE_DTYPE)
+        for what, given, names, codes in (("node_selection", node_selection, _capi.ENH_NODE_SELECTION, self.node_selection),
+                                          ("branching", branching, _capi.ENH_BRANCHING, self.branching)):
+            if given is None or not any(g is not None for g in given):
+                continue
+            if not self.is_tree:
+                raise ValueError("TableauPack: `%s` needs `integers` (a pack with trees)" % what)
+            if len(given) != n:
+                raise ValueError("TableauPack: %d %s entries for %d LPs" % (len(given), what, n))
+            for i, g in enumerate(given):
+                if g is not None and g not in names:
+                    raise ValueError("TableauPack: LP %d: %s is None or one of %s, not %r" % (i, what, ", ".join(names), g))
+                codes[i] = 0 if g is None else names[g]
+        self.is_enhanced = (self.node_selection != 0) | (self.branching != 0)
+        self.has_enhanced = bool(self.is_enhanced.any())
+        for i in np.flatnonzero(self.is_enhanced):
+            if self.is_mir[i] or self.n_optional[i] > 0:
+                raise ValueError("TableauPack: LP %d: an enhanced LP (node_selection / branching) has neither `mir` nor optional objectives "
+                                 "(include/jslpe_tree_enhanced.h)" % i)
+        if self.has_enhanced and self.lib.has_pack and not getattr(self.lib, "has_tree_enh", False):
+            raise _capi.EngineError("TableauPack: %s does not export the enhanced tree extension (include/jslpe_tree_enhanced.h)" % self.lib.path)
         if self.has_mir and self.lib.has_pack and not getattr(self.lib, "has_tree_mir", False):
             raise _capi.EngineError("TableauPack: %s does not export the MIR tree extension (include/jslpc_tree_mir.h)" % self.lib.path)
         if self.is_tree and self.lib.has_pack and not getattr(self.lib, "has_tree", False):
@@ -1143,7 +1175,13 @@ class TableauPack:
             raise _capi.EngineError("TableauPack: %s does not export the optional-objective extension (include/jslps_soft.h)" % self.lib.path)
         if self.lib.has_pack:
             self._h = _capi.C.c_void_p()
-            if self.has_optional and self.is_tree:
+            if self.has_enhanced:
+                self.lib.check(self.lib.jslpe_tree_pack_create_mixed(
+                    _capi.C.byref(self._h), self.device, n, _capi.ptr_i32(self.heights), _capi.ptr_i32(self.widths), _capi.ptr_f64(self.precision),
+                    _capi.ptr_i32(self.cut_rows), _capi.ptr_i32(self.heap_cap), _capi.ptr_i32(self.n_optional) if self.has_optional else None,
+                    _capi.ptr_i32(self.row_extra) if self.has_mir else None, _capi.ptr_i32(self.node_selection), _capi.ptr_i32(self.branching),
+                    self.trace_cap, self.max_pivots, self.max_nodes), "jslpe_tree_pack_create")
+            elif self.has_optional and self.is_tree:
                 self.lib.check(self.lib.jslps_tree_pack_create(_capi.C.byref(self._h), self.device, n, _capi.ptr_i32(self.heights),
                                                                _capi.ptr_i32(self.widths), _capi.ptr_f64(self.precision), _capi.ptr_i32(self.cut_rows),
                                                                _capi.ptr_i32(self.heap_cap), _capi.ptr_i32(self.n_optional), self.trace_cap,
@@ -1187,6 +1225,9 @@ class TableauPack:
                 if self.is_mir[i] and not 0 < tree_mir_lds_bytes(h, w, rc) <= _capi.JSLPP_LDS_LIMIT:
                     raise _capi.EngineError("jslpc_tree_pack_create failed (%d): pack_create: LP %d: the MIR LP's LDS image at its row capacity "
                                             "exceeds 64 KiB" % (_capi.JSLP_ERR_UNSUPPORTED, i))
+                if self.is_enhanced[i] and len(set(self.integers[i].tolist())) != self.integers[i].shape[0]:
+                    raise _capi.EngineError("jslpt_pack_set_integers failed (%d): pack_set_integers: LP %d: the integer variables of an enhanced "
+                                            "LP are distinct" % (_capi.JSLP_ERR_ARG, i))
                 if self.is_tree and not 0 < tree_lds_bytes(h, w, rc, no) <= _capi.JSLPP_LDS_LIMIT:
                     raise _capi.EngineError("jslpt_pack_create failed (%d): pack_create: LP %d: the tableau's LDS image at its row capacity exceeds "
                                             "64 KiB" % (_capi.JSLP_ERR_UNSUPPORTED, i))
@@ -1295,16 +1336,21 @@ class TableauPack:
         are solved; the call then raises EngineError naming the first such LP.  The restatement walks branch_and_cut.branch_and_cut on one
         engine per LP with the same capacities enforced (max_pivots excepted: the engine's own cap).
         A MIR LP (`mir=`) runs every node's MIR loop, in the kernel as in the restatement (round by round, mirRound); `mir` keeps its
-        counters; its capacities are the row capacity (`row_extra` in the message) and JSLPR_MAX_ROUNDS rounds of one node (`mir rounds`)."""
+        counters; its capacities are the row capacity (`row_extra` in the message) and JSLPR_MAX_ROUNDS rounds of one node (`mir rounds`).
+        An enhanced LP (`node_selection=` / `branching=`) is walked under the enhanced service, in the kernel as in the restatement
+        (incremental_branch_and_cut.enhanced_branch_and_cut with CountingContainers); `enhanced` keeps its counters; in `tree` its
+        heap_high_water counts stack and heap together and nodes_pushed the new branches."""
         if not self.is_tree:
             raise _capi.EngineError("TableauPack.branch_and_cut: the pack was made without `integers`")
         flags = self._flags(check_cycles)
         out = self.results.copy()
         tree = self.tree.copy()
         mir = self.mir.copy()
+        enhanced = self.enhanced.copy()
         status = np.zeros(self.n, dtype=np.int32)
         if self._twins is not None:
             from . import branch_and_cut as bc
+            from . import incremental_branch_and_cut as ibc
             rc, msg = _capi.JSLP_OK, ""
             for i, (t, c) in enumerate(zip(self._twins, flags)):
                 counters = None
@@ -1313,7 +1359,17 @@ class TableauPack:
                         t.simplex(check_cycles=bool(c))
                         rec = (0, 0, t.last.height, 0, 0, 0)
                         mir_rec = (0, 0, 1, 0, 0) if self.is_mir[i] else (0, 0, 0, 0, 0)
+                        enh_rec = (0,) * 8
+                    elif self.is_enhanced[i]:  # the enhanced service on the LP's twin, its stack and heap sharing heap_cap
+                        boxes = ibc.CountingContainers(heap_cap=int(self.heap_cap[i]), cut_rows=int(self.cut_rows[i]), max_nodes=self.max_nodes)
+                        selection, rule = self.policy(i)
+                        iterations, integral = ibc.enhanced_branch_and_cut(t, _TreeModel(self.integers[i], c), node_selection=selection,
+                                                                           branching=rule, containers=boxes)
+                        rec = (iterations, int(integral), t.last.height, boxes.pushes, boxes.high_water, boxes.cuts_high_water)
+                        mir_rec = (0, 0, 0, 0, 0)
+                        enh_rec = boxes.record() + (0, 0)
                     else:
+                        enh_rec = (0,) * 8
                         heap = bc.CountingHeap(heap_cap=int(self.heap_cap[i]), cut_rows=int(self.cut_rows[i]))
                         if self.is_mir[i]:
                             counters = _MirCounters(t)
@@ -1326,6 +1382,7 @@ class TableauPack:
                     out[i] = np.frombuffer(res, dtype=_capi.RESULT_DTYPE)[0]
                     tree[i] = rec
                     mir[i] = mir_rec
+                    enhanced[i] = enh_rec
                 except (bc.TreeCapacity, _capi.EngineError) as e:
                     status[i] = _capi.JSLP_ERR_CAPACITY if isinstance(e, bc.TreeCapacity) or "(%d)" % _capi.JSLP_ERR_CAPACITY in str(e) else _capi.JSLP_ERR_DEVICE
                     if self.is_mir[i] and "row capacity exceeded" in str(e):  # (an engine's refusal of a round's or a cut list's rows)
@@ -1348,10 +1405,13 @@ class TableauPack:
             self._launches = int(self.lib.jslpp_pack_launches(self._h))
             if self.has_mir:
                 self.lib.check(self.lib.jslpc_pack_read_mir(self._h, mir.ctypes.data), "jslpc_pack_read_mir")
+            if self.has_enhanced:
+                self.lib.check(self.lib.jslpe_pack_read_enhanced(self._h, enhanced.ctypes.data), "jslpe_pack_read_enhanced")
         ok = status == _capi.JSLP_OK
         self.results = out
         self.tree = tree
         self.mir = mir
+        self.enhanced = enhanced
         self.status = status
         self.feasible[ok] = out["feasible"][ok] != 0
         self.bounded[ok] = out["bounded"][ok] != 0
@@ -1359,6 +1419,15 @@ class TableauPack:
         if rc != _capi.JSLP_OK:
             raise _capi.EngineError("jslpt_pack_branch_and_cut failed (%d): %s" % (rc, msg))
         return out
+
+    def policy(self, i):
+        """(node selection, branching) LP i's tree is walked under, by name, with the defaults filled in; None for an LP under the default
+        service"""
+        if not self.is_enhanced[i]:
+            return None
+        names = lambda table, code, default: next(k for k, v in table.items() if v == (code or table[default]))  # noqa: E731
+        return (names(_capi.ENH_NODE_SELECTION, int(self.node_selection[i]), "hybrid"),
+                names(_capi.ENH_BRANCHING, int(self.branching[i]), "pseudocost"))
 
     def result(self, i):
         """LP i's result of the last simplex() as a SimplexResult"""

@@ -16,7 +16,7 @@ import math
 import os
 import time
 
-from .branch_and_cut import BranchMinHeap, _rows_by_var, is_integral, js_round, mir_loop
+from .branch_and_cut import BranchMinHeap, TreeCapacity, _rows_by_var, is_integral, js_round, mir_loop
 
 
 class _Branch:
@@ -56,7 +56,56 @@ class _PseudoCosts:
         return max(up * (1 - fraction), 1e-6) * max(down * fraction, 1e-6)
 
 
-def _select_branching_variable(model, rhs, rows, precision, branching, pseudo, strong_candidates=5):
+class CountingContainers:
+    """The depth-first stack and the min-heap of the enhanced service, counting what a device-side tree has to hold
+    (include/jslpe_tree_enhanced.h) and enforcing the same capacities in the kernel's order: per child the cut list first, then the
+    entries stack and heap hold TOGETHER (heap_cap); max_nodes before a node more is evaluated.  What branch_and_cut.CountingHeap is
+    for the default service."""
+
+    def __init__(self, heap_cap=None, cut_rows=None, max_nodes=None):
+        self.heap = BranchMinHeap()
+        self.stack = []
+        self.heap_cap, self.cut_rows, self.max_nodes = heap_cap, cut_rows, max_nodes
+        self.pushes = self.high_water = self.cuts_high_water = 0
+        self.solutions_found = self.stack_high_water = self.moved_to_heap = 0
+        self.pseudo_updates = self.scored_by_pseudocost = self.dropped_nodes = 0
+
+    def _admit(self, branch):
+        if self.cut_rows is not None and len(branch.cuts) > self.cut_rows:
+            raise TreeCapacity("cut_rows")
+        if self.heap_cap is not None and len(self.stack) + len(self.heap) >= self.heap_cap:
+            raise TreeCapacity("heap_cap")
+
+    def _count(self, branch):
+        self.pushes += 1
+        self.high_water = max(self.high_water, len(self.stack) + len(self.heap))
+        self.stack_high_water = max(self.stack_high_water, len(self.stack))
+        self.cuts_high_water = max(self.cuts_high_water, len(branch.cuts))
+
+    def push_stack(self, branch):
+        self._admit(branch)
+        self.stack.append(branch)
+        self._count(branch)
+
+    def push_heap(self, branch):
+        self._admit(branch)
+        self.heap.push(branch.relaxed, branch)
+        self._count(branch)
+
+    def move_to_heap(self):
+        """the hybrid switch: the stack's entries, from the top, into the heap (not counted as pushes)"""
+        while self.stack:
+            b = self.stack.pop()
+            self.heap.push(b.relaxed, b)
+            self.moved_to_heap += 1
+
+    def record(self):
+        """jslpe_tree_result, field for field"""
+        return (self.solutions_found, self.stack_high_water, self.moved_to_heap, self.pseudo_updates, self.scored_by_pseudocost,
+                self.dropped_nodes)
+
+
+def _select_branching_variable(model, rhs, rows, precision, branching, pseudo, strong_candidates=5, counters=None):
     """selectBranchingVariable (incremental-branch-and-cut.ts:176-221; enhanced-branch-and-cut.ts:112-196, which adds the
     "strong" rule): (varIndex, value) or None"""
     candidates = []
@@ -81,6 +130,8 @@ def _select_branching_variable(model, rhs, rows, precision, branching, pseudo, s
         best_score, best = -math.inf, ranked[0]
         for c in ranked:
             d = pseudo._get(c[0])
+            if counters is not None and d[1] >= 2 and d[3] >= 2:
+                counters.scored_by_pseudocost += 1
             score = pseudo.score(c[0], c[2]) if d[1] >= 2 and d[3] >= 2 else c[2] * (1 - c[2])
             if score > best_score:
                 best_score, best = score, c
@@ -93,22 +144,25 @@ def _select_branching_variable(model, rhs, rows, precision, branching, pseudo, s
     return best[0], best[1]
 
 
-def enhanced_branch_and_cut(tableau, model, node_selection="hybrid", branching="pseudocost"):
+def enhanced_branch_and_cut(tableau, model, node_selection="hybrid", branching="pseudocost", containers=None):
     """createEnhancedBranchAndCutService (src/tableau/enhanced-branch-and-cut.ts:58-437), the service `Solve` picks for
     `options.nodeSelection` / `options.branching` (src/main.ts:74-80): the same tree walk as the incremental service
-    with every node evaluated from the saved root (no checkpoints) and the "strong" branching rule."""
+    with every node evaluated from the saved root (no checkpoints) and the "strong" branching rule.
+    containers: a CountingContainers to walk the tree with (it instruments the walk and enforces a device-side tree's capacities)."""
     return incremental_branch_and_cut(tableau, model, node_selection=node_selection, branching=branching, max_checkpoints=0,
-                                      incremental_rules=False)
+                                      incremental_rules=False, containers=containers)
 
 
 def incremental_branch_and_cut(tableau, model, node_selection="hybrid", branching="pseudocost", max_checkpoints=50,
-                               incremental_rules=True):
+                               incremental_rules=True, containers=None):
     """branchAndCut (:283-495).  Leaves `tableau` holding the incumbent; returns (iterations, found_integral).
     `tableau.checkpoints_used` / `tableau.incremental_nodes` report how many checkpoints were taken and how many
     nodes started from one.  incremental_rules=False: the enhanced service's variant of the two places where the
-    services differ (which branching rules exist; both update pseudocosts from the node's last cut)."""
-    heap = BranchMinHeap()     # entries carry the _Branch in the `cuts` position
-    stack = []
+    services differ (which branching rules exist; both update pseudocosts from the node's last cut).
+    containers: a CountingContainers whose stack and heap the walk uses (None: plain ones, nothing counted, no capacity)."""
+    cc = containers
+    heap = cc.heap if cc is not None else BranchMinHeap()     # entries carry the _Branch in the `cuts` position
+    stack = cc.stack if cc is not None else []
     iterations = 0
     checkpoint_count = 0
     incremental_nodes = 0
@@ -132,7 +186,9 @@ def incremental_branch_and_cut(tableau, model, node_selection="hybrid", branchin
     checkpoints = []
 
     root = _Branch(-math.inf, [], 0)
-    if use_depth_first:
+    if cc is not None:
+        (cc.push_stack if use_depth_first else cc.push_heap)(root)
+    elif use_depth_first:
         stack.append(root)
     else:
         heap.push(root.relaxed, root)
@@ -152,6 +208,8 @@ def incremental_branch_and_cut(tableau, model, node_selection="hybrid", branchin
             break
         if branch.relaxed > best_evaluation:
             continue
+        if cc is not None and cc.max_nodes is not None and iterations >= cc.max_nodes:
+            raise TreeCapacity("max_nodes")
         parent_eval = tableau.evaluation
         # applyIncrementalCuts (:246-259) and the MIR loop (:261-276)
         from_checkpoint = branch.checkpoint is not None and branch.new_cut is not None
@@ -177,6 +235,8 @@ def incremental_branch_and_cut(tableau, model, node_selection="hybrid", branchin
         observed = branch.new_cut if incremental_rules else (branch.cuts[-1] if branch.cuts else None)
         if observed is not None and parent_eval != 0:
             pseudo.update(observed["varIndex"], observed["type"] == "min", abs(evaluation - parent_eval), 0.5)
+            if cc is not None:
+                cc.pseudo_updates += 1
         optional_cells = None
         if evaluation == best_evaluation:  # :367-388
             worse = True
@@ -194,6 +254,8 @@ def incremental_branch_and_cut(tableau, model, node_selection="hybrid", branchin
         if is_integral(model, rhs, rows, precision):
             found_integral = True
             solutions_found += 1
+            if cc is not None:
+                cc.solutions_found += 1
             if iterations == 1:
                 tableau.checkpoints_used, tableau.incremental_nodes = 0, 0
                 return iterations, True
@@ -205,6 +267,8 @@ def incremental_branch_and_cut(tableau, model, node_selection="hybrid", branchin
                 best_optional = [float(x) for x in optional_cells]
             if node_selection == "hybrid" and solutions_found >= 1:  # :418-428
                 use_depth_first = False
+                if cc is not None:
+                    cc.move_to_heap()
                 while stack:
                     b = stack.pop()
                     heap.push(b.relaxed, b)
@@ -212,8 +276,10 @@ def incremental_branch_and_cut(tableau, model, node_selection="hybrid", branchin
             if iterations == 1:
                 tableau.save()
             rule = branching if (not incremental_rules or branching == "most-fractional") else "pseudocost"  # (:203-221)
-            sel = _select_branching_variable(model, rhs, rows, precision, rule, pseudo)
+            sel = _select_branching_variable(model, rhs, rows, precision, rule, pseudo, counters=cc)
             if sel is None:
+                if cc is not None:
+                    cc.dropped_nodes += 1
                 continue
             var_index, var_value = sel
             checkpoint = None
@@ -237,12 +303,21 @@ def incremental_branch_and_cut(tableau, model, node_selection="hybrid", branchin
             cuts_low.append(cut_low)
             depth = branch.depth + 1
             if use_depth_first:
-                stack.append(_Branch(evaluation, cuts_low, depth, checkpoint, cut_low))
-                stack.append(_Branch(evaluation, cuts_high, depth, checkpoint, cut_high))
+                b_low, b_high = _Branch(evaluation, cuts_low, depth, checkpoint, cut_low), _Branch(evaluation, cuts_high, depth, checkpoint, cut_high)
+                if cc is not None:
+                    cc.push_stack(b_low)
+                    cc.push_stack(b_high)
+                else:
+                    stack.append(b_low)
+                    stack.append(b_high)
             else:  # best-first nodes start from the root (:485-488)
                 b_high, b_low = _Branch(evaluation, cuts_high, depth), _Branch(evaluation, cuts_low, depth)
-                heap.push(b_high.relaxed, b_high)
-                heap.push(b_low.relaxed, b_low)
+                if cc is not None:
+                    cc.push_heap(b_high)
+                    cc.push_heap(b_low)
+                else:
+                    heap.push(b_high.relaxed, b_high)
+                    heap.push(b_low.relaxed, b_low)
     if best_branch is not None:
         _res, rhs, vibr = tableau.applyCuts(best_branch.cuts, check_cycles=check)  # :491-493, always from the root
         mir_loop(tableau, model, rhs, vibr, check, max_rounds=3, need_feasible=True)  # :228-243

@@ -91,6 +91,16 @@ def _mir_tree_in_scope(m):
     return not (o.get("useIncremental") is True or o.get("nodeSelection") or o.get("branching") or m.tolerance or m.timeout or m.keep_solutions)
 
 
+def _enhanced_tree_in_scope(m):
+    """whether the ENHANCED service alone decides this model's result (main.ts:74-80: options.nodeSelection and/or options.branching, no
+    useIncremental), with nothing that needs the host or a clock and without its own MIR loop (include/jslpe_tree_enhanced.h)"""
+    o = m.options
+    if (o.get("nodeSelection") or "hybrid") not in _capi.ENH_NODE_SELECTION or (o.get("branching") or "pseudocost") not in _capi.ENH_BRANCHING:
+        return False  # (a name the service does not know: Solve walks it as the reference does)
+    return bool(o.get("nodeSelection") or o.get("branching")) and not (o.get("useIncremental") is True or m.useMIRCuts or m.tolerance or m.timeout
+                                                                       or m.keep_solutions)
+
+
 def solve_packed(models, precision=None, lib=None, device=0):
     """[Solve(m, precision, lib=lib, device=device) for m in models], in order, for the workload of many SMALL models.  Every model
     whose tableau -- with its optional objectives, one row per soft constraint priority, when it has any (include/jslps_soft.h) -- fits the
@@ -103,13 +113,17 @@ def solve_packed(models, precision=None, lib=None, device=0):
       * the same with options.useMIRCuts and no optional objectives (include/jslpc_tree_mir.h), as a MIR LP of that pack, when
         row_extra = min(2 per integer variable + 320, the most rows that fit) >= 1, with cut_rows = min(2 per integer variable, row_extra)
         (engine.tree_mir_rows): every node's MIR loop runs in the kernel as well.  Its further capacities are the row capacity
-        height + row_extra, which the root's MIR rows, a node's cuts and the node's MIR rows share, and 64 MIR rounds of one node.
+        height + row_extra, which the root's MIR rows, a node's cuts and the node's MIR rows share, and 64 MIR rounds of one node;
+      * with integer variables and options.nodeSelection and/or options.branching -- the enhanced service -- without useIncremental,
+        useMIRCuts, tolerance, timeout, keep_solutions and optional objectives (include/jslpe_tree_enhanced.h), as an enhanced LP of
+        that same pack, under the cut-row rule of the default service; its depth-first stack and its heap share the heap entries.
     Every other model goes through Solve as it is.  A model Solve rejects raises the same exception before anything is solved."""
     lib = lib if lib is not None else _capi.load_hip()
     models = list(models)
     parsed = [_parse(model, precision, 4) for model in models]
     packed = []  # positions of the models that go into the pack of plain LPs
     trees = []   # (position, cut rows, row_extra or -1) of the models whose tree goes into the pack with trees (row_extra >= 0: a MIR LP)
+    policies = {}  # position -> (options.nodeSelection or None, options.branching or None) of the enhanced LPs among them
     optional = [None] * len(models)  # per model its optional objectives (None: none)
     for k, (m, matrix, _, _) in enumerate(parsed):
         _priorities, optional_rows = m.optional_objectives()
@@ -129,6 +143,11 @@ def solve_packed(models, precision=None, lib=None, device=0):
             row_extra, cut_rows = tree_mir_rows(matrix.shape[0], matrix.shape[1], n_int, lib=lib)
             if row_extra >= 1:
                 trees.append((k, cut_rows, row_extra))
+        elif n_opt == 0 and _enhanced_tree_in_scope(m):
+            cut_rows = tree_cut_rows(matrix.shape[0], matrix.shape[1], n_int, lib=lib)
+            if cut_rows >= 1:
+                trees.append((k, cut_rows, -1))
+                policies[k] = (m.options.get("nodeSelection") or None, m.options.get("branching") or None)
     results = [None] * len(models)
     if packed:
         pack = TableauPack([(parsed[k][1], parsed[k][2], parsed[k][3], parsed[k][0].unrestricted) for k in packed],
@@ -144,15 +163,15 @@ def solve_packed(models, precision=None, lib=None, device=0):
     mir_trees = [t for t in trees if t[2] >= 0]
     if mir_trees and any(optional[k] is not None for k, _, _ in trees):
         trees = [t for t in trees if t[2] < 0]
-        _solve_tree_pack(mir_trees, parsed, optional, lib, device, results)
-    _solve_tree_pack(trees, parsed, optional, lib, device, results)
+        _solve_tree_pack(mir_trees, parsed, optional, lib, device, results, policies)
+    _solve_tree_pack(trees, parsed, optional, lib, device, results, policies)
     for k, model in enumerate(models):
         if results[k] is None:
             results[k] = Solve(model, precision, lib=lib, device=device)
     return results
 
 
-def _solve_tree_pack(trees, parsed, optional, lib, device, results):
+def _solve_tree_pack(trees, parsed, optional, lib, device, results, policies):
     """solve_packed's pack with trees: results[k] for every model of `trees` whose LP reached no capacity (the others stay None: Solve)"""
     if trees:
         with_mir = any(e >= 0 for _, _, e in trees)
@@ -161,7 +180,9 @@ def _solve_tree_pack(trees, parsed, optional, lib, device, results):
                            integers=[[v["index"] for v in parsed[k][0].integerVariables] for k, _, _ in trees], cut_rows=[c for _, c, _ in trees],
                            heap_cap=TREE_HEAP_CAP, max_nodes=TREE_MAX_NODES,
                            optional_objectives=None if with_mir else [optional[k] for k, _, _ in trees],
-                           mir=[e >= 0 for _, _, e in trees] if with_mir else None, row_extra=[e for _, _, e in trees] if with_mir else None)
+                           mir=[e >= 0 for _, _, e in trees] if with_mir else None, row_extra=[e for _, _, e in trees] if with_mir else None,
+                           node_selection=[policies.get(k, (None, None))[0] for k, _, _ in trees],
+                           branching=[policies.get(k, (None, None))[1] for k, _, _ in trees])
         try:
             try:
                 pack.branch_and_cut(check_cycles=[parsed[k][0].checkForCycles for k, _, _ in trees])

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """solve_packed on n small MILPs, on this tree and on another checkout of the project (the parent commit), in ONE session.
-  python tools/tree_packed_times.py [--parent DIR] [--ns 1,8,64,512,4096] [--reps 3] [--rounds 3] [--soft milps|lps] [--mir] [--out profiles/packed_tree_times.md]
+  python tools/tree_packed_times.py [--parent DIR] [--ns 1,8,64,512,4096] [--reps 3] [--rounds 3] [--soft milps|lps] [--mir] [--enh] [--parent-twice] [--out profiles/packed_tree_times.md]
 Workload: the reference's default-policy fuzz MILPs that need no presolve pre-pass (tests/golden/fuzz_services.jsonl.gz), round robin up
 to n models.  On this tree solve_packed walks every tree on the device, one launch for the whole batch (include/jslpt_tree.h); on a tree
 without the extension (--parent: a built checkout of the parent commit) the same call walks each tree on the host through Solve.
@@ -14,7 +14,12 @@ least one optional objective) -- `milps`: those with integer variables under the
 include/jslps_soft.h they run in the OPT builds of the pack kernels; on one without, solve_packed sends every one of them through Solve.
 --mir: every fuzz model gets options.useMIRCuts -- the workload is the reference's recorded runs of the same models with exactly that option
 (the same file), so every result is still verified against a record.  On a tree with include/jslpc_tree_mir.h every node's MIR loop runs
-in the MIR builds of the tree kernel; on one without, solve_packed sends every one of them through Solve."""
+in the MIR builds of the tree kernel; on one without, solve_packed sends every one of them through Solve.
+--enh: the workload is the reference's recorded runs under the ENHANCED service (the same file: {"nodeSelection": "depth-first"},
+{"branching": "strong"}, {"nodeSelection": "best-first", "branching": "most-fractional"}), the three policies interleaved.  On a tree with
+include/jslpe_tree_enhanced.h they run in the ENH builds of the tree kernel; on one without, solve_packed sends every one of them through Solve.
+--parent-twice: the parent checkout is measured as two entries of the alternation: the ratio of the second to the first is the run-to-run
+spread of this tool on one and the same tree."""
 import argparse
 import gzip
 import json
@@ -28,10 +33,17 @@ import warnings
 HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def cases(root, soft=None, mir=False):
+ENH_OPTIONS = [{"nodeSelection": "depth-first"}, {"branching": "strong"}, {"branching": "most-fractional", "nodeSelection": "best-first"}]
+
+
+def cases(root, soft=None, mir=False, enh=False):
     with gzip.open(os.path.join(root, "tests", "golden", "fuzz_soft.jsonl.gz" if soft else "fuzz_services.jsonl.gz"), "rt") as fh:
         cs = [json.loads(line) for line in fh if line.startswith("{")]
     options = {"useMIRCuts": True} if mir else None
+    if enh:  # (model after model, each under its three policies)
+        cs = sorted((c for c in cs if c["model"].get("options") in ENH_OPTIONS and c["fixed"] == 0 and not c["infeasPre"]),
+                    key=lambda c: (c["gen"], c["seed"], ENH_OPTIONS.index(c["model"]["options"])))
+        return cs
     cs = [c for c in cs if (c["model"].get("options") or None) == options and c["fixed"] == 0 and not c["infeasPre"]]
     if soft:  # (the selection of tests/soft_pack_util.py::soft_records)
         if root not in sys.path:
@@ -56,7 +68,7 @@ def worker(a):
     from jslpsolver_amd.solver import solve_packed
     warnings.simplefilter("ignore")
     lib = _capi.Library(os.path.join(a.root, a.lib)) if a.lib else _capi.load_hip()
-    cs = cases(a.root, a.soft, a.mir)
+    cs = cases(a.root, a.soft, a.mir, a.enh)
 
     def verify(results, n):
         for k in range(n):
@@ -74,7 +86,7 @@ def worker(a):
             results = solve_packed(models, lib=lib)
             dt = time.perf_counter() - t0
             verify(results, n)
-            print(json.dumps({"n": n, "wall_ms": 1e3 * dt, "device_tree": bool(getattr(lib, "has_tree_mir" if a.mir else "has_soft" if a.soft else "has_tree", False))}), flush=True)
+            print(json.dumps({"n": n, "wall_ms": 1e3 * dt, "device_tree": bool(getattr(lib, "has_tree_enh" if a.enh else "has_tree_mir" if a.mir else "has_soft" if a.soft else "has_tree", False))}), flush=True)
 
 
 def main():
@@ -86,22 +98,26 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--soft", default=None, choices=["milps", "lps"], help="the recorded soft-constraint runs: those with / without integer variables")
     ap.add_argument("--mir", action="store_true", help="every fuzz model with options.useMIRCuts (the reference's recorded runs with that option)")
+    ap.add_argument("--enh", action="store_true", help="the reference's recorded runs under the enhanced service (nodeSelection / branching), three policies")
+    ap.add_argument("--parent-twice", action="store_true", help="measure the parent checkout as two entries: the tool's spread on one tree")
     ap.add_argument("--worker", action="store_true")
     ap.add_argument("--root", default=HERE)
     ap.add_argument("--lib", default=None, help="engine library, relative to each checkout (default: the HIP product library); "
                     "oracle/libjslp_oracle.so rehearses the tool without a GPU -- its times say nothing")
     a = ap.parse_args()
-    if a.mir and a.soft:
-        ap.error("--mir and --soft are two workloads")
+    if sum(map(bool, (a.mir, a.soft, a.enh))) > 1:
+        ap.error("--mir, --soft and --enh are three workloads")
     if a.worker:
         return worker(a)
     trees = [("this commit", HERE)] + ([("parent commit", os.path.abspath(a.parent))] if a.parent else [])
+    if a.parent and a.parent_twice:
+        trees.append(("parent commit, again", os.path.abspath(a.parent)))
     times = {name: {} for name, _ in trees}
     flags = {}
     for _ in range(a.rounds):
         for name, root in trees:  # (the two alternate, round by round)
             out = subprocess.run([sys.executable, os.path.abspath(__file__), "--worker", "--root", root, "--ns", a.ns, "--reps", str(a.reps)] + (["--lib", a.lib] if a.lib else []) +
-                                 (["--soft", a.soft] if a.soft else []) + (["--mir"] if a.mir else []),
+                                 (["--soft", a.soft] if a.soft else []) + (["--mir"] if a.mir else []) + (["--enh"] if a.enh else []),
                                  check=True, capture_output=True, text=True, timeout=900).stdout
             print("round done: %s" % name, file=sys.stderr, flush=True)
             for line in out.splitlines():
@@ -109,19 +125,23 @@ def main():
                     r = json.loads(line)
                     times[name].setdefault(r["n"], []).append(r["wall_ms"])
                     flags[name] = r["device_tree"]
-    n_models = len(cases(HERE, a.soft, a.mir))
+    n_models = len(cases(HERE, a.soft, a.mir, a.enh))
     what = {None: "default-policy fuzz MILPs", "milps": "recorded soft-constraint MILPs", "lps": "recorded soft-constraint LPs"}[a.soft]
     if a.mir:
         what = "fuzz MILPs with `options.useMIRCuts`"
-    lines = ["# `solve_packed` on small MILPs with MIR cuts: every node's MIR loop in the tree kernel against one engine per model (MI355X)" if a.mir else
+    if a.enh:
+        what = "fuzz MILPs under the enhanced service (three policies)"
+    lines = ["# `solve_packed` on small MILPs with `nodeSelection` / `branching`: the enhanced service's tree in the tree kernel against one engine per model (MI355X)" if a.enh else
+             "# `solve_packed` on small MILPs with MIR cuts: every node's MIR loop in the tree kernel against one engine per model (MI355X)" if a.mir else
              "# `solve_packed` on small MILPs: trees walked on the device against trees walked on the host (MI355X)" if not a.soft else
              "# `solve_packed` on the %s: the pack's OPT builds against one engine per model (MI355X)" % what, "",
-             "`python tools/tree_packed_times.py --parent <checkout of the parent commit>%s --out %s`: one session, one " % (" --mir" if a.mir else "", "profiles/" + os.path.basename(a.out or "packed_tree_times.md")) +
+             "`python tools/tree_packed_times.py --parent <checkout of the parent commit>%s --out %s`: one session, one " % ((" --mir" if a.mir else " --enh" if a.enh else "") + (" --parent-twice" if a.parent_twice else ""), "profiles/" + os.path.basename(a.out or "packed_tree_times.md")) +
              "device, %d rounds alternating between the two checkouts, each in a process of its own; per round one warm-up call and %d timed "
              "calls per n; wall time of `solve_packed(models)` on n models taken round robin from the %d %s; every result "
              "of every call verified against the reference's recorded result before its time was kept." % (a.rounds, a.reps, n_models, what), "",
-             "| n | " + " | ".join("%s: best ms | median ms | trees/s (best)" % name for name, _ in trees) + (" | parent / this (best) |" if a.parent else " |"),
-             "|---|" + "---|---|---|" * len(trees) + ("---|" if a.parent else "")]
+             "| n | " + " | ".join("%s: best ms | median ms | trees/s (best)" % name for name, _ in trees) + (" | parent / this (best) |" if a.parent else " |") +
+             (" parent again / parent (best) |" if a.parent and a.parent_twice else ""),
+             "|---|" + "---|---|---|" * len(trees) + ("---|" if a.parent else "") + ("---|" if a.parent and a.parent_twice else "")]
     for n in [int(x) for x in a.ns.split(",")]:
         row, best = ["%d" % n], {}
         for name, _ in trees:
@@ -130,6 +150,8 @@ def main():
             row += ["%.3f" % min(ts), "%.3f" % statistics.median(ts), "%.0f" % (n / (1e-3 * min(ts)))]
         if a.parent:
             row.append("%.2fx" % (best["parent commit"] / best["this commit"]))
+            if a.parent_twice:
+                row.append("%.2fx" % (best["parent commit, again"] / best["parent commit"]))
         lines.append("| " + " | ".join(row) + " |")
     lines += ["", "- %s: " % ("in the pack" if a.soft else "device-side trees") + ", ".join("%s: %s" % (name, "yes" if flags.get(name) else "no (each tree through `Solve`)") for name, _ in trees) + "."]
     text = "\n".join(lines) + "\n"
