@@ -254,6 +254,19 @@ TREE_ENH_SYMBOLS = {
                                                C.c_int32, C.c_int32, C.c_int32]),
     "jslpe_pack_read_enhanced": (C.c_int, [C.c_void_p, C.c_void_p]),
 }
+# name -> (restype, argtypes); must list EVERY symbol include/jslpi_tree_incremental.h declares.  HIP library only (Library.has_tree_inc).
+TREE_INC_SYMBOLS = {
+    "jslpi_tree_pack_create": (C.c_int, [_P(C.c_void_p), C.c_int, C.c_int32, _i32p, _i32p, _f64p, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p,
+                                         C.c_int32, C.c_int32, C.c_int32]),
+    "jslpi_tree_lds_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    "jslpi_checkpoint_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    "jslpi_pack_read_incremental": (C.c_int, [C.c_void_p, C.c_void_p]),
+}
+# numpy twin of struct jslpi_tree_result
+INC_TREE_DTYPE = np.dtype([(name, np.int32) for name in ("checkpoints_used", "incremental_nodes", "rows_high_water", "checkpoint_rows_high_water",
+                                                         "reserved0", "reserved1", "reserved2", "reserved3")])
+JSLPI_MAX_CHECKPOINTS = 64
+JSLPI_CHECKPOINTS_DEFAULT = 50
 # numpy twin of struct jslpe_tree_result
 ENH_TREE_DTYPE = np.dtype([(name, np.int32) for name in ("solutions_found", "stack_high_water", "moved_to_heap", "pseudo_updates",
                                                          "scored_by_pseudocost", "dropped_nodes", "reserved0", "reserved1")])
@@ -294,6 +307,7 @@ class Library:
         self.has_soft = self.has_tree and self._bind_extension(SOFT_SYMBOLS)
         self.has_tree_mir = self.has_tree and self._bind_extension(TREE_MIR_SYMBOLS)
         self.has_tree_enh = self.has_tree_mir and self.has_soft and self._bind_extension(TREE_ENH_SYMBOLS)
+        self.has_tree_inc = self.has_tree_enh and self._bind_extension(TREE_INC_SYMBOLS)
 
     def _bind_extension(self, symbols):
         """bind a HIP-only extension when the library exports all of it; False otherwise"""

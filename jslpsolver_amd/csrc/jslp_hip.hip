@@ -22,6 +22,7 @@
 #include "../../include/jslps_soft.h"
 #include "../../include/jslpc_tree_mir.h"
 #include "../../include/jslpe_tree_enhanced.h"
+#include "../../include/jslpi_tree_incremental.h"
 #include "jslp_kernels.hip.h"
 #include "jslp_host_mem.h"
 
@@ -3437,7 +3438,9 @@ extern "C" int jslpf_simplex_f32_sweep(jslp_engine* e, const double* precisions,
 extern "C" __attribute__((visibility("hidden"))) int jslpp_packed_launch_tu(int threads, unsigned grid, size_t lds, const void* args, void* stream);
 extern "C" __attribute__((visibility("hidden"))) int jslpc_tree_mir_launch_tu(int threads, unsigned grid, size_t lds, const void* args, void* stream);
 extern "C" __attribute__((visibility("hidden"))) int jslpe_tree_enh_launch_tu(int threads, unsigned grid, size_t lds, const void* args, void* stream);
+extern "C" __attribute__((visibility("hidden"))) int jslpi_tree_inc_launch_tu(int threads, unsigned grid, size_t lds, const void* args, void* stream);
 static int packed_launch(int threads, unsigned grid, size_t lds, const PackLaunch& a, hipStream_t s) {
+    if (a.kind == 1 && a.inc) return jslpi_tree_inc_launch_tu(threads, grid, lds, &a, s);  // (the INC builds of k_tree_packed: jslp_tu_tree_inc.hip)
     if (a.kind == 1 && a.enh) return jslpe_tree_enh_launch_tu(threads, grid, lds, &a, s);  // (the ENH builds of k_tree_packed: jslp_tu_tree_enh.hip)
     if (a.kind == 1 && a.mir) return jslpc_tree_mir_launch_tu(threads, grid, lds, &a, s);  // (the MIR builds of k_tree_packed: jslp_tu_tree_mir.hip)
     return jslpp_packed_launch_tu(threads, grid, lds, &a, s);
@@ -3447,7 +3450,9 @@ static int packed_launch_impl(int threads, unsigned grid, size_t lds, const void
 static int tree_launch_impl(int threads, unsigned grid, size_t lds, const void* bytes, hipStream_t s);    // (jslp_tree.hip.h, there too)
 static int tree_mir_launch_impl(int threads, unsigned grid, size_t lds, const void* bytes, hipStream_t s);  // (its MIR builds)
 static int tree_enh_launch_impl(int threads, unsigned grid, size_t lds, const void* bytes, hipStream_t s);  // (its ENH builds)
+static int tree_inc_launch_impl(int threads, unsigned grid, size_t lds, const void* bytes, hipStream_t s);  // (its INC builds)
 static int packed_launch(int threads, unsigned grid, size_t lds, const PackLaunch& a, hipStream_t s) {
+    if (a.kind == 1 && a.inc) return tree_inc_launch_impl(threads, grid, lds, &a, s);
     if (a.kind == 1 && a.enh) return tree_enh_launch_impl(threads, grid, lds, &a, s);
     if (a.kind == 1 && a.mir) return tree_mir_launch_impl(threads, grid, lds, &a, s);
     return a.kind == 1 ? tree_launch_impl(threads, grid, lds, &a, s) : packed_launch_impl(threads, grid, lds, &a, s);
@@ -3479,6 +3484,12 @@ struct jslpp_pack {
     // | branching << 4: an ENH build of the tree kernel, a pseudocost table behind its heap, a TreeEnhRec in the result block)
     bool has_enh = false;
     std::vector<int32_t> policy;
+    // a pack made by jslpi_tree_pack_create (include/jslpi_tree_incremental.h): which LPs are INCREMENTAL LPs and their max_checkpoints.  Such an LP
+    // is an enhanced LP in everything but its kernel build (INC), its row capacity (height + row_extra), the checkpoint arena behind its
+    // pseudocost table and the TreeIncRec behind its TreeEnhRec: with has_inc the result block holds the two records side by side per LP
+    bool has_inc = false;
+    std::vector<uint8_t> inc;
+    std::vector<int32_t> max_ckpt;
     TreeLp* d_trees = nullptr;
     char* d_tree_mem = nullptr;
     size_t tree_mem_bytes = 0;
@@ -3495,10 +3506,11 @@ struct jslpp_pack {
     int32_t *d_order = nullptr, *d_cc = nullptr;
     int2 *d_hist = nullptr, *d_trace = nullptr;
     // the launch groups, in launch order: [0] one wave, [1] 256 threads, [2] one wave with OPT, [3] 256 threads with OPT, [4] one wave
-    // with MIR, [5] 256 threads with MIR, [6] one wave with ENH, [7] 256 threads with ENH (a plain simplex of a MIR or an enhanced LP runs
-    // in the build of group & 1)
-    int32_t n_group[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    size_t lds_group[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    // with MIR, [5] 256 threads with MIR, [6] one wave with ENH, [7] 256 threads with ENH, [8] one wave with INC, [9] 256 threads with INC
+    // (a plain simplex of a MIR, an enhanced or an incremental LP runs in the build of group & 1)
+    static constexpr int N_GROUPS = 10;
+    int32_t n_group[N_GROUPS] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    size_t lds_group[N_GROUPS] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     // optional objectives (include/jslps_soft.h): rows per LP, whether they were set, and where they lie in the result block (in doubles)
     std::vector<int32_t> n_opt;
     std::vector<uint8_t> opt_set;
@@ -3516,8 +3528,9 @@ struct jslpp_pack {
     size_t res_enh_off() const {  // (has_enh: a TreeEnhRec per LP, behind the MIR records when the pack has them)
         return ((has_mir ? res_mir_off() + sizeof(TreeMirRec) * (size_t)n : res_tree_off() + sizeof(TreeRec) * (size_t)n) + 255) & ~(size_t)255;
     }
+    size_t enh_stride() const { return has_inc ? sizeof(TreeEnhRec) + sizeof(TreeIncRec) : sizeof(TreeEnhRec); }  // (has_inc: LP i's TreeIncRec follows its TreeEnhRec)
     size_t res_plain_bytes() const {
-        if (has_enh) return res_enh_off() + sizeof(TreeEnhRec) * (size_t)n;
+        if (has_enh) return res_enh_off() + enh_stride() * (size_t)n;
         if (has_mir) return res_mir_off() + sizeof(TreeMirRec) * (size_t)n;
         return tree ? res_tree_off() + sizeof(TreeRec) * (size_t)n : res_rows_off() + sizeof(int32_t) * (size_t)offs[n];
     }
@@ -3525,12 +3538,14 @@ struct jslpp_pack {
     size_t res_bytes() const { return opt_offs[n] ? res_opt_off() + sizeof(double) * (size_t)opt_offs[n] : res_plain_bytes(); }
     TreeRec* h_tree() const { return reinterpret_cast<TreeRec*>(result.h.p + res_tree_off()); }
     TreeMirRec* h_mir() const { return reinterpret_cast<TreeMirRec*>(result.h.p + res_mir_off()); }
-    TreeEnhRec* h_enh() const { return reinterpret_cast<TreeEnhRec*>(result.h.p + res_enh_off()); }
+    TreeEnhRec* h_enh(size_t i) const { return reinterpret_cast<TreeEnhRec*>(result.h.p + res_enh_off() + enh_stride() * i); }
     bool is_mir(size_t i) const { return has_mir && mir[i]; }
-    bool is_enh(size_t i) const { return has_enh && policy[i] != 0; }
-    size_t tree_lp_bytes(size_t i) const {  // LP i's share of d_tree_mem: heap, (pseudocost table,) pool, free stack, best_opt
+    bool is_enh(size_t i) const { return has_enh && policy[i] != 0; }  // (an incremental LP is one too)
+    bool is_inc(size_t i) const { return has_inc && inc[i]; }
+    size_t ckpt_arena_bytes(size_t i) const { return is_inc(i) ? (size_t)tree_ckpt_bytes(RC[i], W[i]) * (size_t)max_ckpt[i] : 0; }
+    size_t tree_lp_bytes(size_t i) const {  // LP i's share of d_tree_mem: heap, (pseudocost table, (checkpoint arena,)) pool, free stack, best_opt
         const size_t slots = (size_t)heap_cap[i] + 3;
-        return sizeof(TreeEntry) * (size_t)heap_cap[i] + (is_enh(i) ? (size_t)tree_pseudo_bytes(RC[i], W[i]) : 0) + (size_t)tree_slot_bytes(cut_rows[i]) * slots +
+        return sizeof(TreeEntry) * (size_t)heap_cap[i] + (is_enh(i) ? (size_t)tree_pseudo_bytes(RC[i], W[i]) : 0) + ckpt_arena_bytes(i) + (size_t)tree_slot_bytes(cut_rows[i]) * slots +
                ((sizeof(int32_t) * slots + 15) & ~(size_t)15) + ((sizeof(double) * (size_t)n_opt[i] + 15) & ~(size_t)15);
     }
     size_t lds_bytes(size_t i) const { return is_mir(i) ? (size_t)tree_mir_lds_bytes(RC[i], W[i]) : (size_t)pk_lds_bytes(RC[i], W[i], n_opt[i]); }
@@ -3589,10 +3604,10 @@ static int pack_init(jslpp_pack* p, int32_t max_pivots) {
     std::vector<PackLp> lps(n);
     std::vector<int32_t> order(n);
     int32_t k = 0;
-    for (int g = 0; g < 8; g++)  // the one-wave LPs first, then the 256-thread ones, then the same two with optional objectives, with MIR, with ENH, each in pack order
+    for (int g = 0; g < jslpp_pack::N_GROUPS; g++)  // the one-wave LPs first, then the 256-thread ones, then the same two with optional objectives, with MIR, with ENH, with INC, each in pack order
         for (size_t i = 0; i < n; i++) {
             const bool wave = (long long)p->RC[i] * p->W[i] <= PACK_CELLS_WAVE;  // (tableau cells at the row capacity, optional rows or not)
-            if ((wave ? 0 : 1) + (p->n_opt[i] > 0 ? 2 : 0) + (p->is_mir(i) ? 4 : 0) + (p->is_enh(i) ? 6 : 0) != g) continue;
+            if ((wave ? 0 : 1) + (p->n_opt[i] > 0 ? 2 : 0) + (p->is_mir(i) ? 4 : 0) + (p->is_inc(i) ? 8 : p->is_enh(i) ? 6 : 0) != g) continue;
             order[k++] = (int32_t)i;
             p->n_group[g] += 1;
             p->lds_group[g] = std::max(p->lds_group[g], p->lds_bytes(i));
@@ -3625,6 +3640,7 @@ static int pack_init(jslpp_pack* p, int32_t max_pivots) {
             t.heap = reinterpret_cast<TreeEntry*>(p->d_tree_mem + off);
             off += sizeof(TreeEntry) * (size_t)p->heap_cap[i];
             if (p->is_enh(i)) off += (size_t)tree_pseudo_bytes(p->RC[i], p->W[i]);  // (the pseudocost table: behind the heap array, where the kernel looks for it)
+            off += p->ckpt_arena_bytes(i);  // (an incremental LP's checkpoint arena: behind the table, where the kernel looks for it)
             t.pool = p->d_tree_mem + off;
             off += (size_t)tree_slot_bytes(p->cut_rows[i]) * slots;
             t.free_list = reinterpret_cast<int32_t*>(p->d_tree_mem + off);
@@ -3633,8 +3649,9 @@ static int pack_init(jslpp_pack* p, int32_t max_pivots) {
             off += (sizeof(double) * (size_t)p->n_opt[i] + 15) & ~(size_t)15;
             if (p->is_mir(i)) t.mir_out = reinterpret_cast<TreeMirRec*>(p->result.d.p + p->res_mir_off()) + i;  // (never with optional objectives)
             t.rcoef = js_round(1.0 / p->precision[i]);
-            if (p->is_enh(i)) t.enh_out = reinterpret_cast<TreeEnhRec*>(p->result.d.p + p->res_enh_off()) + i;  // (never with optional objectives or MIR)
-            t.cut_rows = p->cut_rows[i]; t.heap_cap = p->heap_cap[i]; t.max_nodes = p->max_nodes; t.policy = p->is_enh(i) ? p->policy[i] : 0;
+            if (p->is_enh(i)) t.enh_out = reinterpret_cast<TreeEnhRec*>(p->result.d.p + p->res_enh_off() + p->enh_stride() * i);  // (never with optional objectives or MIR)
+            t.cut_rows = p->cut_rows[i]; t.heap_cap = p->heap_cap[i]; t.max_nodes = p->max_nodes;
+            t.policy = p->is_enh(i) ? p->policy[i] | (p->is_inc(i) ? p->max_ckpt[i] << 8 : 0) : 0;
         }
         HIPC(hipMemcpyAsync(p->d_trees, trees.data(), sizeof(TreeLp) * n, hipMemcpyHostToDevice, p->stream));
         HIPC(hipStreamSynchronize(p->stream));
@@ -3649,11 +3666,12 @@ static int pack_init(jslpp_pack* p, int32_t max_pivots) {
 
 // jslps_pack_create, jslps_tree_pack_create and jslpc_tree_pack_create (cut_rows / heap_cap: null for a pack without trees; n_optional: null
 // for none; row_extra: null for a pack without MIR LPs -- never with n_optional; node_selection / branching: null for a pack without
-// enhanced LPs, include/jslpe_tree_enhanced.h)
+// enhanced LPs, include/jslpe_tree_enhanced.h; incremental / max_checkpoints: null for a pack without incremental LPs,
+// include/jslpi_tree_incremental.h -- such an LP's row_extra is its row capacity and makes no MIR LP of it)
 static int pack_create(jslpp_pack** out, int device, int32_t n, const int32_t* height, const int32_t* width, const double* precision,
                        const int32_t* cut_rows, const int32_t* heap_cap, const int32_t* n_optional, int32_t trace_cap, int32_t max_pivots,
                        int32_t max_nodes, const int32_t* row_extra = nullptr, const int32_t* node_selection = nullptr,
-                       const int32_t* branching = nullptr) {
+                       const int32_t* branching = nullptr, const int32_t* incremental = nullptr, const int32_t* max_checkpoints = nullptr) {
     const bool tree = cut_rows != nullptr;
     if (!out || n < 0 || (n > 0 && (!height || !width || !precision))) return fail(JSLP_ERR_ARG, "pack_create: bad arguments");
     if (trace_cap < 0 || max_pivots < 0 || max_nodes < 0) return fail(JSLP_ERR_ARG, "pack_create: negative trace_cap, max_pivots or max_nodes");
@@ -3663,7 +3681,17 @@ static int pack_create(jslpp_pack** out, int device, int32_t n, const int32_t* h
         if (tree && (cut_rows[i] < 0 || heap_cap[i] < 1 || heap_cap[i] > (1 << 24)))
             return pack_fail(JSLP_ERR_ARG, "pack_create", i, "cut_rows is at least 0 and heap_cap between 1 and 2^24");
         if (n_optional && n_optional[i] < 0) return pack_fail(JSLP_ERR_ARG, "pack_create", i, "n_optional is at least 0");
-        const bool mir = row_extra && row_extra[i] >= 0;
+        if (incremental && (incremental[i] < 0 || incremental[i] > 1)) return pack_fail(JSLP_ERR_ARG, "pack_create", i, "incremental is 0 or 1");
+        const bool inc = incremental && incremental[i];
+        if (inc) {
+            if (max_checkpoints[i] < 0 || max_checkpoints[i] > JSLPI_MAX_CHECKPOINTS)
+                return pack_fail(JSLP_ERR_ARG, "pack_create", i, "max_checkpoints of an incremental LP is between 0 and JSLPI_MAX_CHECKPOINTS (64)");
+            if (!row_extra || row_extra[i] < cut_rows[i])
+                return pack_fail(JSLP_ERR_ARG, "pack_create", i, "row_extra of an incremental LP is its row capacity beyond height: at least its cut_rows");
+            if (n_optional && n_optional[i] > 0)
+                return pack_fail(JSLP_ERR_ARG, "pack_create", i, "an incremental LP has no optional objectives (a checkpoint carries none) and no MIR cuts");
+        }
+        const bool mir = !inc && row_extra && row_extra[i] >= 0;
         if (node_selection) {
             if (node_selection[i] < 0 || node_selection[i] > 3) return pack_fail(JSLP_ERR_ARG, "pack_create", i, "node_selection is 0 (the default service), 1 best-first, 2 depth-first or 3 hybrid");
             if (branching[i] < 0 || branching[i] > 3) return pack_fail(JSLP_ERR_ARG, "pack_create", i, "branching is 0 (the default service), 1 most-fractional, 2 pseudocost or 3 strong");
@@ -3672,7 +3700,7 @@ static int pack_create(jslpp_pack** out, int device, int32_t n, const int32_t* h
         }
         if (mir && row_extra[i] < cut_rows[i])
             return pack_fail(JSLP_ERR_ARG, "pack_create", i, "row_extra of a MIR LP is at least its cut_rows (a negative one makes a plain tree LP)");
-        const long long rc = (long long)height[i] + (mir ? row_extra[i] : tree ? cut_rows[i] : 0);
+        const long long rc = (long long)height[i] + (mir || inc ? row_extra[i] : tree ? cut_rows[i] : 0);
         const long long no = n_optional ? n_optional[i] : 0;
         // (cells beyond the limit first: the byte count of an absurd shape must not overflow before it is compared)
         if (mir && ((rc + no) * width[i] > JSLPP_LDS_LIMIT / 8 || tree_mir_lds_bytes((int32_t)rc, width[i]) > (long long)WGLDS_MAX_BYTES))
@@ -3680,6 +3708,7 @@ static int pack_create(jslpp_pack** out, int device, int32_t n, const int32_t* h
                              "the MIR LP's LDS image at its row capacity exceeds 64 KiB (jslpc_tree_lds_bytes): a smaller row_extra, or solve it through a jslp_engine");
         if ((rc + no) * width[i] > JSLPP_LDS_LIMIT / 8 || pk_lds_bytes((int32_t)rc, width[i], (int32_t)no) > (long long)WGLDS_MAX_BYTES)
             return pack_fail(JSLP_ERR_UNSUPPORTED, "pack_create", i,
+                             inc ? "the incremental LP's LDS image at its row capacity exceeds 64 KiB (jslpi_tree_lds_bytes): a smaller row_extra, or solve it through a jslp_engine" :
                              tree ? "the tableau's LDS image at its row capacity exceeds 64 KiB (jslpt_lds_bytes): fewer cut rows, or solve it through a jslp_engine"
                                   : "the tableau's LDS image exceeds 64 KiB (jslpp_lds_bytes): solve it through a jslp_engine");
     }
@@ -3703,19 +3732,28 @@ static int pack_create(jslpp_pack** out, int device, int32_t n, const int32_t* h
         p->max_nodes = max_nodes > 0 ? max_nodes : JSLPT_MAX_NODES_DEFAULT;
         if (row_extra) {
             p->mir.resize((size_t)n);
-            for (int32_t i = 0; i < n; i++) p->mir[i] = row_extra[i] >= 0;
+            for (int32_t i = 0; i < n; i++) p->mir[i] = row_extra[i] >= 0 && !(incremental && incremental[i]);
             p->has_mir = true;
+        }
+        if (incremental) {
+            p->inc.resize((size_t)n);
+            p->max_ckpt.assign((size_t)n, 0);
+            for (int32_t i = 0; i < n; i++) {
+                p->inc[i] = incremental[i] != 0;
+                if (p->inc[i]) p->max_ckpt[i] = max_checkpoints[i];
+            }
+            p->has_inc = true;
         }
         if (node_selection) {  // an LP with exactly one of the two set gets the other's default, hybrid / pseudocost (main.ts:76-77)
             p->policy.resize((size_t)n);
             for (int32_t i = 0; i < n; i++)
-                p->policy[i] = (node_selection[i] || branching[i]) ? (node_selection[i] ? node_selection[i] : (int32_t)ENH_HYBRID) |
+                p->policy[i] = (node_selection[i] || branching[i] || p->is_inc((size_t)i)) ? (node_selection[i] ? node_selection[i] : (int32_t)ENH_HYBRID) |
                                                                          (branching[i] ? branching[i] : (int32_t)ENH_PSEUDOCOST) << 4
                                                                    : 0;
             p->has_enh = true;
         }
         for (int32_t i = 0; i < n; i++) {
-            p->RC[i] = height[i] + (p->is_mir(i) ? row_extra[i] : cut_rows[i]);
+            p->RC[i] = height[i] + (p->is_mir(i) || p->is_inc((size_t)i) ? row_extra[i] : cut_rows[i]);
             p->tree_mem_bytes += p->tree_lp_bytes((size_t)i);
         }
     }
@@ -3781,6 +3819,39 @@ extern "C" int jslpe_tree_pack_create(jslpp_pack** out, int device, int32_t n, c
     return jslpe_tree_pack_create_mixed(out, device, n, height, width, precision, cut_rows, heap_cap, nullptr, nullptr, node_selection, branching, trace_cap,
                                         max_pivots, max_nodes);
 }
+// include/jslpi_tree_incremental.h
+extern "C" int jslpi_tree_pack_create(jslpp_pack** out, int device, int32_t n, const int32_t* height, const int32_t* width, const double* precision,
+                                      const int32_t* cut_rows, const int32_t* heap_cap, const int32_t* n_optional, const int32_t* row_extra,
+                                      const int32_t* node_selection, const int32_t* branching, const int32_t* incremental,
+                                      const int32_t* max_checkpoints, int32_t trace_cap, int32_t max_pivots, int32_t max_nodes) {
+    if (n > 0 && (!cut_rows || !heap_cap || !node_selection || !branching || !incremental || !max_checkpoints)) return fail(JSLP_ERR_ARG, "pack_create: bad arguments");
+    if (n_optional && row_extra)
+        for (int32_t i = 0; i < n; i++)
+            if (row_extra[i] >= 0 && n_optional[i] > 0 && !incremental[i]) return pack_fail(JSLP_ERR_ARG, "pack_create", i, "a MIR LP has no optional objectives");
+    static const int32_t none = 0;
+    return pack_create(out, device, n, height, width, precision, cut_rows ? cut_rows : &none, heap_cap ? heap_cap : &none, n_optional, trace_cap,
+                       max_pivots, max_nodes, row_extra, node_selection ? node_selection : &none, branching ? branching : &none,
+                       incremental ? incremental : &none, max_checkpoints ? max_checkpoints : &none);
+}
+extern "C" int64_t jslpi_tree_lds_bytes(int32_t height, int32_t width, int32_t row_capacity) { return jslpt_lds_bytes(height, width, row_capacity); }
+extern "C" int64_t jslpi_checkpoint_bytes(int32_t height, int32_t width, int32_t row_capacity) {
+    if (height < 2 || width < 2 || row_capacity < height) return 0;
+    return (int64_t)tree_ckpt_bytes(row_capacity, width);
+}
+extern "C" int jslpi_pack_read_incremental(jslpp_pack* p, jslpi_tree_result* out) {
+    if (!p || (p->n > 0 && !out)) return fail(JSLP_ERR_ARG, "pack_read_incremental: bad arguments");
+    if (!p->tree) return fail(JSLP_ERR_STATE, "pack_read_incremental: not a pack with trees (jslpi_tree_pack_create, jslpt_pack_create)");
+    if (!p->uploaded || !p->tree_ran) return fail(JSLP_ERR_STATE, "pack_read_incremental before jslpt_pack_branch_and_cut");
+    if ((int32_t)p->tree_status.size() != p->n) return fail(JSLP_ERR_STATE, "pack_read_incremental: the last jslpt_pack_branch_and_cut did not finish");
+    static_assert(sizeof(jslpi_tree_result) == 32 && sizeof(TreeIncRec) == 32 && sizeof(TreeCkptHead) == 16, "jslpi_tree_result is a TreeIncRec");
+    static_assert(JSLPI_MAX_CHECKPOINTS == TREE_MAX_CHECKPOINTS, "include/jslpi_tree_incremental.h and jslp_tree.hip.h agree");
+    for (int32_t i = 0; i < p->n; i++) {
+        if (p->tree_status[(size_t)i] != JSLP_OK) continue;  // (left as it was)
+        memset(&out[i], 0, sizeof out[i]);
+        if (p->is_inc((size_t)i)) memcpy(&out[i], p->h_enh((size_t)i) + 1, sizeof out[i]);  // (the TreeIncRec behind the LP's TreeEnhRec)
+    }
+    return JSLP_OK;
+}
 extern "C" int jslpe_pack_read_enhanced(jslpp_pack* p, jslpe_tree_result* out) {
     if (!p || (p->n > 0 && !out)) return fail(JSLP_ERR_ARG, "pack_read_enhanced: bad arguments");
     if (!p->tree) return fail(JSLP_ERR_STATE, "pack_read_enhanced: not a pack with trees (jslpe_tree_pack_create, jslpt_pack_create)");
@@ -3793,7 +3864,7 @@ extern "C" int jslpe_pack_read_enhanced(jslpp_pack* p, jslpe_tree_result* out) {
     for (int32_t i = 0; i < p->n; i++) {
         if (p->tree_status[(size_t)i] != JSLP_OK) continue;  // (left as it was)
         memset(&out[i], 0, sizeof out[i]);
-        if (p->is_enh((size_t)i)) memcpy(&out[i], &p->h_enh()[i], sizeof out[i]);
+        if (p->is_enh((size_t)i)) memcpy(&out[i], p->h_enh((size_t)i), sizeof out[i]);
     }
     return JSLP_OK;
 }
@@ -3975,7 +4046,7 @@ extern "C" int jslpp_pack_simplex(jslpp_pack* p, const int32_t* check_cycles, js
     const bool dbg = debug_launch_on();
     HIPC(hipEventRecord(p->ev_begin, s));
     int32_t first = 0;
-    for (int g = 0; g < 8; first += p->n_group[g], g++) {  // one launch per kernel build that has LPs (and one per group of MIR or enhanced LPs, in the plain build)
+    for (int g = 0; g < jslpp_pack::N_GROUPS; first += p->n_group[g], g++) {  // one launch per kernel build that has LPs (and one per group of MIR, enhanced or incremental LPs, in the plain build)
         const int32_t cnt = p->n_group[g];
         if (!cnt) continue;
         const int threads = (g & 1) ? 256 : 64;
@@ -4080,6 +4151,7 @@ static int tree_error(const TreeRec& r) {
         case TREE_ERR_BRANCH: return fail(JSLP_ERR_ARG, "branch_and_cut: a node is not integral and has no fractional variable (negative precision?)");
         case TREE_ERR_MIR_ROWS: return fail(JSLP_ERR_CAPACITY, "branch_and_cut: row_extra reached (the rows of a MIR round or of a cut list do not fit the row capacity)");
         case TREE_ERR_MIR_ROUNDS: return fail(JSLP_ERR_CAPACITY, "branch_and_cut: mir rounds: JSLPR_MAX_ROUNDS rounds of one node without a stop");
+        case TREE_ERR_INC_ROWS: return fail(JSLP_ERR_CAPACITY, "branch_and_cut: row_extra reached (the new cut row of a node that starts from a checkpoint does not fit the row capacity)");
     }
     return fail(JSLP_ERR_DEVICE, "unknown tree error code");
 }
@@ -4120,7 +4192,7 @@ extern "C" int jslpt_pack_branch_and_cut(jslpp_pack* p, const int32_t* check_cyc
     p->tree_ran = true;
     HIPC(hipEventRecord(p->ev_begin, s));
     int32_t first = 0;
-    for (int g = 0; g < 8; first += p->n_group[g], g++) {  // one launch per kernel build that has LPs
+    for (int g = 0; g < jslpp_pack::N_GROUPS; first += p->n_group[g], g++) {  // one launch per kernel build that has LPs
         const int32_t cnt = p->n_group[g];
         if (!cnt) continue;
         const int threads = (g & 1) ? 256 : 64;
@@ -4129,10 +4201,12 @@ extern "C" int jslpt_pack_branch_and_cut(jslpp_pack* p, const int32_t* check_cyc
         a.opt = (g >> 1) == 1;
         a.mir = (g >> 1) == 2;
         a.enh = (g >> 1) == 3;
+        a.inc = (g >> 1) == 4;
         (void)packed_launch(threads, (unsigned)cnt, lds, a, s);
         HIPC(hipGetLastError());
         p->launches += 1;
-        if (dbg && a.enh) fprintf(stderr, "[jslp] launch k_tree_packed<%d,enh 1> n %d lds %zu\n", threads, (int)cnt, lds);
+        if (dbg && a.inc) fprintf(stderr, "[jslp] launch k_tree_packed<%d,inc 1> n %d lds %zu\n", threads, (int)cnt, lds);
+        else if (dbg && a.enh) fprintf(stderr, "[jslp] launch k_tree_packed<%d,enh 1> n %d lds %zu\n", threads, (int)cnt, lds);
         else if (dbg && a.mir) fprintf(stderr, "[jslp] launch k_tree_packed<%d,mir 1> n %d lds %zu\n", threads, (int)cnt, lds);
         else if (dbg && a.opt) fprintf(stderr, "[jslp] launch k_tree_packed<%d,opt 1> n %d lds %zu\n", threads, (int)cnt, lds);
         else if (dbg) fprintf(stderr, "[jslp] launch k_tree_packed<%d> n %d lds %zu\n", threads, (int)cnt, lds);
@@ -4193,6 +4267,7 @@ extern "C" int jslpt_pack_read_rhs(jslpp_pack* p, const double** rhs, const int3
 #include "jslp_mir_kernels.hip.h"  // single-unit build: the MIR kernels behind everything else (the product: jslp_tu_mir.hip)
 #define JSLP_PACKED_KERNELS 1
 #define JSLP_TREE_ENH_BUILDS 1
+#define JSLP_TREE_INC_BUILDS 1
 #include "jslp_packed.hip.h"       // ... and the pack's two (the product: jslp_tu_packed.hip)
 #include "jslp_tree.hip.h"         // ... with the tree kernels behind them
 #endif

@@ -75,7 +75,8 @@ struct PackLaunch {
     int32_t cc_all, kind;  // kind 0: k_simplex_packed, 1: k_tree_packed (jslp_tree.hip.h)
     int32_t opt, mir;      // opt 1: the OPT = true build (every LP of `order` has optional objectives); mir 1: the MIR = true build of
                            // k_tree_packed (every LP of `order` is a MIR LP, include/jslpc_tree_mir.h)
-    int32_t enh, pad;      // enh 1: the ENH build of k_tree_packed (every LP of `order` is an enhanced LP, include/jslpe_tree_enhanced.h)
+    int32_t enh, inc;      // enh 1: the ENH build of k_tree_packed (every LP of `order` is an enhanced LP, include/jslpe_tree_enhanced.h);
+                           // inc 1: its INC build (every LP of `order` is an incremental LP, include/jslpi_tree_incremental.h; enh is 0 then)
     void* states;          // result block: DevState per LP (LP order) ...
     double* rhs;           // ... the RHS columns one after the other ...
     int32_t* rows;         // ... and the row maps

@@ -27,6 +27,15 @@ struct TreeMirRec { int32_t rounds, rows_added, simplexes, root_rows, rows_high_
 // A cut of such an LP carries that position in its type: type = (position << 1) | ("max" ? 1 : 0).
 struct TreePseudo { double up_sum, down_sum; int32_t up_count, down_count, pad[2]; };
 struct TreeEnhRec { int32_t solutions_found, stack_high_water, moved_to_heap, pseudo_updates, scored_by_pseudocost, dropped_nodes, pad[2]; };  // jslpe_tree_result
+// An incremental LP (include/jslpi_tree_incremental.h) runs in the INC build of the kernel: an enhanced LP's memory, with the checkpoint arena
+// behind the pseudocost table -- max_checkpoints slots of tree_ckpt_bytes each: a TreeCkptHead, the rows of the row capacity at stride W in
+// 16-byte words (the saved root's layout), the whole integer block.  Its policy carries max_checkpoints above the two rules (<< 8).  The
+// checkpoint an entry starts from rides in its cut list's header, behind the length: TREE_CK_NO_CUT (a best-first child: no new cut, no
+// checkpoint), TREE_CK_NONE (a new cut -- the list's last -- but no checkpoint: the budget was spent), or the checkpoint's number.
+// The LP's TreeIncRec follows its TreeEnhRec in the result block.
+struct TreeCkptHead { int32_t height, feasible; double evaluation; };
+struct TreeIncRec { int32_t checkpoints_used, incremental_nodes, rows_high_water, checkpoint_rows_high_water, pad[4]; };  // jslpi_tree_result
+enum { TREE_CK_NO_CUT = -2, TREE_CK_NONE = -1, TREE_MAX_CHECKPOINTS = 64 };
 enum { ENH_BEST_FIRST = 1, ENH_DEPTH_FIRST = 2, ENH_HYBRID = 3, ENH_MOST_FRACTIONAL = 1, ENH_PSEUDOCOST = 2, ENH_STRONG = 3, ENH_STRONG_CANDIDATES = 5 };
 struct TreeLp {
     TreeEntry* heap;
@@ -34,20 +43,23 @@ struct TreeLp {
     int32_t* free_list;
     double rcoef;  // Math.round(1 / precision), computed on the host like decode_state's
     int32_t cut_rows, heap_cap, max_nodes;
-    int32_t policy;  // 0: the default service; an enhanced LP: node selection | branching << 4 (ENH_*)
+    int32_t policy;  // 0: the default service; an enhanced LP: node selection | branching << 4 (ENH_*); an incremental LP: the same | max_checkpoints << 8
     union {
         double* best_opt;     // n_opt doubles next to the heap: column 0 of the incumbent's optional rows (thread 0 alone reads and writes them)
         TreeMirRec* mir_out;  // a MIR LP (include/jslpc_tree_mir.h; never one with optional objectives): its record in the result block
-        TreeEnhRec* enh_out;  // an enhanced LP (never one with optional objectives or MIR): its record in the result block
+        TreeEnhRec* enh_out;  // an enhanced LP (never one with optional objectives or MIR): its record in the result block (an incremental LP: its TreeIncRec behind it)
     };
 };
-enum { TREE_OK = 0, TREE_ERR_NODES = 1, TREE_ERR_HEAP = 2, TREE_ERR_CUTS = 3, TREE_ERR_BRANCH = 4, TREE_ERR_MIR_ROWS = 5, TREE_ERR_MIR_ROUNDS = 6 };
+enum { TREE_OK = 0, TREE_ERR_NODES = 1, TREE_ERR_HEAP = 2, TREE_ERR_CUTS = 3, TREE_ERR_BRANCH = 4, TREE_ERR_MIR_ROWS = 5, TREE_ERR_MIR_ROUNDS = 6, TREE_ERR_INC_ROWS = 7 };
 struct TreeRec {  // what the kernel reports per LP next to its DevState
     double evaluation;
     int32_t iterations, is_integral, final_height, nodes_pushed, heap_high_water, cuts_high_water, err, pad;
 };
 __host__ __device__ __forceinline__ long long tree_slot_bytes(int32_t cut_rows) { return 16LL * (1 + cut_rows); }
 __host__ __device__ __forceinline__ long long tree_pseudo_bytes(int32_t RC, int32_t W) { return (long long)sizeof(TreePseudo) * pk_n_idx(RC, W); }  // (an LP has at most n_idx integer variables)
+__host__ __device__ __forceinline__ long long tree_ckpt_bytes(int32_t RC, int32_t W) {  // one checkpoint slot of an incremental LP
+    return (long long)sizeof(TreeCkptHead) + 16 * (((long long)RC * W + 1) >> 1) + 4LL * pk_ints(RC, W).total;
+}
 __host__ __device__ __forceinline__ long long tree_ivars_bytes(int32_t RC, int32_t W) { return 16 + 4LL * pk_pad4(pk_n_idx(RC, W)); }
 // A MIR LP (include/jslpc_tree_mir.h) runs in a MIR build of the kernel.  Its LDS image is the tree LP's at its row capacity with
 // variable.isInteger per variable index behind the integer block: n_idx bytes padded to 16, built by the kernel from the image's list of
@@ -132,7 +144,13 @@ __device__ __forceinline__ double tree_round(double x) {
 // table with its order-dependent update, and selectBranchingVariable (:112-196) scanned across the lanes.  Node selection and branching
 // rule are the LP's own (TreeLp::policy), uniform across its workgroup.  ENH = false instantiates the kernel, instruction for instruction,
 // as it was before there was such a build.
-template <int THREADS, bool OPT, bool MIR = false, bool ENH = false>
+// INC = true (with ENH, whose machinery it is built on): the LPs of a model with options.useIncremental (include/jslpi_tree_incremental.h), under
+// the incremental service (incremental-branch-and-cut.ts:280-496).  The enhanced walk, with parent checkpoints: a node that branches
+// while the walk is depth-first copies its solved tableau into the LP's arena (checkpoint_save, the whole workgroup), and a child that
+// carries one starts from it with ONE new cut row (checkpoint_restore + add_cuts_at) instead of the root and its whole list.  Pseudocosts
+// are updated from a node's new cut only, `strong` means pseudocost, and a checkpoint brings its evaluation with it.  INC = false
+// instantiates the kernel as it was before there was such a build.
+template <int THREADS, bool OPT, bool MIR = false, bool ENH = false, bool INC = false>
 __global__ void __launch_bounds__(THREADS) k_tree_packed(const PackLp* __restrict__ lps, const TreeLp* __restrict__ trees, const int32_t* __restrict__ order,
                                                          const int32_t* __restrict__ cc, int cc_all, DevState* __restrict__ out_states,
                                                          double* __restrict__ out_rhs, int32_t* __restrict__ out_rows, TreeRec* __restrict__ out_tree) {
@@ -141,6 +159,8 @@ __global__ void __launch_bounds__(THREADS) k_tree_packed(const PackLp* __restric
     __shared__ TreeMirSm ms;  // (MIR; no other build refers to it)
     static_assert(!(MIR && OPT), "a MIR LP has no optional objectives (include/jslpc_tree_mir.h)");
     static_assert(!(ENH && (OPT || MIR)), "an enhanced LP has neither optional objectives nor MIR cuts (include/jslpe_tree_enhanced.h)");
+    static_assert(!(INC && (OPT || MIR)), "an incremental LP has neither optional objectives nor MIR cuts (include/jslpi_tree_incremental.h)");
+    static_assert(!INC || ENH, "the INC build is the ENH build with checkpoints");
     const int idx = order[blockIdx.x];
     const PackLp m = lps[idx];
     const TreeLp t = trees[idx];
@@ -177,13 +197,14 @@ __global__ void __launch_bounds__(THREADS) k_tree_packed(const PackLp* __restric
     int32_t* free_list = many_global(t.free_list);
     const long long slot_bytes = tree_slot_bytes(t.cut_rows);
 
-    // the saved root's rows and the whole integer block: image <-> LDS, 16-byte words (stride W <-> stride S)
+    // `rows` rows and the whole integer block, global <-> LDS in 16-byte words (stride W <-> stride S; a word may hold the last cell of one row
+    // and the first of the next, and the last word half a pair when rows * W is odd): the saved root's, and (INC) a checkpoint's
     int Hs = H0;  // rows of the saved root: the LP's own, (MIR) with the root's MIR rows from save() on
     const int words = io.total >> 2;
-    auto restore = [&]() {
-        const int cells = Hs * W, pairs = (cells + 1) >> 1;
+    auto rows_in = [&](const double2* srcA, const int4* srcI, int rows) {
+        const int cells = rows * W, pairs = (cells + 1) >> 1;
         for (int q = tid; q < pairs; q += THREADS) {
-            const double2 v = gA[q];
+            const double2 v = srcA[q];
             const int e = 2 * q, r = e / W, c = e - r * W;
             A[r * S + c] = v.x;
             if (e + 1 < cells) {
@@ -191,7 +212,23 @@ __global__ void __launch_bounds__(THREADS) k_tree_packed(const PackLp* __restric
                 A[(wrap ? r + 1 : r) * S + (wrap ? 0 : c + 1)] = v.y;
             }
         }
-        for (int q = tid; q < words; q += THREADS) reinterpret_cast<int4*>(ints)[q] = gI[q];
+        for (int q = tid; q < words; q += THREADS) reinterpret_cast<int4*>(ints)[q] = srcI[q];
+    };
+    auto rows_out = [&](double2* dstA, int4* dstI, int rows) {
+        const int cells = rows * W, pairs = (cells + 1) >> 1;
+        for (int q = tid; q < pairs; q += THREADS) {
+            const int e = 2 * q, r = e / W, c = e - r * W;
+            const bool wrap = c + 1 == W;
+            double2 v;
+            v.x = A[r * S + c];
+            v.y = e + 1 < cells ? A[(wrap ? r + 1 : r) * S + (wrap ? 0 : c + 1)] : 0.0;
+            dstA[q] = v;
+        }
+        for (int q = tid; q < words; q += THREADS) dstI[q] = reinterpret_cast<const int4*>(ints)[q];
+    };
+    // the saved root: image <-> LDS
+    auto restore = [&]() {
+        rows_in(gA, gI, Hs);
         if constexpr (OPT)
             for (int q = tid; q < n_opt * W; q += THREADS) {
                 const int o = q / W;
@@ -199,16 +236,7 @@ __global__ void __launch_bounds__(THREADS) k_tree_packed(const PackLp* __restric
             }
     };
     auto save = [&]() {
-        const int cells = Hs * W, pairs = (cells + 1) >> 1;
-        for (int q = tid; q < pairs; q += THREADS) {
-            const int e = 2 * q, r = e / W, c = e - r * W;
-            const bool wrap = c + 1 == W;
-            double2 v;
-            v.x = A[r * S + c];
-            v.y = e + 1 < cells ? A[(wrap ? r + 1 : r) * S + (wrap ? 0 : c + 1)] : 0.0;
-            gA[q] = v;
-        }
-        for (int q = tid; q < words; q += THREADS) gI[q] = reinterpret_cast<const int4*>(ints)[q];
+        rows_out(gA, gI, Hs);
         if constexpr (OPT)
             for (int q = tid; q < n_opt * W; q += THREADS) {
                 const int o = q / W;
@@ -217,14 +245,15 @@ __global__ void __launch_bounds__(THREADS) k_tree_packed(const PackLp* __restric
     };
     // addCutConstraints (cutting-strategies.ts:16-72) of the list in `slot` on the restored root: every cut row reads rows below Hs
     // and the restored maps only, so the rows are built side by side, one (cut, column) cell per thread and step; returns the height
-    // ((MIR) or -1 with nothing written: the root's MIR rows have left the list no room below the row capacity)
-    auto add_cuts = [&](int slot) -> int {
-        if (slot < 0) return Hs;
+    // ((MIR) or -1 with nothing written: the root's MIR rows have left the list no room below the row capacity).  In general the list's cuts
+    // from `first` on, on a tableau `base` rows tall: the restored root and 0, or (INC) a restored checkpoint and the list's last cut
+    auto add_cuts_at = [&](int slot, int base, int first) -> int {
+        if (slot < 0) return base;
         const char* sp = pool + slot * slot_bytes;
-        const int n = *reinterpret_cast<const int32_t*>(sp);
+        const int n = *reinterpret_cast<const int32_t*>(sp) - first;
         if constexpr (MIR)
-            if (Hs + n > RC) return -1;
-        const TreeCut* cuts = reinterpret_cast<const TreeCut*>(sp + 16);
+            if (base + n > RC) return -1;
+        const TreeCut* cuts = reinterpret_cast<const TreeCut*>(sp + 16) + first;
         for (int q = tid; q < n * W; q += THREADS) {
             const int h = q / W, col = q - h * W;
             TreeCut c = cuts[h];
@@ -239,17 +268,18 @@ __global__ void __launch_bounds__(THREADS) k_tree_packed(const PackLp* __restric
                 const double s = A[var_row * S + col];
                 v = col == 0 ? sign * (c.value - s) : -sign * s;
             }
-            A[(Hs + h) * S + col] = v;
+            A[(base + h) * S + col] = v;
         }
         __syncthreads();  // (the maps read above are written below)
         for (int h = tid; h < n; h += THREADS) {  // getNewElementIndex + map updates (:64-69)
-            const int slack = W + Hs - 2 + h;
-            vibr[Hs + h] = slack;
-            rbv[slack] = Hs + h;
+            const int slack = W + base - 2 + h;
+            vibr[base + h] = slack;
+            rbv[slack] = base + h;
             cbv[slack] = -1;
         }
-        return Hs + n;
+        return base + n;
     };
+    auto add_cuts = [&](int slot) -> int { return add_cuts_at(slot, Hs, 0); };
 
     if constexpr (MIR) {  // variable.isInteger, from the image's list (restore() below moves the integer block in front of it only)
         for (int q = tid; q < tree_mir_flag_words(RC, W); q += THREADS) reinterpret_cast<int32_t*>(is_int)[q] = 0;
@@ -263,6 +293,26 @@ __global__ void __launch_bounds__(THREADS) k_tree_packed(const PackLp* __restric
             TreePseudo z; z.up_sum = 0.0; z.down_sum = 0.0; z.up_count = 0; z.down_count = 0; z.pad[0] = z.pad[1] = 0;
             pseudo[k] = z;
         }
+    // (INC) the checkpoint arena behind the pseudocost table.  checkpoint_save: what LDS holds now -- the node's solved tableau, H rows, and
+    // the whole integer block -- into slot k, with tableau.evaluation and tableau.feasible (createCheckpoint, :55-70); checkpoint_restore:
+    // slot k back (restoreCheckpoint, :72-107), returns its head.  The copies are the whole workgroup's, like save() / restore(); thread 0
+    // writes the head; the caller places the barriers.  A slot is written once per call (the counter only goes up) and read after a barrier.
+    char* ck_arena = reinterpret_cast<char*>(pseudo) + tree_pseudo_bytes(RC, W);
+    const long long ck_bytes = tree_ckpt_bytes(RC, W), ck_ints_off = ck_bytes - 4LL * io.total;
+    auto checkpoint_save = [&](int k, int rows, double eval, int feas) {
+        char* cp = ck_arena + k * ck_bytes;
+        if (tid == 0) {
+            TreeCkptHead h; h.height = rows; h.feasible = feas; h.evaluation = eval;
+            *reinterpret_cast<TreeCkptHead*>(cp) = h;
+        }
+        rows_out(reinterpret_cast<double2*>(cp + sizeof(TreeCkptHead)), reinterpret_cast<int4*>(cp + ck_ints_off), rows);
+    };
+    auto checkpoint_restore = [&](int k) -> TreeCkptHead {
+        const char* cp = ck_arena + k * ck_bytes;
+        const TreeCkptHead h = *reinterpret_cast<const TreeCkptHead*>(cp);
+        rows_in(reinterpret_cast<const double2*>(cp + sizeof(TreeCkptHead)), reinterpret_cast<const int4*>(cp + ck_ints_off), h.height);
+        return h;
+    };
     restore();
     long long trace_n = st->trace_n;
     if constexpr (OPT)  // bestOptionalObjectivesEvaluations (:66-69)
@@ -280,7 +330,13 @@ __global__ void __launch_bounds__(THREADS) k_tree_packed(const PackLp* __restric
     // (ENH) the enhanced service's registers, uniform like the others: which container the next node comes from, the stack's size, and
     // what the LP's TreeEnhRec reports.  The root starts on the stack unless the selection is best-first (:246-255); the heap's sequence
     // numbers count its own pushes only.
-    const int node_sel = t.policy & 15, branching = t.policy >> 4;
+    // (INC) `strong` does not exist in the incremental service and means pseudocost (:202-219); max_checkpoints rides above the two rules
+    const int node_sel = t.policy & 15;
+    const int branching = INC ? (((t.policy >> 4) & 15) == ENH_STRONG ? (int)ENH_PSEUDOCOST : (t.policy >> 4) & 15) : t.policy >> 4;
+    const int max_ck = INC ? min(t.policy >> 8, (int)TREE_MAX_CHECKPOINTS) : 0;
+    // (INC) checkpoints taken (the next free slot), nodes that started from one, the tallest tableau and the tallest checkpoint; what the
+    // node under evaluation starts from and what its children will (TREE_CK_*, or a checkpoint's number)
+    int ck_count = 0, inc_nodes = 0, rows_hw = H0, ck_rows_hw = H0, cur_ck = TREE_CK_NO_CUT, child_ck = TREE_CK_NO_CUT;
     bool use_df = ENH && node_sel != ENH_BEST_FIRST;
     int stack_n = 0, stack_hw = use_df ? 1 : 0, solutions = 0, moved = 0, pseudo_updates = 0, scored = 0, dropped = 0;
     if constexpr (ENH)
@@ -352,7 +408,21 @@ __global__ void __launch_bounds__(THREADS) k_tree_packed(const PackLp* __restric
             if (key > best_eval) { release(cur_slot); continue; }  // :89-92
         }
         if (iterations >= t.max_nodes) { terr = TREE_ERR_NODES; break; }
-        if (!root) {  // applyCuts: restore + addCutConstraints (:33-37)
+        if constexpr (INC) {  // :342: parentEval before applyIncrementalCuts, which may bring a checkpoint's evaluation
+            parent_eval = evaluation;
+            cur_ck = (!root && cur_slot >= 0) ? reinterpret_cast<const int32_t*>(pool + cur_slot * slot_bytes)[1] : (int)TREE_CK_NO_CUT;
+        }
+        if (INC && cur_ck >= 0) {  // :249-253: the parent's checkpoint and the ONE new cut, the list's last
+            const TreeCkptHead ch = checkpoint_restore(cur_ck);
+            __syncthreads();
+            evaluation = ch.evaluation;
+            feasible = ch.feasible;
+            H = ch.height;
+            if (H + 1 > RC) { terr = TREE_ERR_INC_ROWS; break; }
+            H = add_cuts_at(cur_slot, H, *reinterpret_cast<const int32_t*>(pool + cur_slot * slot_bytes) - 1);
+            __syncthreads();
+            inc_nodes += 1;
+        } else if (!root) {  // applyCuts: restore + addCutConstraints (:33-37)
             restore();
             __syncthreads();
             H = add_cuts(cur_slot);
@@ -361,12 +431,13 @@ __global__ void __launch_bounds__(THREADS) k_tree_packed(const PackLp* __restric
                 if (H < 0) { H = Hs; terr = TREE_ERR_MIR_ROWS; break; }
         }
         root = false;
-        if constexpr (ENH) parent_eval = evaluation;  // tableau.evaluation as the PREVIOUS node left it (:287)
+        if constexpr (ENH && !INC) parent_eval = evaluation;  // tableau.evaluation as the PREVIOUS node left it (:287)
         iters_left = m.iters_cap;
         o = pk_simplex<THREADS, OPT>(A, pcol, H, W, S, vibr, vibc, rbv, cbv, unr, precision, check_cycles, m, ghist, gtrace, sm.ps, iters_left, trace_n, oo, n_opt);
         __syncthreads();
         if (o.outcome >= 5) { serr = o.outcome == 5 ? (int)ERR_ITER_LIMIT : (int)ERR_HIST_FULL; break; }
         iterations += 1;
+        if constexpr (INC) rows_hw = max(rows_hw, H);
         feasible = (o.outcome == 3 || o.outcome == 4) ? 0 : 1;
         unb_var = o.outcome == 2 ? vibc[o.unbounded_col] : -1;
         if (o.outcome == 1)  // setEvaluation (tableau.ts:420-430); a node that reaches no optimum keeps the previous node's
@@ -382,8 +453,8 @@ __global__ void __launch_bounds__(THREADS) k_tree_packed(const PackLp* __restric
         if constexpr (ENH) {  // enhanced-branch-and-cut.ts:292-427; every path ends this iteration
             if (!feasible || evaluation > best_eval) { release(cur_slot); continue; }  // :292-299
             // :301-314: the pseudocost of the node's LAST cut, from the evaluation the previous node left (a node off the stack or the heap
-            // has at least one cut; NaN !== 0)
-            if (cur_slot >= 0 && parent_eval != 0.0) {
+            // has at least one cut; NaN !== 0).  (INC) :358-367: of the node's NEW cut, which the children of a depth-first node have
+            if ((INC ? cur_ck != TREE_CK_NO_CUT : cur_slot >= 0) && parent_eval != 0.0) {
                 if (tid == 0) {
                     const char* sp = pool + cur_slot * slot_bytes;
                     const int n = *reinterpret_cast<const int32_t*>(sp);
@@ -453,7 +524,7 @@ __global__ void __launch_bounds__(THREADS) k_tree_packed(const PackLp* __restric
                 return __dmul_rn(js_max(__dmul_rn(up, __dsub_rn(1.0, f)), 1e-6), js_max(__dmul_rn(down, f), 1e-6));
             };
             Cand b; b.v = -2.0; b.i = 0; b.b = 0;
-            if (branching == ENH_STRONG) {
+            if (!INC && branching == ENH_STRONG) {
                 // :161-193: the five most fractional -- a stable descending sort keeps model order among equals, so five first-wins maxima,
                 // each over what the earlier ones left -- then the first strictly greatest score among them, from -Infinity on
                 int top[ENH_STRONG_CANDIDATES];
@@ -500,6 +571,15 @@ __global__ void __launch_bounds__(THREADS) k_tree_packed(const PackLp* __restric
                 b = pk_reduce<THREADS>(b, MaxFirst(), sm.ps.g);
             }
             if (b.i == 0) { dropped += 1; release(cur_slot); continue; }  // :384: no candidate -- the node is dropped
+            if constexpr (INC) {  // :440-445, :476-488: a checkpoint for both children while the walk is depth-first and the budget lasts
+                child_ck = use_df ? TREE_CK_NONE : TREE_CK_NO_CUT;
+                if (use_df && ck_count < max_ck) {
+                    checkpoint_save(ck_count, H, evaluation, feasible);  // (read again behind the barriers below and the next pop's)
+                    child_ck = ck_count;
+                    ck_count += 1;
+                    ck_rows_hw = max(ck_rows_hw, H);
+                }
+            }
             if (tid == 0) {  // :386-426: the two children's cut lists, then the stack (low first, so that high is popped first) or the heap (high first)
                 const int pos = b.i - 1, var = ivars[pos];
                 const double value = A[rbv[var] * S];
@@ -527,6 +607,7 @@ __global__ void __launch_bounds__(THREADS) k_tree_packed(const PackLp* __restric
                     }
                     if (code != TREE_OK) break;
                     *reinterpret_cast<int32_t*>(dp) = n;
+                    if constexpr (INC) reinterpret_cast<int32_t*>(dp)[1] = child_ck;
                     len[child] = n;
                     if (sn + hn >= t.heap_cap) { code = TREE_ERR_HEAP; break; }  // (stack and heap share the array)
                     TreeEntry e; e.key = evaluation; e.slot = slot;
@@ -670,6 +751,7 @@ __global__ void __launch_bounds__(THREADS) k_tree_packed(const PackLp* __restric
             o = pk_simplex<THREADS, OPT>(A, pcol, H, W, S, vibr, vibc, rbv, cbv, unr, precision, check_cycles, m, ghist, gtrace, sm.ps, iters_left, trace_n, oo, n_opt);
             __syncthreads();
             if (o.outcome >= 5) serr = o.outcome == 5 ? (int)ERR_ITER_LIMIT : (int)ERR_HIST_FULL;
+            if constexpr (INC) rows_hw = max(rows_hw, H);
             feasible = (o.outcome == 3 || o.outcome == 4) ? 0 : 1;
             unb_var = o.outcome == 2 ? vibc[o.unbounded_col] : -1;
             if (o.outcome == 1)
@@ -745,6 +827,13 @@ __global__ void __launch_bounds__(THREADS) k_tree_packed(const PackLp* __restric
             er.pad[0] = er.pad[1] = 0;
             *many_global(t.enh_out) = er;
         }
+        if constexpr (INC) {
+            TreeIncRec ir;
+            ir.checkpoints_used = ck_count; ir.incremental_nodes = inc_nodes; ir.rows_high_water = rows_hw - H0;
+            ir.checkpoint_rows_high_water = ck_rows_hw - H0;
+            ir.pad[0] = ir.pad[1] = ir.pad[2] = ir.pad[3] = 0;
+            *reinterpret_cast<TreeIncRec*>(many_global(t.enh_out) + 1) = ir;
+        }
     }
     __syncthreads();
     if (tid < (int)(sizeof(DevState) / 8))
@@ -754,6 +843,7 @@ __global__ void __launch_bounds__(THREADS) k_tree_packed(const PackLp* __restric
 // as packed_launch_impl, for the tree kernels (PackLaunch::kind == 1).  The plain and OPT builds and the MIR builds have a launch function
 // each, so that a unit can hold one set without the other (-DJSLP_TREE_NO_MIR_BUILDS: jslp_tu_packed.hip; -DJSLP_TREE_NO_PLAIN_BUILDS:
 // jslp_tu_tree_mir.hip), and so have the ENH builds (-DJSLP_TREE_ENH_BUILDS: jslp_tu_tree_enh.hip and the single-unit build)
+// and the INC builds (-DJSLP_TREE_INC_BUILDS: jslp_tu_tree_inc.hip and the single-unit build)
 #ifndef JSLP_TREE_NO_PLAIN_BUILDS
 static int tree_launch_impl(int threads, unsigned grid, size_t lds, const void* bytes, hipStream_t s) {
     const PackLaunch a = *static_cast<const PackLaunch*>(bytes);
@@ -800,6 +890,22 @@ static int tree_enh_launch_impl(int threads, unsigned grid, size_t lds, const vo
         hipLaunchKernelGGL((k_tree_packed<64, false, false, true>), dim3(grid), dim3(64), lds, s, a.lps, trees, a.order, a.cc, a.cc_all, states, a.rhs, a.rows, recs);
     else if (threads == 256 && !a.opt && !a.mir)
         hipLaunchKernelGGL((k_tree_packed<256, false, false, true>), dim3(grid), dim3(256), lds, s, a.lps, trees, a.order, a.cc, a.cc_all, states, a.rhs, a.rows, recs);
+    else
+        return -1;
+    return (int)hipPeekAtLastError();
+}
+#endif
+#ifdef JSLP_TREE_INC_BUILDS
+// the INC builds (PackLaunch::inc == 1; never with opt or mir)
+static int tree_inc_launch_impl(int threads, unsigned grid, size_t lds, const void* bytes, hipStream_t s) {
+    const PackLaunch a = *static_cast<const PackLaunch*>(bytes);
+    DevState* states = static_cast<DevState*>(a.states);
+    const TreeLp* trees = static_cast<const TreeLp*>(a.trees);
+    TreeRec* recs = static_cast<TreeRec*>(a.tree_out);
+    if (threads == 64 && !a.opt && !a.mir)
+        hipLaunchKernelGGL((k_tree_packed<64, false, false, true, true>), dim3(grid), dim3(64), lds, s, a.lps, trees, a.order, a.cc, a.cc_all, states, a.rhs, a.rows, recs);
+    else if (threads == 256 && !a.opt && !a.mir)
+        hipLaunchKernelGGL((k_tree_packed<256, false, false, true, true>), dim3(grid), dim3(256), lds, s, a.lps, trees, a.order, a.cc, a.cc_all, states, a.rhs, a.rows, recs);
     else
         return -1;
     return (int)hipPeekAtLastError();

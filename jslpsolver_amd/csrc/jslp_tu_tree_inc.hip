@@ -1,0 +1,27 @@
+// jslp_tu_tree_inc.hip -- the INC builds of k_tree_packed (include/jslpi_tree_incremental.h: 64 or 256 threads) as a translation unit of their
+// own, so that the units of the other pack kernels (jslp_tu_packed.hip, jslp_tu_tree_mir.hip, jslp_tu_tree_enh.hip) compile what they
+// compiled before and the four run side by side (__graft_entry__.build()).
+//
+// As there, the kernel headers are included inside a namespace of the unit's own, so every kernel and helper has internal linkage and the
+// units never meet at link time; the unit exports ONE hidden function that launches the build a thread count names, its arguments
+// travelling as bytes (PackLaunch, jslp_packed.hip.h: the same struct in every unit).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <math.h>
+#include <stddef.h>
+#include <string.h>
+
+namespace {
+#include "jslp_kernels.hip.h"
+#define JSLP_PACKED_KERNELS 1
+#define JSLP_PACKED_NO_LAUNCH 1      // pk_simplex alone: k_simplex_packed is jslp_tu_packed.hip's
+#define JSLP_TREE_NO_PLAIN_BUILDS 1  // ... and so are the plain and OPT builds of k_tree_packed
+#define JSLP_TREE_NO_MIR_BUILDS 1    // ... the MIR builds are jslp_tu_tree_mir.hip's, the ENH builds jslp_tu_tree_enh.hip's
+#define JSLP_TREE_INC_BUILDS 1
+#include "jslp_packed.hip.h"
+#include "jslp_tree.hip.h"
+}  // namespace
+
+extern "C" __attribute__((visibility("hidden"))) int jslpi_tree_inc_launch_tu(int threads, unsigned grid, size_t lds, const void* args, void* stream) {
+    return tree_inc_launch_impl(threads, grid, lds, args, static_cast<hipStream_t>(stream));
+}

@@ -963,6 +963,41 @@ def tree_mir_rows(height, width, n_int, lib=None, cut_rows=None):
     return hi, min(cuts, hi)
 
 
+INCREMENTAL_ROW_HEADROOM = 256  # rows an incremental LP gets beyond 2 per integer variable by default, as Solve gives an engine (solver._prepare)
+
+
+def incremental_rows(height, width, n_int, lib=None, cut_rows=None):
+    """(row_extra, cut_rows) a model with options.useIncremental and n_int integer variables joins a tree pack with
+    (include/jslpi_tree_incremental.h): row_extra = min(2 per integer variable + INCREMENTAL_ROW_HEADROOM, the most rows that fit the LDS
+    limit) and cut_rows = min(2 per integer variable, row_extra); (0, 0) when not even one row fits.  cut_rows: the LP's own count instead
+    of 2 per integer variable."""
+    def fits(extra):
+        if lib is not None and getattr(lib, "has_tree_inc", False):
+            b = int(lib.jslpi_tree_lds_bytes(int(height), int(width), int(height) + extra))
+        else:
+            b = tree_lds_bytes(height, width, int(height) + extra)
+        return 0 < b <= _capi.JSLPP_LDS_LIMIT
+    cuts = 2 * int(n_int) if cut_rows is None else int(cut_rows)
+    lo, hi = 0, cuts + INCREMENTAL_ROW_HEADROOM
+    if not fits(hi):
+        while lo < hi:  # (the byte count is monotone in the row capacity)
+            mid = (lo + hi + 1) // 2
+            lo, hi = (mid, hi) if fits(mid) else (lo, mid - 1)
+        hi = lo
+    return hi, min(cuts, hi)
+
+
+def checkpoint_bytes(height, width, row_capacity):
+    """jslpi_checkpoint_bytes (include/jslpi_tree_incremental.h) restated: one checkpoint slot of an incremental LP -- a 16-byte header, the
+    rows of the row capacity in 16-byte words, the whole integer block of tree_lds_bytes"""
+    h, w, rc = int(height), int(width), int(row_capacity)
+    if h < 2 or w < 2 or rc < h:
+        return 0
+    pad4 = lambda n: (n + 3) & ~3  # noqa: E731
+    n_idx = w + 2 * rc + 2
+    return 16 + 16 * ((rc * w + 1) // 2) + 4 * (pad4(rc) + pad4(w) + 2 * pad4(n_idx) + pad4((n_idx + 3) // 4))
+
+
 class _TreeModel:
     """what branch_and_cut.branch_and_cut reads of a model, for an LP of a pack: the default service, no tolerance, no timeout"""
     tolerance = 0
@@ -1059,10 +1094,20 @@ class TableauPack:
     with either is an ENHANCED LP: its tree is walked under the enhanced service (one of the two left None gets its default, hybrid /
     pseudocost); its depth-first stack and its heap share heap_cap.  `enhanced` (_capi.ENH_TREE_DTYPE: solutions_found, stack_high_water,
     moved_to_heap, pseudo_updates, scored_by_pseudocost, dropped_nodes) is the read-back of the last branch_and_cut(), zero for the other
-    LPs; `is_enhanced` holds the flags.  Not for an LP with `mir` or with optional objectives."""
+    LPs; `is_enhanced` holds the flags.  Not for an LP with `mir` or with optional objectives.
+
+    incremental: one flag per LP of a pack with trees (include/jslpi_tree_incremental.h): the LP's model has options.useIncremental, and its
+    tree is walked under the incremental service -- the enhanced walk (node_selection / branching as above, hybrid / pseudocost when
+    None; `strong` means pseudocost) with parent checkpoints on the device, at most max_checkpoints (one number or one per LP; default
+    50, the reference's) per call.  Such an LP has ONE row capacity, height + row_extra (one number or one per LP; default:
+    incremental_rows), which the cut rows of a node that starts from the root and the stacked rows of a chain of checkpoints share.
+    `incremental` (_capi.INC_TREE_DTYPE: checkpoints_used, incremental_nodes, rows_high_water, checkpoint_rows_high_water) is the
+    read-back of the last branch_and_cut(), zero for the other LPs; `is_incremental` holds the flags; `enhanced` and `tree` report for such
+    an LP what they report for an enhanced one.  Not for an LP with `mir` or with optional objectives."""
 
     def __init__(self, lps, precision=1e-8, lib=None, device=0, trace_cap=0, max_pivots=0, integers=None, cut_rows=None, heap_cap=None,
-                 max_nodes=0, optional_objectives=None, mir=None, row_extra=None, node_selection=None, branching=None):
+                 max_nodes=0, optional_objectives=None, mir=None, row_extra=None, node_selection=None, branching=None, incremental=None,
+                 max_checkpoints=_capi.JSLPI_CHECKPOINTS_DEFAULT):
         self.lib = lib if lib is not None else _capi.load_hip()
         self._lps = []
         for matrix, vibr, vibc, unr in lps:
@@ -1131,9 +1176,11 @@ class TableauPack:
                 raise ValueError("TableauPack: `mir` needs `integers` (a pack with trees)")
             if len(mir) != n:
                 raise ValueError("TableauPack: %d mir flags for %d LPs" % (len(mir), n))
-            if self.has_optional:
-                raise ValueError("TableauPack: MIR LPs and optional objectives do not share a pack (include/jslpc_tree_mir.h)")
             self.is_mir = np.array([bool(f) for f in mir], dtype=bool)
+            # (a pack with incremental LPs is made by jslpi_tree_pack_create, which takes every kind of tree LP: there a MIR LP and an LP
+            # with optional objectives may stand side by side, though never in one LP)
+            if self.has_optional and (incremental is None or not any(incremental) or (self.is_mir & (self.n_optional > 0)).any()):
+                raise ValueError("TableauPack: MIR LPs and optional objectives do not share a pack (include/jslpc_tree_mir.h)")
             if row_extra is None:
                 extra = [tree_mir_rows(h, w, 0, lib=self.lib, cut_rows=c)[0] for h, w, c in zip(self.heights, self.widths, self.cut_rows)]
             else:
@@ -1159,12 +1206,43 @@ class TableauPack:
                 if g is not None and g not in names:
                     raise ValueError("TableauPack: LP %d: %s is None or one of %s, not %r" % (i, what, ", ".join(names), g))
                 codes[i] = 0 if g is None else names[g]
-        self.is_enhanced = (self.node_selection != 0) | (self.branching != 0)
+        # incremental LPs (include/jslpi_tree_incremental.h): the flags, max_checkpoints and row_extra per LP
+        self.is_incremental = np.zeros(n, dtype=bool)
+        self.incremental = np.zeros(n, dtype=_capi.INC_TREE_DTYPE)
+        self.max_checkpoints = np.zeros(n, dtype=np.int32)
+        if incremental is not None and any(incremental):
+            if not self.is_tree:
+                raise ValueError("TableauPack: `incremental` needs `integers` (a pack with trees)")
+            if len(incremental) != n:
+                raise ValueError("TableauPack: %d incremental flags for %d LPs" % (len(incremental), n))
+            self.is_incremental = np.array([bool(f) for f in incremental], dtype=bool)
+            limits = per_lp(max_checkpoints, None)
+            if limits.shape[0] != n:
+                raise ValueError("TableauPack: max_checkpoints is one number or one per LP")
+            self.max_checkpoints = np.where(self.is_incremental, limits, 0).astype(np.int32)
+            if row_extra is None:
+                extra = [incremental_rows(h, w, 0, lib=self.lib, cut_rows=c)[0] for h, w, c in zip(self.heights, self.widths, self.cut_rows)]
+            else:
+                extra = per_lp(row_extra, None)
+                if extra.shape[0] != n:
+                    raise ValueError("TableauPack: row_extra is one number or one per LP")
+            for i in np.flatnonzero(self.is_incremental):
+                if self.is_mir[i] or self.n_optional[i] > 0:
+                    raise ValueError("TableauPack: LP %d: an incremental LP has neither `mir` nor optional objectives "
+                                     "(include/jslpi_tree_incremental.h)" % i)
+                if not 0 <= self.max_checkpoints[i] <= _capi.JSLPI_MAX_CHECKPOINTS:
+                    raise ValueError("TableauPack: LP %d: max_checkpoints is between 0 and %d" % (i, _capi.JSLPI_MAX_CHECKPOINTS))
+            self.row_extra = np.where(self.is_incremental, _capi.as_i32(extra), self.row_extra).astype(np.int32)
+            self.row_capacity = np.where(self.is_incremental, self.heights + self.row_extra, self.row_capacity).astype(np.int32)
+        self.has_incremental = bool(self.is_incremental.any())
+        self.is_enhanced = (self.node_selection != 0) | (self.branching != 0) | self.is_incremental  # (an incremental LP is walked as one)
         self.has_enhanced = bool(self.is_enhanced.any())
         for i in np.flatnonzero(self.is_enhanced):
             if self.is_mir[i] or self.n_optional[i] > 0:
                 raise ValueError("TableauPack: LP %d: an enhanced LP (node_selection / branching) has neither `mir` nor optional objectives "
                                  "(include/jslpe_tree_enhanced.h)" % i)
+        if self.has_incremental and self.lib.has_pack and not getattr(self.lib, "has_tree_inc", False):
+            raise _capi.EngineError("TableauPack: %s does not export the incremental tree extension (include/jslpi_tree_incremental.h)" % self.lib.path)
         if self.has_enhanced and self.lib.has_pack and not getattr(self.lib, "has_tree_enh", False):
             raise _capi.EngineError("TableauPack: %s does not export the enhanced tree extension (include/jslpe_tree_enhanced.h)" % self.lib.path)
         if self.has_mir and self.lib.has_pack and not getattr(self.lib, "has_tree_mir", False):
@@ -1175,7 +1253,14 @@ class TableauPack:
             raise _capi.EngineError("TableauPack: %s does not export the optional-objective extension (include/jslps_soft.h)" % self.lib.path)
         if self.lib.has_pack:
             self._h = _capi.C.c_void_p()
-            if self.has_enhanced:
+            if self.has_incremental:
+                self.lib.check(self.lib.jslpi_tree_pack_create(
+                    _capi.C.byref(self._h), self.device, n, _capi.ptr_i32(self.heights), _capi.ptr_i32(self.widths), _capi.ptr_f64(self.precision),
+                    _capi.ptr_i32(self.cut_rows), _capi.ptr_i32(self.heap_cap), _capi.ptr_i32(self.n_optional) if self.has_optional else None,
+                    _capi.ptr_i32(self.row_extra), _capi.ptr_i32(self.node_selection), _capi.ptr_i32(self.branching),
+                    _capi.ptr_i32(self.is_incremental.astype(np.int32)), _capi.ptr_i32(self.max_checkpoints), self.trace_cap, self.max_pivots,
+                    self.max_nodes), "jslpi_tree_pack_create")
+            elif self.has_enhanced:
                 self.lib.check(self.lib.jslpe_tree_pack_create_mixed(
                     _capi.C.byref(self._h), self.device, n, _capi.ptr_i32(self.heights), _capi.ptr_i32(self.widths), _capi.ptr_f64(self.precision),
                     _capi.ptr_i32(self.cut_rows), _capi.ptr_i32(self.heap_cap), _capi.ptr_i32(self.n_optional) if self.has_optional else None,
@@ -1225,6 +1310,12 @@ class TableauPack:
                 if self.is_mir[i] and not 0 < tree_mir_lds_bytes(h, w, rc) <= _capi.JSLPP_LDS_LIMIT:
                     raise _capi.EngineError("jslpc_tree_pack_create failed (%d): pack_create: LP %d: the MIR LP's LDS image at its row capacity "
                                             "exceeds 64 KiB" % (_capi.JSLP_ERR_UNSUPPORTED, i))
+                if self.is_incremental[i] and self.row_extra[i] < self.cut_rows[i]:
+                    raise _capi.EngineError("jslpi_tree_pack_create failed (%d): pack_create: LP %d: row_extra of an incremental LP is its row "
+                                            "capacity beyond height: at least its cut_rows" % (_capi.JSLP_ERR_ARG, i))
+                if self.is_incremental[i] and not 0 < tree_lds_bytes(h, w, rc) <= _capi.JSLPP_LDS_LIMIT:
+                    raise _capi.EngineError("jslpi_tree_pack_create failed (%d): pack_create: LP %d: the incremental LP's LDS image at its row "
+                                            "capacity exceeds 64 KiB" % (_capi.JSLP_ERR_UNSUPPORTED, i))
                 if self.is_enhanced[i] and len(set(self.integers[i].tolist())) != self.integers[i].shape[0]:
                     raise _capi.EngineError("jslpt_pack_set_integers failed (%d): pack_set_integers: LP %d: the integer variables of an enhanced "
                                             "LP are distinct" % (_capi.JSLP_ERR_ARG, i))
@@ -1339,7 +1430,10 @@ class TableauPack:
         counters; its capacities are the row capacity (`row_extra` in the message) and JSLPR_MAX_ROUNDS rounds of one node (`mir rounds`).
         An enhanced LP (`node_selection=` / `branching=`) is walked under the enhanced service, in the kernel as in the restatement
         (incremental_branch_and_cut.enhanced_branch_and_cut with CountingContainers); `enhanced` keeps its counters; in `tree` its
-        heap_high_water counts stack and heap together and nodes_pushed the new branches."""
+        heap_high_water counts stack and heap together and nodes_pushed the new branches.
+        An incremental LP (`incremental=`) is walked under the incremental service, in the kernel as in the restatement
+        (incremental_branch_and_cut.incremental_branch_and_cut with CountingContainers, the checkpoints being the twin engine's);
+        `incremental` keeps its counters; a row that does not fit its row capacity is the capacity `row_extra`."""
         if not self.is_tree:
             raise _capi.EngineError("TableauPack.branch_and_cut: the pack was made without `integers`")
         flags = self._flags(check_cycles)
@@ -1347,6 +1441,7 @@ class TableauPack:
         tree = self.tree.copy()
         mir = self.mir.copy()
         enhanced = self.enhanced.copy()
+        incremental = self.incremental.copy()
         status = np.zeros(self.n, dtype=np.int32)
         if self._twins is not None:
             from . import branch_and_cut as bc
@@ -1354,12 +1449,23 @@ class TableauPack:
             rc, msg = _capi.JSLP_OK, ""
             for i, (t, c) in enumerate(zip(self._twins, flags)):
                 counters = None
+                inc_rec = (0,) * 8
                 try:
                     if self.integers[i].shape[0] == 0:
                         t.simplex(check_cycles=bool(c))
                         rec = (0, 0, t.last.height, 0, 0, 0)
                         mir_rec = (0, 0, 1, 0, 0) if self.is_mir[i] else (0, 0, 0, 0, 0)
                         enh_rec = (0,) * 8
+                    elif self.is_incremental[i]:  # the incremental service on the LP's twin: its checkpoints are the engine's
+                        boxes = ibc.CountingContainers(heap_cap=int(self.heap_cap[i]), cut_rows=int(self.cut_rows[i]), max_nodes=self.max_nodes)
+                        selection, rule = self.policy(i)
+                        iterations, integral = ibc.incremental_branch_and_cut(t, _TreeModel(self.integers[i], c), node_selection=selection, branching=rule,
+                                                                              max_checkpoints=int(self.max_checkpoints[i]), containers=boxes)
+                        rec = (iterations, int(integral), t.last.height, boxes.pushes, boxes.high_water, boxes.cuts_high_water)
+                        mir_rec = (0, 0, 0, 0, 0)
+                        enh_rec = boxes.record() + (0, 0)
+                        inc_rec = (t.checkpoints_used, t.incremental_nodes, max(boxes.rows_high_water - t.height0, 0),
+                                   max(boxes.checkpoint_rows_high_water - t.height0, 0), 0, 0, 0, 0)
                     elif self.is_enhanced[i]:  # the enhanced service on the LP's twin, its stack and heap sharing heap_cap
                         boxes = ibc.CountingContainers(heap_cap=int(self.heap_cap[i]), cut_rows=int(self.cut_rows[i]), max_nodes=self.max_nodes)
                         selection, rule = self.policy(i)
@@ -1383,9 +1489,10 @@ class TableauPack:
                     tree[i] = rec
                     mir[i] = mir_rec
                     enhanced[i] = enh_rec
+                    incremental[i] = inc_rec
                 except (bc.TreeCapacity, _capi.EngineError) as e:
                     status[i] = _capi.JSLP_ERR_CAPACITY if isinstance(e, bc.TreeCapacity) or "(%d)" % _capi.JSLP_ERR_CAPACITY in str(e) else _capi.JSLP_ERR_DEVICE
-                    if self.is_mir[i] and "row capacity exceeded" in str(e):  # (an engine's refusal of a round's or a cut list's rows)
+                    if (self.is_mir[i] or self.is_incremental[i]) and "row capacity exceeded" in str(e):  # (an engine's refusal of a round's or a cut list's rows)
                         e = "branch_and_cut: row_extra reached (%s)" % e
                     if rc == _capi.JSLP_OK:
                         rc, msg = int(status[i]), "pack_branch_and_cut: LP %d: %s" % (i, e)
@@ -1407,11 +1514,14 @@ class TableauPack:
                 self.lib.check(self.lib.jslpc_pack_read_mir(self._h, mir.ctypes.data), "jslpc_pack_read_mir")
             if self.has_enhanced:
                 self.lib.check(self.lib.jslpe_pack_read_enhanced(self._h, enhanced.ctypes.data), "jslpe_pack_read_enhanced")
+            if self.has_incremental:
+                self.lib.check(self.lib.jslpi_pack_read_incremental(self._h, incremental.ctypes.data), "jslpi_pack_read_incremental")
         ok = status == _capi.JSLP_OK
         self.results = out
         self.tree = tree
         self.mir = mir
         self.enhanced = enhanced
+        self.incremental = incremental
         self.status = status
         self.feasible[ok] = out["feasible"][ok] != 0
         self.bounded[ok] = out["bounded"][ok] != 0

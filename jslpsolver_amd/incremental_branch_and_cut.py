@@ -60,7 +60,8 @@ class CountingContainers:
     """The depth-first stack and the min-heap of the enhanced service, counting what a device-side tree has to hold
     (include/jslpe_tree_enhanced.h) and enforcing the same capacities in the kernel's order: per child the cut list first, then the
     entries stack and heap hold TOGETHER (heap_cap); max_nodes before a node more is evaluated.  What branch_and_cut.CountingHeap is
-    for the default service."""
+    for the default service.  Under the incremental service it also keeps the tallest tableau a node had and the tallest one a checkpoint
+    holds (include/jslpi_tree_incremental.h), as heights."""
 
     def __init__(self, heap_cap=None, cut_rows=None, max_nodes=None):
         self.heap = BranchMinHeap()
@@ -69,6 +70,7 @@ class CountingContainers:
         self.pushes = self.high_water = self.cuts_high_water = 0
         self.solutions_found = self.stack_high_water = self.moved_to_heap = 0
         self.pseudo_updates = self.scored_by_pseudocost = self.dropped_nodes = 0
+        self.rows_high_water = self.checkpoint_rows_high_water = 0
 
     def _admit(self, branch):
         if self.cut_rows is not None and len(branch.cuts) > self.cut_rows:
@@ -159,7 +161,17 @@ def incremental_branch_and_cut(tableau, model, node_selection="hybrid", branchin
     `tableau.checkpoints_used` / `tableau.incremental_nodes` report how many checkpoints were taken and how many
     nodes started from one.  incremental_rules=False: the enhanced service's variant of the two places where the
     services differ (which branching rules exist; both update pseudocosts from the node's last cut).
-    containers: a CountingContainers whose stack and heap the walk uses (None: plain ones, nothing counted, no capacity)."""
+    containers: a CountingContainers whose stack and heap the walk uses (None: plain ones, nothing counted, no capacity).
+    The checkpoints go back to the engine when the walk ends, also when a capacity (TreeCapacity, the engine's row capacity) ends it."""
+    checkpoints = []
+    try:
+        return _walk(tableau, model, node_selection, branching, max_checkpoints, incremental_rules, containers, checkpoints)
+    finally:
+        for c in checkpoints:
+            tableau.releaseCheckpoint(c)
+
+
+def _walk(tableau, model, node_selection, branching, max_checkpoints, incremental_rules, containers, checkpoints):
     cc = containers
     heap = cc.heap if cc is not None else BranchMinHeap()     # entries carry the _Branch in the `cuts` position
     stack = cc.stack if cc is not None else []
@@ -183,7 +195,6 @@ def incremental_branch_and_cut(tableau, model, node_selection="hybrid", branchin
     pseudo = _PseudoCosts()
     solutions_found = 0
     use_depth_first = node_selection in ("depth-first", "hybrid")
-    checkpoints = []
 
     root = _Branch(-math.inf, [], 0)
     if cc is not None:
@@ -225,6 +236,8 @@ def incremental_branch_and_cut(tableau, model, node_selection="hybrid", branchin
             rhs, vibr = mir_loop(tableau, model, rhs, vibr, check, max_rounds=3, need_feasible=True)
         incremental_nodes += 1 if from_checkpoint else 0
         iterations += 1
+        if cc is not None:
+            cc.rows_high_water = max(cc.rows_high_water, tableau.last.height)
         if not tableau.feasible:
             continue
         evaluation = tableau.evaluation
@@ -287,6 +300,8 @@ def incremental_branch_and_cut(tableau, model, node_selection="hybrid", branchin
                 checkpoint = tableau.createCheckpoint()
                 checkpoints.append(checkpoint)
                 checkpoint_count += 1
+                if cc is not None:
+                    cc.checkpoint_rows_high_water = max(cc.checkpoint_rows_high_water, tableau.last.height)
             cuts_high, cuts_low = [], []
             for cut in branch.cuts:
                 if cut["varIndex"] == var_index:
@@ -321,7 +336,7 @@ def incremental_branch_and_cut(tableau, model, node_selection="hybrid", branchin
     if best_branch is not None:
         _res, rhs, vibr = tableau.applyCuts(best_branch.cuts, check_cycles=check)  # :491-493, always from the root
         mir_loop(tableau, model, rhs, vibr, check, max_rounds=3, need_feasible=True)  # :228-243
-    for c in checkpoints:
-        tableau.releaseCheckpoint(c)
+        if cc is not None:
+            cc.rows_high_water = max(cc.rows_high_water, tableau.last.height)
     tableau.checkpoints_used, tableau.incremental_nodes = checkpoint_count, incremental_nodes
     return iterations, found_integral

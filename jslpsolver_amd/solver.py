@@ -9,7 +9,7 @@ import numpy as np
 
 from . import _capi
 from .branch_and_cut import branch_and_cut, js_round
-from .engine import Tableau, TableauPack, pack_fits, simplex_many, tree_cut_rows, tree_mir_rows
+from .engine import Tableau, TableauPack, checkpoint_bytes, incremental_rows, pack_fits, simplex_many, tree_cut_rows, tree_mir_rows
 from .model import Model, js_keys
 
 EPSILON = 2.220446049250313e-16
@@ -17,6 +17,10 @@ _presolve_warned = False
 # solve_packed: the heap entries and the nodes a tree in the pack may use before it is handed to Solve (include/jslpt_tree.h)
 TREE_HEAP_CAP = 128
 TREE_MAX_NODES = 1 << 16
+# solve_packed(incremental=True): the checkpoints an incremental LP may take (maxCheckpoints of the reference) and the device memory the
+# checkpoint arenas of ONE pack may take together -- a memory budget, not a tuned value: the incremental LPs beyond it get a pack of their own
+TREE_MAX_CHECKPOINTS = _capi.JSLPI_CHECKPOINTS_DEFAULT
+PACK_CHECKPOINT_BYTES = 4 << 30
 
 
 def _round_value(v, rounding_coeff):
@@ -74,6 +78,9 @@ class _PackedLp:
         self.evaluation = float(pack.evaluation[i])
         self.feasible = bool(pack.feasible[i])
         self.bounded = bool(pack.bounded[i])
+        # (what a full result reports as `checkpoints` / `incrementalNodes`: an incremental LP's, 0 for every other)
+        self.checkpoints_used = int(pack.incremental[i]["checkpoints_used"])
+        self.incremental_nodes = int(pack.incremental[i]["incremental_nodes"])
 
     def read_rhs(self):
         return self._pack.read_rhs(self._i)
@@ -101,7 +108,16 @@ def _enhanced_tree_in_scope(m):
                                                                        or m.keep_solutions)
 
 
-def solve_packed(models, precision=None, lib=None, device=0):
+def _incremental_tree_in_scope(m):
+    """whether the INCREMENTAL service alone decides this model's result (main.ts:62-72: options.useIncremental), with nothing that needs
+    the host or a clock and without its MIR loop (include/jslpi_tree_incremental.h)"""
+    o = m.options
+    if (o.get("nodeSelection") or "hybrid") not in _capi.ENH_NODE_SELECTION or (o.get("branching") or "pseudocost") not in _capi.ENH_BRANCHING:
+        return False  # (a name the service does not know: Solve walks it as the reference does)
+    return o.get("useIncremental") is True and not (m.useMIRCuts or m.tolerance or m.timeout or m.keep_solutions)
+
+
+def solve_packed(models, precision=None, lib=None, device=0, incremental=False):
     """[Solve(m, precision, lib=lib, device=device) for m in models], in order, for the workload of many SMALL models.  Every model
     whose tableau -- with its optional objectives, one row per soft constraint priority, when it has any (include/jslps_soft.h) -- fits the
     pack's LDS limit goes through an engine.TableauPack -- one arena, one upload, one launch per kernel build (64 or 256 threads, each with
@@ -117,13 +133,21 @@ def solve_packed(models, precision=None, lib=None, device=0):
       * with integer variables and options.nodeSelection and/or options.branching -- the enhanced service -- without useIncremental,
         useMIRCuts, tolerance, timeout, keep_solutions and optional objectives (include/jslpe_tree_enhanced.h), as an enhanced LP of
         that same pack, under the cut-row rule of the default service; its depth-first stack and its heap share the heap entries.
+      * incremental=True (opt-in): with integer variables and options.useIncremental -- the incremental service -- without useMIRCuts,
+        tolerance, timeout, keep_solutions and optional objectives (include/jslpi_tree_incremental.h), as an incremental LP of that same
+        pack, when row_extra = min(2 per integer variable + 256, the most rows that fit) >= 1, with cut_rows = min(2 per integer
+        variable, row_extra) (engine.incremental_rows) and 50 checkpoints.  Its further capacity is the row capacity height +
+        row_extra, which a chain of checkpoints fills one row per level.  The checkpoint arenas of one pack stay within
+        PACK_CHECKPOINT_BYTES: the incremental LPs beyond that go into a following pack.  Without the keyword such a model goes through
+        Solve.
     Every other model goes through Solve as it is.  A model Solve rejects raises the same exception before anything is solved."""
     lib = lib if lib is not None else _capi.load_hip()
     models = list(models)
     parsed = [_parse(model, precision, 4) for model in models]
     packed = []  # positions of the models that go into the pack of plain LPs
     trees = []   # (position, cut rows, row_extra or -1) of the models whose tree goes into the pack with trees (row_extra >= 0: a MIR LP)
-    policies = {}  # position -> (options.nodeSelection or None, options.branching or None) of the enhanced LPs among them
+    policies = {}  # position -> (options.nodeSelection or None, options.branching or None) of the enhanced and the incremental LPs among them
+    inc = set()    # positions of the incremental LPs among them (their row_extra is their row capacity: no MIR LPs)
     optional = [None] * len(models)  # per model its optional objectives (None: none)
     for k, (m, matrix, _, _) in enumerate(parsed):
         _priorities, optional_rows = m.optional_objectives()
@@ -148,6 +172,12 @@ def solve_packed(models, precision=None, lib=None, device=0):
             if cut_rows >= 1:
                 trees.append((k, cut_rows, -1))
                 policies[k] = (m.options.get("nodeSelection") or None, m.options.get("branching") or None)
+        elif incremental and n_opt == 0 and _incremental_tree_in_scope(m):
+            row_extra, cut_rows = incremental_rows(matrix.shape[0], matrix.shape[1], n_int, lib=lib)
+            if row_extra >= 1:
+                trees.append((k, cut_rows, row_extra))
+                inc.add(k)
+                policies[k] = (m.options.get("nodeSelection") or None, m.options.get("branching") or None)
     results = [None] * len(models)
     if packed:
         pack = TableauPack([(parsed[k][1], parsed[k][2], parsed[k][3], parsed[k][0].unrestricted) for k in packed],
@@ -160,27 +190,50 @@ def solve_packed(models, precision=None, lib=None, device=0):
         finally:
             pack.close()
     # (a pack holds MIR LPs or LPs with optional objectives, never both: when both kinds are there, the MIR LPs get a pack of their own)
-    mir_trees = [t for t in trees if t[2] >= 0]
+    mir_trees = [t for t in trees if t[2] >= 0 and t[0] not in inc]
     if mir_trees and any(optional[k] is not None for k, _, _ in trees):
-        trees = [t for t in trees if t[2] < 0]
+        trees = [t for t in trees if t[2] < 0 or t[0] in inc]
         _solve_tree_pack(mir_trees, parsed, optional, lib, device, results, policies)
-    _solve_tree_pack(trees, parsed, optional, lib, device, results, policies)
+    for chunk in _within_checkpoint_budget(trees, inc, parsed, lib):
+        _solve_tree_pack(chunk, parsed, optional, lib, device, results, policies, inc)
     for k, model in enumerate(models):
         if results[k] is None:
             results[k] = Solve(model, precision, lib=lib, device=device)
     return results
 
 
-def _solve_tree_pack(trees, parsed, optional, lib, device, results, policies):
+def _within_checkpoint_budget(trees, inc, parsed, lib):
+    """`trees` in order, cut into consecutive packs whose checkpoint arenas -- TREE_MAX_CHECKPOINTS slots per incremental LP -- stay within
+    PACK_CHECKPOINT_BYTES each (one pack when there is no incremental LP)"""
+    chunks, used = [[]], 0
+    for entry in trees:
+        k, _, row_extra = entry
+        need = 0
+        if k in inc:
+            h, w = parsed[k][1].shape
+            slot = lib.jslpi_checkpoint_bytes(h, w, h + row_extra) if getattr(lib, "has_tree_inc", False) else checkpoint_bytes(h, w, h + row_extra)
+            need = TREE_MAX_CHECKPOINTS * int(slot)
+        if chunks[-1] and used + need > PACK_CHECKPOINT_BYTES:
+            chunks.append([])
+            used = 0
+        chunks[-1].append(entry)
+        used += need
+    return [c for c in chunks if c]
+
+
+def _solve_tree_pack(trees, parsed, optional, lib, device, results, policies, inc=frozenset()):
     """solve_packed's pack with trees: results[k] for every model of `trees` whose LP reached no capacity (the others stay None: Solve)"""
     if trees:
-        with_mir = any(e >= 0 for _, _, e in trees)
+        with_mir = any(e >= 0 and k not in inc for k, _, e in trees)
+        with_inc = any(k in inc for k, _, _ in trees)
         pack = TableauPack([(parsed[k][1], parsed[k][2], parsed[k][3], parsed[k][0].unrestricted) for k, _, _ in trees],
                            precision=[parsed[k][0].precision for k, _, _ in trees], lib=lib, device=device,
                            integers=[[v["index"] for v in parsed[k][0].integerVariables] for k, _, _ in trees], cut_rows=[c for _, c, _ in trees],
                            heap_cap=TREE_HEAP_CAP, max_nodes=TREE_MAX_NODES,
                            optional_objectives=None if with_mir else [optional[k] for k, _, _ in trees],
-                           mir=[e >= 0 for _, _, e in trees] if with_mir else None, row_extra=[e for _, _, e in trees] if with_mir else None,
+                           mir=[e >= 0 and k not in inc for k, _, e in trees] if with_mir else None,
+                           row_extra=[e for _, _, e in trees] if with_mir or with_inc else None,
+                           incremental=[k in inc for k, _, _ in trees] if with_inc else None, max_checkpoints=TREE_MAX_CHECKPOINTS,
                            node_selection=[policies.get(k, (None, None))[0] for k, _, _ in trees],
                            branching=[policies.get(k, (None, None))[1] for k, _, _ in trees])
         try:

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """solve_packed on n small MILPs, on this tree and on another checkout of the project (the parent commit), in ONE session.
-  python tools/tree_packed_times.py [--parent DIR] [--ns 1,8,64,512,4096] [--reps 3] [--rounds 3] [--soft milps|lps] [--mir] [--enh] [--parent-twice] [--out profiles/packed_tree_times.md]
+  python tools/tree_packed_times.py [--parent DIR] [--ns 1,8,64,512,4096] [--reps 3] [--rounds 3] [--soft milps|lps] [--mir] [--enh] [--inc] [--parent-twice] [--out profiles/packed_tree_times.md]
 Workload: the reference's default-policy fuzz MILPs that need no presolve pre-pass (tests/golden/fuzz_services.jsonl.gz), round robin up
 to n models.  On this tree solve_packed walks every tree on the device, one launch for the whole batch (include/jslpt_tree.h); on a tree
 without the extension (--parent: a built checkout of the parent commit) the same call walks each tree on the host through Solve.
@@ -18,6 +18,10 @@ in the MIR builds of the tree kernel; on one without, solve_packed sends every o
 --enh: the workload is the reference's recorded runs under the ENHANCED service (the same file: {"nodeSelection": "depth-first"},
 {"branching": "strong"}, {"nodeSelection": "best-first", "branching": "most-fractional"}), the three policies interleaved.  On a tree with
 include/jslpe_tree_enhanced.h they run in the ENH builds of the tree kernel; on one without, solve_packed sends every one of them through Solve.
+--inc: the workload is the reference's recorded runs under the INCREMENTAL service (the same file: {"useIncremental": true}), and the call is
+solve_packed(models, incremental=True).  On a tree with include/jslpi_tree_incremental.h they run in the INC builds of the tree kernel, parent
+checkpoints on the device; on one whose solve_packed has no such keyword every one of them goes through Solve.  The table then also reports
+the share of evaluated nodes that started from a checkpoint (incremental_nodes / iterations over the workload's packs).
 --parent-twice: the parent checkout is measured as two entries of the alternation: the ratio of the second to the first is the run-to-run
 spread of this tool on one and the same tree."""
 import argparse
@@ -36,10 +40,10 @@ HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENH_OPTIONS = [{"nodeSelection": "depth-first"}, {"branching": "strong"}, {"branching": "most-fractional", "nodeSelection": "best-first"}]
 
 
-def cases(root, soft=None, mir=False, enh=False):
+def cases(root, soft=None, mir=False, enh=False, inc=False):
     with gzip.open(os.path.join(root, "tests", "golden", "fuzz_soft.jsonl.gz" if soft else "fuzz_services.jsonl.gz"), "rt") as fh:
         cs = [json.loads(line) for line in fh if line.startswith("{")]
-    options = {"useMIRCuts": True} if mir else None
+    options = {"useMIRCuts": True} if mir else {"useIncremental": True} if inc else None
     if enh:  # (model after model, each under its three policies)
         cs = sorted((c for c in cs if c["model"].get("options") in ENH_OPTIONS and c["fixed"] == 0 and not c["infeasPre"]),
                     key=lambda c: (c["gen"], c["seed"], ENH_OPTIONS.index(c["model"]["options"])))
@@ -65,10 +69,25 @@ def worker(a):
     import numpy as np
     import golden_util as G
     from jslpsolver_amd import _capi
-    from jslpsolver_amd.solver import solve_packed
+    from jslpsolver_amd import solver
     warnings.simplefilter("ignore")
     lib = _capi.Library(os.path.join(a.root, a.lib)) if a.lib else _capi.load_hip()
-    cs = cases(a.root, a.soft, a.mir, a.enh)
+    cs = cases(a.root, a.soft, a.mir, a.enh, a.inc)
+    # --inc: the keyword, on a tree whose solve_packed has it (the parent's sends these models through Solve whatever it is called with)
+    import inspect
+    with_keyword = a.inc and "incremental" in inspect.signature(solver.solve_packed).parameters
+    solve_packed = (lambda models, lib: solver.solve_packed(models, lib=lib, incremental=True)) if with_keyword else solver.solve_packed
+    seen = []  # (--inc) every pack the warm-up calls make: (nodes from a checkpoint, nodes) of its incremental LPs
+    if with_keyword:
+        plain = solver.TableauPack
+
+        class Spy(plain):
+            def branch_and_cut(self, check_cycles=True):
+                try:
+                    return plain.branch_and_cut(self, check_cycles=check_cycles)
+                finally:
+                    mine = self.is_incremental & (self.status == 0)
+                    seen.append((int(self.incremental["incremental_nodes"][mine].sum()), int(self.tree["iterations"][mine].sum())))
 
     def verify(results, n):
         for k in range(n):
@@ -80,13 +99,19 @@ def worker(a):
 
     for n in [int(x) for x in a.ns.split(",")]:
         models = [cs[k % len(cs)]["model"] for k in range(n)]
+        if with_keyword:
+            del seen[:]
+            solver.TableauPack = Spy
         verify(solve_packed(models, lib=lib), n)  # warm-up: code objects, pooled streams, the allocator
+        if with_keyword:
+            solver.TableauPack = plain
         for _ in range(a.reps):
             t0 = time.perf_counter()
             results = solve_packed(models, lib=lib)
             dt = time.perf_counter() - t0
             verify(results, n)
-            print(json.dumps({"n": n, "wall_ms": 1e3 * dt, "device_tree": bool(getattr(lib, "has_tree_enh" if a.enh else "has_tree_mir" if a.mir else "has_soft" if a.soft else "has_tree", False))}), flush=True)
+            print(json.dumps({"n": n, "wall_ms": 1e3 * dt, "from_checkpoint": sum(x for x, _ in seen), "nodes": sum(y for _, y in seen),
+                              "device_tree": with_keyword and bool(getattr(lib, "has_tree_inc", False)) if a.inc else bool(getattr(lib, "has_tree_enh" if a.enh else "has_tree_mir" if a.mir else "has_soft" if a.soft else "has_tree", False))}), flush=True)
 
 
 def main():
@@ -99,14 +124,15 @@ def main():
     ap.add_argument("--soft", default=None, choices=["milps", "lps"], help="the recorded soft-constraint runs: those with / without integer variables")
     ap.add_argument("--mir", action="store_true", help="every fuzz model with options.useMIRCuts (the reference's recorded runs with that option)")
     ap.add_argument("--enh", action="store_true", help="the reference's recorded runs under the enhanced service (nodeSelection / branching), three policies")
+    ap.add_argument("--inc", action="store_true", help="the reference's recorded runs under the incremental service (useIncremental), solve_packed(..., incremental=True)")
     ap.add_argument("--parent-twice", action="store_true", help="measure the parent checkout as two entries: the tool's spread on one tree")
     ap.add_argument("--worker", action="store_true")
     ap.add_argument("--root", default=HERE)
     ap.add_argument("--lib", default=None, help="engine library, relative to each checkout (default: the HIP product library); "
                     "oracle/libjslp_oracle.so rehearses the tool without a GPU -- its times say nothing")
     a = ap.parse_args()
-    if sum(map(bool, (a.mir, a.soft, a.enh))) > 1:
-        ap.error("--mir, --soft and --enh are three workloads")
+    if sum(map(bool, (a.mir, a.soft, a.enh, a.inc))) > 1:
+        ap.error("--mir, --soft, --enh and --inc are four workloads")
     if a.worker:
         return worker(a)
     trees = [("this commit", HERE)] + ([("parent commit", os.path.abspath(a.parent))] if a.parent else [])
@@ -114,10 +140,11 @@ def main():
         trees.append(("parent commit, again", os.path.abspath(a.parent)))
     times = {name: {} for name, _ in trees}
     flags = {}
+    shares = {}  # (--inc) n -> (nodes that started from a checkpoint, nodes evaluated) on this tree
     for _ in range(a.rounds):
         for name, root in trees:  # (the two alternate, round by round)
             out = subprocess.run([sys.executable, os.path.abspath(__file__), "--worker", "--root", root, "--ns", a.ns, "--reps", str(a.reps)] + (["--lib", a.lib] if a.lib else []) +
-                                 (["--soft", a.soft] if a.soft else []) + (["--mir"] if a.mir else []) + (["--enh"] if a.enh else []),
+                                 (["--soft", a.soft] if a.soft else []) + (["--mir"] if a.mir else []) + (["--enh"] if a.enh else []) + (["--inc"] if a.inc else []),
                                  check=True, capture_output=True, text=True, timeout=900).stdout
             print("round done: %s" % name, file=sys.stderr, flush=True)
             for line in out.splitlines():
@@ -125,17 +152,22 @@ def main():
                     r = json.loads(line)
                     times[name].setdefault(r["n"], []).append(r["wall_ms"])
                     flags[name] = r["device_tree"]
-    n_models = len(cases(HERE, a.soft, a.mir, a.enh))
+                    if r.get("nodes"):
+                        shares[r["n"]] = (r["from_checkpoint"], r["nodes"])
+    n_models = len(cases(HERE, a.soft, a.mir, a.enh, a.inc))
     what = {None: "default-policy fuzz MILPs", "milps": "recorded soft-constraint MILPs", "lps": "recorded soft-constraint LPs"}[a.soft]
     if a.mir:
         what = "fuzz MILPs with `options.useMIRCuts`"
     if a.enh:
         what = "fuzz MILPs under the enhanced service (three policies)"
-    lines = ["# `solve_packed` on small MILPs with `nodeSelection` / `branching`: the enhanced service's tree in the tree kernel against one engine per model (MI355X)" if a.enh else
+    if a.inc:
+        what = "fuzz MILPs with `options.useIncremental`"
+    lines = ["# `solve_packed(..., incremental=True)` on small MILPs with `useIncremental`: the incremental service's tree and its checkpoints in the tree kernel against one engine per model (MI355X)" if a.inc else
+             "# `solve_packed` on small MILPs with `nodeSelection` / `branching`: the enhanced service's tree in the tree kernel against one engine per model (MI355X)" if a.enh else
              "# `solve_packed` on small MILPs with MIR cuts: every node's MIR loop in the tree kernel against one engine per model (MI355X)" if a.mir else
              "# `solve_packed` on small MILPs: trees walked on the device against trees walked on the host (MI355X)" if not a.soft else
              "# `solve_packed` on the %s: the pack's OPT builds against one engine per model (MI355X)" % what, "",
-             "`python tools/tree_packed_times.py --parent <checkout of the parent commit>%s --out %s`: one session, one " % ((" --mir" if a.mir else " --enh" if a.enh else "") + (" --parent-twice" if a.parent_twice else ""), "profiles/" + os.path.basename(a.out or "packed_tree_times.md")) +
+             "`python tools/tree_packed_times.py --parent <checkout of the parent commit>%s --out %s`: one session, one " % ((" --mir" if a.mir else " --enh" if a.enh else " --inc" if a.inc else "") + (" --parent-twice" if a.parent_twice else ""), "profiles/" + os.path.basename(a.out or "packed_tree_times.md")) +
              "device, %d rounds alternating between the two checkouts, each in a process of its own; per round one warm-up call and %d timed "
              "calls per n; wall time of `solve_packed(models)` on n models taken round robin from the %d %s; every result "
              "of every call verified against the reference's recorded result before its time was kept." % (a.rounds, a.reps, n_models, what), "",
@@ -154,6 +186,9 @@ def main():
                 row.append("%.2fx" % (best["parent commit, again"] / best["parent commit"]))
         lines.append("| " + " | ".join(row) + " |")
     lines += ["", "- %s: " % ("in the pack" if a.soft else "device-side trees") + ", ".join("%s: %s" % (name, "yes" if flags.get(name) else "no (each tree through `Solve`)") for name, _ in trees) + "."]
+    if shares:
+        lines.append("- nodes that started from a checkpoint on this commit (`incremental_nodes / iterations`): " +
+                     ", ".join("n = %d: %d of %d (%.1f %%)" % (n, x, y, 100.0 * x / y) for n, (x, y) in sorted(shares.items())) + ".")
     text = "\n".join(lines) + "\n"
     print(text)
     if a.out:
