@@ -3434,30 +3434,58 @@ extern "C" int jslpf_simplex_f32_sweep(jslp_engine* e, const double* precisions,
 // A pack call holds no jslp_engine and takes no g_many_mu.  The kernels live in jslp_tu_packed.hip (jslp_packed.hip.h).
 #include "jslp_packed.hip.h"
 #include "jslp_tree.hip.h"  // (the layout of a pack with cut rows and a heap per LP, include/jslpt_tree.h)
+// The units that hold the builds of the pack kernels: each launches the build (a.tree, threads, a.build) names, or answers -1 for one that is
+// not its own (pack_dispatch, jslp_tree.hip.h).  The product has four (jslp_tu_packed.hip, jslp_tu_tree_mir.hip, _enh, _inc); a single-unit
+// build has this file, the kernels at its end.
+typedef int (*PackUnit)(int threads, unsigned grid, size_t lds, const void* args, void* stream);
 #ifdef JSLP_SPLIT_TU
 extern "C" __attribute__((visibility("hidden"))) int jslpp_packed_launch_tu(int threads, unsigned grid, size_t lds, const void* args, void* stream);
 extern "C" __attribute__((visibility("hidden"))) int jslpc_tree_mir_launch_tu(int threads, unsigned grid, size_t lds, const void* args, void* stream);
 extern "C" __attribute__((visibility("hidden"))) int jslpe_tree_enh_launch_tu(int threads, unsigned grid, size_t lds, const void* args, void* stream);
 extern "C" __attribute__((visibility("hidden"))) int jslpi_tree_inc_launch_tu(int threads, unsigned grid, size_t lds, const void* args, void* stream);
-static int packed_launch(int threads, unsigned grid, size_t lds, const PackLaunch& a, hipStream_t s) {
-    if (a.kind == 1 && a.inc) return jslpi_tree_inc_launch_tu(threads, grid, lds, &a, s);  // (the INC builds of k_tree_packed: jslp_tu_tree_inc.hip)
-    if (a.kind == 1 && a.enh) return jslpe_tree_enh_launch_tu(threads, grid, lds, &a, s);  // (the ENH builds of k_tree_packed: jslp_tu_tree_enh.hip)
-    if (a.kind == 1 && a.mir) return jslpc_tree_mir_launch_tu(threads, grid, lds, &a, s);  // (the MIR builds of k_tree_packed: jslp_tu_tree_mir.hip)
-    return jslpp_packed_launch_tu(threads, grid, lds, &a, s);
-}
+static constexpr PackUnit PACK_UNITS[] = {jslpp_packed_launch_tu, jslpc_tree_mir_launch_tu, jslpe_tree_enh_launch_tu, jslpi_tree_inc_launch_tu};
 #else
-static int packed_launch_impl(int threads, unsigned grid, size_t lds, const void* bytes, hipStream_t s);  // (jslp_packed.hip.h, at the end of this file)
-static int tree_launch_impl(int threads, unsigned grid, size_t lds, const void* bytes, hipStream_t s);    // (jslp_tree.hip.h, there too)
-static int tree_mir_launch_impl(int threads, unsigned grid, size_t lds, const void* bytes, hipStream_t s);  // (its MIR builds)
-static int tree_enh_launch_impl(int threads, unsigned grid, size_t lds, const void* bytes, hipStream_t s);  // (its ENH builds)
-static int tree_inc_launch_impl(int threads, unsigned grid, size_t lds, const void* bytes, hipStream_t s);  // (its INC builds)
-static int packed_launch(int threads, unsigned grid, size_t lds, const PackLaunch& a, hipStream_t s) {
-    if (a.kind == 1 && a.inc) return tree_inc_launch_impl(threads, grid, lds, &a, s);
-    if (a.kind == 1 && a.enh) return tree_enh_launch_impl(threads, grid, lds, &a, s);
-    if (a.kind == 1 && a.mir) return tree_mir_launch_impl(threads, grid, lds, &a, s);
-    return a.kind == 1 ? tree_launch_impl(threads, grid, lds, &a, s) : packed_launch_impl(threads, grid, lds, &a, s);
-}
+static int pack_dispatch(int threads, unsigned grid, size_t lds, const void* bytes, void* stream);  // (jslp_tree.hip.h, at the end of this file)
+static constexpr PackUnit PACK_UNITS[] = {pack_dispatch};
 #endif
+static int packed_launch(int threads, unsigned grid, size_t lds, const PackLaunch& a, hipStream_t s) {
+    for (PackUnit unit : PACK_UNITS) {
+        const int le = unit(threads, grid, lds, &a, s);
+        if (le != -1) return le;
+    }
+    return -1;
+}
+
+// THE launch groups of a pack, in launch order: the LPs of one kind that run with one thread count, and what the launch line says behind the
+// thread count.  pack_init sorts the LPs into them, pack_run launches them.  (A plain simplex has the plain and the OPT build only: it runs a
+// group of MIR, enhanced or incremental LPs in the plain build of the group's thread count, and says so.)
+struct PackGroup { PackKind kind; int threads; const char* suffix; };
+static constexpr PackGroup PACK_GROUPS[] = {{PACK_PLAIN, 64, ""},      {PACK_PLAIN, 256, ""},      {PACK_OPT, 64, ",opt 1"}, {PACK_OPT, 256, ",opt 1"},
+                                            {PACK_MIR, 64, ",mir 1"},  {PACK_MIR, 256, ",mir 1"},  {PACK_ENH, 64, ",enh 1"}, {PACK_ENH, 256, ",enh 1"},
+                                            {PACK_INC, 64, ",inc 1"},  {PACK_INC, 256, ",inc 1"}};
+// The result block [states | RHS columns | row maps | (a TreeRec per LP | (a TreeMirRec per LP) | (a TreeEnhRec per LP, an incremental pack's with
+// the LP's TreeIncRec behind it)) | optional rows]: the byte offset of every piece, each at a 256-byte boundary, computed ONCE at create
+struct PackLayout { size_t rhs, rows, tree, mir, enh, enh_stride, opt, bytes; };
+static PackLayout pack_layout(size_t n, size_t n_rows, size_t opt_doubles, bool tree, bool has_mir, bool has_enh, bool has_inc) {
+    PackLayout l{};
+    l.rhs = (sizeof(DevState) * n + 255) & ~(size_t)255;
+    l.rows = (l.rhs + sizeof(double) * n_rows + 255) & ~(size_t)255;
+    l.tree = (l.rows + sizeof(int32_t) * n_rows + 255) & ~(size_t)255;
+    l.mir = (l.tree + sizeof(TreeRec) * n + 255) & ~(size_t)255;  // (has_mir: a TreeMirRec per LP)
+    // (has_enh: a TreeEnhRec per LP, behind the MIR records when the pack has them; has_inc: LP i's TreeIncRec follows its TreeEnhRec)
+    l.enh = ((has_mir ? l.mir + sizeof(TreeMirRec) * n : l.tree + sizeof(TreeRec) * n) + 255) & ~(size_t)255;
+    l.enh_stride = has_inc ? sizeof(TreeEnhRec) + sizeof(TreeIncRec) : sizeof(TreeEnhRec);
+    const size_t plain_bytes = has_enh ? l.enh + l.enh_stride * n
+                               : has_mir ? l.mir + sizeof(TreeMirRec) * n
+                               : tree  ? l.tree + sizeof(TreeRec) * n
+                                       : l.rows + sizeof(int32_t) * n_rows;
+    l.opt = (plain_bytes + 255) & ~(size_t)255;
+    l.bytes = opt_doubles ? l.opt + sizeof(double) * opt_doubles : plain_bytes;
+    return l;
+}
+// LP i's share of d_tree_mem, from byte `heap` on: the heap, (an enhanced LP's pseudocost table behind the heap array, (an incremental LP's
+// checkpoint arena behind the table,) where the kernel looks for them,) the cut-list pool, the free stack, best_opt
+struct TreeCarve { size_t heap, pool, free_list, best_opt, end; };
 
 struct jslpp_pack {
     int device = 0;
@@ -3471,25 +3499,18 @@ struct jslpp_pack {
     hipEvent_t ev_begin = nullptr, ev_end = nullptr;
     std::vector<int32_t> H, W;
     std::vector<int32_t> RC;        // rows LP i's image, LDS layout and result block are sized for: H[i], or H[i] + cut_rows[i] (jslpt_pack_create)
+    // every LP's ONE kind: plain; with optional objectives (include/jslps_soft.h); a MIR LP (include/jslpc_tree_mir.h: row capacity height +
+    // row_extra, a TreeMirRec in the result block); an enhanced LP (include/jslpe_tree_enhanced.h: a pseudocost table behind its heap, a
+    // TreeEnhRec in the result block); an incremental LP (include/jslpi_tree_incremental.h: an enhanced LP in everything but its kernel build,
+    // its row capacity height + row_extra, the checkpoint arena behind its pseudocost table and the TreeIncRec behind its TreeEnhRec)
+    std::vector<PackKind> kind;
     // a pack made by jslpt_pack_create: per LP a heap and a pool of cut lists (jslp_tree.hip.h); tree_ran: the arena holds saved roots
     bool tree = false, tree_ran = false;
     int32_t max_nodes = 0;
     std::vector<int32_t> cut_rows, heap_cap;
-    // a pack made by jslpc_tree_pack_create (include/jslpc_tree_mir.h): which LPs are MIR LPs (row capacity height + row_extra, a MIR build of
-    // the tree kernel, a TreeMirRec in the result block), and the status of every LP after the last tree call (jslpc_pack_read_mir)
-    bool has_mir = false;
-    std::vector<uint8_t> mir;
-    std::vector<int32_t> tree_status;
-    // a pack made by jslpe_tree_pack_create (include/jslpe_tree_enhanced.h): per LP its tree policy (0: the default service; else node selection
-    // | branching << 4: an ENH build of the tree kernel, a pseudocost table behind its heap, a TreeEnhRec in the result block)
-    bool has_enh = false;
-    std::vector<int32_t> policy;
-    // a pack made by jslpi_tree_pack_create (include/jslpi_tree_incremental.h): which LPs are INCREMENTAL LPs and their max_checkpoints.  Such an LP
-    // is an enhanced LP in everything but its kernel build (INC), its row capacity (height + row_extra), the checkpoint arena behind its
-    // pseudocost table and the TreeIncRec behind its TreeEnhRec: with has_inc the result block holds the two records side by side per LP
-    bool has_inc = false;
-    std::vector<uint8_t> inc;
-    std::vector<int32_t> max_ckpt;
+    std::vector<int32_t> tree_status;  // the status of every LP after the last tree call (jslpc_pack_read_mir and its like)
+    std::vector<int32_t> policy;       // an enhanced or incremental LP's node selection | branching << 4; 0 for every other LP
+    std::vector<int32_t> max_ckpt;     // an incremental LP's max_checkpoints; 0 for every other LP
     TreeLp* d_trees = nullptr;
     char* d_tree_mem = nullptr;
     size_t tree_mem_bytes = 0;
@@ -3501,16 +3522,14 @@ struct jslpp_pack {
     DevBuf arena;
     PinBuf h_image, h_cc;
     StagePair result;
+    PackLayout at;  // where the pieces of the result block lie
     char* d_image = nullptr;
     PackLp* d_lps = nullptr;
     int32_t *d_order = nullptr, *d_cc = nullptr;
     int2 *d_hist = nullptr, *d_trace = nullptr;
-    // the launch groups, in launch order: [0] one wave, [1] 256 threads, [2] one wave with OPT, [3] 256 threads with OPT, [4] one wave
-    // with MIR, [5] 256 threads with MIR, [6] one wave with ENH, [7] 256 threads with ENH, [8] one wave with INC, [9] 256 threads with INC
-    // (a plain simplex of a MIR, an enhanced or an incremental LP runs in the build of group & 1)
-    static constexpr int N_GROUPS = 10;
-    int32_t n_group[N_GROUPS] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    size_t lds_group[N_GROUPS] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    static constexpr int N_GROUPS = (int)(sizeof PACK_GROUPS / sizeof PACK_GROUPS[0]);
+    int32_t n_group[N_GROUPS] = {};  // LPs per launch group (d_order holds them group after group), and the largest LDS image of each
+    size_t lds_group[N_GROUPS] = {};
     // optional objectives (include/jslps_soft.h): rows per LP, whether they were set, and where they lie in the result block (in doubles)
     std::vector<int32_t> n_opt;
     std::vector<uint8_t> opt_set;
@@ -3519,34 +3538,31 @@ struct jslpp_pack {
     int uploaded = 0;
     int32_t launches = 0;
     DevState* h_states() const { return result.h.as<DevState>(); }
-    double* h_rhs() const { return reinterpret_cast<double*>(result.h.p + res_rhs_off()); }
-    int32_t* h_rows() const { return reinterpret_cast<int32_t*>(result.h.p + res_rows_off()); }
-    size_t res_rhs_off() const { return (sizeof(DevState) * (size_t)n + 255) & ~(size_t)255; }
-    size_t res_rows_off() const { return (res_rhs_off() + sizeof(double) * (size_t)offs[n] + 255) & ~(size_t)255; }
-    size_t res_tree_off() const { return (res_rows_off() + sizeof(int32_t) * (size_t)offs[n] + 255) & ~(size_t)255; }
-    size_t res_mir_off() const { return (res_tree_off() + sizeof(TreeRec) * (size_t)n + 255) & ~(size_t)255; }  // (has_mir: a TreeMirRec per LP)
-    size_t res_enh_off() const {  // (has_enh: a TreeEnhRec per LP, behind the MIR records when the pack has them)
-        return ((has_mir ? res_mir_off() + sizeof(TreeMirRec) * (size_t)n : res_tree_off() + sizeof(TreeRec) * (size_t)n) + 255) & ~(size_t)255;
-    }
-    size_t enh_stride() const { return has_inc ? sizeof(TreeEnhRec) + sizeof(TreeIncRec) : sizeof(TreeEnhRec); }  // (has_inc: LP i's TreeIncRec follows its TreeEnhRec)
-    size_t res_plain_bytes() const {
-        if (has_enh) return res_enh_off() + enh_stride() * (size_t)n;
-        if (has_mir) return res_mir_off() + sizeof(TreeMirRec) * (size_t)n;
-        return tree ? res_tree_off() + sizeof(TreeRec) * (size_t)n : res_rows_off() + sizeof(int32_t) * (size_t)offs[n];
-    }
-    size_t res_opt_off() const { return (res_plain_bytes() + 255) & ~(size_t)255; }
-    size_t res_bytes() const { return opt_offs[n] ? res_opt_off() + sizeof(double) * (size_t)opt_offs[n] : res_plain_bytes(); }
-    TreeRec* h_tree() const { return reinterpret_cast<TreeRec*>(result.h.p + res_tree_off()); }
-    TreeMirRec* h_mir() const { return reinterpret_cast<TreeMirRec*>(result.h.p + res_mir_off()); }
-    TreeEnhRec* h_enh(size_t i) const { return reinterpret_cast<TreeEnhRec*>(result.h.p + res_enh_off() + enh_stride() * i); }
-    bool is_mir(size_t i) const { return has_mir && mir[i]; }
-    bool is_enh(size_t i) const { return has_enh && policy[i] != 0; }  // (an incremental LP is one too)
-    bool is_inc(size_t i) const { return has_inc && inc[i]; }
+    double* h_rhs() const { return reinterpret_cast<double*>(result.h.p + at.rhs); }
+    int32_t* h_rows() const { return reinterpret_cast<int32_t*>(result.h.p + at.rows); }
+    TreeRec* h_tree() const { return reinterpret_cast<TreeRec*>(result.h.p + at.tree); }
+    TreeMirRec* h_mir() const { return reinterpret_cast<TreeMirRec*>(result.h.p + at.mir); }
+    TreeEnhRec* h_enh(size_t i) const { return reinterpret_cast<TreeEnhRec*>(result.h.p + at.enh + at.enh_stride * i); }
+    bool is_mir(size_t i) const { return kind[i] == PACK_MIR; }
+    bool is_enh(size_t i) const { return kind[i] == PACK_ENH || kind[i] == PACK_INC; }  // (an incremental LP is one too)
+    bool is_inc(size_t i) const { return kind[i] == PACK_INC; }
+    int threads(size_t i) const { return (long long)RC[i] * W[i] <= PACK_CELLS_WAVE ? 64 : 256; }  // (tableau cells at the row capacity, optional rows or not)
     size_t ckpt_arena_bytes(size_t i) const { return is_inc(i) ? (size_t)tree_ckpt_bytes(RC[i], W[i]) * (size_t)max_ckpt[i] : 0; }
-    size_t tree_lp_bytes(size_t i) const {  // LP i's share of d_tree_mem: heap, (pseudocost table, (checkpoint arena,)) pool, free stack, best_opt
+    TreeCarve tree_carve(size_t i, size_t off) const {
         const size_t slots = (size_t)heap_cap[i] + 3;
-        return sizeof(TreeEntry) * (size_t)heap_cap[i] + (is_enh(i) ? (size_t)tree_pseudo_bytes(RC[i], W[i]) : 0) + ckpt_arena_bytes(i) + (size_t)tree_slot_bytes(cut_rows[i]) * slots +
-               ((sizeof(int32_t) * slots + 15) & ~(size_t)15) + ((sizeof(double) * (size_t)n_opt[i] + 15) & ~(size_t)15);
+        TreeCarve c;
+        c.heap = off;
+        off += sizeof(TreeEntry) * (size_t)heap_cap[i];
+        if (is_enh(i)) off += (size_t)tree_pseudo_bytes(RC[i], W[i]);
+        off += ckpt_arena_bytes(i);
+        c.pool = off;
+        off += (size_t)tree_slot_bytes(cut_rows[i]) * slots;
+        c.free_list = off;
+        off += (sizeof(int32_t) * slots + 15) & ~(size_t)15;
+        c.best_opt = off;
+        off += (sizeof(double) * (size_t)n_opt[i] + 15) & ~(size_t)15;
+        c.end = off;
+        return c;
     }
     size_t lds_bytes(size_t i) const { return is_mir(i) ? (size_t)tree_mir_lds_bytes(RC[i], W[i]) : (size_t)pk_lds_bytes(RC[i], W[i], n_opt[i]); }
     size_t ints_off(int32_t i) const { return sizeof(DevState) + 8 * (size_t)pk_image_doubles(RC[i], W[i], n_opt[i]); }
@@ -3600,14 +3616,13 @@ static int pack_init(jslpp_pack* p, int32_t max_pivots) {
     HIPC(p->h_image.reserve(std::max<size_t>(p->image_bytes, 256)));
     memset(p->h_image.p, 0, p->image_bytes);
     HIPC(p->h_cc.reserve(std::max<size_t>(sizeof(int32_t) * n, 256)));
-    HIPC(p->result.reserve(std::max<size_t>(p->res_bytes(), 256)));
+    HIPC(p->result.reserve(std::max<size_t>(p->at.bytes, 256)));
     std::vector<PackLp> lps(n);
     std::vector<int32_t> order(n);
     int32_t k = 0;
-    for (int g = 0; g < jslpp_pack::N_GROUPS; g++)  // the one-wave LPs first, then the 256-thread ones, then the same two with optional objectives, with MIR, with ENH, with INC, each in pack order
+    for (int g = 0; g < jslpp_pack::N_GROUPS; g++)  // group after group (PACK_GROUPS), each in pack order
         for (size_t i = 0; i < n; i++) {
-            const bool wave = (long long)p->RC[i] * p->W[i] <= PACK_CELLS_WAVE;  // (tableau cells at the row capacity, optional rows or not)
-            if ((wave ? 0 : 1) + (p->n_opt[i] > 0 ? 2 : 0) + (p->is_mir(i) ? 4 : 0) + (p->is_inc(i) ? 8 : p->is_enh(i) ? 6 : 0) != g) continue;
+            if (p->kind[i] != PACK_GROUPS[g].kind || p->threads(i) != PACK_GROUPS[g].threads) continue;
             order[k++] = (int32_t)i;
             p->n_group[g] += 1;
             p->lds_group[g] = std::max(p->lds_group[g], p->lds_bytes(i));
@@ -3629,27 +3644,22 @@ static int pack_init(jslpp_pack* p, int32_t max_pivots) {
         m.use_partial = n_columns > m.batch * 2;
         m.RC = p->RC[i];
         m.n_opt = p->n_opt[i];
-        m.opt_out = p->n_opt[i] ? reinterpret_cast<double*>(p->result.d.p + p->res_opt_off()) + p->opt_offs[i] : nullptr;
+        m.opt_out = p->n_opt[i] ? reinterpret_cast<double*>(p->result.d.p + p->at.opt) + p->opt_offs[i] : nullptr;
     }
     if (p->tree && n) {  // every LP's heap, cut-list pool and free stack, carved out of one block
         std::vector<TreeLp> trees(n);
         size_t off = 0;
         for (size_t i = 0; i < n; i++) {
             TreeLp& t = trees[i];
-            const size_t slots = (size_t)p->heap_cap[i] + 3;
-            t.heap = reinterpret_cast<TreeEntry*>(p->d_tree_mem + off);
-            off += sizeof(TreeEntry) * (size_t)p->heap_cap[i];
-            if (p->is_enh(i)) off += (size_t)tree_pseudo_bytes(p->RC[i], p->W[i]);  // (the pseudocost table: behind the heap array, where the kernel looks for it)
-            off += p->ckpt_arena_bytes(i);  // (an incremental LP's checkpoint arena: behind the table, where the kernel looks for it)
-            t.pool = p->d_tree_mem + off;
-            off += (size_t)tree_slot_bytes(p->cut_rows[i]) * slots;
-            t.free_list = reinterpret_cast<int32_t*>(p->d_tree_mem + off);
-            off += (sizeof(int32_t) * slots + 15) & ~(size_t)15;
-            t.best_opt = reinterpret_cast<double*>(p->d_tree_mem + off);
-            off += (sizeof(double) * (size_t)p->n_opt[i] + 15) & ~(size_t)15;
-            if (p->is_mir(i)) t.mir_out = reinterpret_cast<TreeMirRec*>(p->result.d.p + p->res_mir_off()) + i;  // (never with optional objectives)
+            const TreeCarve c = p->tree_carve(i, off);
+            off = c.end;
+            t.heap = reinterpret_cast<TreeEntry*>(p->d_tree_mem + c.heap);
+            t.pool = p->d_tree_mem + c.pool;
+            t.free_list = reinterpret_cast<int32_t*>(p->d_tree_mem + c.free_list);
+            t.best_opt = reinterpret_cast<double*>(p->d_tree_mem + c.best_opt);
+            if (p->is_mir(i)) t.mir_out = reinterpret_cast<TreeMirRec*>(p->result.d.p + p->at.mir) + i;  // (never with optional objectives)
             t.rcoef = js_round(1.0 / p->precision[i]);
-            if (p->is_enh(i)) t.enh_out = reinterpret_cast<TreeEnhRec*>(p->result.d.p + p->res_enh_off() + p->enh_stride() * i);  // (never with optional objectives or MIR)
+            if (p->is_enh(i)) t.enh_out = reinterpret_cast<TreeEnhRec*>(p->result.d.p + p->at.enh + p->at.enh_stride * i);  // (never with optional objectives or MIR)
             t.cut_rows = p->cut_rows[i]; t.heap_cap = p->heap_cap[i]; t.max_nodes = p->max_nodes;
             t.policy = p->is_enh(i) ? p->policy[i] | (p->is_inc(i) ? p->max_ckpt[i] << 8 : 0) : 0;
         }
@@ -3664,49 +3674,74 @@ static int pack_init(jslpp_pack* p, int32_t max_pivots) {
     return JSLP_OK;
 }
 
-// jslps_pack_create, jslps_tree_pack_create and jslpc_tree_pack_create (cut_rows / heap_cap: null for a pack without trees; n_optional: null
-// for none; row_extra: null for a pack without MIR LPs -- never with n_optional; node_selection / branching: null for a pack without
-// enhanced LPs, include/jslpe_tree_enhanced.h; incremental / max_checkpoints: null for a pack without incremental LPs,
-// include/jslpi_tree_incremental.h -- such an LP's row_extra is its row capacity and makes no MIR LP of it)
-static int pack_create(jslpp_pack** out, int device, int32_t n, const int32_t* height, const int32_t* width, const double* precision,
-                       const int32_t* cut_rows, const int32_t* heap_cap, const int32_t* n_optional, int32_t trace_cap, int32_t max_pivots,
-                       int32_t max_nodes, const int32_t* row_extra = nullptr, const int32_t* node_selection = nullptr,
-                       const int32_t* branching = nullptr, const int32_t* incremental = nullptr, const int32_t* max_checkpoints = nullptr) {
-    const bool tree = cut_rows != nullptr;
-    if (!out || n < 0 || (n > 0 && (!height || !width || !precision))) return fail(JSLP_ERR_ARG, "pack_create: bad arguments");
-    if (trace_cap < 0 || max_pivots < 0 || max_nodes < 0) return fail(JSLP_ERR_ARG, "pack_create: negative trace_cap, max_pivots or max_nodes");
+// What a create entry point asks for.  tree / mir / enh / inc say which tables the entry point takes (each then non-null unless n is 0):
+// cut_rows and heap_cap (include/jslpt_tree.h); row_extra (jslpc_tree_pack_create); node_selection and branching
+// (include/jslpe_tree_enhanced.h); incremental and max_checkpoints (include/jslpi_tree_incremental.h).  n_optional is null for no optional
+// objectives; row_extra of an entry point with enh is null for no MIR LP; an incremental LP's row_extra is its row capacity and makes no
+// MIR LP of it.
+struct PackSpec {
+    jslpp_pack** out;
+    int device;
+    int32_t n;
+    const int32_t *height, *width;
+    const double* precision;
+    int32_t trace_cap, max_pivots, max_nodes;
+    bool tree, mir, enh, inc;
+    const int32_t *cut_rows, *heap_cap, *n_optional, *row_extra, *node_selection, *branching, *incremental, *max_checkpoints;
+};
+static PackSpec pack_spec(jslpp_pack** out, int device, int32_t n, const int32_t* height, const int32_t* width, const double* precision, int32_t trace_cap,
+                          int32_t max_pivots, int32_t max_nodes) {
+    PackSpec s{};
+    s.out = out; s.device = device; s.n = n;
+    s.height = height; s.width = width; s.precision = precision;
+    s.trace_cap = trace_cap; s.max_pivots = max_pivots; s.max_nodes = max_nodes;
+    return s;
+}
+static int pack_create(const PackSpec& s) {
+    const int32_t n = s.n;
+    const bool tree = s.tree;
+    // ---- every refusal, before any HIP call: the entry point's own tables, `a MIR LP has no optional objectives`, the common arguments,
+    // then LP after LP
+    if (n > 0 && ((tree && (!s.cut_rows || !s.heap_cap)) || (s.mir && !s.row_extra) || (s.enh && (!s.node_selection || !s.branching)) ||
+                  (s.inc && (!s.incremental || !s.max_checkpoints))))
+        return fail(JSLP_ERR_ARG, "pack_create: bad arguments");
+    if (s.n_optional && s.row_extra)
+        for (int32_t i = 0; i < n; i++)
+            if (s.row_extra[i] >= 0 && s.n_optional[i] > 0 && !(s.incremental && s.incremental[i])) return pack_fail(JSLP_ERR_ARG, "pack_create", i, "a MIR LP has no optional objectives");
+    if (!s.out || n < 0 || (n > 0 && (!s.height || !s.width || !s.precision))) return fail(JSLP_ERR_ARG, "pack_create: bad arguments");
+    if (s.trace_cap < 0 || s.max_pivots < 0 || s.max_nodes < 0) return fail(JSLP_ERR_ARG, "pack_create: negative trace_cap, max_pivots or max_nodes");
     for (int32_t i = 0; i < n; i++) {
-        if (height[i] < 2 || width[i] < 2) return pack_fail(JSLP_ERR_ARG, "pack_create", i, "a tableau has at least 2 rows and 2 columns");
-        if (!(precision[i] == precision[i])) return pack_fail(JSLP_ERR_ARG, "pack_create", i, "precision is not a number");
-        if (tree && (cut_rows[i] < 0 || heap_cap[i] < 1 || heap_cap[i] > (1 << 24)))
+        if (s.height[i] < 2 || s.width[i] < 2) return pack_fail(JSLP_ERR_ARG, "pack_create", i, "a tableau has at least 2 rows and 2 columns");
+        if (!(s.precision[i] == s.precision[i])) return pack_fail(JSLP_ERR_ARG, "pack_create", i, "precision is not a number");
+        if (tree && (s.cut_rows[i] < 0 || s.heap_cap[i] < 1 || s.heap_cap[i] > (1 << 24)))
             return pack_fail(JSLP_ERR_ARG, "pack_create", i, "cut_rows is at least 0 and heap_cap between 1 and 2^24");
-        if (n_optional && n_optional[i] < 0) return pack_fail(JSLP_ERR_ARG, "pack_create", i, "n_optional is at least 0");
-        if (incremental && (incremental[i] < 0 || incremental[i] > 1)) return pack_fail(JSLP_ERR_ARG, "pack_create", i, "incremental is 0 or 1");
-        const bool inc = incremental && incremental[i];
+        if (s.n_optional && s.n_optional[i] < 0) return pack_fail(JSLP_ERR_ARG, "pack_create", i, "n_optional is at least 0");
+        if (s.incremental && (s.incremental[i] < 0 || s.incremental[i] > 1)) return pack_fail(JSLP_ERR_ARG, "pack_create", i, "incremental is 0 or 1");
+        const bool inc = s.incremental && s.incremental[i];
         if (inc) {
-            if (max_checkpoints[i] < 0 || max_checkpoints[i] > JSLPI_MAX_CHECKPOINTS)
+            if (s.max_checkpoints[i] < 0 || s.max_checkpoints[i] > JSLPI_MAX_CHECKPOINTS)
                 return pack_fail(JSLP_ERR_ARG, "pack_create", i, "max_checkpoints of an incremental LP is between 0 and JSLPI_MAX_CHECKPOINTS (64)");
-            if (!row_extra || row_extra[i] < cut_rows[i])
+            if (!s.row_extra || s.row_extra[i] < s.cut_rows[i])
                 return pack_fail(JSLP_ERR_ARG, "pack_create", i, "row_extra of an incremental LP is its row capacity beyond height: at least its cut_rows");
-            if (n_optional && n_optional[i] > 0)
+            if (s.n_optional && s.n_optional[i] > 0)
                 return pack_fail(JSLP_ERR_ARG, "pack_create", i, "an incremental LP has no optional objectives (a checkpoint carries none) and no MIR cuts");
         }
-        const bool mir = !inc && row_extra && row_extra[i] >= 0;
-        if (node_selection) {
-            if (node_selection[i] < 0 || node_selection[i] > 3) return pack_fail(JSLP_ERR_ARG, "pack_create", i, "node_selection is 0 (the default service), 1 best-first, 2 depth-first or 3 hybrid");
-            if (branching[i] < 0 || branching[i] > 3) return pack_fail(JSLP_ERR_ARG, "pack_create", i, "branching is 0 (the default service), 1 most-fractional, 2 pseudocost or 3 strong");
-            if ((node_selection[i] || branching[i]) && (mir || (n_optional && n_optional[i] > 0)))
+        const bool mir = !inc && s.row_extra && s.row_extra[i] >= 0;
+        if (s.node_selection) {
+            if (s.node_selection[i] < 0 || s.node_selection[i] > 3) return pack_fail(JSLP_ERR_ARG, "pack_create", i, "node_selection is 0 (the default service), 1 best-first, 2 depth-first or 3 hybrid");
+            if (s.branching[i] < 0 || s.branching[i] > 3) return pack_fail(JSLP_ERR_ARG, "pack_create", i, "branching is 0 (the default service), 1 most-fractional, 2 pseudocost or 3 strong");
+            if ((s.node_selection[i] || s.branching[i]) && (mir || (s.n_optional && s.n_optional[i] > 0)))
                 return pack_fail(JSLP_ERR_ARG, "pack_create", i, "an enhanced LP (node_selection / branching) has neither MIR cuts (row_extra) nor optional objectives");
         }
-        if (mir && row_extra[i] < cut_rows[i])
+        if (mir && s.row_extra[i] < s.cut_rows[i])
             return pack_fail(JSLP_ERR_ARG, "pack_create", i, "row_extra of a MIR LP is at least its cut_rows (a negative one makes a plain tree LP)");
-        const long long rc = (long long)height[i] + (mir || inc ? row_extra[i] : tree ? cut_rows[i] : 0);
-        const long long no = n_optional ? n_optional[i] : 0;
+        const long long rc = (long long)s.height[i] + (mir || inc ? s.row_extra[i] : tree ? s.cut_rows[i] : 0);
+        const long long no = s.n_optional ? s.n_optional[i] : 0;
         // (cells beyond the limit first: the byte count of an absurd shape must not overflow before it is compared)
-        if (mir && ((rc + no) * width[i] > JSLPP_LDS_LIMIT / 8 || tree_mir_lds_bytes((int32_t)rc, width[i]) > (long long)WGLDS_MAX_BYTES))
+        if (mir && ((rc + no) * s.width[i] > JSLPP_LDS_LIMIT / 8 || tree_mir_lds_bytes((int32_t)rc, s.width[i]) > (long long)WGLDS_MAX_BYTES))
             return pack_fail(JSLP_ERR_UNSUPPORTED, "pack_create", i,
                              "the MIR LP's LDS image at its row capacity exceeds 64 KiB (jslpc_tree_lds_bytes): a smaller row_extra, or solve it through a jslp_engine");
-        if ((rc + no) * width[i] > JSLPP_LDS_LIMIT / 8 || pk_lds_bytes((int32_t)rc, width[i], (int32_t)no) > (long long)WGLDS_MAX_BYTES)
+        if ((rc + no) * s.width[i] > JSLPP_LDS_LIMIT / 8 || pk_lds_bytes((int32_t)rc, s.width[i], (int32_t)no) > (long long)WGLDS_MAX_BYTES)
             return pack_fail(JSLP_ERR_UNSUPPORTED, "pack_create", i,
                              inc ? "the incremental LP's LDS image at its row capacity exceeds 64 KiB (jslpi_tree_lds_bytes): a smaller row_extra, or solve it through a jslp_engine" :
                              tree ? "the tableau's LDS image at its row capacity exceeds 64 KiB (jslpt_lds_bytes): fewer cut rows, or solve it through a jslp_engine"
@@ -3715,46 +3750,36 @@ static int pack_create(jslpp_pack** out, int device, int32_t n, const int32_t* h
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
         return fail(JSLP_ERR_DEVICE, "pack_create: no HIP device visible (this engine has no CPU fallback)");
-    if (device < 0 || device >= ndev) return fail(JSLP_ERR_ARG, "pack_create: device ordinal out of range");
-    HIPC(hipSetDevice(device));
+    if (s.device < 0 || s.device >= ndev) return fail(JSLP_ERR_ARG, "pack_create: device ordinal out of range");
+    HIPC(hipSetDevice(s.device));
     jslpp_pack* p = new jslpp_pack();
-    p->device = device; p->n = n; p->trace_cap = trace_cap;
-    p->hist_cap = max_pivots > 0 ? std::min<int32_t>(max_pivots, JSLPP_HIST_CAP) : JSLPP_HIST_CAP;
-    p->H.assign(height, height + n); p->W.assign(width, width + n); p->precision.assign(precision, precision + n);
+    p->device = s.device; p->n = n; p->trace_cap = s.trace_cap;
+    p->hist_cap = s.max_pivots > 0 ? std::min<int32_t>(s.max_pivots, JSLPP_HIST_CAP) : JSLPP_HIST_CAP;
+    p->H.assign(s.height, s.height + n); p->W.assign(s.width, s.width + n); p->precision.assign(s.precision, s.precision + n);
     p->RC = p->H;
     p->tree = tree;
-    if (n_optional) p->n_opt.assign(n_optional, n_optional + n); else p->n_opt.assign((size_t)n, 0);
+    if (s.n_optional) p->n_opt.assign(s.n_optional, s.n_optional + n); else p->n_opt.assign((size_t)n, 0);
     p->opt_set.assign((size_t)n, 0);
     p->opt_offs.assign((size_t)n + 1, 0);
-    for (int32_t i = 0; i < n; i++) p->opt_offs[i + 1] = p->opt_offs[i] + (int64_t)p->n_opt[i] * width[i];
+    for (int32_t i = 0; i < n; i++) p->opt_offs[i + 1] = p->opt_offs[i] + (int64_t)p->n_opt[i] * s.width[i];
+    p->kind.resize((size_t)n);
+    for (int32_t i = 0; i < n; i++)  // (the refusals above leave an LP at most one of the four)
+        p->kind[i] = tree && s.incremental && s.incremental[i]                             ? PACK_INC
+                     : tree && s.node_selection && (s.node_selection[i] || s.branching[i]) ? PACK_ENH
+                     : tree && s.row_extra && s.row_extra[i] >= 0                          ? PACK_MIR
+                     : p->n_opt[i] > 0                                                     ? PACK_OPT
+                                                                                           : PACK_PLAIN;
     if (tree) {
-        p->cut_rows.assign(cut_rows, cut_rows + n); p->heap_cap.assign(heap_cap, heap_cap + n);
-        p->max_nodes = max_nodes > 0 ? max_nodes : JSLPT_MAX_NODES_DEFAULT;
-        if (row_extra) {
-            p->mir.resize((size_t)n);
-            for (int32_t i = 0; i < n; i++) p->mir[i] = row_extra[i] >= 0 && !(incremental && incremental[i]);
-            p->has_mir = true;
-        }
-        if (incremental) {
-            p->inc.resize((size_t)n);
-            p->max_ckpt.assign((size_t)n, 0);
-            for (int32_t i = 0; i < n; i++) {
-                p->inc[i] = incremental[i] != 0;
-                if (p->inc[i]) p->max_ckpt[i] = max_checkpoints[i];
-            }
-            p->has_inc = true;
-        }
-        if (node_selection) {  // an LP with exactly one of the two set gets the other's default, hybrid / pseudocost (main.ts:76-77)
-            p->policy.resize((size_t)n);
-            for (int32_t i = 0; i < n; i++)
-                p->policy[i] = (node_selection[i] || branching[i] || p->is_inc((size_t)i)) ? (node_selection[i] ? node_selection[i] : (int32_t)ENH_HYBRID) |
-                                                                         (branching[i] ? branching[i] : (int32_t)ENH_PSEUDOCOST) << 4
-                                                                   : 0;
-            p->has_enh = true;
-        }
+        p->cut_rows.assign(s.cut_rows, s.cut_rows + n); p->heap_cap.assign(s.heap_cap, s.heap_cap + n);
+        p->max_nodes = s.max_nodes > 0 ? s.max_nodes : JSLPT_MAX_NODES_DEFAULT;
+        p->policy.assign((size_t)n, 0);
+        p->max_ckpt.assign((size_t)n, 0);
         for (int32_t i = 0; i < n; i++) {
-            p->RC[i] = height[i] + (p->is_mir(i) || p->is_inc((size_t)i) ? row_extra[i] : cut_rows[i]);
-            p->tree_mem_bytes += p->tree_lp_bytes((size_t)i);
+            if (p->is_inc((size_t)i)) p->max_ckpt[i] = s.max_checkpoints[i];
+            if (p->is_enh((size_t)i))  // an LP with exactly one of the two set gets the other's default, hybrid / pseudocost (main.ts:76-77)
+                p->policy[i] = (s.node_selection[i] ? s.node_selection[i] : (int32_t)ENH_HYBRID) | (s.branching[i] ? s.branching[i] : (int32_t)ENH_PSEUDOCOST) << 4;
+            p->RC[i] = s.height[i] + (p->is_mir((size_t)i) || p->is_inc((size_t)i) ? s.row_extra[i] : s.cut_rows[i]);
+            p->tree_mem_bytes = p->tree_carve((size_t)i, p->tree_mem_bytes).end;
         }
     }
     p->evaluation.assign((size_t)n, 0.0);
@@ -3764,12 +3789,14 @@ static int pack_create(jslpp_pack** out, int device, int32_t n, const int32_t* h
     p->offs[0] = 0;
     for (int32_t i = 0; i < n; i++) {
         p->image_off[i] = p->image_bytes;
-        p->image_bytes += pack_image_bytes(p->RC[i], width[i], p->n_opt[i]) + (tree ? (size_t)tree_ivars_bytes(p->RC[i], width[i]) : 0);
+        p->image_bytes += pack_image_bytes(p->RC[i], s.width[i], p->n_opt[i]) + (tree ? (size_t)tree_ivars_bytes(p->RC[i], s.width[i]) : 0);
         p->offs[i + 1] = p->offs[i] + p->RC[i];
     }
-    const int rc = pack_init(p, max_pivots);
+    // (a pack whose entry point takes the table has the records, whichever LPs use them)
+    p->at = pack_layout((size_t)n, (size_t)p->offs[n], (size_t)p->opt_offs[n], tree, tree && (s.mir || s.row_extra), tree && s.enh, tree && s.inc);
+    const int rc = pack_init(p, s.max_pivots);
     if (rc) { jslpp_pack_destroy(p); return rc; }
-    *out = p;
+    *s.out = p;
     return JSLP_OK;
 }
 extern "C" int jslpp_pack_create(jslpp_pack** out, int device, int32_t n, const int32_t* height, const int32_t* width, const double* precision,
@@ -3778,7 +3805,9 @@ extern "C" int jslpp_pack_create(jslpp_pack** out, int device, int32_t n, const 
 }
 extern "C" int jslps_pack_create(jslpp_pack** out, int device, int32_t n, const int32_t* height, const int32_t* width, const double* precision,
                                  const int32_t* n_optional, int32_t trace_cap, int32_t max_pivots) {
-    return pack_create(out, device, n, height, width, precision, nullptr, nullptr, n_optional, trace_cap, max_pivots, 0);
+    PackSpec s = pack_spec(out, device, n, height, width, precision, trace_cap, max_pivots, 0);
+    s.n_optional = n_optional;
+    return pack_create(s);
 }
 extern "C" int jslpt_pack_create(jslpp_pack** out, int device, int32_t n, const int32_t* height, const int32_t* width, const double* precision,
                                  const int32_t* cut_rows, const int32_t* heap_cap, int32_t trace_cap, int32_t max_pivots, int32_t max_nodes) {
@@ -3787,31 +3816,29 @@ extern "C" int jslpt_pack_create(jslpp_pack** out, int device, int32_t n, const 
 extern "C" int jslps_tree_pack_create(jslpp_pack** out, int device, int32_t n, const int32_t* height, const int32_t* width, const double* precision,
                                       const int32_t* cut_rows, const int32_t* heap_cap, const int32_t* n_optional, int32_t trace_cap,
                                       int32_t max_pivots, int32_t max_nodes) {
-    if (n > 0 && (!cut_rows || !heap_cap)) return fail(JSLP_ERR_ARG, "pack_create: bad arguments");
-    static const int32_t none = 0;
-    return pack_create(out, device, n, height, width, precision, cut_rows ? cut_rows : &none, heap_cap ? heap_cap : &none, n_optional, trace_cap,
-                       max_pivots, max_nodes);
+    PackSpec s = pack_spec(out, device, n, height, width, precision, trace_cap, max_pivots, max_nodes);
+    s.tree = true; s.cut_rows = cut_rows; s.heap_cap = heap_cap;
+    s.n_optional = n_optional;
+    return pack_create(s);
 }
 extern "C" int jslpc_tree_pack_create(jslpp_pack** out, int device, int32_t n, const int32_t* height, const int32_t* width, const double* precision,
                                       const int32_t* cut_rows, const int32_t* heap_cap, const int32_t* row_extra, int32_t trace_cap,
                                       int32_t max_pivots, int32_t max_nodes) {
-    if (n > 0 && (!cut_rows || !heap_cap || !row_extra)) return fail(JSLP_ERR_ARG, "pack_create: bad arguments");
-    static const int32_t none = 0;
-    return pack_create(out, device, n, height, width, precision, cut_rows ? cut_rows : &none, heap_cap ? heap_cap : &none, nullptr, trace_cap,
-                       max_pivots, max_nodes, row_extra ? row_extra : &none);
+    PackSpec s = pack_spec(out, device, n, height, width, precision, trace_cap, max_pivots, max_nodes);
+    s.tree = true; s.cut_rows = cut_rows; s.heap_cap = heap_cap;
+    s.mir = true; s.row_extra = row_extra;
+    return pack_create(s);
 }
 // include/jslpe_tree_enhanced.h
 extern "C" int jslpe_tree_pack_create_mixed(jslpp_pack** out, int device, int32_t n, const int32_t* height, const int32_t* width, const double* precision,
                                             const int32_t* cut_rows, const int32_t* heap_cap, const int32_t* n_optional, const int32_t* row_extra,
                                             const int32_t* node_selection, const int32_t* branching, int32_t trace_cap, int32_t max_pivots,
                                             int32_t max_nodes) {
-    if (n > 0 && (!cut_rows || !heap_cap || !node_selection || !branching)) return fail(JSLP_ERR_ARG, "pack_create: bad arguments");
-    if (n_optional && row_extra)
-        for (int32_t i = 0; i < n; i++)
-            if (row_extra[i] >= 0 && n_optional[i] > 0) return pack_fail(JSLP_ERR_ARG, "pack_create", i, "a MIR LP has no optional objectives");
-    static const int32_t none = 0;
-    return pack_create(out, device, n, height, width, precision, cut_rows ? cut_rows : &none, heap_cap ? heap_cap : &none, n_optional, trace_cap,
-                       max_pivots, max_nodes, row_extra, node_selection ? node_selection : &none, branching ? branching : &none);
+    PackSpec s = pack_spec(out, device, n, height, width, precision, trace_cap, max_pivots, max_nodes);
+    s.tree = true; s.cut_rows = cut_rows; s.heap_cap = heap_cap;
+    s.n_optional = n_optional; s.row_extra = row_extra;
+    s.enh = true; s.node_selection = node_selection; s.branching = branching;
+    return pack_create(s);
 }
 extern "C" int jslpe_tree_pack_create(jslpp_pack** out, int device, int32_t n, const int32_t* height, const int32_t* width, const double* precision,
                                       const int32_t* cut_rows, const int32_t* heap_cap, const int32_t* node_selection, const int32_t* branching,
@@ -3824,25 +3851,28 @@ extern "C" int jslpi_tree_pack_create(jslpp_pack** out, int device, int32_t n, c
                                       const int32_t* cut_rows, const int32_t* heap_cap, const int32_t* n_optional, const int32_t* row_extra,
                                       const int32_t* node_selection, const int32_t* branching, const int32_t* incremental,
                                       const int32_t* max_checkpoints, int32_t trace_cap, int32_t max_pivots, int32_t max_nodes) {
-    if (n > 0 && (!cut_rows || !heap_cap || !node_selection || !branching || !incremental || !max_checkpoints)) return fail(JSLP_ERR_ARG, "pack_create: bad arguments");
-    if (n_optional && row_extra)
-        for (int32_t i = 0; i < n; i++)
-            if (row_extra[i] >= 0 && n_optional[i] > 0 && !incremental[i]) return pack_fail(JSLP_ERR_ARG, "pack_create", i, "a MIR LP has no optional objectives");
-    static const int32_t none = 0;
-    return pack_create(out, device, n, height, width, precision, cut_rows ? cut_rows : &none, heap_cap ? heap_cap : &none, n_optional, trace_cap,
-                       max_pivots, max_nodes, row_extra, node_selection ? node_selection : &none, branching ? branching : &none,
-                       incremental ? incremental : &none, max_checkpoints ? max_checkpoints : &none);
+    PackSpec s = pack_spec(out, device, n, height, width, precision, trace_cap, max_pivots, max_nodes);
+    s.tree = true; s.cut_rows = cut_rows; s.heap_cap = heap_cap;
+    s.n_optional = n_optional; s.row_extra = row_extra;
+    s.enh = true; s.node_selection = node_selection; s.branching = branching;
+    s.inc = true; s.incremental = incremental; s.max_checkpoints = max_checkpoints;
+    return pack_create(s);
 }
 extern "C" int64_t jslpi_tree_lds_bytes(int32_t height, int32_t width, int32_t row_capacity) { return jslpt_lds_bytes(height, width, row_capacity); }
 extern "C" int64_t jslpi_checkpoint_bytes(int32_t height, int32_t width, int32_t row_capacity) {
     if (height < 2 || width < 2 || row_capacity < height) return 0;
     return (int64_t)tree_ckpt_bytes(row_capacity, width);
 }
+// what the three record read-backs ask first (`what`: the function, as its messages name it)
+static int pack_read_check(const jslpp_pack* p, const void* out, const char* what, const char* not_a_tree_pack) {
+    if (!p || (p->n > 0 && !out)) return fail(JSLP_ERR_ARG, "%s: bad arguments", what);
+    if (!p->tree) return fail(JSLP_ERR_STATE, "%s: %s", what, not_a_tree_pack);
+    if (!p->uploaded || !p->tree_ran) return fail(JSLP_ERR_STATE, "%s before jslpt_pack_branch_and_cut", what);
+    if ((int32_t)p->tree_status.size() != p->n) return fail(JSLP_ERR_STATE, "%s: the last jslpt_pack_branch_and_cut did not finish", what);
+    return JSLP_OK;
+}
 extern "C" int jslpi_pack_read_incremental(jslpp_pack* p, jslpi_tree_result* out) {
-    if (!p || (p->n > 0 && !out)) return fail(JSLP_ERR_ARG, "pack_read_incremental: bad arguments");
-    if (!p->tree) return fail(JSLP_ERR_STATE, "pack_read_incremental: not a pack with trees (jslpi_tree_pack_create, jslpt_pack_create)");
-    if (!p->uploaded || !p->tree_ran) return fail(JSLP_ERR_STATE, "pack_read_incremental before jslpt_pack_branch_and_cut");
-    if ((int32_t)p->tree_status.size() != p->n) return fail(JSLP_ERR_STATE, "pack_read_incremental: the last jslpt_pack_branch_and_cut did not finish");
+    JSLP_TRY(pack_read_check(p, out, "pack_read_incremental", "not a pack with trees (jslpi_tree_pack_create, jslpt_pack_create)"));
     static_assert(sizeof(jslpi_tree_result) == 32 && sizeof(TreeIncRec) == 32 && sizeof(TreeCkptHead) == 16, "jslpi_tree_result is a TreeIncRec");
     static_assert(JSLPI_MAX_CHECKPOINTS == TREE_MAX_CHECKPOINTS, "include/jslpi_tree_incremental.h and jslp_tree.hip.h agree");
     for (int32_t i = 0; i < p->n; i++) {
@@ -3853,10 +3883,7 @@ extern "C" int jslpi_pack_read_incremental(jslpp_pack* p, jslpi_tree_result* out
     return JSLP_OK;
 }
 extern "C" int jslpe_pack_read_enhanced(jslpp_pack* p, jslpe_tree_result* out) {
-    if (!p || (p->n > 0 && !out)) return fail(JSLP_ERR_ARG, "pack_read_enhanced: bad arguments");
-    if (!p->tree) return fail(JSLP_ERR_STATE, "pack_read_enhanced: not a pack with trees (jslpe_tree_pack_create, jslpt_pack_create)");
-    if (!p->uploaded || !p->tree_ran) return fail(JSLP_ERR_STATE, "pack_read_enhanced before jslpt_pack_branch_and_cut");
-    if ((int32_t)p->tree_status.size() != p->n) return fail(JSLP_ERR_STATE, "pack_read_enhanced: the last jslpt_pack_branch_and_cut did not finish");
+    JSLP_TRY(pack_read_check(p, out, "pack_read_enhanced", "not a pack with trees (jslpe_tree_pack_create, jslpt_pack_create)"));
     static_assert(sizeof(jslpe_tree_result) == 32 && sizeof(TreeEnhRec) == 32 && sizeof(TreePseudo) == 32, "jslpe_tree_result is a TreeEnhRec");
     static_assert(JSLPE_BEST_FIRST == ENH_BEST_FIRST && JSLPE_DEPTH_FIRST == ENH_DEPTH_FIRST && JSLPE_HYBRID == ENH_HYBRID && JSLPE_MOST_FRACTIONAL == ENH_MOST_FRACTIONAL &&
                       JSLPE_PSEUDOCOST == ENH_PSEUDOCOST && JSLPE_STRONG == ENH_STRONG,
@@ -3873,10 +3900,7 @@ extern "C" int64_t jslpc_tree_lds_bytes(int32_t height, int32_t width, int32_t r
     return (int64_t)tree_mir_lds_bytes(row_capacity, width);
 }
 extern "C" int jslpc_pack_read_mir(jslpp_pack* p, jslpc_mir_result* out) {
-    if (!p || (p->n > 0 && !out)) return fail(JSLP_ERR_ARG, "pack_read_mir: bad arguments");
-    if (!p->tree) return fail(JSLP_ERR_STATE, "pack_read_mir: not a pack made by jslpc_tree_pack_create or jslpt_pack_create");
-    if (!p->uploaded || !p->tree_ran) return fail(JSLP_ERR_STATE, "pack_read_mir before jslpt_pack_branch_and_cut");
-    if ((int32_t)p->tree_status.size() != p->n) return fail(JSLP_ERR_STATE, "pack_read_mir: the last jslpt_pack_branch_and_cut did not finish");
+    JSLP_TRY(pack_read_check(p, out, "pack_read_mir", "not a pack made by jslpc_tree_pack_create or jslpt_pack_create"));
     static_assert(sizeof(jslpc_mir_result) == 20 && sizeof(TreeMirRec) == 32, "jslpc_mir_result is the head of a TreeMirRec");
     static_assert(TMIR_MAX_ROUNDS == JSLPR_MAX_ROUNDS, "include/jslpr_mir.h and jslp_tree.hip.h agree");
     for (int32_t i = 0; i < p->n; i++) {
@@ -3910,7 +3934,7 @@ extern "C" int jslps_pack_get_optional_objectives(jslpp_pack* p, int32_t i, doub
     if (!p->uploaded || !p->solved) return fail(JSLP_ERR_STATE, "pack_get_optional_objectives before a solve: the result block holds no rows yet");
     if (n_out) *n_out = p->n_opt[i];
     if (rows && p->n_opt[i])
-        memcpy(rows, reinterpret_cast<const double*>(p->result.h.p + p->res_opt_off()) + p->opt_offs[i], sizeof(double) * (size_t)p->n_opt[i] * p->W[i]);
+        memcpy(rows, reinterpret_cast<const double*>(p->result.h.p + p->at.opt) + p->opt_offs[i], sizeof(double) * (size_t)p->n_opt[i] * p->W[i]);
     return JSLP_OK;
 }
 extern "C" int jslpt_pack_set_integers(jslpp_pack* p, int32_t i, const int32_t* var_indexes, int32_t n) {
@@ -4016,10 +4040,25 @@ extern "C" int jslpp_pack_upload(jslpp_pack* p) {
     return JSLP_OK;
 }
 
-extern "C" int jslpp_pack_simplex(jslpp_pack* p, const int32_t* check_cycles, jslp_simplex_result* out, int32_t* status, double* device_ms) {
-    if (!p || (p->n > 0 && !out)) return fail(JSLP_ERR_ARG, "pack_simplex: bad arguments");
-    if (!p->uploaded) return fail(JSLP_ERR_STATE, "pack_simplex before upload");
-    if (p->tree_ran) return fail(JSLP_ERR_STATE, "pack_simplex: after jslpt_pack_branch_and_cut the arena holds the saved roots; upload first");
+static int tree_error(const TreeRec& r) {
+    switch (r.err) {
+        case TREE_OK: return JSLP_OK;
+        case TREE_ERR_NODES: return fail(JSLP_ERR_CAPACITY, "branch_and_cut: max_nodes reached before the tree was done");
+        case TREE_ERR_HEAP: return fail(JSLP_ERR_CAPACITY, "branch_and_cut: heap_cap reached (the heap is full)");
+        case TREE_ERR_CUTS: return fail(JSLP_ERR_CAPACITY, "branch_and_cut: cut_rows reached (a node's cut list is longer)");
+        case TREE_ERR_BRANCH: return fail(JSLP_ERR_ARG, "branch_and_cut: a node is not integral and has no fractional variable (negative precision?)");
+        case TREE_ERR_MIR_ROWS: return fail(JSLP_ERR_CAPACITY, "branch_and_cut: row_extra reached (the rows of a MIR round or of a cut list do not fit the row capacity)");
+        case TREE_ERR_MIR_ROUNDS: return fail(JSLP_ERR_CAPACITY, "branch_and_cut: mir rounds: JSLPR_MAX_ROUNDS rounds of one node without a stop");
+        case TREE_ERR_INC_ROWS: return fail(JSLP_ERR_CAPACITY, "branch_and_cut: row_extra reached (the new cut row of a node that starts from a checkpoint does not fit the row capacity)");
+    }
+    return fail(JSLP_ERR_DEVICE, "unknown tree error code");
+}
+
+// One call on every LP of an uploaded pack -- simplex(), or with `tree` the whole branch-and-cut tree (include/jslpt_tree.h): the flags, one
+// launch per launch group that has LPs, the ONE D2H copy, then LP after LP what jslp_engine_simplex does after its solve.  An LP that failed
+// keeps its entries of out / tree_out and gets its code in `status`; the call's error names the first such LP.
+static int pack_run(jslpp_pack* p, bool tree, const int32_t* check_cycles, jslp_simplex_result* out, jslpt_tree_result* tree_out, int32_t* status,
+                    double* device_ms) {
     if (device_ms) *device_ms = 0;
     p->launches = 0;
     const int32_t n = p->n;
@@ -4027,7 +4066,9 @@ extern "C" int jslpp_pack_simplex(jslpp_pack* p, const int32_t* check_cycles, js
     HIPC(hipSetDevice(p->device));
     hipStream_t s = p->stream;
     PackLaunch a{};
+    a.tree = tree;
     a.lps = p->d_lps;
+    a.trees = tree ? p->d_trees : nullptr;
     a.cc = nullptr;
     a.cc_all = check_cycles ? (check_cycles[0] != 0) : 1;
     if (check_cycles) {  // one flag for all is an argument; a mixed list is a small copy of its own
@@ -4041,26 +4082,28 @@ extern "C" int jslpp_pack_simplex(jslpp_pack* p, const int32_t* check_cycles, js
         }
     }
     a.states = p->result.d.p;
-    a.rhs = reinterpret_cast<double*>(p->result.d.p + p->res_rhs_off());
-    a.rows = reinterpret_cast<int32_t*>(p->result.d.p + p->res_rows_off());
+    a.rhs = reinterpret_cast<double*>(p->result.d.p + p->at.rhs);
+    a.rows = reinterpret_cast<int32_t*>(p->result.d.p + p->at.rows);
+    a.tree_out = tree ? p->result.d.p + p->at.tree : nullptr;
     const bool dbg = debug_launch_on();
+    if (tree) p->tree_ran = true;
     HIPC(hipEventRecord(p->ev_begin, s));
     int32_t first = 0;
-    for (int g = 0; g < jslpp_pack::N_GROUPS; first += p->n_group[g], g++) {  // one launch per kernel build that has LPs (and one per group of MIR, enhanced or incremental LPs, in the plain build)
+    for (int g = 0; g < jslpp_pack::N_GROUPS; first += p->n_group[g], g++) {  // one launch per group that has LPs
         const int32_t cnt = p->n_group[g];
         if (!cnt) continue;
-        const int threads = (g & 1) ? 256 : 64;
+        const PackGroup& grp = PACK_GROUPS[g];
+        const bool own = tree || grp.kind == PACK_OPT;  // (k_simplex_packed: MIR, enhanced and incremental LPs in the plain build)
         const size_t lds = p->lds_group[g];
         a.order = p->d_order + first;
-        a.opt = (g >> 1) == 1;
-        (void)packed_launch(threads, (unsigned)cnt, lds, a, s);
+        a.build = own ? grp.kind : PACK_PLAIN;
+        (void)packed_launch(grp.threads, (unsigned)cnt, lds, a, s);
         HIPC(hipGetLastError());
         p->launches += 1;
-        if (dbg && a.opt) fprintf(stderr, "[jslp] launch k_simplex_packed<%d,opt 1> n %d lds %zu\n", threads, (int)cnt, lds);
-        else if (dbg) fprintf(stderr, "[jslp] launch k_simplex_packed<%d> n %d lds %zu\n", threads, (int)cnt, lds);
+        if (dbg) fprintf(stderr, "[jslp] launch %s<%d%s> n %d lds %zu\n", tree ? "k_tree_packed" : "k_simplex_packed", grp.threads, own ? grp.suffix : "", (int)cnt, lds);
     }
     HIPC(hipEventRecord(p->ev_end, s));
-    HIPC(hipMemcpyAsync(p->result.h.p, p->result.d.p, p->res_bytes(), hipMemcpyDeviceToHost, s));
+    HIPC(hipMemcpyAsync(p->result.h.p, p->result.d.p, p->at.bytes, hipMemcpyDeviceToHost, s));
     HIPC(hipStreamSynchronize(s));
     p->solved = true;
     float ms = 0;
@@ -4068,11 +4111,21 @@ extern "C" int jslpp_pack_simplex(jslpp_pack* p, const int32_t* check_cycles, js
     if (status) for (int32_t i = 0; i < n; i++) status[i] = JSLP_OK;
     int32_t first_bad = -1; int first_rc = JSLP_OK; char first_msg[sizeof g_err];
     const DevState* sts = p->h_states();
-    for (int32_t i = 0; i < n; i++) {  // what jslp_engine_simplex does after its solve, per LP
+    const TreeRec* recs = p->h_tree();  // (read with `tree` only)
+    if (tree) p->tree_status.assign((size_t)n, JSLP_OK);
+    for (int32_t i = 0; i < n; i++) {
         const DevState& st = sts[i];
         int rc = state_error(st);
+        if (!rc && tree) rc = tree_error(recs[i]);
         if (!rc) {
-            decode_state(st, p->precision[i], p->evaluation[i], &out[i], &p->evaluation[i]);
+            if (tree) {
+                const double evaluation = recs[i].evaluation;  // folded on the device, node after node (a node without an optimum keeps the one before)
+                decode_state(st, p->precision[i], evaluation, &out[i], nullptr);
+                out[i].evaluation = evaluation;
+                p->evaluation[i] = evaluation;
+            } else {
+                decode_state(st, p->precision[i], p->evaluation[i], &out[i], &p->evaluation[i]);
+            }
             if (st.cycle_phase && st.hist_n > 0) {  // the reference's [start, length] message from the LP's history (rare: one small copy)
                 std::vector<int2> h(st.hist_n);
                 if (hipMemcpy(h.data(), p->d_hist + (size_t)i * p->hist_cap, sizeof(int2) * st.hist_n, hipMemcpyDeviceToHost) != hipSuccess)
@@ -4080,17 +4133,31 @@ extern "C" int jslpp_pack_simplex(jslpp_pack* p, const int32_t* check_cycles, js
                 else
                     cycle_message(h, &out[i].cycle_start, &out[i].cycle_length);
             }
+            if (!rc && tree && tree_out) {
+                const TreeRec& r = recs[i];
+                jslpt_tree_result& o = tree_out[i];
+                o.iterations = r.iterations; o.is_integral = r.is_integral; o.final_height = r.final_height;
+                o.nodes_pushed = r.nodes_pushed; o.heap_high_water = r.heap_high_water; o.cuts_high_water = r.cuts_high_water;
+            }
         }
         if (rc) {
+            if (tree) p->tree_status[(size_t)i] = rc;
             if (status) status[i] = rc;
             if (first_bad < 0) { first_bad = i; first_rc = rc; snprintf(first_msg, sizeof first_msg, "%s", g_err); }
         }
     }
     if (first_bad >= 0) {
-        snprintf(g_err, sizeof g_err, "pack_simplex: LP %d: %s", (int)first_bad, first_msg);
+        snprintf(g_err, sizeof g_err, "%s: LP %d: %s", tree ? "pack_branch_and_cut" : "pack_simplex", (int)first_bad, first_msg);
         return first_rc;
     }
     return JSLP_OK;
+}
+
+extern "C" int jslpp_pack_simplex(jslpp_pack* p, const int32_t* check_cycles, jslp_simplex_result* out, int32_t* status, double* device_ms) {
+    if (!p || (p->n > 0 && !out)) return fail(JSLP_ERR_ARG, "pack_simplex: bad arguments");
+    if (!p->uploaded) return fail(JSLP_ERR_STATE, "pack_simplex before upload");
+    if (p->tree_ran) return fail(JSLP_ERR_STATE, "pack_simplex: after jslpt_pack_branch_and_cut the arena holds the saved roots; upload first");
+    return pack_run(p, false, check_cycles, out, nullptr, status, device_ms);
 }
 
 extern "C" int jslpp_pack_read_rhs(jslpp_pack* p, const double** rhs, const int32_t** var_index_by_row, const int64_t** offsets) {
@@ -4142,119 +4209,13 @@ extern "C" int jslpp_pack_pivot_trace(jslpp_pack* p, int32_t i, int32_t* row_col
 }
 
 // ---- the trees of a pack, each walked by its LP's workgroup (include/jslpt_tree.h) ---------------------------------------------------
-static int tree_error(const TreeRec& r) {
-    switch (r.err) {
-        case TREE_OK: return JSLP_OK;
-        case TREE_ERR_NODES: return fail(JSLP_ERR_CAPACITY, "branch_and_cut: max_nodes reached before the tree was done");
-        case TREE_ERR_HEAP: return fail(JSLP_ERR_CAPACITY, "branch_and_cut: heap_cap reached (the heap is full)");
-        case TREE_ERR_CUTS: return fail(JSLP_ERR_CAPACITY, "branch_and_cut: cut_rows reached (a node's cut list is longer)");
-        case TREE_ERR_BRANCH: return fail(JSLP_ERR_ARG, "branch_and_cut: a node is not integral and has no fractional variable (negative precision?)");
-        case TREE_ERR_MIR_ROWS: return fail(JSLP_ERR_CAPACITY, "branch_and_cut: row_extra reached (the rows of a MIR round or of a cut list do not fit the row capacity)");
-        case TREE_ERR_MIR_ROUNDS: return fail(JSLP_ERR_CAPACITY, "branch_and_cut: mir rounds: JSLPR_MAX_ROUNDS rounds of one node without a stop");
-        case TREE_ERR_INC_ROWS: return fail(JSLP_ERR_CAPACITY, "branch_and_cut: row_extra reached (the new cut row of a node that starts from a checkpoint does not fit the row capacity)");
-    }
-    return fail(JSLP_ERR_DEVICE, "unknown tree error code");
-}
-
 extern "C" int jslpt_pack_branch_and_cut(jslpp_pack* p, const int32_t* check_cycles, jslp_simplex_result* out, jslpt_tree_result* tree_out,
                                          int32_t* status, double* device_ms) {
     if (!p || (p->n > 0 && !out)) return fail(JSLP_ERR_ARG, "pack_branch_and_cut: bad arguments");
     if (!p->tree) return fail(JSLP_ERR_STATE, "pack_branch_and_cut: not a pack made by jslpt_pack_create");
     if (!p->uploaded) return fail(JSLP_ERR_STATE, "pack_branch_and_cut before upload");
     if (p->tree_ran) return fail(JSLP_ERR_STATE, "pack_branch_and_cut: the arena holds the saved roots of an earlier call; upload first");
-    if (device_ms) *device_ms = 0;
-    p->launches = 0;
-    const int32_t n = p->n;
-    if (n == 0) return JSLP_OK;
-    HIPC(hipSetDevice(p->device));
-    hipStream_t s = p->stream;
-    PackLaunch a{};
-    a.kind = 1;
-    a.lps = p->d_lps;
-    a.trees = p->d_trees;
-    a.cc = nullptr;
-    a.cc_all = check_cycles ? (check_cycles[0] != 0) : 1;
-    if (check_cycles) {
-        bool mixed = false;
-        for (int32_t i = 1; i < n && !mixed; i++) mixed = (check_cycles[i] != 0) != (a.cc_all != 0);
-        if (mixed) {
-            int32_t* h = p->h_cc.as<int32_t>();
-            for (int32_t i = 0; i < n; i++) h[i] = check_cycles[i] != 0;
-            HIPC(hipMemcpyAsync(p->d_cc, h, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, s));
-            a.cc = p->d_cc;
-        }
-    }
-    a.states = p->result.d.p;
-    a.rhs = reinterpret_cast<double*>(p->result.d.p + p->res_rhs_off());
-    a.rows = reinterpret_cast<int32_t*>(p->result.d.p + p->res_rows_off());
-    a.tree_out = p->result.d.p + p->res_tree_off();
-    const bool dbg = debug_launch_on();
-    p->tree_ran = true;
-    HIPC(hipEventRecord(p->ev_begin, s));
-    int32_t first = 0;
-    for (int g = 0; g < jslpp_pack::N_GROUPS; first += p->n_group[g], g++) {  // one launch per kernel build that has LPs
-        const int32_t cnt = p->n_group[g];
-        if (!cnt) continue;
-        const int threads = (g & 1) ? 256 : 64;
-        const size_t lds = p->lds_group[g];
-        a.order = p->d_order + first;
-        a.opt = (g >> 1) == 1;
-        a.mir = (g >> 1) == 2;
-        a.enh = (g >> 1) == 3;
-        a.inc = (g >> 1) == 4;
-        (void)packed_launch(threads, (unsigned)cnt, lds, a, s);
-        HIPC(hipGetLastError());
-        p->launches += 1;
-        if (dbg && a.inc) fprintf(stderr, "[jslp] launch k_tree_packed<%d,inc 1> n %d lds %zu\n", threads, (int)cnt, lds);
-        else if (dbg && a.enh) fprintf(stderr, "[jslp] launch k_tree_packed<%d,enh 1> n %d lds %zu\n", threads, (int)cnt, lds);
-        else if (dbg && a.mir) fprintf(stderr, "[jslp] launch k_tree_packed<%d,mir 1> n %d lds %zu\n", threads, (int)cnt, lds);
-        else if (dbg && a.opt) fprintf(stderr, "[jslp] launch k_tree_packed<%d,opt 1> n %d lds %zu\n", threads, (int)cnt, lds);
-        else if (dbg) fprintf(stderr, "[jslp] launch k_tree_packed<%d> n %d lds %zu\n", threads, (int)cnt, lds);
-    }
-    HIPC(hipEventRecord(p->ev_end, s));
-    HIPC(hipMemcpyAsync(p->result.h.p, p->result.d.p, p->res_bytes(), hipMemcpyDeviceToHost, s));
-    HIPC(hipStreamSynchronize(s));
-    p->solved = true;
-    float ms = 0;
-    if (device_ms && hipEventElapsedTime(&ms, p->ev_begin, p->ev_end) == hipSuccess) *device_ms = ms;
-    if (status) for (int32_t i = 0; i < n; i++) status[i] = JSLP_OK;
-    int32_t first_bad = -1; int first_rc = JSLP_OK; char first_msg[sizeof g_err];
-    const DevState* sts = p->h_states();
-    const TreeRec* recs = p->h_tree();
-    p->tree_status.assign((size_t)n, JSLP_OK);
-    for (int32_t i = 0; i < n; i++) {
-        const DevState& st = sts[i];
-        const TreeRec& r = recs[i];
-        int rc = state_error(st);
-        if (!rc) rc = tree_error(r);
-        if (!rc) {
-            decode_state(st, p->precision[i], r.evaluation, &out[i], nullptr);
-            out[i].evaluation = r.evaluation;  // folded on the device, node after node (a node without an optimum keeps the one before)
-            p->evaluation[i] = r.evaluation;
-            if (st.cycle_phase && st.hist_n > 0) {
-                std::vector<int2> h(st.hist_n);
-                if (hipMemcpy(h.data(), p->d_hist + (size_t)i * p->hist_cap, sizeof(int2) * st.hist_n, hipMemcpyDeviceToHost) != hipSuccess)
-                    rc = fail(JSLP_ERR_DEVICE, "cycle history read-back failed");
-                else
-                    cycle_message(h, &out[i].cycle_start, &out[i].cycle_length);
-            }
-            if (!rc && tree_out) {
-                jslpt_tree_result& o = tree_out[i];
-                o.iterations = r.iterations; o.is_integral = r.is_integral; o.final_height = r.final_height;
-                o.nodes_pushed = r.nodes_pushed; o.heap_high_water = r.heap_high_water; o.cuts_high_water = r.cuts_high_water;
-            }
-        }
-        if (rc) {
-            p->tree_status[(size_t)i] = rc;
-            if (status) status[i] = rc;
-            if (first_bad < 0) { first_bad = i; first_rc = rc; snprintf(first_msg, sizeof first_msg, "%s", g_err); }
-        }
-    }
-    if (first_bad >= 0) {
-        snprintf(g_err, sizeof g_err, "pack_branch_and_cut: LP %d: %s", (int)first_bad, first_msg);
-        return first_rc;
-    }
-    return JSLP_OK;
+    return pack_run(p, true, check_cycles, out, tree_out, status, device_ms);
 }
 
 extern "C" int jslpt_pack_read_rhs(jslpp_pack* p, const double** rhs, const int32_t** var_index_by_row, const int64_t** offsets) {
@@ -4266,8 +4227,6 @@ extern "C" int jslpt_pack_read_rhs(jslpp_pack* p, const double** rhs, const int3
 #if !defined(JSLP_SPLIT_TU)
 #include "jslp_mir_kernels.hip.h"  // single-unit build: the MIR kernels behind everything else (the product: jslp_tu_mir.hip)
 #define JSLP_PACKED_KERNELS 1
-#define JSLP_TREE_ENH_BUILDS 1
-#define JSLP_TREE_INC_BUILDS 1
 #include "jslp_packed.hip.h"       // ... and the pack's two (the product: jslp_tu_packed.hip)
-#include "jslp_tree.hip.h"         // ... with the tree kernels behind them
+#include "jslp_tree.hip.h"         // ... with the tree kernels behind them, every build (the product: jslp_tu_tree_mir.hip, _enh, _inc too)
 #endif

@@ -67,20 +67,22 @@ struct PackLp {
     int32_t n_opt;      // optional objectives (0: the LP runs in an OPT = false build)
     double* opt_out;    // this LP's n_opt x W optional rows in the result block
 };
+// The kind of an LP of a pack, which is also the build of the kernel its tree runs in: the default service (PACK_PLAIN), the same with
+// optional objectives (PACK_OPT, include/jslps_soft.h), a MIR LP (include/jslpc_tree_mir.h), an enhanced LP (include/jslpe_tree_enhanced.h),
+// an incremental LP (include/jslpi_tree_incremental.h).  k_simplex_packed has the first two builds only.
+enum PackKind : int32_t { PACK_PLAIN = 0, PACK_OPT = 1, PACK_MIR = 2, PACK_ENH = 3, PACK_INC = 4 };
 // arguments of one launch, travelling as bytes between the units (the same struct in every unit)
 struct PackLaunch {
     const PackLp* lps;
     const int32_t* order;  // blockIdx.x -> LP index (the LPs of this build)
     const int32_t* cc;     // per-LP checkForCycles, or nullptr: cc_all for every LP
-    int32_t cc_all, kind;  // kind 0: k_simplex_packed, 1: k_tree_packed (jslp_tree.hip.h)
-    int32_t opt, mir;      // opt 1: the OPT = true build (every LP of `order` has optional objectives); mir 1: the MIR = true build of
-                           // k_tree_packed (every LP of `order` is a MIR LP, include/jslpc_tree_mir.h)
-    int32_t enh, inc;      // enh 1: the ENH build of k_tree_packed (every LP of `order` is an enhanced LP, include/jslpe_tree_enhanced.h);
-                           // inc 1: its INC build (every LP of `order` is an incremental LP, include/jslpi_tree_incremental.h; enh is 0 then)
+    int32_t cc_all, tree;  // tree 0: k_simplex_packed, 1: k_tree_packed (jslp_tree.hip.h)
+    int32_t build;         // the PackKind whose build of that kernel runs: every LP of `order` is of this kind (k_simplex_packed: PACK_OPT, or
+                           // PACK_PLAIN for every other kind)
     void* states;          // result block: DevState per LP (LP order) ...
     double* rhs;           // ... the RHS columns one after the other ...
     int32_t* rows;         // ... and the row maps
-    const void* trees;     // kind 1: the TreeLp table ...
+    const void* trees;     // tree 1: the TreeLp table ...
     void* tree_out;        // ... and the TreeRec per LP
 };
 #endif  // JSLP_PACKED_LAYOUT
@@ -623,23 +625,28 @@ __global__ void __launch_bounds__(THREADS) k_simplex_packed(const PackLp* __rest
         reinterpret_cast<long long*>(out_states + idx)[tid] = reinterpret_cast<const long long*>(st)[tid];
 }
 
-#ifndef JSLP_PACKED_NO_LAUNCH  // (a unit that wants pk_simplex alone: jslp_tu_tree_mir.hip)
-// launches the build for `threads` (64 or 256); returns the hipError_t of the launch, or -1 for an unknown build.  The error is PEEKED
-// at, not taken: the caller's hipGetLastError still sees it and reports it
-static int packed_launch_impl(int threads, unsigned grid, size_t lds, const void* bytes, hipStream_t s) {
-    const PackLaunch a = *static_cast<const PackLaunch*>(bytes);
-    DevState* states = static_cast<DevState*>(a.states);
-    if (threads == 64 && !a.opt)
-        hipLaunchKernelGGL((k_simplex_packed<64, false>), dim3(grid), dim3(64), lds, s, a.lps, a.order, a.cc, a.cc_all, states, a.rhs, a.rows);
-    else if (threads == 256 && !a.opt)
-        hipLaunchKernelGGL((k_simplex_packed<256, false>), dim3(grid), dim3(256), lds, s, a.lps, a.order, a.cc, a.cc_all, states, a.rhs, a.rows);
-    else if (threads == 64)
-        hipLaunchKernelGGL((k_simplex_packed<64, true>), dim3(grid), dim3(64), lds, s, a.lps, a.order, a.cc, a.cc_all, states, a.rhs, a.rows);
-    else if (threads == 256)
-        hipLaunchKernelGGL((k_simplex_packed<256, true>), dim3(grid), dim3(256), lds, s, a.lps, a.order, a.cc, a.cc_all, states, a.rhs, a.rows);
-    else
-        return -1;
-    return (int)hipPeekAtLastError();
+// ---- which builds of the pack kernels this unit holds ------------------------------------------------------------------------------------
+// JSLP_PACK_BUILDS: a mask with bit (1 << PackKind) set for every build the unit instantiates, in plain numbers so that it also works in an #if.
+// Not given: every build (0x1f, the single-unit build).  0x03: k_simplex_packed and the plain and OPT builds of k_tree_packed
+// (jslp_tu_packed.hip); 0x04, 0x08, 0x10: the MIR, ENH, INC builds of k_tree_packed (jslp_tu_tree_mir.hip, _enh, _inc).  A launch of a build
+// that is not the unit's own instantiates nothing (pack_dispatch, jslp_tree.hip.h, then answers -1), as res_row_built does for the
+// register-resident kernel.
+#ifndef JSLP_PACK_BUILDS
+#define JSLP_PACK_BUILDS 0x1f
+#endif
+static_assert((1 << PACK_PLAIN | 1 << PACK_OPT) == 0x03 && 1 << PACK_MIR == 0x04 && 1 << PACK_ENH == 0x08 && 1 << PACK_INC == 0x10, "the units' masks name these builds");
+constexpr bool pack_build_here(int build) { return ((JSLP_PACK_BUILDS) >> build & 1) != 0; }
+
+// one build of k_simplex_packed: launches when (threads, a.build) is its own
+template <int T, int BUILD>
+static bool pk_launch(int threads, unsigned grid, size_t lds, const PackLaunch& a, hipStream_t s) {
+    if constexpr (!pack_build_here(BUILD)) {
+        return false;
+    } else {
+        if (threads != T || a.build != BUILD) return false;
+        hipLaunchKernelGGL((k_simplex_packed<T, BUILD == PACK_OPT>), dim3(grid), dim3(T), lds, s, a.lps, a.order, a.cc, a.cc_all, static_cast<DevState*>(a.states), a.rhs,
+                           a.rows);
+        return true;
+    }
 }
-#endif  // JSLP_PACKED_NO_LAUNCH
 #endif  // JSLP_PACKED_KERNELS

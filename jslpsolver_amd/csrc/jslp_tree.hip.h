@@ -840,75 +840,35 @@ __global__ void __launch_bounds__(THREADS) k_tree_packed(const PackLp* __restric
         reinterpret_cast<long long*>(out_states + idx)[tid] = reinterpret_cast<const long long*>(st)[tid];
 }
 
-// as packed_launch_impl, for the tree kernels (PackLaunch::kind == 1).  The plain and OPT builds and the MIR builds have a launch function
-// each, so that a unit can hold one set without the other (-DJSLP_TREE_NO_MIR_BUILDS: jslp_tu_packed.hip; -DJSLP_TREE_NO_PLAIN_BUILDS:
-// jslp_tu_tree_mir.hip), and so have the ENH builds (-DJSLP_TREE_ENH_BUILDS: jslp_tu_tree_enh.hip and the single-unit build)
-// and the INC builds (-DJSLP_TREE_INC_BUILDS: jslp_tu_tree_inc.hip and the single-unit build)
-#ifndef JSLP_TREE_NO_PLAIN_BUILDS
-static int tree_launch_impl(int threads, unsigned grid, size_t lds, const void* bytes, hipStream_t s) {
-    const PackLaunch a = *static_cast<const PackLaunch*>(bytes);
-    DevState* states = static_cast<DevState*>(a.states);
-    const TreeLp* trees = static_cast<const TreeLp*>(a.trees);
-    TreeRec* recs = static_cast<TreeRec*>(a.tree_out);
-    if (threads == 64 && !a.opt)
-        hipLaunchKernelGGL((k_tree_packed<64, false>), dim3(grid), dim3(64), lds, s, a.lps, trees, a.order, a.cc, a.cc_all, states, a.rhs, a.rows, recs);
-    else if (threads == 256 && !a.opt)
-        hipLaunchKernelGGL((k_tree_packed<256, false>), dim3(grid), dim3(256), lds, s, a.lps, trees, a.order, a.cc, a.cc_all, states, a.rhs, a.rows, recs);
-    else if (threads == 64)
-        hipLaunchKernelGGL((k_tree_packed<64, true>), dim3(grid), dim3(64), lds, s, a.lps, trees, a.order, a.cc, a.cc_all, states, a.rhs, a.rows, recs);
-    else if (threads == 256)
-        hipLaunchKernelGGL((k_tree_packed<256, true>), dim3(grid), dim3(256), lds, s, a.lps, trees, a.order, a.cc, a.cc_all, states, a.rhs, a.rows, recs);
-    else
-        return -1;
-    return (int)hipPeekAtLastError();
+// one build of k_tree_packed, as pk_launch (MIR, ENH and INC come without OPT; an INC build is an ENH build)
+template <int T, int BUILD>
+static bool tree_launch(int threads, unsigned grid, size_t lds, const PackLaunch& a, hipStream_t s) {
+    if constexpr (!pack_build_here(BUILD)) {
+        return false;
+    } else {
+        if (threads != T || a.build != BUILD) return false;
+        hipLaunchKernelGGL((k_tree_packed<T, BUILD == PACK_OPT, BUILD == PACK_MIR, BUILD == PACK_ENH || BUILD == PACK_INC, BUILD == PACK_INC>), dim3(grid), dim3(T), lds, s,
+                           a.lps, static_cast<const TreeLp*>(a.trees), a.order, a.cc, a.cc_all, static_cast<DevState*>(a.states), a.rhs, a.rows,
+                           static_cast<TreeRec*>(a.tree_out));
+        return true;
+    }
 }
-#endif
-#ifndef JSLP_TREE_NO_MIR_BUILDS
-// the MIR builds (PackLaunch::mir == 1; MIR with OPT is not built)
-static int tree_mir_launch_impl(int threads, unsigned grid, size_t lds, const void* bytes, hipStream_t s) {
-    const PackLaunch a = *static_cast<const PackLaunch*>(bytes);
-    DevState* states = static_cast<DevState*>(a.states);
-    const TreeLp* trees = static_cast<const TreeLp*>(a.trees);
-    TreeRec* recs = static_cast<TreeRec*>(a.tree_out);
-    if (threads == 64 && !a.opt)
-        hipLaunchKernelGGL((k_tree_packed<64, false, true>), dim3(grid), dim3(64), lds, s, a.lps, trees, a.order, a.cc, a.cc_all, states, a.rhs, a.rows, recs);
-    else if (threads == 256 && !a.opt)
-        hipLaunchKernelGGL((k_tree_packed<256, false, true>), dim3(grid), dim3(256), lds, s, a.lps, trees, a.order, a.cc, a.cc_all, states, a.rhs, a.rows, recs);
+// THE table of the pack kernels' builds: launches the one (a.tree, threads, a.build) names; returns the hipError_t of the launch, or -1: no such
+// build in this unit.  The error is PEEKED at, not taken: the caller's hipGetLastError still sees it and reports it.
+// (the rows' order is the order the compiler instantiates the kernels in, and their code can depend on it: tools/asm_digest.py)
+static int pack_dispatch(int threads, unsigned grid, size_t lds, const void* bytes, void* stream) {
+    const PackLaunch& a = *static_cast<const PackLaunch*>(bytes);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    bool hit;
+    if (!a.tree)
+        hit = pk_launch<64, PACK_PLAIN>(threads, grid, lds, a, s) || pk_launch<256, PACK_PLAIN>(threads, grid, lds, a, s) ||
+              pk_launch<64, PACK_OPT>(threads, grid, lds, a, s) || pk_launch<256, PACK_OPT>(threads, grid, lds, a, s);
     else
-        return -1;
-    return (int)hipPeekAtLastError();
+        hit = tree_launch<64, PACK_PLAIN>(threads, grid, lds, a, s) || tree_launch<256, PACK_PLAIN>(threads, grid, lds, a, s) ||
+              tree_launch<64, PACK_OPT>(threads, grid, lds, a, s) || tree_launch<256, PACK_OPT>(threads, grid, lds, a, s) ||
+              tree_launch<64, PACK_MIR>(threads, grid, lds, a, s) || tree_launch<256, PACK_MIR>(threads, grid, lds, a, s) ||
+              tree_launch<64, PACK_ENH>(threads, grid, lds, a, s) || tree_launch<256, PACK_ENH>(threads, grid, lds, a, s) ||
+              tree_launch<64, PACK_INC>(threads, grid, lds, a, s) || tree_launch<256, PACK_INC>(threads, grid, lds, a, s);
+    return hit ? (int)hipPeekAtLastError() : -1;
 }
-#endif
-#ifdef JSLP_TREE_ENH_BUILDS
-// the ENH builds (PackLaunch::enh == 1; never with opt or mir)
-static int tree_enh_launch_impl(int threads, unsigned grid, size_t lds, const void* bytes, hipStream_t s) {
-    const PackLaunch a = *static_cast<const PackLaunch*>(bytes);
-    DevState* states = static_cast<DevState*>(a.states);
-    const TreeLp* trees = static_cast<const TreeLp*>(a.trees);
-    TreeRec* recs = static_cast<TreeRec*>(a.tree_out);
-    if (threads == 64 && !a.opt && !a.mir)
-        hipLaunchKernelGGL((k_tree_packed<64, false, false, true>), dim3(grid), dim3(64), lds, s, a.lps, trees, a.order, a.cc, a.cc_all, states, a.rhs, a.rows, recs);
-    else if (threads == 256 && !a.opt && !a.mir)
-        hipLaunchKernelGGL((k_tree_packed<256, false, false, true>), dim3(grid), dim3(256), lds, s, a.lps, trees, a.order, a.cc, a.cc_all, states, a.rhs, a.rows, recs);
-    else
-        return -1;
-    return (int)hipPeekAtLastError();
-}
-#endif
-#ifdef JSLP_TREE_INC_BUILDS
-// the INC builds (PackLaunch::inc == 1; never with opt or mir)
-static int tree_inc_launch_impl(int threads, unsigned grid, size_t lds, const void* bytes, hipStream_t s) {
-    const PackLaunch a = *static_cast<const PackLaunch*>(bytes);
-    DevState* states = static_cast<DevState*>(a.states);
-    const TreeLp* trees = static_cast<const TreeLp*>(a.trees);
-    TreeRec* recs = static_cast<TreeRec*>(a.tree_out);
-    if (threads == 64 && !a.opt && !a.mir)
-        hipLaunchKernelGGL((k_tree_packed<64, false, false, true, true>), dim3(grid), dim3(64), lds, s, a.lps, trees, a.order, a.cc, a.cc_all, states, a.rhs, a.rows, recs);
-    else if (threads == 256 && !a.opt && !a.mir)
-        hipLaunchKernelGGL((k_tree_packed<256, false, false, true, true>), dim3(grid), dim3(256), lds, s, a.lps, trees, a.order, a.cc, a.cc_all, states, a.rhs, a.rows, recs);
-    else
-        return -1;
-    return (int)hipPeekAtLastError();
-}
-#endif
 #endif  // JSLP_PACKED_KERNELS

@@ -14,12 +14,11 @@
 namespace {
 #include "jslp_kernels.hip.h"
 #define JSLP_PACKED_KERNELS 1
-#define JSLP_TREE_NO_MIR_BUILDS 1  // (the MIR builds of k_tree_packed: jslp_tu_tree_mir.hip)
+#define JSLP_PACK_BUILDS 0x03  // (the MIR, ENH and INC builds of k_tree_packed: jslp_tu_tree_mir.hip, jslp_tu_tree_enh.hip, jslp_tu_tree_inc.hip)
 #include "jslp_packed.hip.h"
 #include "jslp_tree.hip.h"  // k_tree_packed (include/jslpt_tree.h): the same LDS layout, the loop as pk_simplex
 }  // namespace
 
 extern "C" __attribute__((visibility("hidden"))) int jslpp_packed_launch_tu(int threads, unsigned grid, size_t lds, const void* args, void* stream) {
-    if (static_cast<const PackLaunch*>(args)->kind == 1) return tree_launch_impl(threads, grid, lds, args, static_cast<hipStream_t>(stream));
-    return packed_launch_impl(threads, grid, lds, args, static_cast<hipStream_t>(stream));
+    return pack_dispatch(threads, grid, lds, args, stream);
 }

@@ -14,14 +14,11 @@
 namespace {
 #include "jslp_kernels.hip.h"
 #define JSLP_PACKED_KERNELS 1
-#define JSLP_PACKED_NO_LAUNCH 1      // pk_simplex alone: k_simplex_packed is jslp_tu_packed.hip's
-#define JSLP_TREE_NO_PLAIN_BUILDS 1  // ... and so are the plain and OPT builds of k_tree_packed
-#define JSLP_TREE_NO_MIR_BUILDS 1    // ... the MIR builds are jslp_tu_tree_mir.hip's, the ENH builds jslp_tu_tree_enh.hip's
-#define JSLP_TREE_INC_BUILDS 1
+#define JSLP_PACK_BUILDS 0x10  // pk_simplex alone: k_simplex_packed is jslp_tu_packed.hip's, and so are the plain and OPT builds of k_tree_packed
 #include "jslp_packed.hip.h"
 #include "jslp_tree.hip.h"
 }  // namespace
 
 extern "C" __attribute__((visibility("hidden"))) int jslpi_tree_inc_launch_tu(int threads, unsigned grid, size_t lds, const void* args, void* stream) {
-    return tree_inc_launch_impl(threads, grid, lds, args, static_cast<hipStream_t>(stream));
+    return pack_dispatch(threads, grid, lds, args, stream);
 }

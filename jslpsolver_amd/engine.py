@@ -1158,19 +1158,17 @@ class TableauPack:
             self.integers = [_capi.as_i32(list(iv)) for iv in integers]
             if len(self.integers) != n:
                 raise ValueError("TableauPack: %d integer lists for %d LPs" % (len(self.integers), n))
-            per_lp = lambda v, default: _capi.as_i32(default if v is None else ([v] * n if isinstance(v, (int, np.integer)) else list(v)))  # noqa: E731
-            self.cut_rows = per_lp(cut_rows, [2 * iv.shape[0] for iv in self.integers])
-            self.heap_cap = per_lp(heap_cap, [128] * n)
+            self.cut_rows = self._per_lp(cut_rows, [2 * iv.shape[0] for iv in self.integers])
+            self.heap_cap = self._per_lp(heap_cap, [128] * n)
             if self.cut_rows.shape[0] != n or self.heap_cap.shape[0] != n:
                 raise ValueError("TableauPack: cut_rows / heap_cap are one number or one per LP")
             self.max_nodes = int(max_nodes) if max_nodes else _capi.JSLPT_MAX_NODES_DEFAULT
             self.row_capacity = self.heights + self.cut_rows
         else:
             self.row_capacity = self.heights
-        # MIR LPs (include/jslpc_tree_mir.h): the flags, and row_extra per LP (-1: a plain tree LP)
+        # MIR LPs (include/jslpc_tree_mir.h): the flags
         self.is_mir = np.zeros(n, dtype=bool)
         self.mir = np.zeros(n, dtype=_capi.MIR_TREE_DTYPE)
-        self.row_extra = np.full(n, -1, dtype=np.int32)
         if mir is not None and any(mir):
             if not self.is_tree:
                 raise ValueError("TableauPack: `mir` needs `integers` (a pack with trees)")
@@ -1181,14 +1179,6 @@ class TableauPack:
             # with optional objectives may stand side by side, though never in one LP)
             if self.has_optional and (incremental is None or not any(incremental) or (self.is_mir & (self.n_optional > 0)).any()):
                 raise ValueError("TableauPack: MIR LPs and optional objectives do not share a pack (include/jslpc_tree_mir.h)")
-            if row_extra is None:
-                extra = [tree_mir_rows(h, w, 0, lib=self.lib, cut_rows=c)[0] for h, w, c in zip(self.heights, self.widths, self.cut_rows)]
-            else:
-                extra = per_lp(row_extra, None)
-                if extra.shape[0] != n:
-                    raise ValueError("TableauPack: row_extra is one number or one per LP")
-            self.row_extra = np.where(self.is_mir, _capi.as_i32(extra), -1).astype(np.int32)
-            self.row_capacity = np.where(self.is_mir, self.heights + self.row_extra, self.row_capacity).astype(np.int32)
         self.has_mir = bool(self.is_mir.any())
         # enhanced LPs (include/jslpe_tree_enhanced.h): the codes as the create takes them (0: not given)
         self.node_selection = np.zeros(n, dtype=np.int32)
@@ -1206,7 +1196,7 @@ class TableauPack:
                 if g is not None and g not in names:
                     raise ValueError("TableauPack: LP %d: %s is None or one of %s, not %r" % (i, what, ", ".join(names), g))
                 codes[i] = 0 if g is None else names[g]
-        # incremental LPs (include/jslpi_tree_incremental.h): the flags, max_checkpoints and row_extra per LP
+        # incremental LPs (include/jslpi_tree_incremental.h): the flags and max_checkpoints per LP
         self.is_incremental = np.zeros(n, dtype=bool)
         self.incremental = np.zeros(n, dtype=_capi.INC_TREE_DTYPE)
         self.max_checkpoints = np.zeros(n, dtype=np.int32)
@@ -1216,25 +1206,30 @@ class TableauPack:
             if len(incremental) != n:
                 raise ValueError("TableauPack: %d incremental flags for %d LPs" % (len(incremental), n))
             self.is_incremental = np.array([bool(f) for f in incremental], dtype=bool)
-            limits = per_lp(max_checkpoints, None)
+            limits = self._per_lp(max_checkpoints, None)
             if limits.shape[0] != n:
                 raise ValueError("TableauPack: max_checkpoints is one number or one per LP")
             self.max_checkpoints = np.where(self.is_incremental, limits, 0).astype(np.int32)
-            if row_extra is None:
-                extra = [incremental_rows(h, w, 0, lib=self.lib, cut_rows=c)[0] for h, w, c in zip(self.heights, self.widths, self.cut_rows)]
-            else:
-                extra = per_lp(row_extra, None)
-                if extra.shape[0] != n:
-                    raise ValueError("TableauPack: row_extra is one number or one per LP")
             for i in np.flatnonzero(self.is_incremental):
                 if self.is_mir[i] or self.n_optional[i] > 0:
                     raise ValueError("TableauPack: LP %d: an incremental LP has neither `mir` nor optional objectives "
                                      "(include/jslpi_tree_incremental.h)" % i)
                 if not 0 <= self.max_checkpoints[i] <= _capi.JSLPI_MAX_CHECKPOINTS:
                     raise ValueError("TableauPack: LP %d: max_checkpoints is between 0 and %d" % (i, _capi.JSLPI_MAX_CHECKPOINTS))
-            self.row_extra = np.where(self.is_incremental, _capi.as_i32(extra), self.row_extra).astype(np.int32)
-            self.row_capacity = np.where(self.is_incremental, self.heights + self.row_extra, self.row_capacity).astype(np.int32)
         self.has_incremental = bool(self.is_incremental.any())
+        # row_extra per LP: a MIR or an incremental LP's row capacity beyond its height (-1: any other LP, whose row capacity is height + cut_rows)
+        self.row_extra = np.full(n, -1, dtype=np.int32)
+        own_rows = self.is_mir | self.is_incremental
+        if own_rows.any():
+            if row_extra is None:
+                extra = [(incremental_rows if inc else tree_mir_rows)(h, w, 0, lib=self.lib, cut_rows=c)[0] if own else -1
+                         for h, w, c, inc, own in zip(self.heights, self.widths, self.cut_rows, self.is_incremental, own_rows)]
+            else:
+                extra = self._per_lp(row_extra, None)
+                if extra.shape[0] != n:
+                    raise ValueError("TableauPack: row_extra is one number or one per LP")
+            self.row_extra = np.where(own_rows, _capi.as_i32(extra), -1).astype(np.int32)
+            self.row_capacity = np.where(own_rows, self.heights + self.row_extra, self.row_capacity).astype(np.int32)
         self.is_enhanced = (self.node_selection != 0) | (self.branching != 0) | self.is_incremental  # (an incremental LP is walked as one)
         self.has_enhanced = bool(self.is_enhanced.any())
         for i in np.flatnonzero(self.is_enhanced):
@@ -1253,40 +1248,29 @@ class TableauPack:
             raise _capi.EngineError("TableauPack: %s does not export the optional-objective extension (include/jslps_soft.h)" % self.lib.path)
         if self.lib.has_pack:
             self._h = _capi.C.c_void_p()
+            # the pack's composition picks the entry point and the tables it takes beyond the shapes; `said` is the name an error reports
+            ptr = _capi.ptr_i32
+            trees = [ptr(self.cut_rows), ptr(self.heap_cap)] if self.is_tree else []
+            optional = ptr(self.n_optional) if self.has_optional else None
+            flags = self.is_incremental.astype(np.int32)
             if self.has_incremental:
-                self.lib.check(self.lib.jslpi_tree_pack_create(
-                    _capi.C.byref(self._h), self.device, n, _capi.ptr_i32(self.heights), _capi.ptr_i32(self.widths), _capi.ptr_f64(self.precision),
-                    _capi.ptr_i32(self.cut_rows), _capi.ptr_i32(self.heap_cap), _capi.ptr_i32(self.n_optional) if self.has_optional else None,
-                    _capi.ptr_i32(self.row_extra), _capi.ptr_i32(self.node_selection), _capi.ptr_i32(self.branching),
-                    _capi.ptr_i32(self.is_incremental.astype(np.int32)), _capi.ptr_i32(self.max_checkpoints), self.trace_cap, self.max_pivots,
-                    self.max_nodes), "jslpi_tree_pack_create")
+                symbol = said = "jslpi_tree_pack_create"
+                tables = trees + [optional, ptr(self.row_extra), ptr(self.node_selection), ptr(self.branching), ptr(flags), ptr(self.max_checkpoints)]
             elif self.has_enhanced:
-                self.lib.check(self.lib.jslpe_tree_pack_create_mixed(
-                    _capi.C.byref(self._h), self.device, n, _capi.ptr_i32(self.heights), _capi.ptr_i32(self.widths), _capi.ptr_f64(self.precision),
-                    _capi.ptr_i32(self.cut_rows), _capi.ptr_i32(self.heap_cap), _capi.ptr_i32(self.n_optional) if self.has_optional else None,
-                    _capi.ptr_i32(self.row_extra) if self.has_mir else None, _capi.ptr_i32(self.node_selection), _capi.ptr_i32(self.branching),
-                    self.trace_cap, self.max_pivots, self.max_nodes), "jslpe_tree_pack_create")
-            elif self.has_optional and self.is_tree:
-                self.lib.check(self.lib.jslps_tree_pack_create(_capi.C.byref(self._h), self.device, n, _capi.ptr_i32(self.heights),
-                                                               _capi.ptr_i32(self.widths), _capi.ptr_f64(self.precision), _capi.ptr_i32(self.cut_rows),
-                                                               _capi.ptr_i32(self.heap_cap), _capi.ptr_i32(self.n_optional), self.trace_cap,
-                                                               self.max_pivots, self.max_nodes), "jslps_tree_pack_create")
+                symbol, said = "jslpe_tree_pack_create_mixed", "jslpe_tree_pack_create"
+                tables = trees + [optional, ptr(self.row_extra) if self.has_mir else None, ptr(self.node_selection), ptr(self.branching)]
             elif self.has_optional:
-                self.lib.check(self.lib.jslps_pack_create(_capi.C.byref(self._h), self.device, n, _capi.ptr_i32(self.heights), _capi.ptr_i32(self.widths),
-                                                          _capi.ptr_f64(self.precision), _capi.ptr_i32(self.n_optional), self.trace_cap,
-                                                          self.max_pivots), "jslps_pack_create")
+                symbol = said = "jslps_tree_pack_create" if self.is_tree else "jslps_pack_create"
+                tables = trees + [optional]
             elif self.has_mir:
-                self.lib.check(self.lib.jslpc_tree_pack_create(_capi.C.byref(self._h), self.device, n, _capi.ptr_i32(self.heights),
-                                                               _capi.ptr_i32(self.widths), _capi.ptr_f64(self.precision), _capi.ptr_i32(self.cut_rows),
-                                                               _capi.ptr_i32(self.heap_cap), _capi.ptr_i32(self.row_extra), self.trace_cap,
-                                                               self.max_pivots, self.max_nodes), "jslpc_tree_pack_create")
-            elif self.is_tree:
-                self.lib.check(self.lib.jslpt_pack_create(_capi.C.byref(self._h), self.device, n, _capi.ptr_i32(self.heights), _capi.ptr_i32(self.widths),
-                                                          _capi.ptr_f64(self.precision), _capi.ptr_i32(self.cut_rows), _capi.ptr_i32(self.heap_cap),
-                                                          self.trace_cap, self.max_pivots, self.max_nodes), "jslpt_pack_create")
+                symbol = said = "jslpc_tree_pack_create"
+                tables = trees + [ptr(self.row_extra)]
             else:
-                self.lib.check(self.lib.jslpp_pack_create(_capi.C.byref(self._h), self.device, n, _capi.ptr_i32(self.heights), _capi.ptr_i32(self.widths),
-                                                          _capi.ptr_f64(self.precision), self.trace_cap, self.max_pivots), "jslpp_pack_create")
+                symbol = said = "jslpt_pack_create" if self.is_tree else "jslpp_pack_create"
+                tables = trees
+            caps = [self.trace_cap, self.max_pivots] + ([self.max_nodes] if self.is_tree else [])
+            self.lib.check(getattr(self.lib, symbol)(_capi.C.byref(self._h), self.device, n, ptr(self.heights), ptr(self.widths), _capi.ptr_f64(self.precision),
+                                                     *tables, *caps), said)
             try:
                 for i, (m, vibr, vibc, unr) in enumerate(self._lps):
                     self.lib.check(self.lib.jslpp_pack_set(self._h, i, _capi.ptr_f64(m), _capi.ptr_i32(vibr), _capi.ptr_i32(vibc), _capi.ptr_i32(unr),
@@ -1330,6 +1314,10 @@ class TableauPack:
                            for i, ((m, vibr, vibc, unr), p, rc, oo) in enumerate(zip(self._lps, self.precision, self.row_capacity, self._optional))]
         else:
             raise _capi.EngineError("TableauPack: %s does not export the pack extension (include/jslpp_packed.h)" % self.lib.path)
+
+    def _per_lp(self, v, default):
+        """one number or one per LP as an int32 array (its length is the caller's to check); None: the default"""
+        return _capi.as_i32(default if v is None else ([v] * self.n if isinstance(v, (int, np.integer)) else list(v)))
 
     # ---- lifetime -------------------------------------------------------------------------------
     def close(self):
@@ -1409,15 +1397,52 @@ class TableauPack:
                 raise _capi.EngineError("jslpp_pack_simplex failed (%d): %s" % (rc, msg))
             self.device_ms = ms.value
             self._launches = int(self.lib.jslpp_pack_launches(self._h))
-        ok = status == _capi.JSLP_OK  # (an LP that failed leaves its scalars alone, as simplex() does)
+        return self._keep(out, status, rc, msg, "jslpp_pack_simplex")
+
+    def _keep(self, out, status, rc, msg, what):
+        """the end of simplex() and branch_and_cut(): the results and the scalars of the LPs that were solved (an LP that failed leaves its own
+        alone, as Tableau.simplex() does), then the call's error"""
+        ok = status == _capi.JSLP_OK
         self.results = out
         self.status = status
         self.feasible[ok] = out["feasible"][ok] != 0
         self.bounded[ok] = out["bounded"][ok] != 0
         self.evaluation[ok] = out["evaluation"][ok]
         if rc != _capi.JSLP_OK:
-            raise _capi.EngineError("jslpp_pack_simplex failed (%d): %s" % (rc, msg))
+            raise _capi.EngineError("%s failed (%d): %s" % (what, rc, msg))
         return out
+
+    def _walk(self, i, t, check_cycles):
+        """the restatement's tree of LP i on its twin engine `t`: the LP's (tree, mir, enhanced, incremental) records"""
+        from . import branch_and_cut as bc
+        from . import incremental_branch_and_cut as ibc
+        none_mir, none_enh, none_inc = (0, 0, 0, 0, 0), (0,) * 8, (0,) * 8
+        if self.integers[i].shape[0] == 0:
+            t.simplex(check_cycles=bool(check_cycles))
+            return (0, 0, t.last.height, 0, 0, 0), (0, 0, 1, 0, 0) if self.is_mir[i] else none_mir, none_enh, none_inc
+        model = _TreeModel(self.integers[i], check_cycles, mir=bool(self.is_mir[i]))
+        if self.is_enhanced[i]:  # the enhanced or the incremental service on the LP's twin, its stack and heap sharing heap_cap
+            boxes = ibc.CountingContainers(heap_cap=int(self.heap_cap[i]), cut_rows=int(self.cut_rows[i]), max_nodes=self.max_nodes)
+            selection, rule = self.policy(i)
+            if self.is_incremental[i]:  # (its checkpoints are the engine's)
+                iterations, integral = ibc.incremental_branch_and_cut(t, model, node_selection=selection, branching=rule,
+                                                                      max_checkpoints=int(self.max_checkpoints[i]), containers=boxes)
+                inc_rec = (t.checkpoints_used, t.incremental_nodes, max(boxes.rows_high_water - t.height0, 0),
+                           max(boxes.checkpoint_rows_high_water - t.height0, 0), 0, 0, 0, 0)
+            else:
+                iterations, integral = ibc.enhanced_branch_and_cut(t, model, node_selection=selection, branching=rule, containers=boxes)
+                inc_rec = none_inc
+            return ((iterations, int(integral), t.last.height, boxes.pushes, boxes.high_water, boxes.cuts_high_water), none_mir,
+                    boxes.record() + (0, 0), inc_rec)
+        heap = bc.CountingHeap(heap_cap=int(self.heap_cap[i]), cut_rows=int(self.cut_rows[i]))
+        counters = _MirCounters(t) if self.is_mir[i] else None
+        try:
+            iterations, integral = bc.branch_and_cut(t, model, heap=heap, max_nodes=self.max_nodes)
+            return ((iterations, int(integral), t.last.height, heap.pushes, heap.high_water, heap.cuts_high_water),
+                    counters.record() if counters is not None else none_mir, none_enh, none_inc)
+        finally:
+            if counters is not None:
+                counters.detach()
 
     def branch_and_cut(self, check_cycles=True):
         """Tableau.solve() of every LP under the default branch-and-cut service, each tree walked by its LP's workgroup inside ONE launch per
@@ -1445,60 +1470,19 @@ class TableauPack:
         status = np.zeros(self.n, dtype=np.int32)
         if self._twins is not None:
             from . import branch_and_cut as bc
-            from . import incremental_branch_and_cut as ibc
             rc, msg = _capi.JSLP_OK, ""
             for i, (t, c) in enumerate(zip(self._twins, flags)):
-                counters = None
-                inc_rec = (0,) * 8
                 try:
-                    if self.integers[i].shape[0] == 0:
-                        t.simplex(check_cycles=bool(c))
-                        rec = (0, 0, t.last.height, 0, 0, 0)
-                        mir_rec = (0, 0, 1, 0, 0) if self.is_mir[i] else (0, 0, 0, 0, 0)
-                        enh_rec = (0,) * 8
-                    elif self.is_incremental[i]:  # the incremental service on the LP's twin: its checkpoints are the engine's
-                        boxes = ibc.CountingContainers(heap_cap=int(self.heap_cap[i]), cut_rows=int(self.cut_rows[i]), max_nodes=self.max_nodes)
-                        selection, rule = self.policy(i)
-                        iterations, integral = ibc.incremental_branch_and_cut(t, _TreeModel(self.integers[i], c), node_selection=selection, branching=rule,
-                                                                              max_checkpoints=int(self.max_checkpoints[i]), containers=boxes)
-                        rec = (iterations, int(integral), t.last.height, boxes.pushes, boxes.high_water, boxes.cuts_high_water)
-                        mir_rec = (0, 0, 0, 0, 0)
-                        enh_rec = boxes.record() + (0, 0)
-                        inc_rec = (t.checkpoints_used, t.incremental_nodes, max(boxes.rows_high_water - t.height0, 0),
-                                   max(boxes.checkpoint_rows_high_water - t.height0, 0), 0, 0, 0, 0)
-                    elif self.is_enhanced[i]:  # the enhanced service on the LP's twin, its stack and heap sharing heap_cap
-                        boxes = ibc.CountingContainers(heap_cap=int(self.heap_cap[i]), cut_rows=int(self.cut_rows[i]), max_nodes=self.max_nodes)
-                        selection, rule = self.policy(i)
-                        iterations, integral = ibc.enhanced_branch_and_cut(t, _TreeModel(self.integers[i], c), node_selection=selection,
-                                                                           branching=rule, containers=boxes)
-                        rec = (iterations, int(integral), t.last.height, boxes.pushes, boxes.high_water, boxes.cuts_high_water)
-                        mir_rec = (0, 0, 0, 0, 0)
-                        enh_rec = boxes.record() + (0, 0)
-                    else:
-                        enh_rec = (0,) * 8
-                        heap = bc.CountingHeap(heap_cap=int(self.heap_cap[i]), cut_rows=int(self.cut_rows[i]))
-                        if self.is_mir[i]:
-                            counters = _MirCounters(t)
-                        iterations, integral = bc.branch_and_cut(t, _TreeModel(self.integers[i], c, mir=self.is_mir[i]), heap=heap,
-                                                                 max_nodes=self.max_nodes)
-                        rec = (iterations, int(integral), t.last.height, heap.pushes, heap.high_water, heap.cuts_high_water)
-                        mir_rec = counters.record() if counters is not None else (0, 0, 0, 0, 0)
+                    tree[i], mir[i], enhanced[i], incremental[i] = self._walk(i, t, c)
                     res = SimplexResult.from_buffer_copy(bytes(t.last))
                     res.evaluation = t.evaluation
                     out[i] = np.frombuffer(res, dtype=_capi.RESULT_DTYPE)[0]
-                    tree[i] = rec
-                    mir[i] = mir_rec
-                    enhanced[i] = enh_rec
-                    incremental[i] = inc_rec
                 except (bc.TreeCapacity, _capi.EngineError) as e:
                     status[i] = _capi.JSLP_ERR_CAPACITY if isinstance(e, bc.TreeCapacity) or "(%d)" % _capi.JSLP_ERR_CAPACITY in str(e) else _capi.JSLP_ERR_DEVICE
                     if (self.is_mir[i] or self.is_incremental[i]) and "row capacity exceeded" in str(e):  # (an engine's refusal of a round's or a cut list's rows)
                         e = "branch_and_cut: row_extra reached (%s)" % e
                     if rc == _capi.JSLP_OK:
                         rc, msg = int(status[i]), "pack_branch_and_cut: LP %d: %s" % (i, e)
-                finally:
-                    if counters is not None:
-                        counters.detach()
             self._launches = 0
         else:
             ms = _capi.C.c_double()
@@ -1516,19 +1500,8 @@ class TableauPack:
                 self.lib.check(self.lib.jslpe_pack_read_enhanced(self._h, enhanced.ctypes.data), "jslpe_pack_read_enhanced")
             if self.has_incremental:
                 self.lib.check(self.lib.jslpi_pack_read_incremental(self._h, incremental.ctypes.data), "jslpi_pack_read_incremental")
-        ok = status == _capi.JSLP_OK
-        self.results = out
-        self.tree = tree
-        self.mir = mir
-        self.enhanced = enhanced
-        self.incremental = incremental
-        self.status = status
-        self.feasible[ok] = out["feasible"][ok] != 0
-        self.bounded[ok] = out["bounded"][ok] != 0
-        self.evaluation[ok] = out["evaluation"][ok]
-        if rc != _capi.JSLP_OK:
-            raise _capi.EngineError("jslpt_pack_branch_and_cut failed (%d): %s" % (rc, msg))
-        return out
+        self.tree, self.mir, self.enhanced, self.incremental = tree, mir, enhanced, incremental
+        return self._keep(out, status, rc, msg, "jslpt_pack_branch_and_cut")
 
     def policy(self, i):
         """(node selection, branching) LP i's tree is walked under, by name, with the defaults filled in; None for an LP under the default

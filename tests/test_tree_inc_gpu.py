@@ -25,6 +25,7 @@ pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LAUNCH = re.compile(r"\[jslp\] launch k_tree_packed<(\d+)(?:,(\w+) 1)?> n (\d+) lds (\d+)")
+SIMPLEX_LAUNCH = re.compile(r"\[jslp\] launch k_simplex_packed<(\d+)(?:,(\w+) 1)?> n (\d+) lds (\d+)")
 LDS_LIMIT = 65536
 LIMITS = (50, 2, 1, 0)
 
@@ -199,6 +200,72 @@ def test_one_mixed_pack_equals_each_lp_alone(hip_lib, oracle_lib, monkeypatch, c
     assert pack.mir[2]["simplexes"] > 0 and pack.incremental[4]["incremental_nodes"] > 0 and pack.incremental[5]["checkpoints_used"] == 2
     pack.close()
     host.close()
+
+
+def one_lp_per_launch_group():
+    """ten LPs, exactly one per launch group, in launch order: [(item, policy, threads, kind)].  Of the five 256-thread LPs two are
+    Knapsack_1 as it is, three the small fixtures with cut_rows / row_extra pushed over 2048 cells of row capacity x width."""
+    wood, shop = U.fixture("Integer_Wood_Problem")["model"], U.fixture("Integer_Wood_Shop_Problem")["model"]
+    soft = copy.deepcopy(wood)
+    name = next(iter(soft["constraints"]))
+    soft["constraints"][name] = dict(soft["constraints"][name], weight=1, priority=1)
+    tall_soft = S.SoftItem(soft)
+    tall_soft.cut_rows = 680
+    knap = U.fixture("Knapsack_1")["model"]  # (52 x 51: 256 threads by its own size, beside the inflated ones)
+    return [(U.Item(wood), None, 64, "plain"), (U.Item(knap), None, 256, "plain"),
+            (S.SoftItem(soft), None, 64, "opt"), (tall_soft, None, 256, "opt"),
+            (M.MirItem(_with(wood, useMIRCuts=True)), None, 64, "mir"), (M.MirItem(_with(wood, useMIRCuts=True), row_extra=680), None, 256, "mir"),
+            (U.Item(shop), ("depth-first", None), 64, "enh"), (U.Item(knap), ("hybrid", "strong"), 256, "enh"),
+            (I.Item(shop), I.Inc("depth-first", "most-fractional", 2), 64, "inc"), (I.Item(shop, row_extra=520), I.Inc(), 256, "inc")]
+
+
+def test_one_lp_per_launch_group_in_launch_order(hip_lib, oracle_lib, monkeypatch, capfd):
+    """the ten LPs stand in the pack in the REVERSE of the launch order: the exact sequence of launch lines of branch_and_cut() and of
+    simplex() (one wave before 256 threads; plain, optional objectives, MIR, enhanced, incremental), each line's LDS bytes, and every LP's
+    records where the host walk, a pack of its own and the oracle-backed pack have them"""
+    groups = one_lp_per_launch_group()
+    want = [(threads, kind) for _, _, threads, kind in groups]
+    assert want == [(64, "plain"), (256, "plain"), (64, "opt"), (256, "opt"), (64, "mir"), (256, "mir"), (64, "enh"), (256, "enh"), (64, "inc"), (256, "inc")]
+    lds = []
+    for it, _, threads, kind in groups:  # every LP's own byte count, on the CPU: below the 64 KiB refusal, and the thread count is the group's
+        h, w = it.lp[0].shape
+        rc = h + (it.row_extra if kind in ("mir", "inc") else it.cut_rows)
+        count = {"mir": hip_lib.jslpc_tree_lds_bytes, "inc": hip_lib.jslpi_tree_lds_bytes, "enh": hip_lib.jslpt_lds_bytes}.get(kind)
+        lds.append(count(h, w, rc) if count else hip_lib.jslps_tree_lds_bytes(h, w, rc, getattr(it, "n_optional", 0)))
+        assert 0 < lds[-1] <= LDS_LIMIT and (rc * w > 2048) == (threads == 256), (kind, threads, rc, w)
+    items, policies = [g[0] for g in groups][::-1], [g[1] for g in groups][::-1]
+    checks = [it.check for it in items]
+    monkeypatch.setenv("JSLP_DEBUG_LAUNCH", "1")
+    capfd.readouterr()
+    pack, host = I.against_host(hip_lib, oracle_lib, items, policies)
+    lines = LAUNCH.findall(capfd.readouterr().err)
+    assert [(int(t), kind or "plain", int(n), int(b)) for t, kind, n, b in lines] == [(t, kind, 1, b) for (t, kind), b in zip(want, lds)], lines
+    assert pack.launches == 10 and not pack.status.any()
+    fresh = I.make_pack(hip_lib, items, policies)
+    capfd.readouterr()
+    fresh.simplex(check_cycles=checks)
+    lines = SIMPLEX_LAUNCH.findall(capfd.readouterr().err)
+    monkeypatch.delenv("JSLP_DEBUG_LAUNCH")
+    assert [(int(t), kind or "plain", int(n), int(b)) for t, kind, n, b in lines] == [
+        (t, "opt" if kind == "opt" else "plain", 1, b) for (t, kind), b in zip(want, lds)], lines
+    assert fresh.launches == 10
+    ref = I.make_pack(oracle_lib, items, policies)
+    ref.simplex(check_cycles=checks)
+    assert fresh.results.tobytes() == ref.results.tobytes() and fresh.evaluation.tobytes() == ref.evaluation.tobytes()
+    got = I.states(pack)
+    for i in range(len(items)):
+        assert [a.tobytes() for a in fresh.read_rhs(i)] == [a.tobytes() for a in ref.read_rhs(i)], i
+        assert fresh.pivot_trace(i).tobytes() == np.ascontiguousarray(ref.pivot_trace(i), dtype=np.int32).tobytes(), i
+        assert [a.tobytes() for a in fresh.download(i)[:3]] == [a.tobytes() for a in ref.download(i)[:3]], i
+        assert fresh.optional_objectives(i).tobytes() == ref.optional_objectives(i).tobytes(), i
+        alone = I.solve(hip_lib, [items[i]], [policies[i]])
+        assert I.state(alone, 0) == got[i], i
+        assert alone.optional_objectives(0).tobytes() == pack.optional_objectives(i).tobytes() == host.optional_objectives(i).tobytes(), i
+        alone.close()
+    # (pack index = 9 - group) both MIR LPs ran their loop, the one-wave incremental LP spent its two checkpoints
+    assert pack.mir[5]["simplexes"] > 0 and pack.mir[4]["simplexes"] > 0 and pack.incremental[1]["checkpoints_used"] == 2
+    for p in (pack, host, fresh, ref):
+        p.close()
 
 
 def test_arena_addressing_under_oversubscription(hip_lib, oracle_lib):
