@@ -119,7 +119,8 @@ struct PkRun { int phase, it1, it2, hist_n, entered2, outcome, unbounded_col; };
 // (jslp_core.inc.h) over LDS with its scalars in registers, as simplex_wg_lds does over global memory; arithmetic, orders and tie-breaks
 // are the core's own functions.  Bounded by iters_left.  The caller puts a barrier in front (LDS complete) and one behind.
 // A SECOND COPY of k_simplex_packed's loop below, line for line, on purpose: with the kernel calling this function its 256-thread build
-// took 59 VGPRs instead of 57 (profiles/packed_tree_kernel_resources.md), so the kernel keeps its own text.  Change both together.
+// took 59 VGPRs instead of 57 (profiles/packed_tree_kernel_resources.md), so the kernel keeps its own text.  Change both together:
+// tests/test_pack_edges_gpu.py holds each copy to the oracle at the edges of these loops (the kernel's through the LP packs, this one as tree roots).
 // OPT: the LP has n_opt >= 1 optional objectives, their rows at oo (stride S); every line of theirs sits under `if constexpr (OPT)`.
 template <int THREADS, bool OPT>
 __device__ __forceinline__ PkRun pk_simplex(double* A, double* pcol, const int H, const int W, const int S, int32_t* vibr, int32_t* vibc, int32_t* rbv,
