@@ -34,7 +34,7 @@
  *
  * Out of scope: an incremental LP with MIR cuts (the service's MIR loop, :261-276: three rounds, feasible nodes only) or with optional
  * objectives (a checkpoint carries none, so the rows a node starts from would depend on the walk) -- JSLP_ERR_ARG naming the LP -- and
- * what jslpt_tree.h leaves out (tolerance, timeout, keep_solutions).
+ * what jslpt_tree.h leaves out (timeout, keep_solutions; options.tolerance comes through jslpg_tree_tolerance.h).
  */
 #ifndef JSLPI_TREE_INCREMENTAL_H
 #define JSLPI_TREE_INCREMENTAL_H

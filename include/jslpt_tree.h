@@ -12,7 +12,8 @@
  * there is one, the last node's otherwise), the final RHS column and row map, the iteration count, and the pivot trace of EVERY node
  * in order, the final re-evaluation included.  A node that reaches no optimum keeps the evaluation of the node before it.
  *
- * Out of scope, by design (such models go through a jslp_engine): the incremental service, tolerance, timeout, keep_solutions, and
+ * Out of scope, by design (such models go through a jslp_engine): the incremental service, timeout, keep_solutions (options.tolerance
+ * comes through jslpg_tree_tolerance.h), and
  * an LP whose LDS image at its row capacity exceeds JSLPP_LDS_LIMIT.  Optional objectives come through jslps_soft.h, and MIR cuts
  * (options.useMIRCuts: every node's MIR loop run in the kernel) through jslpc_tree_mir.h -- the two together stay out of scope.  The
  * enhanced service (options.nodeSelection / options.branching) comes through jslpe_tree_enhanced.h, without MIR cuts and without

@@ -262,6 +262,15 @@ TREE_INC_SYMBOLS = {
     "jslpi_checkpoint_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     "jslpi_pack_read_incremental": (C.c_int, [C.c_void_p, C.c_void_p]),
 }
+# name -> (restype, argtypes); must list EVERY symbol include/jslpg_tree_tolerance.h declares.  HIP library only (Library.has_tree_tol).
+TREE_TOL_SYMBOLS = {
+    "jslpg_tree_pack_create": (C.c_int, [_P(C.c_void_p), C.c_int, C.c_int32, _i32p, _i32p, _f64p, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p,
+                                         _f64p, _i32p, C.c_int32, C.c_int32, C.c_int32]),
+    "jslpg_pack_read_tolerance": (C.c_int, [C.c_void_p, C.c_void_p]),
+}
+# numpy twin of struct jslpg_tolerance_result
+TOL_TREE_DTYPE = np.dtype([("best_possible", np.float64), ("threshold", np.float64), ("stopped", np.int32), ("left", np.int32),
+                           ("reserved0", np.int32), ("reserved1", np.int32)])
 # numpy twin of struct jslpi_tree_result
 INC_TREE_DTYPE = np.dtype([(name, np.int32) for name in ("checkpoints_used", "incremental_nodes", "rows_high_water", "checkpoint_rows_high_water",
                                                          "reserved0", "reserved1", "reserved2", "reserved3")])
@@ -308,6 +317,7 @@ class Library:
         self.has_tree_mir = self.has_tree and self._bind_extension(TREE_MIR_SYMBOLS)
         self.has_tree_enh = self.has_tree_mir and self.has_soft and self._bind_extension(TREE_ENH_SYMBOLS)
         self.has_tree_inc = self.has_tree_enh and self._bind_extension(TREE_INC_SYMBOLS)
+        self.has_tree_tol = self.has_tree_inc and self._bind_extension(TREE_TOL_SYMBOLS)
 
     def _bind_extension(self, symbols):
         """bind a HIP-only extension when the library exports all of it; False otherwise"""

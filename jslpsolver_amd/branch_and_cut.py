@@ -244,7 +244,8 @@ EVAL_STATS = {"seconds": 0.0, "batches": 0, "nodes": 0}  # speculative batches s
 TIE_STATS = {"ties": 0, "won": 0}
 
 
-def branch_and_cut(tableau, model, speculate=1, evaluate_batch=None, read_back=None, heap=None, max_nodes=None):
+def branch_and_cut(tableau, model, speculate=1, evaluate_batch=None, read_back=None, heap=None, max_nodes=None, tolerance_out=None,
+                   _late_stop=True):
     """branch-and-cut.ts:54-199.  Leaves `tableau` holding the incumbent; returns the iteration count and
     whether an integral node was accepted (tableau.__isIntegral).
 
@@ -264,6 +265,12 @@ def branch_and_cut(tableau, model, speculate=1, evaluate_batch=None, read_back=N
     loop.  Without speculation JSLP_TREE_MIR=1 makes every node after the root one Tableau.applyCutsMIR call.
 
     heap: the BranchMinHeap to use (a CountingHeap instruments the walk); max_nodes: raise TreeCapacity before evaluating one node more.
+
+    tolerance_out: a dict that gets what include/jslpg_tree_tolerance.h reports of a model with options.tolerance -- best_possible (the
+    tableau's bestPossibleEval), threshold (the last acceptableThreshold computed), stopped (the loop ended on toleranceFlag with entries
+    still waiting) and left (how many); default: off.  _late_stop is PRIVATE to the tests: False ends the loop on the very turn that lowers the
+    flag, which is NOT the reference's rule (:73-87: that turn still runs), so that a test can show the late node matters; no caller of
+    the package passes it.
     """
     branches = heap if heap is not None else BranchMinHeap()
     iterations = 0
@@ -336,6 +343,13 @@ def branch_and_cut(tableau, model, speculate=1, evaluate_batch=None, read_back=N
             EVAL_STATS["batches"] += 1
             EVAL_STATS["nodes"] += len(cut_lists)
 
+    def report(threshold):
+        if tolerance_out is not None and tolerance > 0:
+            stopped = not tolerance_flag and len(branches) > 0
+            tolerance_out.update(best_possible=float(tableau.bestPossibleEval), threshold=float(threshold), stopped=int(stopped),
+                                 left=len(branches) if stopped else 0)
+
+    acceptable = 0.0
     branches.push(-math.inf, [])
     while len(branches) > 0 and tolerance_flag and time.time() * 1000.0 < terminal_time:
         if model.isMinimization:
@@ -344,6 +358,8 @@ def branch_and_cut(tableau, model, speculate=1, evaluate_batch=None, read_back=N
             acceptable = tableau.bestPossibleEval * (1 - tolerance)
         if tolerance > 0 and best_evaluation < acceptable:
             tolerance_flag = False
+            if not _late_stop:
+                break
         relaxed, seq, cuts = branches.pop()
         if relaxed > best_evaluation:
             continue
@@ -401,6 +417,7 @@ def branch_and_cut(tableau, model, speculate=1, evaluate_batch=None, read_back=N
         if is_integral(model, rhs, rows, precision):
             found_integral = True
             if iterations == 1:
+                report(acceptable)
                 return iterations, True
             best_cuts = cuts
             best_evaluation = evaluation
@@ -427,6 +444,7 @@ def branch_and_cut(tableau, model, speculate=1, evaluate_batch=None, read_back=N
             cuts_low.append({"type": "max", "varIndex": var_index, "value": float(math.floor(var_value))})
             branches.push(evaluation, cuts_high)
             branches.push(evaluation, cuts_low)
+    report(acceptable)
     if best_cuts is not None:
         _res, rhs, vibr = tableau.applyCuts(best_cuts, check_cycles=check)
         mir_loop(tableau, model, rhs, vibr, check)
@@ -437,4 +455,6 @@ def branch_and_cut(tableau, model, speculate=1, evaluate_batch=None, read_back=N
     if watched_set and watched_before != list(model.integer_index_array):
         tableau.set_watched_variables(watched_before)  # (the caller's registration was borrowed for the compact read-back)
     tableau.speculated_nodes = speculated
+    if tolerance_out:  # (the final re-evaluation is a simplex like any other: tableau.ts:420-430)
+        tolerance_out["best_possible"] = float(tableau.bestPossibleEval)
     return iterations, found_integral

@@ -23,6 +23,7 @@
 #include "../../include/jslpc_tree_mir.h"
 #include "../../include/jslpe_tree_enhanced.h"
 #include "../../include/jslpi_tree_incremental.h"
+#include "../../include/jslpg_tree_tolerance.h"
 #include "jslp_kernels.hip.h"
 #include "jslp_host_mem.h"
 
@@ -3443,7 +3444,10 @@ extern "C" __attribute__((visibility("hidden"))) int jslpp_packed_launch_tu(int 
 extern "C" __attribute__((visibility("hidden"))) int jslpc_tree_mir_launch_tu(int threads, unsigned grid, size_t lds, const void* args, void* stream);
 extern "C" __attribute__((visibility("hidden"))) int jslpe_tree_enh_launch_tu(int threads, unsigned grid, size_t lds, const void* args, void* stream);
 extern "C" __attribute__((visibility("hidden"))) int jslpi_tree_inc_launch_tu(int threads, unsigned grid, size_t lds, const void* args, void* stream);
-static constexpr PackUnit PACK_UNITS[] = {jslpp_packed_launch_tu, jslpc_tree_mir_launch_tu, jslpe_tree_enh_launch_tu, jslpi_tree_inc_launch_tu};
+extern "C" __attribute__((visibility("hidden"))) int jslpg_tree_tol1_launch_tu(int threads, unsigned grid, size_t lds, const void* args, void* stream);
+extern "C" __attribute__((visibility("hidden"))) int jslpg_tree_tol2_launch_tu(int threads, unsigned grid, size_t lds, const void* args, void* stream);
+static constexpr PackUnit PACK_UNITS[] = {jslpp_packed_launch_tu, jslpc_tree_mir_launch_tu, jslpe_tree_enh_launch_tu, jslpi_tree_inc_launch_tu,
+                                          jslpg_tree_tol1_launch_tu, jslpg_tree_tol2_launch_tu};
 #else
 static int pack_dispatch(int threads, unsigned grid, size_t lds, const void* bytes, void* stream);  // (jslp_tree.hip.h, at the end of this file)
 static constexpr PackUnit PACK_UNITS[] = {pack_dispatch};
@@ -3465,8 +3469,9 @@ static constexpr PackGroup PACK_GROUPS[] = {{PACK_PLAIN, 64, ""},      {PACK_PLA
                                             {PACK_INC, 64, ",inc 1"},  {PACK_INC, 256, ",inc 1"}};
 // The result block [states | RHS columns | row maps | (a TreeRec per LP | (a TreeMirRec per LP) | (a TreeEnhRec per LP, an incremental pack's with
 // the LP's TreeIncRec behind it)) | optional rows]: the byte offset of every piece, each at a 256-byte boundary, computed ONCE at create
-struct PackLayout { size_t rhs, rows, tree, mir, enh, enh_stride, opt, bytes; };
-static PackLayout pack_layout(size_t n, size_t n_rows, size_t opt_doubles, bool tree, bool has_mir, bool has_enh, bool has_inc) {
+// (a pack with a tolerance table, include/jslpg_tree_tolerance.h: a TreeTolRec per LP behind everything else)
+struct PackLayout { size_t rhs, rows, tree, mir, enh, enh_stride, opt, tol, bytes; };
+static PackLayout pack_layout(size_t n, size_t n_rows, size_t opt_doubles, bool tree, bool has_mir, bool has_enh, bool has_inc, bool has_tol) {
     PackLayout l{};
     l.rhs = (sizeof(DevState) * n + 255) & ~(size_t)255;
     l.rows = (l.rhs + sizeof(double) * n_rows + 255) & ~(size_t)255;
@@ -3481,6 +3486,8 @@ static PackLayout pack_layout(size_t n, size_t n_rows, size_t opt_doubles, bool 
                                        : l.rows + sizeof(int32_t) * n_rows;
     l.opt = (plain_bytes + 255) & ~(size_t)255;
     l.bytes = opt_doubles ? l.opt + sizeof(double) * opt_doubles : plain_bytes;
+    l.tol = (l.bytes + 255) & ~(size_t)255;
+    if (has_tol) l.bytes = l.tol + sizeof(TreeTolRec) * n;
     return l;
 }
 // LP i's share of d_tree_mem, from byte `heap` on: the heap, (an enhanced LP's pseudocost table behind the heap array, (an incremental LP's
@@ -3511,6 +3518,9 @@ struct jslpp_pack {
     std::vector<int32_t> tree_status;  // the status of every LP after the last tree call (jslpc_pack_read_mir and its like)
     std::vector<int32_t> policy;       // an enhanced or incremental LP's node selection | branching << 4; 0 for every other LP
     std::vector<int32_t> max_ckpt;     // an incremental LP's max_checkpoints; 0 for every other LP
+    // options.tolerance (include/jslpg_tree_tolerance.h): which LPs have one, and their 1 + tolerance or 1 - tolerance; empty: a pack without the table
+    std::vector<uint8_t> has_tol;
+    std::vector<double> tol_factor;
     TreeLp* d_trees = nullptr;
     char* d_tree_mem = nullptr;
     size_t tree_mem_bytes = 0;
@@ -3527,7 +3537,9 @@ struct jslpp_pack {
     PackLp* d_lps = nullptr;
     int32_t *d_order = nullptr, *d_cc = nullptr;
     int2 *d_hist = nullptr, *d_trace = nullptr;
-    static constexpr int N_GROUPS = (int)(sizeof PACK_GROUPS / sizeof PACK_GROUPS[0]);
+    // (every group twice: its LPs without a tolerance, then those with one -- slot 2 g and 2 g + 1; a tree call launches the two in the
+    // build and the TOL build of the group's kind, a plain simplex launches them as one)
+    static constexpr int N_GROUPS = 2 * (int)(sizeof PACK_GROUPS / sizeof PACK_GROUPS[0]);
     int32_t n_group[N_GROUPS] = {};  // LPs per launch group (d_order holds them group after group), and the largest LDS image of each
     size_t lds_group[N_GROUPS] = {};
     // optional objectives (include/jslps_soft.h): rows per LP, whether they were set, and where they lie in the result block (in doubles)
@@ -3542,6 +3554,8 @@ struct jslpp_pack {
     int32_t* h_rows() const { return reinterpret_cast<int32_t*>(result.h.p + at.rows); }
     TreeRec* h_tree() const { return reinterpret_cast<TreeRec*>(result.h.p + at.tree); }
     TreeMirRec* h_mir() const { return reinterpret_cast<TreeMirRec*>(result.h.p + at.mir); }
+    TreeTolRec* h_tol() const { return reinterpret_cast<TreeTolRec*>(result.h.p + at.tol); }
+    bool is_tol(size_t i) const { return !has_tol.empty() && has_tol[i]; }
     TreeEnhRec* h_enh(size_t i) const { return reinterpret_cast<TreeEnhRec*>(result.h.p + at.enh + at.enh_stride * i); }
     bool is_mir(size_t i) const { return kind[i] == PACK_MIR; }
     bool is_enh(size_t i) const { return kind[i] == PACK_ENH || kind[i] == PACK_INC; }  // (an incremental LP is one too)
@@ -3569,6 +3583,14 @@ struct jslpp_pack {
     size_t opt_rows_off(int32_t i) const { return sizeof(DevState) + 8 * (size_t)pk_opt_image_off(RC[i], W[i]); }
     size_t ivars_off(int32_t i) const { return ints_off(i) + 4 * (size_t)pk_ints(RC[i], W[i]).total; }
 };
+// An LP with a tolerance (include/jslpg_tree_tolerance.h): the three spare words of its image's integer-variable header, as jslp_tree.hip.h
+// reads them -- where the TreeTolRec array lies behind the TreeRec array, in units of 256 bytes, and the factor
+static void pack_write_tol_head(jslpp_pack* p, int32_t i) {
+    if (!p->is_tol((size_t)i)) return;
+    int32_t* v = reinterpret_cast<int32_t*>(p->h_image.p + p->image_off[i] + p->ivars_off(i));
+    v[1] = (int32_t)((p->at.tol - p->at.tree) / 256);
+    memcpy(v + 2, &p->tol_factor[i], sizeof(double));
+}
 static int pack_fail(int code, const char* what, int32_t i, const char* why) {
     snprintf(g_err, sizeof g_err, "%s: LP %d: %s", what, (int)i, why);
     return code;
@@ -3615,6 +3637,7 @@ static int pack_init(jslpp_pack* p, int32_t max_pivots) {
     HIPC_CARVE(p->arena, [&](Carver& cv) { pack_carve(p, cv); });
     HIPC(p->h_image.reserve(std::max<size_t>(p->image_bytes, 256)));
     memset(p->h_image.p, 0, p->image_bytes);
+    if (p->tree) for (int32_t i = 0; i < p->n; i++) pack_write_tol_head(p, i);
     HIPC(p->h_cc.reserve(std::max<size_t>(sizeof(int32_t) * n, 256)));
     HIPC(p->result.reserve(std::max<size_t>(p->at.bytes, 256)));
     std::vector<PackLp> lps(n);
@@ -3622,7 +3645,7 @@ static int pack_init(jslpp_pack* p, int32_t max_pivots) {
     int32_t k = 0;
     for (int g = 0; g < jslpp_pack::N_GROUPS; g++)  // group after group (PACK_GROUPS), each in pack order
         for (size_t i = 0; i < n; i++) {
-            if (p->kind[i] != PACK_GROUPS[g].kind || p->threads(i) != PACK_GROUPS[g].threads) continue;
+            if (p->kind[i] != PACK_GROUPS[g / 2].kind || p->threads(i) != PACK_GROUPS[g / 2].threads || p->is_tol(i) != ((g & 1) != 0)) continue;
             order[k++] = (int32_t)i;
             p->n_group[g] += 1;
             p->lds_group[g] = std::max(p->lds_group[g], p->lds_bytes(i));
@@ -3688,6 +3711,8 @@ struct PackSpec {
     int32_t trace_cap, max_pivots, max_nodes;
     bool tree, mir, enh, inc;
     const int32_t *cut_rows, *heap_cap, *n_optional, *row_extra, *node_selection, *branching, *incremental, *max_checkpoints;
+    const double* tolerance;  // (include/jslpg_tree_tolerance.h; either may be null)
+    const int32_t* minimize;
 };
 static PackSpec pack_spec(jslpp_pack** out, int device, int32_t n, const int32_t* height, const int32_t* width, const double* precision, int32_t trace_cap,
                           int32_t max_pivots, int32_t max_nodes) {
@@ -3717,6 +3742,7 @@ static int pack_create(const PackSpec& s) {
             return pack_fail(JSLP_ERR_ARG, "pack_create", i, "cut_rows is at least 0 and heap_cap between 1 and 2^24");
         if (s.n_optional && s.n_optional[i] < 0) return pack_fail(JSLP_ERR_ARG, "pack_create", i, "n_optional is at least 0");
         if (s.incremental && (s.incremental[i] < 0 || s.incremental[i] > 1)) return pack_fail(JSLP_ERR_ARG, "pack_create", i, "incremental is 0 or 1");
+        if (s.minimize && (s.minimize[i] < 0 || s.minimize[i] > 1)) return pack_fail(JSLP_ERR_ARG, "pack_create", i, "minimize is 0 (the model maximises) or 1");
         const bool inc = s.incremental && s.incremental[i];
         if (inc) {
             if (s.max_checkpoints[i] < 0 || s.max_checkpoints[i] > JSLPI_MAX_CHECKPOINTS)
@@ -3781,6 +3807,15 @@ static int pack_create(const PackSpec& s) {
             p->RC[i] = s.height[i] + (p->is_mir((size_t)i) || p->is_inc((size_t)i) ? s.row_extra[i] : s.cut_rows[i]);
             p->tree_mem_bytes = p->tree_carve((size_t)i, p->tree_mem_bytes).end;
         }
+        if (s.tolerance) {  // `tolerance > 0` decides (false for NaN); the factor as branch-and-cut.ts:77-81 computes it
+            p->has_tol.assign((size_t)n, 0);
+            p->tol_factor.assign((size_t)n, 0.0);
+            for (int32_t i = 0; i < n; i++) {
+                if (!(s.tolerance[i] > 0)) continue;
+                p->has_tol[i] = 1;
+                p->tol_factor[i] = (!s.minimize || s.minimize[i]) ? 1 + s.tolerance[i] : 1 - s.tolerance[i];
+            }
+        }
     }
     p->evaluation.assign((size_t)n, 0.0);
     p->is_set.assign((size_t)n, 0);
@@ -3793,7 +3828,7 @@ static int pack_create(const PackSpec& s) {
         p->offs[i + 1] = p->offs[i] + p->RC[i];
     }
     // (a pack whose entry point takes the table has the records, whichever LPs use them)
-    p->at = pack_layout((size_t)n, (size_t)p->offs[n], (size_t)p->opt_offs[n], tree, tree && (s.mir || s.row_extra), tree && s.enh, tree && s.inc);
+    p->at = pack_layout((size_t)n, (size_t)p->offs[n], (size_t)p->opt_offs[n], tree, tree && (s.mir || s.row_extra), tree && s.enh, tree && s.inc, tree && s.tolerance);
     const int rc = pack_init(p, s.max_pivots);
     if (rc) { jslpp_pack_destroy(p); return rc; }
     *s.out = p;
@@ -3858,6 +3893,20 @@ extern "C" int jslpi_tree_pack_create(jslpp_pack** out, int device, int32_t n, c
     s.inc = true; s.incremental = incremental; s.max_checkpoints = max_checkpoints;
     return pack_create(s);
 }
+// include/jslpg_tree_tolerance.h
+extern "C" int jslpg_tree_pack_create(jslpp_pack** out, int device, int32_t n, const int32_t* height, const int32_t* width, const double* precision,
+                                      const int32_t* cut_rows, const int32_t* heap_cap, const int32_t* n_optional, const int32_t* row_extra,
+                                      const int32_t* node_selection, const int32_t* branching, const int32_t* incremental,
+                                      const int32_t* max_checkpoints, const double* tolerance, const int32_t* minimize, int32_t trace_cap,
+                                      int32_t max_pivots, int32_t max_nodes) {
+    PackSpec s = pack_spec(out, device, n, height, width, precision, trace_cap, max_pivots, max_nodes);
+    s.tree = true; s.cut_rows = cut_rows; s.heap_cap = heap_cap;
+    s.n_optional = n_optional; s.row_extra = row_extra;
+    s.enh = true; s.node_selection = node_selection; s.branching = branching;
+    s.inc = true; s.incremental = incremental; s.max_checkpoints = max_checkpoints;
+    s.tolerance = tolerance; s.minimize = minimize;
+    return pack_create(s);
+}
 extern "C" int64_t jslpi_tree_lds_bytes(int32_t height, int32_t width, int32_t row_capacity) { return jslpt_lds_bytes(height, width, row_capacity); }
 extern "C" int64_t jslpi_checkpoint_bytes(int32_t height, int32_t width, int32_t row_capacity) {
     if (height < 2 || width < 2 || row_capacity < height) return 0;
@@ -3869,6 +3918,17 @@ static int pack_read_check(const jslpp_pack* p, const void* out, const char* wha
     if (!p->tree) return fail(JSLP_ERR_STATE, "%s: %s", what, not_a_tree_pack);
     if (!p->uploaded || !p->tree_ran) return fail(JSLP_ERR_STATE, "%s before jslpt_pack_branch_and_cut", what);
     if ((int32_t)p->tree_status.size() != p->n) return fail(JSLP_ERR_STATE, "%s: the last jslpt_pack_branch_and_cut did not finish", what);
+    return JSLP_OK;
+}
+extern "C" int jslpg_pack_read_tolerance(jslpp_pack* p, jslpg_tolerance_result* out) {
+    JSLP_TRY(pack_read_check(p, out, "pack_read_tolerance", "not a pack with trees (jslpg_tree_pack_create, jslpt_pack_create)"));
+    static_assert(sizeof(jslpg_tolerance_result) == 32 && sizeof(TreeTolRec) == 32, "jslpg_tolerance_result is a TreeTolRec");
+    for (int32_t i = 0; i < p->n; i++) {
+        if (p->tree_status[(size_t)i] != JSLP_OK) continue;  // (left as it was)
+        memset(&out[i], 0, sizeof out[i]);
+        if (p->is_tol((size_t)i)) memcpy(&out[i], &p->h_tol()[i], sizeof out[i]);
+        if (out[i].threshold != out[i].threshold) out[i].threshold = std::numeric_limits<double>::quiet_NaN();  // (0 * Infinity: THE quiet NaN, whatever sign the multiplier gave it)
+    }
     return JSLP_OK;
 }
 extern "C" int jslpi_pack_read_incremental(jslpp_pack* p, jslpi_tree_result* out) {
@@ -3955,6 +4015,7 @@ extern "C" int jslpt_pack_set_integers(jslpp_pack* p, int32_t i, const int32_t* 
     memset(v, 0, (size_t)tree_ivars_bytes(p->RC[i], p->W[i]));
     v[0] = n;
     if (n) memcpy(v + 4, var_indexes, sizeof(int32_t) * (size_t)n);
+    pack_write_tol_head(p, i);
     p->uploaded = 0;  // (the device copy is stale until the next upload)
     return JSLP_OK;
 }
@@ -4089,18 +4150,27 @@ static int pack_run(jslpp_pack* p, bool tree, const int32_t* check_cycles, jslp_
     if (tree) p->tree_ran = true;
     HIPC(hipEventRecord(p->ev_begin, s));
     int32_t first = 0;
-    for (int g = 0; g < jslpp_pack::N_GROUPS; first += p->n_group[g], g++) {  // one launch per group that has LPs
-        const int32_t cnt = p->n_group[g];
+    for (int g = 0; g < jslpp_pack::N_GROUPS; g++) {  // one launch per group that has LPs
+        int32_t cnt = p->n_group[g];
+        size_t lds = p->lds_group[g];
+        const int32_t begin = first;
+        first += cnt;
+        const bool tol = tree && (g & 1);
+        if (!tree) {  // (k_simplex_packed knows no tolerance: the two halves of a group are ONE launch, made at the first)
+            if (g & 1) continue;
+            cnt += p->n_group[g + 1];
+            lds = std::max(lds, p->lds_group[g + 1]);
+        }
         if (!cnt) continue;
-        const PackGroup& grp = PACK_GROUPS[g];
+        const PackGroup& grp = PACK_GROUPS[g / 2];
         const bool own = tree || grp.kind == PACK_OPT;  // (k_simplex_packed: MIR, enhanced and incremental LPs in the plain build)
-        const size_t lds = p->lds_group[g];
-        a.order = p->d_order + first;
+        a.order = p->d_order + begin;
         a.build = own ? grp.kind : PACK_PLAIN;
+        a.tol = tol ? 1 : 0;
         (void)packed_launch(grp.threads, (unsigned)cnt, lds, a, s);
         HIPC(hipGetLastError());
         p->launches += 1;
-        if (dbg) fprintf(stderr, "[jslp] launch %s<%d%s> n %d lds %zu\n", tree ? "k_tree_packed" : "k_simplex_packed", grp.threads, own ? grp.suffix : "", (int)cnt, lds);
+        if (dbg) fprintf(stderr, "[jslp] launch %s<%d%s%s> n %d lds %zu\n", tree ? "k_tree_packed" : "k_simplex_packed", grp.threads, own ? grp.suffix : "", tol ? ",tol 1" : "", (int)cnt, lds);
     }
     HIPC(hipEventRecord(p->ev_end, s));
     HIPC(hipMemcpyAsync(p->result.h.p, p->result.d.p, p->at.bytes, hipMemcpyDeviceToHost, s));

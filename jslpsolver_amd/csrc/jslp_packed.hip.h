@@ -77,6 +77,7 @@ struct PackLaunch {
     const int32_t* order;  // blockIdx.x -> LP index (the LPs of this build)
     const int32_t* cc;     // per-LP checkForCycles, or nullptr: cc_all for every LP
     int32_t cc_all, tree;  // tree 0: k_simplex_packed, 1: k_tree_packed (jslp_tree.hip.h)
+    int32_t tol;           // k_tree_packed: 1: the TOL build of that kind (include/jslpg_tree_tolerance.h; every LP of `order` has a tolerance), 0: the other
     int32_t build;         // the PackKind whose build of that kernel runs: every LP of `order` is of this kind (k_simplex_packed: PACK_OPT, or
                            // PACK_PLAIN for every other kind)
     void* states;          // result block: DevState per LP (LP order) ...
@@ -637,11 +638,18 @@ __global__ void __launch_bounds__(THREADS) k_simplex_packed(const PackLp* __rest
 #endif
 static_assert((1 << PACK_PLAIN | 1 << PACK_OPT) == 0x03 && 1 << PACK_MIR == 0x04 && 1 << PACK_ENH == 0x08 && 1 << PACK_INC == 0x10, "the units' masks name these builds");
 constexpr bool pack_build_here(int build) { return ((JSLP_PACK_BUILDS) >> build & 1) != 0; }
+// JSLP_PACK_TOL: which side of k_tree_packed's TOL flag (include/jslpg_tree_tolerance.h) the unit instantiates -- 0 (not given in a unit
+// that names its builds): the builds without it, and k_simplex_packed, as before there was such a flag; 1: the TOL twins of the unit's
+// builds alone (jslp_tu_tree_tol.hip: a unit of their own, so that the other units compile what they compiled); 2: both (the single-unit build).
+#ifndef JSLP_PACK_TOL
+#define JSLP_PACK_TOL 2
+#endif
+constexpr bool pack_tol_here(bool tol) { return (JSLP_PACK_TOL) == 2 || ((JSLP_PACK_TOL) == 1) == tol; }
 
 // one build of k_simplex_packed: launches when (threads, a.build) is its own
 template <int T, int BUILD>
 static bool pk_launch(int threads, unsigned grid, size_t lds, const PackLaunch& a, hipStream_t s) {
-    if constexpr (!pack_build_here(BUILD)) {
+    if constexpr (!pack_build_here(BUILD) || !pack_tol_here(false)) {
         return false;
     } else {
         if (threads != T || a.build != BUILD) return false;

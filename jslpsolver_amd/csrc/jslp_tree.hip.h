@@ -35,6 +35,11 @@ struct TreeEnhRec { int32_t solutions_found, stack_high_water, moved_to_heap, ps
 // The LP's TreeIncRec follows its TreeEnhRec in the result block.
 struct TreeCkptHead { int32_t height, feasible; double evaluation; };
 struct TreeIncRec { int32_t checkpoints_used, incremental_nodes, rows_high_water, checkpoint_rows_high_water, pad[4]; };  // jslpi_tree_result
+// An LP with options.tolerance (include/jslpg_tree_tolerance.h) runs in the TOL build of its kind.  TreeLp and the kernel's arguments are what
+// they were: what such an LP adds rides in the three spare words of its image's integer-variable header (behind n_int) -- word 1 the distance,
+// in units of 256 bytes, from the pack's TreeRec array to its TreeTolRec array in the result block, words 2 and 3 the factor, the host's
+// 1 + tolerance (a minimisation) or 1 - tolerance (a maximisation), any double.
+struct TreeTolRec { double best_possible, threshold; int32_t stopped, left, pad[2]; };  // jslpg_tolerance_result
 enum { TREE_CK_NO_CUT = -2, TREE_CK_NONE = -1, TREE_MAX_CHECKPOINTS = 64 };
 enum { ENH_BEST_FIRST = 1, ENH_DEPTH_FIRST = 2, ENH_HYBRID = 3, ENH_MOST_FRACTIONAL = 1, ENH_PSEUDOCOST = 2, ENH_STRONG = 3, ENH_STRONG_CANDIDATES = 5 };
 struct TreeLp {
@@ -150,7 +155,12 @@ __device__ __forceinline__ double tree_round(double x) {
 // carries one starts from it with ONE new cut row (checkpoint_restore + add_cuts_at) instead of the root and its whole list.  Pseudocosts
 // are updated from a node's new cut only, `strong` means pseudocost, and a checkpoint brings its evaluation with it.  INC = false
 // instantiates the kernel as it was before there was such a build.
-template <int THREADS, bool OPT, bool MIR = false, bool ENH = false, bool INC = false>
+// TOL = true (with any of the above): the LPs of a model with options.tolerance (include/jslpg_tree_tolerance.h).  bestPossibleEval is the
+// evaluation of the LP's first simplex that ends optimal (tableau.ts:420-430, `simplexIters === 0`); the threshold is looked at at the top of
+// every turn behind the emptiness test and BEFORE the pop, and a turn that finds the incumbent below it lowers toleranceFlag and still runs:
+// the loop ends at the next turn's condition (branch-and-cut.ts:73-87).  Every line of it is under `if constexpr (TOL)`: TOL = false
+// instantiates the kernel, instruction for instruction, as it was before there was such a build.
+template <int THREADS, bool OPT, bool MIR = false, bool ENH = false, bool INC = false, bool TOL = false>
 __global__ void __launch_bounds__(THREADS) k_tree_packed(const PackLp* __restrict__ lps, const TreeLp* __restrict__ trees, const int32_t* __restrict__ order,
                                                          const int32_t* __restrict__ cc, int cc_all, DevState* __restrict__ out_states,
                                                          double* __restrict__ out_rhs, int32_t* __restrict__ out_rows, TreeRec* __restrict__ out_tree) {
@@ -347,6 +357,20 @@ __global__ void __launch_bounds__(THREADS) k_tree_packed(const PackLp* __restric
         if (tid == 0) free_list[free_n] = slot;
         free_n += 1;
     };
+    // (TOL) bestPossibleEval * factor as of now (0 * factor until the first optimum), whether bestPossibleEval is still open, !toleranceFlag,
+    // whether the loop ended on it, and the LP's record: best_possible and the last threshold go there as they arise (thread 0)
+    double tol_threshold = 0.0, tol_factor = 0.0;
+    bool bp_open = true, tol_stop = false, tol_broke = false;
+    TreeTolRec* tol_rec = nullptr;
+    if constexpr (TOL) {
+        tol_factor = __hiloint2double(gV[3], gV[2]);
+        tol_rec = reinterpret_cast<TreeTolRec*>(reinterpret_cast<char*>(out_tree) + 256LL * gV[1]) + idx;
+        tol_threshold = __dmul_rn(0.0, tol_factor);  // (the root's turn: its threshold is the record's first, and an incumbent of +Infinity lowers no flag)
+        if (tid == 0) {
+            TreeTolRec z; z.best_possible = 0.0; z.threshold = tol_threshold; z.stopped = 0; z.left = 0; z.pad[0] = z.pad[1] = 0;
+            *tol_rec = z;
+        }
+    }
     // (MIR) the loop behind a node's simplex (branch-and-cut.ts:38-52); false: the LP has ended with terr or serr set
     int mir_rounds = 0, mir_rows = 0, mir_simplexes = 0, mir_tallest = H0;
     auto mir_loop = [&]() -> bool {
@@ -371,6 +395,12 @@ __global__ void __launch_bounds__(THREADS) k_tree_packed(const PackLp* __restric
                     evaluation = __ddiv_rn(tree_round(__dmul_rn(__dadd_rn(2.220446049250313e-16, A[0]), t.rcoef)), t.rcoef);
                 else if (o.outcome == 2)
                     evaluation = -INFINITY;
+                if constexpr (TOL)  // setEvaluation while simplexIters === 0 (tableau.ts:420-430): the LP's first optimum is bestPossibleEval
+                    if (o.outcome == 1 && bp_open) {
+                        if (tid == 0) tol_rec->best_possible = evaluation;
+                        tol_threshold = __dmul_rn(evaluation, tol_factor);
+                        bp_open = false;
+                    }
                 const double after = tmir_volume<THREADS>(A, S, vibr, H, is_int, precision, pcol, ms);
                 if (after >= 0.9 * before) return true;  // (false for NaN: the loop goes on, as the reference's does)
                 before = after;
@@ -383,6 +413,11 @@ __global__ void __launch_bounds__(THREADS) k_tree_packed(const PackLp* __restric
         if (!root) {
             if constexpr (ENH) {  // :257-280: the stack's top while the walk is depth-first, the heap's best after
                 if ((use_df ? stack_n : heap_n) == 0) break;
+                if constexpr (TOL) {  // the loop condition's toleranceFlag, then :73-87 -- before the pop; strict, false for NaN
+                    if (tol_stop) { tol_broke = true; break; }
+                    if (tid == 0) tol_rec->threshold = tol_threshold;  // (the last one a turn computed)
+                    tol_stop = best_eval < tol_threshold;
+                }
                 if (tid == 0) {
                     const TreeEntry e = use_df ? heap[t.heap_cap - stack_n] : tree_pop(heap, heap_n);
                     sm.key = e.key;
@@ -390,6 +425,11 @@ __global__ void __launch_bounds__(THREADS) k_tree_packed(const PackLp* __restric
                 }
             } else {
                 if (heap_n == 0) break;
+                if constexpr (TOL) {  // the loop condition's toleranceFlag, then :73-87 -- before the pop; strict, false for NaN
+                    if (tol_stop) { tol_broke = true; break; }
+                    if (tid == 0) tol_rec->threshold = tol_threshold;  // (the last one a turn computed)
+                    tol_stop = best_eval < tol_threshold;
+                }
                 if (tid == 0) {
                     const TreeEntry e = tree_pop(heap, heap_n);
                     sm.key = e.key;
@@ -444,6 +484,12 @@ __global__ void __launch_bounds__(THREADS) k_tree_packed(const PackLp* __restric
             evaluation = __ddiv_rn(tree_round(__dmul_rn(__dadd_rn(2.220446049250313e-16, A[0]), t.rcoef)), t.rcoef);
         else if (o.outcome == 2)
             evaluation = -INFINITY;
+        if constexpr (TOL)  // setEvaluation while simplexIters === 0 (tableau.ts:420-430): the LP's first optimum is bestPossibleEval
+            if (o.outcome == 1 && bp_open) {
+                if (tid == 0) tol_rec->best_possible = evaluation;
+                tol_threshold = __dmul_rn(evaluation, tol_factor);
+                bp_open = false;
+            }
         if constexpr (MIR) {
             mir_simplexes += 1;
             mir_tallest = max(mir_tallest, H);
@@ -758,6 +804,12 @@ __global__ void __launch_bounds__(THREADS) k_tree_packed(const PackLp* __restric
                 evaluation = __ddiv_rn(tree_round(__dmul_rn(__dadd_rn(2.220446049250313e-16, A[0]), t.rcoef)), t.rcoef);
             else if (o.outcome == 2)
                 evaluation = -INFINITY;
+            if constexpr (TOL)  // setEvaluation while simplexIters === 0 (tableau.ts:420-430): the LP's first optimum is bestPossibleEval
+                if (o.outcome == 1 && bp_open) {
+                    if (tid == 0) tol_rec->best_possible = evaluation;
+                    tol_threshold = __dmul_rn(evaluation, tol_factor);
+                    bp_open = false;
+                }
             if constexpr (MIR) {
                 mir_simplexes += 1;
                 mir_tallest = max(mir_tallest, H);
@@ -827,6 +879,11 @@ __global__ void __launch_bounds__(THREADS) k_tree_packed(const PackLp* __restric
             er.pad[0] = er.pad[1] = 0;
             *many_global(t.enh_out) = er;
         }
+        if constexpr (TOL)
+            if (tol_broke) {  // (nothing has touched heap or stack since the loop ended)
+                tol_rec->stopped = 1;
+                tol_rec->left = heap_n + stack_n;
+            }
         if constexpr (INC) {
             TreeIncRec ir;
             ir.checkpoints_used = ck_count; ir.incremental_nodes = inc_nodes; ir.rows_high_water = rows_hw - H0;
@@ -841,13 +898,13 @@ __global__ void __launch_bounds__(THREADS) k_tree_packed(const PackLp* __restric
 }
 
 // one build of k_tree_packed, as pk_launch (MIR, ENH and INC come without OPT; an INC build is an ENH build)
-template <int T, int BUILD>
+template <int T, int BUILD, bool TOL = false>
 static bool tree_launch(int threads, unsigned grid, size_t lds, const PackLaunch& a, hipStream_t s) {
-    if constexpr (!pack_build_here(BUILD)) {
+    if constexpr (!pack_build_here(BUILD) || !pack_tol_here(TOL)) {
         return false;
     } else {
-        if (threads != T || a.build != BUILD) return false;
-        hipLaunchKernelGGL((k_tree_packed<T, BUILD == PACK_OPT, BUILD == PACK_MIR, BUILD == PACK_ENH || BUILD == PACK_INC, BUILD == PACK_INC>), dim3(grid), dim3(T), lds, s,
+        if (threads != T || a.build != BUILD || (a.tol != 0) != TOL) return false;
+        hipLaunchKernelGGL((k_tree_packed<T, BUILD == PACK_OPT, BUILD == PACK_MIR, BUILD == PACK_ENH || BUILD == PACK_INC, BUILD == PACK_INC, TOL>), dim3(grid), dim3(T), lds, s,
                            a.lps, static_cast<const TreeLp*>(a.trees), a.order, a.cc, a.cc_all, static_cast<DevState*>(a.states), a.rhs, a.rows,
                            static_cast<TreeRec*>(a.tree_out));
         return true;
@@ -868,7 +925,13 @@ static int pack_dispatch(int threads, unsigned grid, size_t lds, const void* byt
               tree_launch<64, PACK_OPT>(threads, grid, lds, a, s) || tree_launch<256, PACK_OPT>(threads, grid, lds, a, s) ||
               tree_launch<64, PACK_MIR>(threads, grid, lds, a, s) || tree_launch<256, PACK_MIR>(threads, grid, lds, a, s) ||
               tree_launch<64, PACK_ENH>(threads, grid, lds, a, s) || tree_launch<256, PACK_ENH>(threads, grid, lds, a, s) ||
-              tree_launch<64, PACK_INC>(threads, grid, lds, a, s) || tree_launch<256, PACK_INC>(threads, grid, lds, a, s);
+              tree_launch<64, PACK_INC>(threads, grid, lds, a, s) || tree_launch<256, PACK_INC>(threads, grid, lds, a, s) ||
+              // (the TOL builds behind every other, so that those are instantiated in the order they were)
+              tree_launch<64, PACK_PLAIN, true>(threads, grid, lds, a, s) || tree_launch<256, PACK_PLAIN, true>(threads, grid, lds, a, s) ||
+              tree_launch<64, PACK_OPT, true>(threads, grid, lds, a, s) || tree_launch<256, PACK_OPT, true>(threads, grid, lds, a, s) ||
+              tree_launch<64, PACK_MIR, true>(threads, grid, lds, a, s) || tree_launch<256, PACK_MIR, true>(threads, grid, lds, a, s) ||
+              tree_launch<64, PACK_ENH, true>(threads, grid, lds, a, s) || tree_launch<256, PACK_ENH, true>(threads, grid, lds, a, s) ||
+              tree_launch<64, PACK_INC, true>(threads, grid, lds, a, s) || tree_launch<256, PACK_INC, true>(threads, grid, lds, a, s);
     return hit ? (int)hipPeekAtLastError() : -1;
 }
 #endif  // JSLP_PACKED_KERNELS

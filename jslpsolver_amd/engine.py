@@ -999,12 +999,12 @@ def checkpoint_bytes(height, width, row_capacity):
 
 
 class _TreeModel:
-    """what branch_and_cut.branch_and_cut reads of a model, for an LP of a pack: the default service, no tolerance, no timeout"""
-    tolerance = 0
+    """what branch_and_cut.branch_and_cut reads of a model, for an LP of a pack: its tolerance (0: none) and its sense, no timeout"""
     timeout = None
-    isMinimization = True
 
-    def __init__(self, integers, check_cycles, mir=False):
+    def __init__(self, integers, check_cycles, mir=False, tolerance=0, minimize=True):
+        self.tolerance = tolerance
+        self.isMinimization = bool(minimize)
         self.integer_index_array = np.asarray(integers, dtype=np.int64)
         self.integer_index_set = frozenset(int(i) for i in integers)
         self.integerVariables = [{"index": int(i)} for i in integers]  # (what the enhanced service's selectBranchingVariable reads)
@@ -1103,11 +1103,22 @@ class TableauPack:
     incremental_rows), which the cut rows of a node that starts from the root and the stacked rows of a chain of checkpoints share.
     `incremental` (_capi.INC_TREE_DTYPE: checkpoints_used, incremental_nodes, rows_high_water, checkpoint_rows_high_water) is the
     read-back of the last branch_and_cut(), zero for the other LPs; `is_incremental` holds the flags; `enhanced` and `tree` report for such
-    an LP what they report for an enhanced one.  Not for an LP with `mir` or with optional objectives."""
+    an LP what they report for an enhanced one.  Not for an LP with `mir` or with optional objectives.
+
+    NOTE the two meanings of one name, which include/jslpg_tree_tolerance.h's Python face was asked to have: the ARGUMENT `tolerance=` takes the
+    models' options.tolerance VALUES; the ATTRIBUTE `pack.tolerance` is the RECORD array a tree call reads back.  The values given are kept
+    as `pack.tolerances` (plural).
+    tolerance / minimize: one entry per LP of a pack with trees (include/jslpg_tree_tolerance.h): the model's options.tolerance (None, a value
+    <= 0 or NaN: none, as `tolerance > 0` decides in the reference; any other value as it is) and whether the model minimises (default:
+    every LP does).  An LP with a tolerance ends its walk as the reference's services end theirs: one node after the incumbent came within
+    bestPossibleEval * (1 +- tolerance).  `tolerance` (_capi.TOL_TREE_DTYPE: best_possible, threshold,
+    stopped, left) is the read-back of the last branch_and_cut(), zero for the other LPs; such an LP runs in the TOL twin of its kind's build,
+    a launch of its own beside the LPs without a tolerance; `tolerances` holds the values given (0: none),
+    `is_tolerance` the flags, `has_tolerance` whether any LP has one."""
 
     def __init__(self, lps, precision=1e-8, lib=None, device=0, trace_cap=0, max_pivots=0, integers=None, cut_rows=None, heap_cap=None,
                  max_nodes=0, optional_objectives=None, mir=None, row_extra=None, node_selection=None, branching=None, incremental=None,
-                 max_checkpoints=_capi.JSLPI_CHECKPOINTS_DEFAULT):
+                 max_checkpoints=_capi.JSLPI_CHECKPOINTS_DEFAULT, tolerance=None, minimize=None):
         self.lib = lib if lib is not None else _capi.load_hip()
         self._lps = []
         for matrix, vibr, vibc, unr in lps:
@@ -1217,6 +1228,26 @@ class TableauPack:
                 if not 0 <= self.max_checkpoints[i] <= _capi.JSLPI_MAX_CHECKPOINTS:
                     raise ValueError("TableauPack: LP %d: max_checkpoints is between 0 and %d" % (i, _capi.JSLPI_MAX_CHECKPOINTS))
         self.has_incremental = bool(self.is_incremental.any())
+        # options.tolerance (include/jslpg_tree_tolerance.h): the values (0: none), the models' sense, the record
+        self.tolerances = np.zeros(n, dtype=np.float64)
+        self.minimize = np.ones(n, dtype=np.int32)
+        self.tolerance = np.zeros(n, dtype=_capi.TOL_TREE_DTYPE)
+        if tolerance is not None:
+            if len(tolerance) != n:
+                raise ValueError("TableauPack: %d tolerance entries for %d LPs" % (len(tolerance), n))
+            given = _capi.as_f64([0.0 if v is None else float(v) for v in tolerance])
+            self.tolerances = np.where(given > 0, given, 0.0)  # (`tolerance > 0`: false for NaN)
+        if minimize is not None:
+            if len(minimize) != n:
+                raise ValueError("TableauPack: %d minimize flags for %d LPs" % (len(minimize), n))
+            self.minimize = _capi.as_i32([int(f) for f in minimize])
+            for i in np.flatnonzero((self.minimize != 0) & (self.minimize != 1)):  # (refused here, whichever library and create are behind)
+                raise _capi.EngineError("jslpg_tree_pack_create failed (%d): pack_create: LP %d: minimize is 0 (the model maximises) or 1"
+                                        % (_capi.JSLP_ERR_ARG, i))
+        self.is_tolerance = self.tolerances > 0
+        self.has_tolerance = bool(self.is_tolerance.any())
+        if self.has_tolerance and not self.is_tree:
+            raise ValueError("TableauPack: `tolerance` needs `integers` (a pack with trees)")
         # row_extra per LP: a MIR or an incremental LP's row capacity beyond its height (-1: any other LP, whose row capacity is height + cut_rows)
         self.row_extra = np.full(n, -1, dtype=np.int32)
         own_rows = self.is_mir | self.is_incremental
@@ -1236,6 +1267,8 @@ class TableauPack:
             if self.is_mir[i] or self.n_optional[i] > 0:
                 raise ValueError("TableauPack: LP %d: an enhanced LP (node_selection / branching) has neither `mir` nor optional objectives "
                                  "(include/jslpe_tree_enhanced.h)" % i)
+        if self.has_tolerance and self.lib.has_pack and not getattr(self.lib, "has_tree_tol", False):
+            raise _capi.EngineError("TableauPack: %s does not export the tolerance extension (include/jslpg_tree_tolerance.h)" % self.lib.path)
         if self.has_incremental and self.lib.has_pack and not getattr(self.lib, "has_tree_inc", False):
             raise _capi.EngineError("TableauPack: %s does not export the incremental tree extension (include/jslpi_tree_incremental.h)" % self.lib.path)
         if self.has_enhanced and self.lib.has_pack and not getattr(self.lib, "has_tree_enh", False):
@@ -1253,7 +1286,11 @@ class TableauPack:
             trees = [ptr(self.cut_rows), ptr(self.heap_cap)] if self.is_tree else []
             optional = ptr(self.n_optional) if self.has_optional else None
             flags = self.is_incremental.astype(np.int32)
-            if self.has_incremental:
+            if self.has_tolerance:
+                symbol = said = "jslpg_tree_pack_create"
+                tables = trees + [optional, ptr(self.row_extra), ptr(self.node_selection), ptr(self.branching), ptr(flags), ptr(self.max_checkpoints),
+                                  _capi.ptr_f64(self.tolerances), ptr(self.minimize)]
+            elif self.has_incremental:
                 symbol = said = "jslpi_tree_pack_create"
                 tables = trees + [optional, ptr(self.row_extra), ptr(self.node_selection), ptr(self.branching), ptr(flags), ptr(self.max_checkpoints)]
             elif self.has_enhanced:
@@ -1413,36 +1450,50 @@ class TableauPack:
         return out
 
     def _walk(self, i, t, check_cycles):
-        """the restatement's tree of LP i on its twin engine `t`: the LP's (tree, mir, enhanced, incremental) records"""
+        """the restatement's tree of LP i on its twin engine `t`: the LP's (tree, mir, enhanced, incremental, tolerance) records"""
         from . import branch_and_cut as bc
         from . import incremental_branch_and_cut as ibc
         none_mir, none_enh, none_inc = (0, 0, 0, 0, 0), (0,) * 8, (0,) * 8
+        t.simplexIters, t.bestPossibleEval = 0, 0.0  # (every call starts a Tableau.solve() of its own: tableau.ts:61, 87)
+        tol = {}
+        # (a NaN threshold -- 0 * Infinity -- is reported as THE quiet NaN, as jslpg_pack_read_tolerance reports it: its sign is the multiplier's whim)
+        canon = lambda x: float("nan") if x != x else x  # noqa: E731
+        tol_rec = lambda: (tol.get("best_possible", 0.0), canon(tol.get("threshold", 0.0)), tol.get("stopped", 0), tol.get("left", 0), 0, 0)  # noqa: E731
         if self.integers[i].shape[0] == 0:
             t.simplex(check_cycles=bool(check_cycles))
-            return (0, 0, t.last.height, 0, 0, 0), (0, 0, 1, 0, 0) if self.is_mir[i] else none_mir, none_enh, none_inc
-        model = _TreeModel(self.integers[i], check_cycles, mir=bool(self.is_mir[i]))
+            if self.is_tolerance[i]:  # (the kernel's one turn: the threshold of the root's turn, bestPossibleEval from its simplex)
+                tol.update(best_possible=float(t.bestPossibleEval), threshold=0.0 * self._factor(i))
+            return (0, 0, t.last.height, 0, 0, 0), (0, 0, 1, 0, 0) if self.is_mir[i] else none_mir, none_enh, none_inc, tol_rec()
+        model = _TreeModel(self.integers[i], check_cycles, mir=bool(self.is_mir[i]), tolerance=float(self.tolerances[i]),
+                           minimize=bool(self.minimize[i]))
         if self.is_enhanced[i]:  # the enhanced or the incremental service on the LP's twin, its stack and heap sharing heap_cap
             boxes = ibc.CountingContainers(heap_cap=int(self.heap_cap[i]), cut_rows=int(self.cut_rows[i]), max_nodes=self.max_nodes)
             selection, rule = self.policy(i)
             if self.is_incremental[i]:  # (its checkpoints are the engine's)
                 iterations, integral = ibc.incremental_branch_and_cut(t, model, node_selection=selection, branching=rule,
-                                                                      max_checkpoints=int(self.max_checkpoints[i]), containers=boxes)
+                                                                      max_checkpoints=int(self.max_checkpoints[i]), containers=boxes,
+                                                                      tolerance_out=tol)
                 inc_rec = (t.checkpoints_used, t.incremental_nodes, max(boxes.rows_high_water - t.height0, 0),
                            max(boxes.checkpoint_rows_high_water - t.height0, 0), 0, 0, 0, 0)
             else:
-                iterations, integral = ibc.enhanced_branch_and_cut(t, model, node_selection=selection, branching=rule, containers=boxes)
+                iterations, integral = ibc.enhanced_branch_and_cut(t, model, node_selection=selection, branching=rule, containers=boxes,
+                                                                   tolerance_out=tol)
                 inc_rec = none_inc
             return ((iterations, int(integral), t.last.height, boxes.pushes, boxes.high_water, boxes.cuts_high_water), none_mir,
-                    boxes.record() + (0, 0), inc_rec)
+                    boxes.record() + (0, 0), inc_rec, tol_rec())
         heap = bc.CountingHeap(heap_cap=int(self.heap_cap[i]), cut_rows=int(self.cut_rows[i]))
         counters = _MirCounters(t) if self.is_mir[i] else None
         try:
-            iterations, integral = bc.branch_and_cut(t, model, heap=heap, max_nodes=self.max_nodes)
+            iterations, integral = bc.branch_and_cut(t, model, heap=heap, max_nodes=self.max_nodes, tolerance_out=tol)
             return ((iterations, int(integral), t.last.height, heap.pushes, heap.high_water, heap.cuts_high_water),
-                    counters.record() if counters is not None else none_mir, none_enh, none_inc)
+                    counters.record() if counters is not None else none_mir, none_enh, none_inc, tol_rec())
         finally:
             if counters is not None:
                 counters.detach()
+
+    def _factor(self, i):
+        """acceptableThreshold / bestPossibleEval of LP i (branch-and-cut.ts:77-81)"""
+        return 1 + float(self.tolerances[i]) if self.minimize[i] else 1 - float(self.tolerances[i])
 
     def branch_and_cut(self, check_cycles=True):
         """Tableau.solve() of every LP under the default branch-and-cut service, each tree walked by its LP's workgroup inside ONE launch per
@@ -1458,7 +1509,9 @@ class TableauPack:
         heap_high_water counts stack and heap together and nodes_pushed the new branches.
         An incremental LP (`incremental=`) is walked under the incremental service, in the kernel as in the restatement
         (incremental_branch_and_cut.incremental_branch_and_cut with CountingContainers, the checkpoints being the twin engine's);
-        `incremental` keeps its counters; a row that does not fit its row capacity is the capacity `row_extra`."""
+        `incremental` keeps its counters; a row that does not fit its row capacity is the capacity `row_extra`.
+        An LP with a tolerance (`tolerance=`) ends its walk on the reference's toleranceFlag, in the kernel as in the restatement (the three
+        host walks with the LP's tolerance and sense); `tolerance` keeps its record."""
         if not self.is_tree:
             raise _capi.EngineError("TableauPack.branch_and_cut: the pack was made without `integers`")
         flags = self._flags(check_cycles)
@@ -1467,13 +1520,14 @@ class TableauPack:
         mir = self.mir.copy()
         enhanced = self.enhanced.copy()
         incremental = self.incremental.copy()
+        tolerance = self.tolerance.copy()
         status = np.zeros(self.n, dtype=np.int32)
         if self._twins is not None:
             from . import branch_and_cut as bc
             rc, msg = _capi.JSLP_OK, ""
             for i, (t, c) in enumerate(zip(self._twins, flags)):
                 try:
-                    tree[i], mir[i], enhanced[i], incremental[i] = self._walk(i, t, c)
+                    tree[i], mir[i], enhanced[i], incremental[i], tolerance[i] = self._walk(i, t, c)
                     res = SimplexResult.from_buffer_copy(bytes(t.last))
                     res.evaluation = t.evaluation
                     out[i] = np.frombuffer(res, dtype=_capi.RESULT_DTYPE)[0]
@@ -1500,7 +1554,11 @@ class TableauPack:
                 self.lib.check(self.lib.jslpe_pack_read_enhanced(self._h, enhanced.ctypes.data), "jslpe_pack_read_enhanced")
             if self.has_incremental:
                 self.lib.check(self.lib.jslpi_pack_read_incremental(self._h, incremental.ctypes.data), "jslpi_pack_read_incremental")
-        self.tree, self.mir, self.enhanced, self.incremental = tree, mir, enhanced, incremental
+            if self.has_tolerance:
+                self.lib.check(self.lib.jslpg_pack_read_tolerance(self._h, tolerance.ctypes.data), "jslpg_pack_read_tolerance")
+            else:  # (zeros for every LP that was solved, as the read-back and the restatement give an LP without tolerance)
+                tolerance[status == _capi.JSLP_OK] = np.zeros((), dtype=_capi.TOL_TREE_DTYPE)
+        self.tree, self.mir, self.enhanced, self.incremental, self.tolerance = tree, mir, enhanced, incremental, tolerance
         return self._keep(out, status, rc, msg, "jslpt_pack_branch_and_cut")
 
     def policy(self, i):

@@ -146,32 +146,37 @@ def _select_branching_variable(model, rhs, rows, precision, branching, pseudo, s
     return best[0], best[1]
 
 
-def enhanced_branch_and_cut(tableau, model, node_selection="hybrid", branching="pseudocost", containers=None):
+def enhanced_branch_and_cut(tableau, model, node_selection="hybrid", branching="pseudocost", containers=None, tolerance_out=None,
+                            _late_stop=True):
     """createEnhancedBranchAndCutService (src/tableau/enhanced-branch-and-cut.ts:58-437), the service `Solve` picks for
     `options.nodeSelection` / `options.branching` (src/main.ts:74-80): the same tree walk as the incremental service
     with every node evaluated from the saved root (no checkpoints) and the "strong" branching rule.
-    containers: a CountingContainers to walk the tree with (it instruments the walk and enforces a device-side tree's capacities)."""
+    containers: a CountingContainers to walk the tree with (it instruments the walk and enforces a device-side tree's capacities).
+    tolerance_out, _late_stop: as branch_and_cut.branch_and_cut's."""
     return incremental_branch_and_cut(tableau, model, node_selection=node_selection, branching=branching, max_checkpoints=0,
-                                      incremental_rules=False, containers=containers)
+                                      incremental_rules=False, containers=containers, tolerance_out=tolerance_out, _late_stop=_late_stop)
 
 
 def incremental_branch_and_cut(tableau, model, node_selection="hybrid", branching="pseudocost", max_checkpoints=50,
-                               incremental_rules=True, containers=None):
+                               incremental_rules=True, containers=None, tolerance_out=None, _late_stop=True):
     """branchAndCut (:283-495).  Leaves `tableau` holding the incumbent; returns (iterations, found_integral).
     `tableau.checkpoints_used` / `tableau.incremental_nodes` report how many checkpoints were taken and how many
     nodes started from one.  incremental_rules=False: the enhanced service's variant of the two places where the
     services differ (which branching rules exist; both update pseudocosts from the node's last cut).
     containers: a CountingContainers whose stack and heap the walk uses (None: plain ones, nothing counted, no capacity).
-    The checkpoints go back to the engine when the walk ends, also when a capacity (TreeCapacity, the engine's row capacity) ends it."""
+    The checkpoints go back to the engine when the walk ends, also when a capacity (TreeCapacity, the engine's row capacity) ends it.
+    tolerance_out, _late_stop: as branch_and_cut.branch_and_cut's (left counts stack and heap together)."""
     checkpoints = []
     try:
-        return _walk(tableau, model, node_selection, branching, max_checkpoints, incremental_rules, containers, checkpoints)
+        return _walk(tableau, model, node_selection, branching, max_checkpoints, incremental_rules, containers, checkpoints, tolerance_out,
+                     _late_stop)
     finally:
         for c in checkpoints:
             tableau.releaseCheckpoint(c)
 
 
-def _walk(tableau, model, node_selection, branching, max_checkpoints, incremental_rules, containers, checkpoints):
+def _walk(tableau, model, node_selection, branching, max_checkpoints, incremental_rules, containers, checkpoints, tolerance_out=None,
+          _late_stop=True):
     cc = containers
     heap = cc.heap if cc is not None else BranchMinHeap()     # entries carry the _Branch in the `cuts` position
     stack = cc.stack if cc is not None else []
@@ -204,6 +209,13 @@ def _walk(tableau, model, node_selection, branching, max_checkpoints, incrementa
     else:
         heap.push(root.relaxed, root)
 
+    def report(threshold):
+        if tolerance_out is not None and tolerance > 0:
+            stopped = not tolerance_flag and (len(stack) > 0 if use_depth_first else len(heap) > 0)
+            tolerance_out.update(best_possible=float(tableau.bestPossibleEval), threshold=float(threshold), stopped=int(stopped),
+                                 left=len(stack) + len(heap) if stopped else 0)
+
+    acceptable = 0.0
     while (len(stack) > 0 if use_depth_first else len(heap) > 0) and tolerance_flag and time.time() * 1000.0 < terminal_time:
         if model.isMinimization:
             acceptable = tableau.bestPossibleEval * (1 + tolerance)
@@ -211,6 +223,8 @@ def _walk(tableau, model, node_selection, branching, max_checkpoints, incrementa
             acceptable = tableau.bestPossibleEval * (1 - tolerance)
         if tolerance > 0 and best_evaluation < acceptable:
             tolerance_flag = False
+            if not _late_stop:
+                break
         if use_depth_first and stack:
             branch = stack.pop()
         elif len(heap) > 0:
@@ -271,6 +285,7 @@ def _walk(tableau, model, node_selection, branching, max_checkpoints, incrementa
                 cc.solutions_found += 1
             if iterations == 1:
                 tableau.checkpoints_used, tableau.incremental_nodes = 0, 0
+                report(acceptable)
                 return iterations, True
             best_branch = branch
             best_evaluation = evaluation
@@ -333,10 +348,13 @@ def _walk(tableau, model, node_selection, branching, max_checkpoints, incrementa
                 else:
                     heap.push(b_high.relaxed, b_high)
                     heap.push(b_low.relaxed, b_low)
+    report(acceptable)
     if best_branch is not None:
         _res, rhs, vibr = tableau.applyCuts(best_branch.cuts, check_cycles=check)  # :491-493, always from the root
         mir_loop(tableau, model, rhs, vibr, check, max_rounds=3, need_feasible=True)  # :228-243
         if cc is not None:
             cc.rows_high_water = max(cc.rows_high_water, tableau.last.height)
     tableau.checkpoints_used, tableau.incremental_nodes = checkpoint_count, incremental_nodes
+    if tolerance_out:  # (the final re-evaluation is a simplex like any other: tableau.ts:420-430)
+        tolerance_out["best_possible"] = float(tableau.bestPossibleEval)
     return iterations, found_integral

@@ -86,38 +86,40 @@ class _PackedLp:
         return self._pack.read_rhs(self._i)
 
 
-def _tree_in_scope(m):
+def _tree_in_scope(m, tolerance=False):
     """whether the default branch-and-cut service alone decides this model's result, with nothing that needs the host or a clock
-    (include/jslpt_tree.h)"""
-    return not m.useMIRCuts and _mir_tree_in_scope(m)
+    (include/jslpt_tree.h).  tolerance=True (all four scope tests): options.tolerance keeps no model out -- the tree kernel honours it
+    (include/jslpg_tree_tolerance.h)"""
+    return not m.useMIRCuts and _mir_tree_in_scope(m, tolerance)
 
 
-def _mir_tree_in_scope(m):
+def _mir_tree_in_scope(m, tolerance=False):
     """_tree_in_scope whatever options.useMIRCuts says: the default service's MIR loop runs in the tree kernel too (include/jslpc_tree_mir.h)"""
     o = m.options
-    return not (o.get("useIncremental") is True or o.get("nodeSelection") or o.get("branching") or m.tolerance or m.timeout or m.keep_solutions)
+    return not (o.get("useIncremental") is True or o.get("nodeSelection") or o.get("branching") or (m.tolerance and not tolerance) or m.timeout
+                or m.keep_solutions)
 
 
-def _enhanced_tree_in_scope(m):
+def _enhanced_tree_in_scope(m, tolerance=False):
     """whether the ENHANCED service alone decides this model's result (main.ts:74-80: options.nodeSelection and/or options.branching, no
     useIncremental), with nothing that needs the host or a clock and without its own MIR loop (include/jslpe_tree_enhanced.h)"""
     o = m.options
     if (o.get("nodeSelection") or "hybrid") not in _capi.ENH_NODE_SELECTION or (o.get("branching") or "pseudocost") not in _capi.ENH_BRANCHING:
         return False  # (a name the service does not know: Solve walks it as the reference does)
-    return bool(o.get("nodeSelection") or o.get("branching")) and not (o.get("useIncremental") is True or m.useMIRCuts or m.tolerance or m.timeout
-                                                                       or m.keep_solutions)
+    return bool(o.get("nodeSelection") or o.get("branching")) and not (o.get("useIncremental") is True or m.useMIRCuts or (m.tolerance and not tolerance)
+                                                                       or m.timeout or m.keep_solutions)
 
 
-def _incremental_tree_in_scope(m):
+def _incremental_tree_in_scope(m, tolerance=False):
     """whether the INCREMENTAL service alone decides this model's result (main.ts:62-72: options.useIncremental), with nothing that needs
     the host or a clock and without its MIR loop (include/jslpi_tree_incremental.h)"""
     o = m.options
     if (o.get("nodeSelection") or "hybrid") not in _capi.ENH_NODE_SELECTION or (o.get("branching") or "pseudocost") not in _capi.ENH_BRANCHING:
         return False  # (a name the service does not know: Solve walks it as the reference does)
-    return o.get("useIncremental") is True and not (m.useMIRCuts or m.tolerance or m.timeout or m.keep_solutions)
+    return o.get("useIncremental") is True and not (m.useMIRCuts or (m.tolerance and not tolerance) or m.timeout or m.keep_solutions)
 
 
-def solve_packed(models, precision=None, lib=None, device=0, incremental=False):
+def solve_packed(models, precision=None, lib=None, device=0, incremental=False, tolerance=False):
     """[Solve(m, precision, lib=lib, device=device) for m in models], in order, for the workload of many SMALL models.  Every model
     whose tableau -- with its optional objectives, one row per soft constraint priority, when it has any (include/jslps_soft.h) -- fits the
     pack's LDS limit goes through an engine.TableauPack -- one arena, one upload, one launch per kernel build (64 or 256 threads, each with
@@ -140,6 +142,10 @@ def solve_packed(models, precision=None, lib=None, device=0, incremental=False):
         row_extra, which a chain of checkpoints fills one row per level.  The checkpoint arenas of one pack stay within
         PACK_CHECKPOINT_BYTES: the incremental LPs beyond that go into a following pack.  Without the keyword such a model goes through
         Solve.
+      * tolerance=True (opt-in): options.tolerance keeps a model out of none of the four tree routes above: its LP carries the tolerance and
+        the model's sense into the pack, and its walk ends on the reference's toleranceFlag inside the kernel, one node late as the
+        reference's does (include/jslpg_tree_tolerance.h).  options.timeout (a clock) and keep_solutions still keep a model out.  Without
+        the keyword a model with a tolerance goes through Solve.
     Every other model goes through Solve as it is.  A model Solve rejects raises the same exception before anything is solved."""
     lib = lib if lib is not None else _capi.load_hip()
     models = list(models)
@@ -159,20 +165,20 @@ def solve_packed(models, precision=None, lib=None, device=0, incremental=False):
         if n_int == 0:
             if pack_fits(*matrix.shape, lib=lib, n_optional=n_opt):
                 packed.append(k)
-        elif _tree_in_scope(m):
+        elif _tree_in_scope(m, tolerance):
             cut_rows = tree_cut_rows(matrix.shape[0], matrix.shape[1], n_int, lib=lib, n_optional=n_opt)
             if cut_rows >= 1:
                 trees.append((k, cut_rows, -1))
-        elif m.useMIRCuts and n_opt == 0 and _mir_tree_in_scope(m):
+        elif m.useMIRCuts and n_opt == 0 and _mir_tree_in_scope(m, tolerance):
             row_extra, cut_rows = tree_mir_rows(matrix.shape[0], matrix.shape[1], n_int, lib=lib)
             if row_extra >= 1:
                 trees.append((k, cut_rows, row_extra))
-        elif n_opt == 0 and _enhanced_tree_in_scope(m):
+        elif n_opt == 0 and _enhanced_tree_in_scope(m, tolerance):
             cut_rows = tree_cut_rows(matrix.shape[0], matrix.shape[1], n_int, lib=lib)
             if cut_rows >= 1:
                 trees.append((k, cut_rows, -1))
                 policies[k] = (m.options.get("nodeSelection") or None, m.options.get("branching") or None)
-        elif incremental and n_opt == 0 and _incremental_tree_in_scope(m):
+        elif incremental and n_opt == 0 and _incremental_tree_in_scope(m, tolerance):
             row_extra, cut_rows = incremental_rows(matrix.shape[0], matrix.shape[1], n_int, lib=lib)
             if row_extra >= 1:
                 trees.append((k, cut_rows, row_extra))
@@ -226,6 +232,7 @@ def _solve_tree_pack(trees, parsed, optional, lib, device, results, policies, in
     if trees:
         with_mir = any(e >= 0 and k not in inc for k, _, e in trees)
         with_inc = any(k in inc for k, _, _ in trees)
+        with_tol = any(parsed[k][0].tolerance for k, _, _ in trees)  # (solve_packed(tolerance=True) alone lets such a model in)
         pack = TableauPack([(parsed[k][1], parsed[k][2], parsed[k][3], parsed[k][0].unrestricted) for k, _, _ in trees],
                            precision=[parsed[k][0].precision for k, _, _ in trees], lib=lib, device=device,
                            integers=[[v["index"] for v in parsed[k][0].integerVariables] for k, _, _ in trees], cut_rows=[c for _, c, _ in trees],
@@ -235,7 +242,9 @@ def _solve_tree_pack(trees, parsed, optional, lib, device, results, policies, in
                            row_extra=[e for _, _, e in trees] if with_mir or with_inc else None,
                            incremental=[k in inc for k, _, _ in trees] if with_inc else None, max_checkpoints=TREE_MAX_CHECKPOINTS,
                            node_selection=[policies.get(k, (None, None))[0] for k, _, _ in trees],
-                           branching=[policies.get(k, (None, None))[1] for k, _, _ in trees])
+                           branching=[policies.get(k, (None, None))[1] for k, _, _ in trees],
+                           tolerance=[parsed[k][0].tolerance or None for k, _, _ in trees] if with_tol else None,
+                           minimize=[bool(parsed[k][0].isMinimization) for k, _, _ in trees] if with_tol else None)
         try:
             try:
                 pack.branch_and_cut(check_cycles=[parsed[k][0].checkForCycles for k, _, _ in trees])
