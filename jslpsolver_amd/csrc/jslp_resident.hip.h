@@ -152,7 +152,7 @@ struct RSmem {
     double colb[2][JSLP_R_MAXROWS];
     double rhsb[JSLP_R_MAXROWS];
     u64_t part_k[JSLP_F_MAXG / 64];
-    int32_t part_r[JSLP_F_MAXG / 64], part_rdeg[JSLP_F_MAXG / 64];
+    int32_t part_r[JSLP_F_MAXG / 64], part_rdeg[JSLP_F_MAXG / 64];  // (lean pipelined loops: part_r[0] = the polling wave's winner, part_r[1] = its verdict on the gather itself -- one 8-byte word, gather_post / gather_close)
     double xq2[2];
     double ook[2][4];  // the optional objectives' entries of the pivot column, broadcast with quot (OPT builds of the lean kernel)
     // All-gather protocol: what only workgroup 0 knows in the gather-by-leader protocol lives in EVERY workgroup's LDS -- the

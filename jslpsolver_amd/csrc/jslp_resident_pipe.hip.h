@@ -31,12 +31,18 @@
 //   * four waves poll (lane w = workgroup w, one 16-byte sc1 load each) and reduce their 64 summaries in registers (DPP);
 //     the four partial results meet in LDS under the barrier that also drains the row stores: no separate decision stage;
 //   * pricing moved to the top of the loop (the loop is entered with the tableau whole and leaves a pending update to its epilogue);
-//   * 6 workgroup barriers per pivot instead of 8 (cycle check off).
+//   * 6 barrier SITES per pivot instead of 8 (cycle check off) -- the one that closes the gather was the runtime's voting barrier
+//     `__syncthreads_and`, which the compiler expands to three `s_barrier`: see the barrier diet below.
 //
 // Round 6 (profiles/r06_headline_sections.md): the 2- / 4-column geometries with <= 8 rows per workgroup publish the candidate row already NORMALISED, with
 // quot and the cost row's new entry in a checksummed 32-byte record (NPUB: no division and no barrier between the row fetch and the next pricing); ONE wave polls
 // the summaries, four looks per lane; the pricing's reduction words are double-buffered by pivot parity; workgroup 0's global commit follows one iteration
-// later as fire-and-forget stores; 5 workgroup barriers per pivot.
+// later as fire-and-forget stores; 5 barrier sites per pivot (three in the pricing, the summary's, the gather's) -- in the ISA of the headline instance SEVEN
+// `s_barrier`, the gather's voting barrier being three of them.
+// Barrier diet (profiles/barrier_diet.md), the 8-row geometries with 2 / 4 columns per lane: the gather closes in ONE plain barrier (gather_post / gather_close:
+// the polling wave's verdict travels with the winner) -- FIVE `s_barrier` per pivot in the ISA.  The tall / wide geometries keep the voting barrier and
+// their seven (they sit at their register limit: PipeDiet).  Measured with it and left out (profiles/barrier_diet_rejected.patch): the pricing in two
+// atomic rounds on packed keys (-2.3 % alone, -1.5 % on top of the one-barrier gather) and the iteration cap / ld pinned in front of the loops (level).
 // (The lab notebook of these loops -- every variant measured and left out, with its numbers -- lives in profiles/r02_r04_measurement_log.md (rounds 3 and 4)
 //  and profiles/r06_headline_sections.md (round 6); the rejected variants' code is profiles/r06_rejected_switches.patch.)
 // ===================================================================================================================
@@ -206,6 +212,40 @@ __device__ __forceinline__ u64_t u64_wave_add_halves(u64_t x) {
 }
 // a lane's checksum -> the wave's word
 #define JSLP_CK_WAVE(CK) u64_wave_add_halves((CK) * (u64_t)(unsigned)(2 * tid + 1))
+
+// ---- the barrier that closes the gather (both pipelined loops) --------------------------------------------------------------------------
+// `swept` -- did the looks at the summaries come home, or did the poll give up / the host ask for an abort? -- is written by the ONE polling
+// wave only; for every other thread it is the constant `true`.  So the workgroup's vote is that wave's bit: its lane 0 stores the bit next to
+// the winner it stores anyway (sm.part_r[0] / [1]: one 8-byte word), ONE plain barrier follows and every thread reads winner and verdict in one
+// LDS read.  As `__syncthreads_and(swept)` the runtime's voting barrier cost every wave, at every pivot and behind the slowest workgroup's
+// summary, a load of the block dimensions from the dispatch packet with its wait, an LDS write, a barrier, a five-step DPP fold, an LDS atomic,
+// a barrier, an LDS read and a third barrier (profiles/barrier_diet.md; the node kernels dropped it in round 2: jslp_wglds.hip.h).
+// The word is rewritten by the next pivot's polling wave, behind that pivot's pricing and summary barriers: every reader is long past it.
+static_assert(offsetof(RSmem, part_r) % 8 == 0 && JSLP_F_MAXG / 64 >= 2, "winner and verdict are one aligned 8-byte word");
+// (the 8-row geometries with 2 / 4 columns per lane, as ONE_FOLD.  The tall / wide instances sit at their register limit: built with this AND the two-round
+//  pricing of profiles/barrier_diet_rejected.patch, <512,4,16> with unrestricted variables, <512,6,12> and <512,8,8> with optional objectives gained 4-12 bytes
+//  of scratch per lane; they were not built with this alone and keep the voting barrier)
+template <int CPT, int ROWS>
+struct PipeDiet {
+    static constexpr bool ONE_BARRIER = ROWS <= 8 && CPT <= 4;
+};
+template <bool ONE>
+__device__ __forceinline__ void gather_post(RSmem& sm, int winner, bool swept) {  // lane 0 of the polling wave, in front of the barrier
+    if (ONE) *reinterpret_cast<int2*>(&sm.part_r[0]) = make_int2(winner, swept ? 1 : 0);
+    else sm.part_r[0] = winner;
+}
+template <bool ONE>
+__device__ __forceinline__ bool gather_close(RSmem& sm, bool swept, int* winner) {  // every thread; false: the gather failed (uniform)
+    if (ONE) {
+        __syncthreads();
+        const int2 v = *reinterpret_cast<const int2*>(&sm.part_r[0]);
+        *winner = v.x;
+        return v.y != 0;
+    }
+    const bool ok = __syncthreads_and(swept ? 1 : 0) != 0;
+    *winner = sm.part_r[0];
+    return ok;
+}
 
 // ---- pricing of the lean pipelined phase 2 (simplex.ts:118-219), round 6 -------------------------------------------------------------------
 // price_row_lds's three LDS-atomic rounds (first batch holding a candidate, best value in it, first column with that value) on reduction words
@@ -1092,19 +1132,20 @@ __device__ __forceinline__ void resident_phase2_pipe(const ResCtx& f, RSmem& sm,
                        min(__builtin_amdgcn_readlane(rdeg, 32), __builtin_amdgcn_readlane(rdeg, 48)));
             }
             x = ki_wave_min(x);
-            if (lane == 0) { sm.part_k[0] = x.k; sm.part_r[0] = x.k == KI_NONE_KEY ? 0 : x.i; if (!ONE_FOLD) sm.part_rdeg[0] = rdeg; }
+            // (the gather's own verdict -- did the looks come home? -- travels with the winner: `swept` is the polling wave's alone, wave-uniform)
+            if (lane == 0) { sm.part_k[0] = x.k; gather_post<PipeDiet<CPT, ROWS>::ONE_BARRIER>(sm, x.k == KI_NONE_KEY ? 0 : x.i, swept); if (!ONE_FOLD) sm.part_rdeg[0] = rdeg; }
         }
         RT_STAMP(2);  // my wave's 64 summaries are in
         RT_MARK(1);
         if (!TAGGED && !CKS) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every wave: my stores of the candidate row have reached the L2 (the winner's release below builds on it; XL / winner-only: the row carries its tags)
-        const int all_swept = __syncthreads_and(swept ? 1 : 0);
-        if (!all_swept) { R.end_code = 5; break; }
+        int wr;
+        if (!gather_close<PipeDiet<CPT, ROWS>::ONE_BARRIER>(sm, swept, &wr)) { R.end_code = 5; break; }
         RT_STAMP(3);  // gather closed
         RT_MARK(3);
-        // ---- D: every thread reads the polling wave's verdict ------------------------------------------------------------------
+        // ---- D: every thread has read the polling wave's verdict ----------------------------------------------------------------
         int pr = 0, stop = 0;
         {
-            const int wr = sm.part_r[0], wrdeg = ONE_FOLD ? 0x7fffffff : sm.part_rdeg[0];  // (ONE_FOLD: a degenerate winner is part_r itself)
+            const int wrdeg = ONE_FOLD ? 0x7fffffff : sm.part_rdeg[0];  // (ONE_FOLD: a degenerate winner is part_r itself)
             if (wrdeg != 0x7fffffff) pr = wrdeg;
             else if (wr != 0) pr = wr;
             else stop = 3;  // unbounded (simplex.ts:298-303)
@@ -1605,15 +1646,14 @@ __device__ __forceinline__ void resident_phase1_pipe(const ResCtx& f, RSmem& sm,
                 x = ki_min(x, y);
             }
             x = ki_wave_min(x);
-            if (lane == 0) { sm.part_k[0] = x.k; sm.part_r[0] = x.k == KI_NONE_KEY ? 0 : x.i; }
+            if (lane == 0) { sm.part_k[0] = x.k; gather_post<PipeDiet<CPT, ROWS>::ONE_BARRIER>(sm, x.k == KI_NONE_KEY ? 0 : x.i, swept); }
         }
         RT_MARK(1);
         if (!TAGGED && !CKS) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every wave: my stores of the candidate row have reached the L2
-        const int all_swept = __syncthreads_and(swept ? 1 : 0);
-        if (!all_swept) { R.end_code = 5; break; }
+        int pr;  // (the polling wave's verdict)
+        if (!gather_close<PipeDiet<CPT, ROWS>::ONE_BARRIER>(sm, swept, &pr)) { R.end_code = 5; break; }
         RT_MARK(3);
         // ---- D ---------------------------------------------------------------------------------------------------------------
-        const int pr = sm.part_r[0];  // (the polling wave's verdict)
         if (pr == 0) { done = true; break; }  // no violated row: feasible (simplex.ts:51-54); uniform
         const bool leaving_unr = UNR && sm.lunr[sm.lvibr[pr]] != 0;  // (see phase 2)
         // ---- the winner releases its row (see phase 2) ---------------------------------------------------------------------------
