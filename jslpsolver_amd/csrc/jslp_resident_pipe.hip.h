@@ -43,6 +43,13 @@
 // the polling wave's verdict travels with the winner) -- FIVE `s_barrier` per pivot in the ISA.  The tall / wide geometries keep the voting barrier and
 // their seven (they sit at their register limit: PipeDiet).  Measured with it and left out (profiles/barrier_diet_rejected.patch): the pricing in two
 // atomic rounds on packed keys (-2.3 % alone, -1.5 % on top of the one-barrier gather) and the iteration cap / ld pinned in front of the loops (level).
+// Serial-chain diet (profiles/serial_chain_diet.md), the same 8-row geometries: the ISA of the pricing rounds was not what the source said -- LLVM's atomic optimizer
+// turned `if (cand) atomicMax(&lds, bits)` into a scalar loop over the candidate lanes (~14 instructions per lane for the 64-bit maximum, ~7 for the 32-bit minimum)
+// + a v_mbcnt election + ONE single-lane ds_max_u64 / ds_min_i32, in exactly the waves the next barrier waits for.  The rounds' atomics now leave as the candidate
+// lanes' own ds_* (lds_max_u64_raw / lds_min_i32_raw, drained by lds_raw_drain in front of the barrier): rounds 1 / 2 / 3 of the headline instance go from 20 / 16 / 7
+// vector and 21 / 27 / 14 scalar instructions to 17 / 9 / 3 and 20 / 16 / 5, no loop: config 3a 219.0 k -> 223.6 k pivots/s (+2.1 %).  Measured with it and left out
+// (profiles/serial_chain_diet_rejected.patch): column 0's LDS mirror kept by the ratio-test wave instead of wave 0 in step N (-1.6 %: the work moved INTO the one wave
+// the summary waits for) and the winner's workgroup as a multiply-shift with the fetch's winner-independent address terms in front of the gather's barrier (-0.4 %).
 // (The lab notebook of these loops -- every variant measured and left out, with its numbers -- lives in profiles/r02_r04_measurement_log.md (rounds 3 and 4)
 //  and profiles/r06_headline_sections.md (round 6); the rejected variants' code is profiles/r06_rejected_switches.patch.)
 // ===================================================================================================================
@@ -228,7 +235,22 @@ static_assert(offsetof(RSmem, part_r) % 8 == 0 && JSLP_F_MAXG / 64 >= 2, "winner
 template <int CPT, int ROWS>
 struct PipeDiet {
     static constexpr bool ONE_BARRIER = ROWS <= 8 && CPT <= 4;
+    // serial-chain diet (profiles/serial_chain_diet.md), the same instances: the pricing's LDS atomics issued by the candidate lanes themselves (lds_*_raw below)
+    static constexpr bool RAW_ATOMICS = ROWS <= 8 && CPT <= 4;
 };
+
+// ---- LDS atomics as the hardware has them ------------------------------------------------------------------------------------------------
+// `atomicMax(&lds_word, x)` under a divergent `if` is rewritten by LLVM's atomic optimizer: a scalar loop over the active lanes (s_ff1, two
+// v_readlane, a 64-bit compare, two s_cselect and the mask bookkeeping: ~14 instructions per lane for the u64 maximum, ~7 for the i32 minimum),
+// then v_mbcnt, a compare, a second s_and_saveexec and ONE single-lane ds_max_u64 / ds_min_i32 -- in exactly the waves the next barrier waits
+// for, the ones that hold candidates.  Maximum and minimum do not depend on order: issued by the candidate lanes themselves, under their own
+// EXEC mask, the LDS unit leaves the same word.  The compiler does not count LDS operations of inline assembly, so the barrier that follows
+// needs lds_raw_drain() in front of it.  (Config 3a: 1.64 lanes per round-2 on average, 8 at the 99th percentile, 26 -- a whole batch of 50
+// columns -- at most; round 3 one lane, two at most: tools/pricing_lanes.py.)
+__device__ __forceinline__ unsigned lds_offset(const void* p) { return (unsigned)(size_t)(__attribute__((address_space(3))) const void*)p; }
+__device__ __forceinline__ void lds_max_u64_raw(u64_t* p, u64_t v) { asm volatile("ds_max_u64 %0, %1" : : "v"(lds_offset(p)), "v"(v) : "memory"); }
+__device__ __forceinline__ void lds_min_i32_raw(int32_t* p, int v) { asm volatile("ds_min_i32 %0, %1" : : "v"(lds_offset(p)), "v"(v) : "memory"); }
+__device__ __forceinline__ void lds_raw_drain() { asm volatile("s_waitcnt lgkmcnt(0)" : : : "memory"); }
 template <bool ONE>
 __device__ __forceinline__ void gather_post(RSmem& sm, int winner, bool swept) {  // lane 0 of the polling wave, in front of the barrier
     if (ONE) *reinterpret_cast<int2*>(&sm.part_r[0]) = make_int2(winner, swept ? 1 : 0);
@@ -256,7 +278,9 @@ __device__ __forceinline__ bool gather_close(RSmem& sm, bool swept, int* winner)
 //  pivots, that wave folds value and column in registers and goes straight on to the ratio test, two barriers fewer: 163.1 k against 179.1 k
 //  pivots/s on config 3a, profiles/r06_rejected_switches.patch.)
 // Returns the entering column (0: none -> optimal; uniform).
-template <int THREADS, int CPT, bool UNR>
+// RAW (PipeDiet::RAW_ATOMICS): the three rounds' atomics leave as ds_min_i32 / ds_max_u64 / ds_min_i32 of the lanes that take part, drained in front of
+// each barrier -- no scalar loop over the candidate lanes, no v_mbcnt election: +2.1 % on config 3a (profiles/serial_chain_diet.md)
+template <int THREADS, int CPT, bool UNR, bool RAW>
 __device__ __forceinline__ int price_row_pipe(const double (&x)[CPT], int c0, const int (&pb)[CPT], const Ctx& c, RSmem& sm, int par,
                                               double* value, unsigned unr, int* neg, bool* claim) {
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -279,9 +303,10 @@ __device__ __forceinline__ int price_row_pipe(const double (&x)[CPT], int c0, co
         if (m != 0ull) {
             const int first = __ffsll((long long)m) - 1;
             const int wave_b = __builtin_amdgcn_readlane(bb, first);
-            if (lane == 0) atomicMin(&sm.pw_batch[par], wave_b);
+            if (lane == 0) { if (RAW) lds_min_i32_raw(&sm.pw_batch[par], wave_b); else atomicMin(&sm.pw_batch[par], wave_b); }
         }
     }
+    if (RAW) lds_raw_drain();
     __syncthreads();
     const int wb = sm.pw_batch[par];
     if (tid == THREADS - 1) { sm.pw_batch[par ^ 1] = 0x7fffffff; sm.pw_val[par ^ 1] = 0; sm.pw_col[par ^ 1] = 0x7fffffff; }  // the NEXT pivot's words: last read two barriers ago, first used behind two more
@@ -289,10 +314,12 @@ __device__ __forceinline__ int price_row_pipe(const double (&x)[CPT], int c0, co
     if (wb == 0x7fffffff) return 0;  // uniform: no candidate anywhere -> optimal
     const u64_t bits = (u64_t)__double_as_longlong(bv);
     const bool cand = bi != 0 && bb == wb;
-    if (cand) atomicMax(&sm.pw_val[par], bits);
+    if (cand) { if (RAW) lds_max_u64_raw(&sm.pw_val[par], bits); else atomicMax(&sm.pw_val[par], bits); }
+    if (RAW) lds_raw_drain();
     __syncthreads();
     const u64_t wvv = sm.pw_val[par];
-    if (cand && bits == wvv) atomicMin(&sm.pw_col[par], bi);
+    if (cand && bits == wvv) { if (RAW) lds_min_i32_raw(&sm.pw_col[par], bi); else atomicMin(&sm.pw_col[par], bi); }
+    if (RAW) lds_raw_drain();
     __syncthreads();
     const int pcol = sm.pw_col[par];
     double v = __longlong_as_double((long long)wvv);
@@ -874,7 +901,7 @@ __device__ __forceinline__ void resident_phase2_pipe(const ResCtx& f, RSmem& sm,
         {
             int neg_now = 0;
             RT_STAMP(5);  // at the pricing
-            pc = price_row_pipe<THREADS, CPT, UNR>(r0, c0, pb, c, sm, par, &k0, R.unr, &neg_now, &claim);
+            pc = price_row_pipe<THREADS, CPT, UNR, PipeDiet<CPT, ROWS>::RAW_ATOMICS>(r0, c0, pb, c, sm, par, &k0, R.unr, &neg_now, &claim);
             RT_STAMP(6);  // priced
             JSLP_PIPE_SWAP_LDS_MAPS();  // (the pending pivot's basis change in my LDS maps: every wave is past its reads of them -- the pricing's barriers)
             if (UNR) R.neg = neg_now;  // isReducedCostNegative of the entering column (simplex.ts:164-177): the ratio test's sign
@@ -1420,6 +1447,7 @@ __device__ __forceinline__ void resident_phase1_pipe(const ResCtx& f, RSmem& sm,
     constexpr bool TAGGED = XL;                   // rows travel with their tags: 16 bytes per double
     constexpr bool CKS = !TAGGED && JSLP_PIPE_ROW_CHECKSUM != 0 && CPT <= JSLP_PIPE_ROW_CHECKSUM_MAXCPT;  // checksummed hand-over of the candidate rows (see JSLP_PIPE_ROW_CHECKSUM)
     constexpr int HAWV = 1;
+    constexpr bool RAW = PipeDiet<CPT, ROWS>::RAW_ATOMICS;  // step E1's two LDS atomics as the candidate lanes' own ds_max_u64 / ds_min_i32
     constexpr bool NPUB = false;  // (phase 1 knows its entering column only once the pivot row has arrived: the row travels as it is)
     const double quot_p = 1.0, pub_k0 = 0.0;
     const int pub_pc = 0;
@@ -1731,12 +1759,14 @@ __device__ __forceinline__ void resident_phase1_pipe(const ResCtx& f, RSmem& sm,
         const u64_t qkey = bi != 0 ? key_asc(bq) : 0ull;  // (key_asc > 0 for every double; -0 folded into +0: simplex.ts compares them equal)
         {
             const u64_t wmax = u64_wave_max(qkey);
-            if (lane == 0 && wmax != 0ull) atomicMax(&sm.p_val, wmax);
+            if (lane == 0 && wmax != 0ull) { if (RAW) lds_max_u64_raw(&sm.p_val, wmax); else atomicMax(&sm.p_val, wmax); }
         }
+        if (RAW) lds_raw_drain();
         __syncthreads();
         const u64_t wkey = sm.p_val;
         if (wkey == 0ull) { R.end_code = 7; break; }  // infeasible (simplex.ts:73-76); uniform
-        if (bi != 0 && qkey == wkey) atomicMin(&sm.p_col, bi);
+        if (bi != 0 && qkey == wkey) { if (RAW) lds_min_i32_raw(&sm.p_col, bi); else atomicMin(&sm.p_col, bi); }
+        if (RAW) lds_raw_drain();
         __syncthreads();
         const int pc = sm.p_col;
         const bool has_pc = colok && pc >= c0 && pc < c0 + CPT;
