@@ -50,6 +50,13 @@
 // vector and 21 / 27 / 14 scalar instructions to 17 / 9 / 3 and 20 / 16 / 5, no loop: config 3a 219.0 k -> 223.6 k pivots/s (+2.1 %).  Measured with it and left out
 // (profiles/serial_chain_diet_rejected.patch): column 0's LDS mirror kept by the ratio-test wave instead of wave 0 in step N (-1.6 %: the work moved INTO the one wave
 // the summary waits for) and the winner's workgroup as a multiply-shift with the fetch's winner-independent address terms in front of the gather's barrier (-0.4 %).
+// Two-round pricing (profiles/pricing_two_rounds.md), the 1024-lane instances <1024,2,8>: with the atomics issued by the lanes themselves the packed keys of
+// the barrier diet's rejected item win -- {127 - batch | value bits >> 6} as a ds_max_u64 of EVERY candidate lane, then {value bits & 63 | 65535 - column} as a
+// ds_max_u32 of the lanes that hold the first result: FOUR `s_barrier` per pivot in the ISA, round 3's segment gone: config 3a 223.9 k -> 229.6 k pivots/s
+// (+2.5 %).  Measured with it and left out (profiles/pricing_two_rounds_rejected.patch): round 1 restricted to the lanes of each wave's earliest batch (a third
+// of the atomics, six scalar instructions in front of them: 0.3-0.6 % below the unrestricted form in every run), the same two rounds in <512,4,8> (config 3a
+// through JSLP_RES_CPT=4, cycle check off, -1.4 %; +2.8 % with the check on) and the winner's workgroup as a multiply-shift with nothing hoisted (+0.2 % alone,
+// +0.5 % on top: inside three spreads).
 // (The lab notebook of these loops -- every variant measured and left out, with its numbers -- lives in profiles/r02_r04_measurement_log.md (rounds 3 and 4)
 //  and profiles/r06_headline_sections.md (round 6); the rejected variants' code is profiles/r06_rejected_switches.patch.)
 // ===================================================================================================================
@@ -237,6 +244,9 @@ struct PipeDiet {
     static constexpr bool ONE_BARRIER = ROWS <= 8 && CPT <= 4;
     // serial-chain diet (profiles/serial_chain_diet.md), the same instances: the pricing's LDS atomics issued by the candidate lanes themselves (lds_*_raw below)
     static constexpr bool RAW_ATOMICS = ROWS <= 8 && CPT <= 4;
+    // (profiles/pricing_two_rounds.md) phase 2 of the 1024-lane instances: the pricing in TWO such atomic rounds on packed keys instead of three (price_row_pipe).
+    // (<512,4,8> keeps the three: with two, config 3a through JSLP_RES_CPT=4 ran 183.9 k -> 181.4 k pivots/s, cycle check off, every run below the parent's)
+    static constexpr bool TWO_ROUNDS = ROWS <= 8 && CPT <= 2;
 };
 
 // ---- LDS atomics as the hardware has them ------------------------------------------------------------------------------------------------
@@ -250,6 +260,7 @@ struct PipeDiet {
 __device__ __forceinline__ unsigned lds_offset(const void* p) { return (unsigned)(size_t)(__attribute__((address_space(3))) const void*)p; }
 __device__ __forceinline__ void lds_max_u64_raw(u64_t* p, u64_t v) { asm volatile("ds_max_u64 %0, %1" : : "v"(lds_offset(p)), "v"(v) : "memory"); }
 __device__ __forceinline__ void lds_min_i32_raw(int32_t* p, int v) { asm volatile("ds_min_i32 %0, %1" : : "v"(lds_offset(p)), "v"(v) : "memory"); }
+__device__ __forceinline__ void lds_max_u32_raw(unsigned* p, unsigned v) { asm volatile("ds_max_u32 %0, %1" : : "v"(lds_offset(p)), "v"(v) : "memory"); }
 __device__ __forceinline__ void lds_raw_drain() { asm volatile("s_waitcnt lgkmcnt(0)" : : : "memory"); }
 template <bool ONE>
 __device__ __forceinline__ void gather_post(RSmem& sm, int winner, bool swept) {  // lane 0 of the polling wave, in front of the barrier
@@ -280,7 +291,17 @@ __device__ __forceinline__ bool gather_close(RSmem& sm, bool swept, int* winner)
 // Returns the entering column (0: none -> optimal; uniform).
 // RAW (PipeDiet::RAW_ATOMICS): the three rounds' atomics leave as ds_min_i32 / ds_max_u64 / ds_min_i32 of the lanes that take part, drained in front of
 // each barrier -- no scalar loop over the candidate lanes, no v_mbcnt election: +2.1 % on config 3a (profiles/serial_chain_diet.md)
-template <int THREADS, int CPT, bool UNR, bool RAW>
+// TWO (PipeDiet::TWO_ROUNDS, the 1024-lane instances; profiles/pricing_two_rounds.md): the order is lexicographic in (batch ascending, value descending, column ascending) and the
+// three parts fit two such atomics -- {127 - batch : 7 | value bits >> 6 : 57} as a 64-bit maximum, then {value bits & 63 : 6 | 65535 - column : 16} as a
+// 32-bit maximum among the lanes that hold the first round's result, which agree in batch and in every bit of the value above the low six: exact, and one
+// barrier, one atomic and one read-back fewer per pivot (FOUR `s_barrier` in the ISA).  EVERY lane that holds a candidate goes through round 1 -- ~106 of
+// the 1024 per pivot on config 3a, 13 in the busiest wave -- with no ballot, readlane or compare in front of its ds_max_u64: restricted to the lanes of
+// each wave's earliest batch (31 per pivot, 5 in the busiest wave) the round was 0.3-0.6 % SLOWER in every run: the LDS unit takes a wave's same-address
+// atomics faster than sixteen waves issue the six scalar instructions that spare them.  sm.pw_val[par] holds the first key, sm.pw_col[par] the second
+// (identity 0 both), sm.pw_batch is unused.  As atomicMax() through LLVM's scalar loop the same two rounds LOST 2.3 % (profiles/barrier_diet.md).
+#define JSLP_PW_BATCH_MAX 127       // the first key's batch field: 7 bits
+#define JSLP_PW_BATCH_SMALLEST 50  // the smallest partial-pricing batch the host ever sets (jslp_engine_create: min(500, max(50, floor(sqrt(columns)))))
+template <int THREADS, int CPT, bool UNR, bool RAW, bool TWO>
 __device__ __forceinline__ int price_row_pipe(const double (&x)[CPT], int c0, const int (&pb)[CPT], const Ctx& c, RSmem& sm, int par,
                                               double* value, unsigned unr, int* neg, bool* claim) {
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -297,6 +318,41 @@ __device__ __forceinline__ int price_row_pipe(const double (&x)[CPT], int c0, co
         bi = take ? col : bi;
         bb = take ? pb[j] : bb;
         bneg = take ? (isneg ? 1 : 0) : bneg;
+    }
+    if (TWO) {
+        static_assert(!TWO || RAW, "the two rounds are the lanes' own ds_max_u64 / ds_max_u32");
+        static_assert(!TWO || (THREADS * CPT - 1) / JSLP_PW_BATCH_SMALLEST <= JSLP_PW_BATCH_MAX, "more than 128 pricing batches: this geometry keeps the three-round form");
+        static_assert(!TWO || THREADS * CPT <= 0xffff, "the second key's column field: 16 bits");
+        // round 1: the earliest batch holding a candidate and the top 57 bits of the best value in it, one 64-bit maximum.  A candidate's value is a
+        // positive double above the precision (+Infinity included, NaN never: `val > precision`): its bit pattern is below 2^63, orders like the value,
+        // and its top 57 bits are not zero -- a key of 0 means "no candidate".
+        const u64_t bits = (u64_t)__double_as_longlong(bv);
+        const u64_t key1 = ((u64_t)(unsigned)(JSLP_PW_BATCH_MAX - bb) << 57) | (bits >> 6);
+        if (bi != 0) lds_max_u64_raw(&sm.pw_val[par], key1);
+        lds_raw_drain();
+        __syncthreads();
+        const u64_t w1 = sm.pw_val[par];
+        if (tid == THREADS - 1) { sm.pw_val[par ^ 1] = 0; sm.pw_col[par ^ 1] = 0; }  // the NEXT pivot's words: last read three barriers ago, first used behind three more
+        *claim = false;
+        if (w1 == 0ull) return 0;  // uniform: no candidate anywhere -> optimal
+        // round 2: the lanes whose batch and truncated value ARE the winner's agree in every higher bit, so the low 6 bits of the value, then the
+        // smaller column, decide among them exactly: one 32-bit maximum on {low 6 bits | 65535 - column}
+        const bool cand = bi != 0 && key1 == w1;
+        if (cand) lds_max_u32_raw(reinterpret_cast<unsigned*>(&sm.pw_col[par]), (((unsigned)bits & 63u) << 16) | (0xffffu - (unsigned)bi));
+        lds_raw_drain();
+        __syncthreads();
+        const unsigned w2 = (unsigned)sm.pw_col[par];
+        const int pcol = (int)(0xffffu - (w2 & 0xffffu));
+        double v = __longlong_as_double((long long)(((w1 & ((1ull << 57) - 1ull)) << 6) | (u64_t)(w2 >> 16)));
+        if (UNR) {  // the lane holding the winner knows the sign of its reduced cost
+            if (cand && bi == pcol) sm.pw_neg[par] = bneg;
+            __syncthreads();
+            *neg = sm.pw_neg[par];
+            if (*neg) v = -v;
+        }
+        *value = v;
+        *claim = wv == ((pcol / CPT) >> 6);
+        return pcol;
     }
     {   // batch ids grow with the lane index: the wave's earliest batch is that of its first candidate lane
         const unsigned long long m = __ballot(bi != 0);
@@ -876,7 +932,7 @@ __device__ __forceinline__ void resident_phase2_pipe(const ResCtx& f, RSmem& sm,
     if (tid == 0) {
 #pragma unroll
         for (int i = 0; i < ROWS; i++) sm.rhsb[i] = a[i][0];
-        for (int q = 0; q < 2; q++) { sm.pw_batch[q] = 0x7fffffff; sm.pw_val[q] = 0; sm.pw_col[q] = 0x7fffffff; sm.pw_neg[q] = 0; }
+        for (int q = 0; q < 2; q++) { sm.pw_batch[q] = 0x7fffffff; sm.pw_val[q] = 0; sm.pw_col[q] = PipeDiet<CPT, ROWS>::TWO_ROUNDS ? 0 : 0x7fffffff; sm.pw_neg[q] = 0; }
     }
     __syncthreads();
 
@@ -894,14 +950,14 @@ __device__ __forceinline__ void resident_phase2_pipe(const ResCtx& f, RSmem& sm,
             break;
         }
         RT_MARK(7);
-        // ---- G: price the cost row -> entering column (simplex.ts:118-219; three LDS-atomic rounds) -------------------------------
+        // ---- G: price the cost row -> entering column (simplex.ts:118-219; two LDS-atomic rounds in <1024,2,8>, three elsewhere) ----
         double k0 = 0.0;  // reduced cost of the entering column
         int pc;
         bool claim = false;  // (price_row_pipe: this wave holds the entering column and runs the ratio test)
         {
             int neg_now = 0;
             RT_STAMP(5);  // at the pricing
-            pc = price_row_pipe<THREADS, CPT, UNR, PipeDiet<CPT, ROWS>::RAW_ATOMICS>(r0, c0, pb, c, sm, par, &k0, R.unr, &neg_now, &claim);
+            pc = price_row_pipe<THREADS, CPT, UNR, PipeDiet<CPT, ROWS>::RAW_ATOMICS, PipeDiet<CPT, ROWS>::TWO_ROUNDS>(r0, c0, pb, c, sm, par, &k0, R.unr, &neg_now, &claim);
             RT_STAMP(6);  // priced
             JSLP_PIPE_SWAP_LDS_MAPS();  // (the pending pivot's basis change in my LDS maps: every wave is past its reads of them -- the pricing's barriers)
             if (UNR) R.neg = neg_now;  // isReducedCostNegative of the entering column (simplex.ts:164-177): the ratio test's sign

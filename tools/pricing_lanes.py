@@ -32,6 +32,34 @@ def stats(x):
     return "%.2f / %d / %d" % (x.mean(), int(np.percentile(x, 99)), x.max()) if len(x) else "-"
 
 
+def two_round_lanes(cost, cand, batch_of, lane_of):
+    """price_row_pipe's two-round form restated on its packed keys: round 1 is a 64-bit maximum of {127 - batch : 7 | value bits >> 6 : 57} over the
+    lanes' offers, round 2 a 32-bit maximum of {value bits & 63 : 6 | 65535 - column : 16} among the lanes whose first key won.  Returns the column
+    the two rounds name and the lanes that go through round 1 in either form (every lane with a candidate / the lanes of their wave's earliest
+    batch) and through round 2."""
+    ci = np.nonzero(cand)[0]
+    order = np.lexsort((ci, -cost[ci], batch_of[ci], lane_of[ci]))  # a lane's offer: earliest batch, larger value, first column
+    ci = ci[order]
+    ln = lane_of[ci]
+    first = np.r_[True, ln[1:] != ln[:-1]]
+    col, ln = ci[first], ln[first]
+    bits = np.ascontiguousarray(cost[col]).view(np.uint64)
+    bb = batch_of[col].astype(np.uint64)
+    assert bb.max() <= 127 and col.max() <= 0xffff
+    key1 = ((np.uint64(127) - bb) << np.uint64(57)) | (bits >> np.uint64(6))
+    wv = ln // 64
+    wave_first = np.r_[True, wv[1:] != wv[:-1]]  # (lanes ascend: a wave's first candidate lane holds its earliest batch)
+    wave_b = np.zeros(wv.max() + 1, dtype=np.uint64)
+    wave_b[wv[wave_first]] = bb[wave_first]
+    early = bb == wave_b[wv]
+    w1 = key1.max()
+    assert key1[early].max() == w1
+    second = key1 == w1
+    key2 = ((bits & np.uint64(63)) << np.uint64(16)) | (np.uint64(0xffff) - col.astype(np.uint64))
+    w2 = int(key2[second].max())
+    return 0xffff - (w2 & 0xffff), ln, ln[early], ln[second]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("kind", choices=("3a", "3b"))
@@ -58,7 +86,11 @@ def main():
     wave_of = lane_of // 64
     batch_of = np.where(cols >= 1, (cols - 1) // batch, 0) if partial else np.zeros(W, dtype=np.int64)
     r2, r3, r2w, r3w, p1, p1w = [], [], [], [], [], []
-    wrong = 0
+    # the two-round pricing (profiles/pricing_two_rounds.md): who goes through its FIRST round -- "all": every lane that holds a candidate;
+    # "earliest": the lanes whose offer lies in their own wave's earliest batch -- and who goes through its second (top 57 bits equal to the winner's)
+    t1 = {"all": ([], []), "earliest": ([], [])}
+    t2, t2w = [], []
+    wrong = wrong2 = 0
     buf = np.empty_like(M)
     for it, (pr, pc) in enumerate(trace):
         if it >= res.pivots_phase1:
@@ -78,6 +110,11 @@ def main():
             wrong += pick != pc
             r2.append(len(lanes2)); r3.append(len(lanes3))
             r2w.append(np.bincount(lanes2 // 64).max()); r3w.append(np.bincount(lanes3 // 64).max())
+            pick2, lanes_all, lanes_early, lanes_second = two_round_lanes(cost, cand, batch_of, lane_of)
+            wrong2 += pick2 != pc
+            for form, lanes in (("all", lanes_all), ("earliest", lanes_early)):
+                t1[form][0].append(len(lanes)); t1[form][1].append(np.bincount(lanes // 64).max())
+            t2.append(len(lanes_second)); t2w.append(np.bincount(lanes_second // 64).max())
         else:
             coef = M[pr]
             cand = (cols >= 1) & (coef < -prec)
@@ -117,7 +154,14 @@ def main():
     print("| %s n = %d | %d | %d (%d + %d) | %s | %s | %s | %s | %s | %s | %s | %s |" % (
         a.kind, a.n, a.cpt, len(trace), res.pivots_phase1, max(res.pivots_phase2, 0), stats(r2), stats(r2w), stats(r3), stats(r3w), stats(p1), stats(p1w),
         "every pivot" if wrong == 0 else "%d DIFFER" % wrong, "bit for bit" if same else "DIFFERS"))
-    return 0 if same and wrong == 0 else 1
+    if t2:
+        print()
+        print("| instance | columns per lane | two-round pricing: round 1 lanes per workgroup, every candidate lane: mean / p99 / max | ... in the busiest wave | round 1 lanes per workgroup, the waves' earliest batches | ... in the busiest wave | round 2 lanes per workgroup | ... in the busiest wave | entering column = oracle's |")
+        print("|---|---|---|---|---|---|---|---|---|")
+        print("| %s n = %d | %d | %s | %s | %s | %s | %s | %s | %s |" % (
+            a.kind, a.n, a.cpt, stats(t1["all"][0]), stats(t1["all"][1]), stats(t1["earliest"][0]), stats(t1["earliest"][1]), stats(t2), stats(t2w),
+            "every pivot" if wrong2 == 0 else "%d DIFFER" % wrong2))
+    return 0 if same and wrong == 0 and wrong2 == 0 else 1
 
 
 if __name__ == "__main__":
