@@ -19,7 +19,7 @@
  *   - a pack has no cut rows, no save / restore / relax, no work counters: none of them has an entry point here (optional
  *     objectives come through jslps_soft.h, cut rows and trees through jslpt_tree.h).  The one refusal a caller meets is the LDS
  *     limit: an LP whose LDS image (jslpp_lds_bytes) exceeds 64 KiB is refused at create with JSLP_ERR_UNSUPPORTED.  Such models
- *     go through a jslp_engine.
+ *     go through a jslp_engine -- or, up to 156 KiB, through a pack made with big_lds (jslpb_big_lds.h).
  *
  * Errors: argument and state errors are reported before any work, and then nothing is solved.  An LP that reaches its pivot cap or
  * its history capacity gets the engine's code (JSLP_ERR_CAPACITY) in status[i] and its out[i] is left as it was; every other LP is
@@ -78,7 +78,8 @@ int jslpp_pack_upload(jslpp_pack* p);
  * A second call without an upload continues from the final tableaus.
  */
 int jslpp_pack_simplex(jslpp_pack* p, const int32_t* check_cycles, jslp_simplex_result* out, int32_t* status, double* device_ms);
-/* kernel launches of the last jslpp_pack_simplex: 0, 1 or 2 -- up to 4 in a pack with optional objectives (jslps_soft.h) */
+/* kernel launches of the last jslpp_pack_simplex: 0, 1 or 2 -- up to 4 in a pack with optional objectives (jslps_soft.h), up to 6 with
+ * large LPs (jslpb_big_lds.h) */
 int32_t jslpp_pack_launches(const jslpp_pack* p);
 
 /*

@@ -1,7 +1,8 @@
 """ctypes binding of the C ABI declared in include/jslp_engine.h (SYMBOLS) and of its HIP-only extensions include/jslpx_branch.h
 (BRANCH_SYMBOLS), include/jslpm_many.h (MANY_SYMBOLS), include/jslpf_f32.h (F32_SYMBOLS), include/jslpr_mir.h (MIR_SYMBOLS) and
 include/jslpp_packed.h (PACK_SYMBOLS) with include/jslpt_tree.h (TREE_SYMBOLS), include/jslps_soft.h (SOFT_SYMBOLS) and
-include/jslpc_tree_mir.h (TREE_MIR_SYMBOLS) and include/jslpe_tree_enhanced.h (TREE_ENH_SYMBOLS).
+include/jslpc_tree_mir.h (TREE_MIR_SYMBOLS), include/jslpe_tree_enhanced.h (TREE_ENH_SYMBOLS), include/jslpi_tree_incremental.h
+(TREE_INC_SYMBOLS), include/jslpg_tree_tolerance.h (TREE_TOL_SYMBOLS) and include/jslpb_big_lds.h (BIG_SYMBOLS).
 
 The same binding class serves two libraries that export identical symbols:
   * jslpsolver_amd/csrc/libjslp_hip.so -- the product (hand-written HIP kernels, gfx950)
@@ -268,6 +269,14 @@ TREE_TOL_SYMBOLS = {
                                          _f64p, _i32p, C.c_int32, C.c_int32, C.c_int32]),
     "jslpg_pack_read_tolerance": (C.c_int, [C.c_void_p, C.c_void_p]),
 }
+# name -> (restype, argtypes); must list EVERY symbol include/jslpb_big_lds.h declares.  HIP library only (Library.has_big_lds).
+BIG_SYMBOLS = {
+    "jslpb_pack_create": (C.c_int, [_P(C.c_void_p), C.c_int, C.c_int32, _i32p, _i32p, _f64p, _i32p, C.c_int32, C.c_int32, C.c_int32]),
+    "jslpb_tree_pack_create": (C.c_int, [_P(C.c_void_p), C.c_int, C.c_int32, _i32p, _i32p, _f64p, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p,
+                                         _f64p, _i32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "jslpb_pack_big_threads": (C.c_int32, []),
+}
+JSLPB_LDS_LIMIT = 159744
 # numpy twin of struct jslpg_tolerance_result
 TOL_TREE_DTYPE = np.dtype([("best_possible", np.float64), ("threshold", np.float64), ("stopped", np.int32), ("left", np.int32),
                            ("reserved0", np.int32), ("reserved1", np.int32)])
@@ -318,6 +327,7 @@ class Library:
         self.has_tree_enh = self.has_tree_mir and self.has_soft and self._bind_extension(TREE_ENH_SYMBOLS)
         self.has_tree_inc = self.has_tree_enh and self._bind_extension(TREE_INC_SYMBOLS)
         self.has_tree_tol = self.has_tree_inc and self._bind_extension(TREE_TOL_SYMBOLS)
+        self.has_big_lds = self.has_tree_tol and self._bind_extension(BIG_SYMBOLS)
 
     def _bind_extension(self, symbols):
         """bind a HIP-only extension when the library exports all of it; False otherwise"""

@@ -24,6 +24,7 @@
 #include "../../include/jslpe_tree_enhanced.h"
 #include "../../include/jslpi_tree_incremental.h"
 #include "../../include/jslpg_tree_tolerance.h"
+#include "../../include/jslpb_big_lds.h"
 #include "jslp_kernels.hip.h"
 #include "jslp_host_mem.h"
 
@@ -3431,13 +3432,15 @@ extern "C" int jslpf_simplex_f32_sweep(jslp_engine* e, const double* precisions,
 // One object, one arena: [LP images | descriptor table | launch order | per-LP checkForCycles | histories | traces].  The images have a
 // pinned twin (the ONE H2D copy of upload); the result block [states | RHS columns | row maps | (tree records) | optional rows] has another
 // (the ONE D2H copy of simplex).  An LP with optional objectives (include/jslps_soft.h) carries their rows in its image behind the matrix and
-// runs in the OPT build of its kernel: up to four launches per call, 64 or 256 threads, each with or without OPT.
+// runs in the OPT build of its kernel: up to four launches per call, 64 or 256 threads, each with or without OPT -- six in a pack made with
+// big_lds (include/jslpb_big_lds.h), whose LPs above 64 KiB of LDS run in the large builds.
 // A pack call holds no jslp_engine and takes no g_many_mu.  The kernels live in jslp_tu_packed.hip (jslp_packed.hip.h).
 #include "jslp_packed.hip.h"
 #include "jslp_tree.hip.h"  // (the layout of a pack with cut rows and a heap per LP, include/jslpt_tree.h)
 // The units that hold the builds of the pack kernels: each launches the build (a.tree, threads, a.build) names, or answers -1 for one that is
-// not its own (pack_dispatch, jslp_tree.hip.h).  The product has four (jslp_tu_packed.hip, jslp_tu_tree_mir.hip, _enh, _inc); a single-unit
-// build has this file, the kernels at its end.
+// not its own (pack_dispatch, jslp_tree.hip.h).  The product has seven (jslp_tu_packed.hip, jslp_tu_tree_mir.hip, _enh, _inc, the two parts of
+// jslp_tu_tree_tol.hip, and jslp_tu_packed_big.hip with the large builds of include/jslpb_big_lds.h); a single-unit build has this file, the
+// kernels at its end.
 typedef int (*PackUnit)(int threads, unsigned grid, size_t lds, const void* args, void* stream);
 #ifdef JSLP_SPLIT_TU
 extern "C" __attribute__((visibility("hidden"))) int jslpp_packed_launch_tu(int threads, unsigned grid, size_t lds, const void* args, void* stream);
@@ -3446,8 +3449,9 @@ extern "C" __attribute__((visibility("hidden"))) int jslpe_tree_enh_launch_tu(in
 extern "C" __attribute__((visibility("hidden"))) int jslpi_tree_inc_launch_tu(int threads, unsigned grid, size_t lds, const void* args, void* stream);
 extern "C" __attribute__((visibility("hidden"))) int jslpg_tree_tol1_launch_tu(int threads, unsigned grid, size_t lds, const void* args, void* stream);
 extern "C" __attribute__((visibility("hidden"))) int jslpg_tree_tol2_launch_tu(int threads, unsigned grid, size_t lds, const void* args, void* stream);
+extern "C" __attribute__((visibility("hidden"))) int jslpb_packed_big_launch_tu(int threads, unsigned grid, size_t lds, const void* args, void* stream);
 static constexpr PackUnit PACK_UNITS[] = {jslpp_packed_launch_tu, jslpc_tree_mir_launch_tu, jslpe_tree_enh_launch_tu, jslpi_tree_inc_launch_tu,
-                                          jslpg_tree_tol1_launch_tu, jslpg_tree_tol2_launch_tu};
+                                          jslpg_tree_tol1_launch_tu, jslpg_tree_tol2_launch_tu, jslpb_packed_big_launch_tu};
 #else
 static int pack_dispatch(int threads, unsigned grid, size_t lds, const void* bytes, void* stream);  // (jslp_tree.hip.h, at the end of this file)
 static constexpr PackUnit PACK_UNITS[] = {pack_dispatch};
@@ -3463,10 +3467,12 @@ static int packed_launch(int threads, unsigned grid, size_t lds, const PackLaunc
 // THE launch groups of a pack, in launch order: the LPs of one kind that run with one thread count, and what the launch line says behind the
 // thread count.  pack_init sorts the LPs into them, pack_run launches them.  (A plain simplex has the plain and the OPT build only: it runs a
 // group of MIR, enhanced or incremental LPs in the plain build of the group's thread count, and says so.)
-struct PackGroup { PackKind kind; int threads; const char* suffix; };
+struct PackGroup { PackKind kind; int threads; const char* suffix; bool big = false; };  // (big: the large class, whatever its thread count)
 static constexpr PackGroup PACK_GROUPS[] = {{PACK_PLAIN, 64, ""},      {PACK_PLAIN, 256, ""},      {PACK_OPT, 64, ",opt 1"}, {PACK_OPT, 256, ",opt 1"},
                                             {PACK_MIR, 64, ",mir 1"},  {PACK_MIR, 256, ",mir 1"},  {PACK_ENH, 64, ",enh 1"}, {PACK_ENH, 256, ",enh 1"},
-                                            {PACK_INC, 64, ",inc 1"},  {PACK_INC, 256, ",inc 1"}};
+                                            {PACK_INC, 64, ",inc 1"},  {PACK_INC, 256, ",inc 1"},
+                                            // (the large LPs of a pack with big_lds, include/jslpb_big_lds.h: an image above 64 KiB is a plain LP's or an OPT LP's)
+                                            {PACK_PLAIN, JSLP_PACK_BIG_THREADS, "", true}, {PACK_OPT, JSLP_PACK_BIG_THREADS, ",opt 1", true}};
 // The result block [states | RHS columns | row maps | (a TreeRec per LP | (a TreeMirRec per LP) | (a TreeEnhRec per LP, an incremental pack's with
 // the LP's TreeIncRec behind it)) | optional rows]: the byte offset of every piece, each at a 256-byte boundary, computed ONCE at create
 // (a pack with a tolerance table, include/jslpg_tree_tolerance.h: a TreeTolRec per LP behind everything else)
@@ -3560,7 +3566,10 @@ struct jslpp_pack {
     bool is_mir(size_t i) const { return kind[i] == PACK_MIR; }
     bool is_enh(size_t i) const { return kind[i] == PACK_ENH || kind[i] == PACK_INC; }  // (an incremental LP is one too)
     bool is_inc(size_t i) const { return kind[i] == PACK_INC; }
-    int threads(size_t i) const { return (long long)RC[i] * W[i] <= PACK_CELLS_WAVE ? 64 : 256; }  // (tableau cells at the row capacity, optional rows or not)
+    bool is_big(size_t i) const { return lds_bytes(i) > (size_t)PACK_SMALL_LDS; }  // a large LP (include/jslpb_big_lds.h; create lets none into a pack without big_lds)
+    int threads(size_t i) const {  // (tableau cells at the row capacity, optional rows or not)
+        return is_big(i) ? JSLP_PACK_BIG_THREADS : (long long)RC[i] * W[i] <= PACK_CELLS_WAVE ? 64 : 256;
+    }
     size_t ckpt_arena_bytes(size_t i) const { return is_inc(i) ? (size_t)tree_ckpt_bytes(RC[i], W[i]) * (size_t)max_ckpt[i] : 0; }
     TreeCarve tree_carve(size_t i, size_t off) const {
         const size_t slots = (size_t)heap_cap[i] + 3;
@@ -3645,7 +3654,7 @@ static int pack_init(jslpp_pack* p, int32_t max_pivots) {
     int32_t k = 0;
     for (int g = 0; g < jslpp_pack::N_GROUPS; g++)  // group after group (PACK_GROUPS), each in pack order
         for (size_t i = 0; i < n; i++) {
-            if (p->kind[i] != PACK_GROUPS[g / 2].kind || p->threads(i) != PACK_GROUPS[g / 2].threads || p->is_tol(i) != ((g & 1) != 0)) continue;
+            if (p->kind[i] != PACK_GROUPS[g / 2].kind || p->threads(i) != PACK_GROUPS[g / 2].threads || p->is_big(i) != PACK_GROUPS[g / 2].big || p->is_tol(i) != ((g & 1) != 0)) continue;
             order[k++] = (int32_t)i;
             p->n_group[g] += 1;
             p->lds_group[g] = std::max(p->lds_group[g], p->lds_bytes(i));
@@ -3713,6 +3722,7 @@ struct PackSpec {
     const int32_t *cut_rows, *heap_cap, *n_optional, *row_extra, *node_selection, *branching, *incremental, *max_checkpoints;
     const double* tolerance;  // (include/jslpg_tree_tolerance.h; either may be null)
     const int32_t* minimize;
+    bool big_lds;  // (include/jslpb_big_lds.h) the pack's limit is JSLPB_LDS_LIMIT
 };
 static PackSpec pack_spec(jslpp_pack** out, int device, int32_t n, const int32_t* height, const int32_t* width, const double* precision, int32_t trace_cap,
                           int32_t max_pivots, int32_t max_nodes) {
@@ -3763,6 +3773,22 @@ static int pack_create(const PackSpec& s) {
             return pack_fail(JSLP_ERR_ARG, "pack_create", i, "row_extra of a MIR LP is at least its cut_rows (a negative one makes a plain tree LP)");
         const long long rc = (long long)s.height[i] + (mir || inc ? s.row_extra[i] : tree ? s.cut_rows[i] : 0);
         const long long no = s.n_optional ? s.n_optional[i] : 0;
+        if (s.big_lds) {  // (include/jslpb_big_lds.h) the large builds are the default service's: every other kind keeps the 64 KiB rule
+            const bool enh = s.node_selection && (s.node_selection[i] || s.branching[i]);
+            const bool tol = s.tolerance && s.tolerance[i] > 0;
+            const bool own = mir || inc || enh || tol;  // (its kind has no large build)
+            const long long limit = own ? JSLPP_LDS_LIMIT : JSLPB_LDS_LIMIT;
+            if ((rc + no) * s.width[i] > limit / 8 ||
+                (mir ? tree_mir_lds_bytes((int32_t)rc, s.width[i]) : pk_lds_bytes((int32_t)rc, s.width[i], (int32_t)no)) > limit)
+                return pack_fail(JSLP_ERR_UNSUPPORTED, "pack_create", i,
+                                 mir ? "the MIR LP's LDS image at its row capacity exceeds 64 KiB (jslpc_tree_lds_bytes; the large builds of jslpb_big_lds.h hold no MIR LP): a smaller row_extra, or solve it through a jslp_engine" :
+                                 inc ? "the incremental LP's LDS image at its row capacity exceeds 64 KiB (jslpi_tree_lds_bytes; the large builds of jslpb_big_lds.h hold no incremental LP): a smaller row_extra, or solve it through a jslp_engine" :
+                                 enh ? "the enhanced LP's LDS image at its row capacity exceeds 64 KiB (jslpt_lds_bytes; the large builds of jslpb_big_lds.h hold no enhanced LP): fewer cut rows, or solve it through a jslp_engine" :
+                                 tol ? "the LDS image of the LP with a tolerance exceeds 64 KiB at its row capacity (the large builds of jslpb_big_lds.h hold no LP with a tolerance): fewer cut rows, or solve it through a jslp_engine" :
+                                 tree ? "the tableau's LDS image at its row capacity exceeds JSLPB_LDS_LIMIT, 156 KiB (jslpt_lds_bytes): fewer cut rows, or solve it through a jslp_engine"
+                                      : "the tableau's LDS image exceeds JSLPB_LDS_LIMIT, 156 KiB (jslpp_lds_bytes): solve it through a jslp_engine");
+            continue;
+        }
         // (cells beyond the limit first: the byte count of an absurd shape must not overflow before it is compared)
         if (mir && ((rc + no) * s.width[i] > JSLPP_LDS_LIMIT / 8 || tree_mir_lds_bytes((int32_t)rc, s.width[i]) > (long long)WGLDS_MAX_BYTES))
             return pack_fail(JSLP_ERR_UNSUPPORTED, "pack_create", i,
@@ -3778,6 +3804,14 @@ static int pack_create(const PackSpec& s) {
         return fail(JSLP_ERR_DEVICE, "pack_create: no HIP device visible (this engine has no CPU fallback)");
     if (s.device < 0 || s.device >= ndev) return fail(JSLP_ERR_ARG, "pack_create: device ordinal out of range");
     HIPC(hipSetDevice(s.device));
+    if (s.big_lds) {  // a large LP's workgroup takes (nearly) all of a compute unit's LDS: the device must have 160 KiB per workgroup
+        int per_block = 0;
+        HIPC(hipDeviceGetAttribute(&per_block, hipDeviceAttributeMaxSharedMemoryPerBlock, s.device));
+        if (per_block < PACK_CU_LDS) {
+            snprintf(g_err, sizeof g_err, "pack_create: device %d offers %d bytes of LDS to a workgroup: big_lds needs 163840 (include/jslpb_big_lds.h)", s.device, per_block);
+            return JSLP_ERR_UNSUPPORTED;
+        }
+    }
     jslpp_pack* p = new jslpp_pack();
     p->device = s.device; p->n = n; p->trace_cap = s.trace_cap;
     p->hist_cap = s.max_pivots > 0 ? std::min<int32_t>(s.max_pivots, JSLPP_HIST_CAP) : JSLPP_HIST_CAP;
@@ -3907,6 +3941,36 @@ extern "C" int jslpg_tree_pack_create(jslpp_pack** out, int device, int32_t n, c
     s.tolerance = tolerance; s.minimize = minimize;
     return pack_create(s);
 }
+// include/jslpb_big_lds.h
+static_assert(JSLPB_LDS_LIMIT == PACK_BIG_LDS && JSLPP_LDS_LIMIT == PACK_SMALL_LDS, "the headers' limits are the kernels' (jslp_packed.hip.h)");
+extern "C" int jslpb_pack_create(jslpp_pack** out, int device, int32_t n, const int32_t* height, const int32_t* width, const double* precision,
+                                 const int32_t* n_optional, int32_t trace_cap, int32_t max_pivots, int32_t big_lds) {
+    if (big_lds == 0) return jslps_pack_create(out, device, n, height, width, precision, n_optional, trace_cap, max_pivots);
+    if (big_lds != 1) return fail(JSLP_ERR_ARG, "pack_create: big_lds is 0 or 1");
+    PackSpec s = pack_spec(out, device, n, height, width, precision, trace_cap, max_pivots, 0);
+    s.n_optional = n_optional;
+    s.big_lds = true;
+    return pack_create(s);
+}
+extern "C" int jslpb_tree_pack_create(jslpp_pack** out, int device, int32_t n, const int32_t* height, const int32_t* width, const double* precision,
+                                      const int32_t* cut_rows, const int32_t* heap_cap, const int32_t* n_optional, const int32_t* row_extra,
+                                      const int32_t* node_selection, const int32_t* branching, const int32_t* incremental,
+                                      const int32_t* max_checkpoints, const double* tolerance, const int32_t* minimize, int32_t trace_cap,
+                                      int32_t max_pivots, int32_t max_nodes, int32_t big_lds) {
+    if (big_lds == 0)
+        return jslpg_tree_pack_create(out, device, n, height, width, precision, cut_rows, heap_cap, n_optional, row_extra, node_selection, branching, incremental,
+                                      max_checkpoints, tolerance, minimize, trace_cap, max_pivots, max_nodes);
+    if (big_lds != 1) return fail(JSLP_ERR_ARG, "pack_create: big_lds is 0 or 1");
+    PackSpec s = pack_spec(out, device, n, height, width, precision, trace_cap, max_pivots, max_nodes);
+    s.tree = true; s.cut_rows = cut_rows; s.heap_cap = heap_cap;
+    s.n_optional = n_optional; s.row_extra = row_extra;
+    s.enh = true; s.node_selection = node_selection; s.branching = branching;
+    s.inc = true; s.incremental = incremental; s.max_checkpoints = max_checkpoints;
+    s.tolerance = tolerance; s.minimize = minimize;
+    s.big_lds = true;
+    return pack_create(s);
+}
+extern "C" int32_t jslpb_pack_big_threads(void) { return JSLP_PACK_BIG_THREADS; }
 extern "C" int64_t jslpi_tree_lds_bytes(int32_t height, int32_t width, int32_t row_capacity) { return jslpt_lds_bytes(height, width, row_capacity); }
 extern "C" int64_t jslpi_checkpoint_bytes(int32_t height, int32_t width, int32_t row_capacity) {
     if (height < 2 || width < 2 || row_capacity < height) return 0;
@@ -4167,8 +4231,15 @@ static int pack_run(jslpp_pack* p, bool tree, const int32_t* check_cycles, jslp_
         a.order = p->d_order + begin;
         a.build = own ? grp.kind : PACK_PLAIN;
         a.tol = tol ? 1 : 0;
-        (void)packed_launch(grp.threads, (unsigned)cnt, lds, a, s);
+        const int le = packed_launch(grp.threads, (unsigned)cnt, lds, a, s);
         HIPC(hipGetLastError());
+        // (a large build says what forbade its launch -- the LDS attribute refused, static plus dynamic LDS beyond the compute unit's -- and
+        // a group no unit holds a build for is an error, never a launch skipped in silence)
+        if (grp.big && le != (int)hipSuccess) {
+            snprintf(g_err, sizeof g_err, "pack launch %s<%d%s> lds %zu: %s", tree ? "k_tree_packed" : "k_simplex_packed", grp.threads, own ? grp.suffix : "", lds,
+                     le == -1 ? "no unit holds this build" : hipGetErrorString((hipError_t)le));
+            return JSLP_ERR_DEVICE;
+        }
         p->launches += 1;
         if (dbg) fprintf(stderr, "[jslp] launch %s<%d%s%s> n %d lds %zu\n", tree ? "k_tree_packed" : "k_simplex_packed", grp.threads, own ? grp.suffix : "", tol ? ",tol 1" : "", (int)cnt, lds);
     }

@@ -86,6 +86,16 @@ struct PackLaunch {
     const void* trees;     // tree 1: the TreeLp table ...
     void* tree_out;        // ... and the TreeRec per LP
 };
+// The large class (include/jslpb_big_lds.h): an LP whose LDS image exceeds PACK_SMALL_LDS runs in the large build of its kind, a workgroup of
+// PACK_BIG_THREADS threads with a compute unit to itself (jslp_tu_packed_big.hip).  ONE thread count ships (profiles/packed_big_times.md has
+// the candidates' table); -DJSLP_PACK_BIG_THREADS on every unit builds a development library at another.
+#ifndef JSLP_PACK_BIG_THREADS
+#define JSLP_PACK_BIG_THREADS 1024
+#endif
+static_assert(JSLP_PACK_BIG_THREADS == 256 || JSLP_PACK_BIG_THREADS == 512 || JSLP_PACK_BIG_THREADS == 1024, "the large builds' thread count");
+#define PACK_SMALL_LDS 65536       // JSLPP_LDS_LIMIT: the dynamic LDS of the 64- and 256-thread builds at most
+#define PACK_BIG_LDS (156 * 1024)  // JSLPB_LDS_LIMIT: of the large builds
+#define PACK_CU_LDS (160 * 1024)   // static plus dynamic LDS of one workgroup at most
 #endif  // JSLP_PACKED_LAYOUT
 
 #if defined(JSLP_PACKED_KERNELS) && !defined(JSLP_PACKED_KERNELS_DONE)
@@ -645,14 +655,47 @@ constexpr bool pack_build_here(int build) { return ((JSLP_PACK_BUILDS) >> build 
 #define JSLP_PACK_TOL 2
 #endif
 constexpr bool pack_tol_here(bool tol) { return (JSLP_PACK_TOL) == 2 || ((JSLP_PACK_TOL) == 1) == tol; }
+// JSLP_PACK_BIG: which side of the large class (include/jslpb_big_lds.h) the unit instantiates -- 0 (every unit that names its builds): the
+// 64- and 256-thread builds, as before there was such a class; 1: the large builds of the unit's kinds alone (jslp_tu_packed_big.hip: a unit
+// of their own, so that the other units compile what they compiled); 2 (not given): both (the single-unit build).
+#ifndef JSLP_PACK_BIG
+#define JSLP_PACK_BIG 2
+#endif
+constexpr bool pack_big_here(bool big) { return (JSLP_PACK_BIG) == 2 || ((JSLP_PACK_BIG) == 1) == big; }
+// A large build's launch: the first one on a device raises the kernel's dynamic-LDS ceiling to PACK_BIG_LDS (the runtime refuses more than
+// 64 KiB without it) and holds static plus dynamic LDS to the compute unit's 160 KiB.  Returns hipSuccess, or the error that forbids the launch.
+template <class Kernel>
+static hipError_t pack_big_prepare(Kernel kernel, size_t lds, unsigned long long* ready) {
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    const unsigned long long bit = 1ull << (dev & 63);
+    if (!(__atomic_load_n(ready, __ATOMIC_ACQUIRE) & bit)) {
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, PACK_BIG_LDS);
+        if (e != hipSuccess) return e;
+        hipFuncAttributes fa;
+        e = hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(kernel));
+        if (e != hipSuccess) return e;
+        // sharedSizeBytes + lds <= 160 KiB for every lds a launch may come with (the unit's static_assert holds the structs to the reserve)
+        if (fa.sharedSizeBytes + (size_t)PACK_BIG_LDS > (size_t)PACK_CU_LDS) return hipErrorLaunchOutOfResources;
+        __atomic_fetch_or(ready, bit, __ATOMIC_RELEASE);
+    }
+    return lds <= (size_t)PACK_BIG_LDS ? hipSuccess : hipErrorLaunchOutOfResources;
+}
 
-// one build of k_simplex_packed: launches when (threads, a.build) is its own
-template <int T, int BUILD>
-static bool pk_launch(int threads, unsigned grid, size_t lds, const PackLaunch& a, hipStream_t s) {
-    if constexpr (!pack_build_here(BUILD) || !pack_tol_here(false)) {
+// one build of k_simplex_packed: launches when (threads, a.build) and the class of `lds` are its own.  BIG: a large build -- *err is what
+// forbade its launch, if anything did
+template <int T, int BUILD, bool BIG = false>
+static bool pk_launch(int threads, unsigned grid, size_t lds, const PackLaunch& a, hipStream_t s, hipError_t* err) {
+    if constexpr (!pack_build_here(BUILD) || !pack_tol_here(false) || !pack_big_here(BIG)) {
         return false;
     } else {
-        if (threads != T || a.build != BUILD) return false;
+        if (threads != T || a.build != BUILD || (lds > PACK_SMALL_LDS) != BIG) return false;
+        if constexpr (BIG) {
+            static unsigned long long ready = 0;
+            *err = pack_big_prepare(k_simplex_packed<T, BUILD == PACK_OPT>, lds, &ready);
+            if (*err != hipSuccess) return true;
+        }
         hipLaunchKernelGGL((k_simplex_packed<T, BUILD == PACK_OPT>), dim3(grid), dim3(T), lds, s, a.lps, a.order, a.cc, a.cc_all, static_cast<DevState*>(a.states), a.rhs,
                            a.rows);
         return true;

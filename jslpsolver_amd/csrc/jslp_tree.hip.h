@@ -898,12 +898,17 @@ __global__ void __launch_bounds__(THREADS) k_tree_packed(const PackLp* __restric
 }
 
 // one build of k_tree_packed, as pk_launch (MIR, ENH and INC come without OPT; an INC build is an ENH build)
-template <int T, int BUILD, bool TOL = false>
-static bool tree_launch(int threads, unsigned grid, size_t lds, const PackLaunch& a, hipStream_t s) {
-    if constexpr (!pack_build_here(BUILD) || !pack_tol_here(TOL)) {
+template <int T, int BUILD, bool TOL = false, bool BIG = false>
+static bool tree_launch(int threads, unsigned grid, size_t lds, const PackLaunch& a, hipStream_t s, hipError_t* err) {
+    if constexpr (!pack_build_here(BUILD) || !pack_tol_here(TOL) || !pack_big_here(BIG)) {
         return false;
     } else {
-        if (threads != T || a.build != BUILD || (a.tol != 0) != TOL) return false;
+        if (threads != T || a.build != BUILD || (a.tol != 0) != TOL || (lds > PACK_SMALL_LDS) != BIG) return false;
+        if constexpr (BIG) {
+            static unsigned long long ready = 0;
+            *err = pack_big_prepare(k_tree_packed<T, BUILD == PACK_OPT, BUILD == PACK_MIR, BUILD == PACK_ENH || BUILD == PACK_INC, BUILD == PACK_INC, TOL>, lds, &ready);
+            if (*err != hipSuccess) return true;
+        }
         hipLaunchKernelGGL((k_tree_packed<T, BUILD == PACK_OPT, BUILD == PACK_MIR, BUILD == PACK_ENH || BUILD == PACK_INC, BUILD == PACK_INC, TOL>), dim3(grid), dim3(T), lds, s,
                            a.lps, static_cast<const TreeLp*>(a.trees), a.order, a.cc, a.cc_all, static_cast<DevState*>(a.states), a.rhs, a.rows,
                            static_cast<TreeRec*>(a.tree_out));
@@ -917,21 +922,28 @@ static int pack_dispatch(int threads, unsigned grid, size_t lds, const void* byt
     const PackLaunch& a = *static_cast<const PackLaunch*>(bytes);
     hipStream_t s = static_cast<hipStream_t>(stream);
     bool hit;
+    hipError_t err = hipSuccess;  // (a large build: what forbade its launch)
+    constexpr int B = JSLP_PACK_BIG_THREADS;
     if (!a.tree)
-        hit = pk_launch<64, PACK_PLAIN>(threads, grid, lds, a, s) || pk_launch<256, PACK_PLAIN>(threads, grid, lds, a, s) ||
-              pk_launch<64, PACK_OPT>(threads, grid, lds, a, s) || pk_launch<256, PACK_OPT>(threads, grid, lds, a, s);
+        hit = pk_launch<64, PACK_PLAIN>(threads, grid, lds, a, s, &err) || pk_launch<256, PACK_PLAIN>(threads, grid, lds, a, s, &err) ||
+              pk_launch<64, PACK_OPT>(threads, grid, lds, a, s, &err) || pk_launch<256, PACK_OPT>(threads, grid, lds, a, s, &err) ||
+              // (the large builds behind every other, as the TOL builds below)
+              pk_launch<B, PACK_PLAIN, true>(threads, grid, lds, a, s, &err) || pk_launch<B, PACK_OPT, true>(threads, grid, lds, a, s, &err);
     else
-        hit = tree_launch<64, PACK_PLAIN>(threads, grid, lds, a, s) || tree_launch<256, PACK_PLAIN>(threads, grid, lds, a, s) ||
-              tree_launch<64, PACK_OPT>(threads, grid, lds, a, s) || tree_launch<256, PACK_OPT>(threads, grid, lds, a, s) ||
-              tree_launch<64, PACK_MIR>(threads, grid, lds, a, s) || tree_launch<256, PACK_MIR>(threads, grid, lds, a, s) ||
-              tree_launch<64, PACK_ENH>(threads, grid, lds, a, s) || tree_launch<256, PACK_ENH>(threads, grid, lds, a, s) ||
-              tree_launch<64, PACK_INC>(threads, grid, lds, a, s) || tree_launch<256, PACK_INC>(threads, grid, lds, a, s) ||
+        hit = tree_launch<64, PACK_PLAIN>(threads, grid, lds, a, s, &err) || tree_launch<256, PACK_PLAIN>(threads, grid, lds, a, s, &err) ||
+              tree_launch<64, PACK_OPT>(threads, grid, lds, a, s, &err) || tree_launch<256, PACK_OPT>(threads, grid, lds, a, s, &err) ||
+              tree_launch<64, PACK_MIR>(threads, grid, lds, a, s, &err) || tree_launch<256, PACK_MIR>(threads, grid, lds, a, s, &err) ||
+              tree_launch<64, PACK_ENH>(threads, grid, lds, a, s, &err) || tree_launch<256, PACK_ENH>(threads, grid, lds, a, s, &err) ||
+              tree_launch<64, PACK_INC>(threads, grid, lds, a, s, &err) || tree_launch<256, PACK_INC>(threads, grid, lds, a, s, &err) ||
               // (the TOL builds behind every other, so that those are instantiated in the order they were)
-              tree_launch<64, PACK_PLAIN, true>(threads, grid, lds, a, s) || tree_launch<256, PACK_PLAIN, true>(threads, grid, lds, a, s) ||
-              tree_launch<64, PACK_OPT, true>(threads, grid, lds, a, s) || tree_launch<256, PACK_OPT, true>(threads, grid, lds, a, s) ||
-              tree_launch<64, PACK_MIR, true>(threads, grid, lds, a, s) || tree_launch<256, PACK_MIR, true>(threads, grid, lds, a, s) ||
-              tree_launch<64, PACK_ENH, true>(threads, grid, lds, a, s) || tree_launch<256, PACK_ENH, true>(threads, grid, lds, a, s) ||
-              tree_launch<64, PACK_INC, true>(threads, grid, lds, a, s) || tree_launch<256, PACK_INC, true>(threads, grid, lds, a, s);
+              tree_launch<64, PACK_PLAIN, true>(threads, grid, lds, a, s, &err) || tree_launch<256, PACK_PLAIN, true>(threads, grid, lds, a, s, &err) ||
+              tree_launch<64, PACK_OPT, true>(threads, grid, lds, a, s, &err) || tree_launch<256, PACK_OPT, true>(threads, grid, lds, a, s, &err) ||
+              tree_launch<64, PACK_MIR, true>(threads, grid, lds, a, s, &err) || tree_launch<256, PACK_MIR, true>(threads, grid, lds, a, s, &err) ||
+              tree_launch<64, PACK_ENH, true>(threads, grid, lds, a, s, &err) || tree_launch<256, PACK_ENH, true>(threads, grid, lds, a, s, &err) ||
+              tree_launch<64, PACK_INC, true>(threads, grid, lds, a, s, &err) || tree_launch<256, PACK_INC, true>(threads, grid, lds, a, s, &err) ||
+              // (the large builds, include/jslpb_big_lds.h: the default service, plain and OPT)
+              tree_launch<B, PACK_PLAIN, false, true>(threads, grid, lds, a, s, &err) || tree_launch<B, PACK_OPT, false, true>(threads, grid, lds, a, s, &err);
+    if (hit && err != hipSuccess) return (int)err;
     return hit ? (int)hipPeekAtLastError() : -1;
 }
 #endif  // JSLP_PACKED_KERNELS

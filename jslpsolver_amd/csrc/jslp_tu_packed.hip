@@ -15,6 +15,7 @@ namespace {
 #include "jslp_kernels.hip.h"
 #define JSLP_PACKED_KERNELS 1
 #define JSLP_PACK_TOL 0  // (the TOL twins of these builds: jslp_tu_tree_tol.hip)
+#define JSLP_PACK_BIG 0  // (the large builds, include/jslpb_big_lds.h: jslp_tu_packed_big.hip)
 #define JSLP_PACK_BUILDS 0x03  // (the MIR, ENH and INC builds of k_tree_packed: jslp_tu_tree_mir.hip, jslp_tu_tree_enh.hip, jslp_tu_tree_inc.hip)
 #include "jslp_packed.hip.h"
 #include "jslp_tree.hip.h"  // k_tree_packed (include/jslpt_tree.h): the same LDS layout, the loop as pk_simplex

@@ -15,6 +15,7 @@ namespace {
 #include "jslp_kernels.hip.h"
 #define JSLP_PACKED_KERNELS 1
 #define JSLP_PACK_TOL 0  // (the TOL twins of these builds: jslp_tu_tree_tol.hip)
+#define JSLP_PACK_BIG 0  // (the large builds, include/jslpb_big_lds.h: jslp_tu_packed_big.hip)
 #define JSLP_PACK_BUILDS 0x08  // pk_simplex alone: k_simplex_packed is jslp_tu_packed.hip's, and so are the plain and OPT builds of k_tree_packed
 #include "jslp_packed.hip.h"
 #include "jslp_tree.hip.h"

@@ -21,6 +21,7 @@ namespace {
 #include "jslp_kernels.hip.h"
 #define JSLP_PACKED_KERNELS 1
 #define JSLP_PACK_TOL 1
+#define JSLP_PACK_BIG 0  // (the large builds, include/jslpb_big_lds.h: jslp_tu_packed_big.hip)
 #if JSLP_TOL_PART == 1
 #define JSLP_PACK_BUILDS 0x07
 #else

@@ -910,9 +910,11 @@ def tree_lds_bytes(height, width, row_capacity, n_optional=0):
     return pack_lds_bytes(rc, w, n_optional)
 
 
-def tree_cut_rows(height, width, n_int, lib=None, n_optional=0):
+def tree_cut_rows(height, width, n_int, lib=None, n_optional=0, limit=None):
     """the cut rows a model with n_int integer variables (and n_optional optional objectives) joins a tree pack with: 2 per integer variable
-    -- the most a cut list can hold (branch-and-cut.ts:166-179) -- or the most that fit the LDS limit; 0 when not even one fits"""
+    -- the most a cut list can hold (branch-and-cut.ts:166-179) -- or the most that fit the LDS limit; 0 when not even one fits.
+    limit: the pack's LDS limit in bytes (None: JSLPP_LDS_LIMIT; a pack with big_lds: JSLPB_LDS_LIMIT, include/jslpb_big_lds.h)"""
+    limit = _capi.JSLPP_LDS_LIMIT if limit is None else int(limit)
     def fits(cut_rows):
         if n_optional and lib is not None and getattr(lib, "has_soft", False):
             b = int(lib.jslps_tree_lds_bytes(int(height), int(width), int(height) + cut_rows, int(n_optional)))
@@ -920,7 +922,7 @@ def tree_cut_rows(height, width, n_int, lib=None, n_optional=0):
             b = int(lib.jslpt_lds_bytes(int(height), int(width), int(height) + cut_rows))
         else:
             b = tree_lds_bytes(height, width, int(height) + cut_rows, n_optional)
-        return 0 < b <= _capi.JSLPP_LDS_LIMIT
+        return 0 < b <= limit
     lo, hi = 0, 2 * int(n_int)
     if fits(hi):
         return hi
@@ -1055,16 +1057,16 @@ class _MirCounters:
         return (self.rounds, self.rows_added, self.simplexes, self.root_rows, self.tallest - self.height0)
 
 
-def pack_fits(height, width, lib=None, n_optional=0):
+def pack_fits(height, width, lib=None, n_optional=0, limit=None):
     """whether a tableau of this shape (with n_optional optional objectives) can join a TableauPack: its LDS image stays within the 64 KiB
-    the pack kernels are launched with"""
+    the pack kernels are launched with -- or within `limit` bytes (a pack with big_lds: JSLPB_LDS_LIMIT, include/jslpb_big_lds.h)"""
     if n_optional and lib is not None and getattr(lib, "has_soft", False):
         b = int(lib.jslps_lds_bytes(int(height), int(width), int(n_optional)))
     elif not n_optional and lib is not None and getattr(lib, "has_pack", False):
         b = int(lib.jslpp_lds_bytes(int(height), int(width)))
     else:
         b = pack_lds_bytes(height, width, n_optional)
-    return 0 < b <= _capi.JSLPP_LDS_LIMIT
+    return 0 < b <= (_capi.JSLPP_LDS_LIMIT if limit is None else int(limit))
 
 
 class TableauPack:
@@ -1114,12 +1116,19 @@ class TableauPack:
     bestPossibleEval * (1 +- tolerance).  `tolerance` (_capi.TOL_TREE_DTYPE: best_possible, threshold,
     stopped, left) is the read-back of the last branch_and_cut(), zero for the other LPs; such an LP runs in the TOL twin of its kind's build,
     a launch of its own beside the LPs without a tolerance; `tolerances` holds the values given (0: none),
-    `is_tolerance` the flags, `has_tolerance` whether any LP has one."""
+    `is_tolerance` the flags, `has_tolerance` whether any LP has one.
+
+    big_lds=True (include/jslpb_big_lds.h): the pack's LDS limit is JSLPB_LDS_LIMIT, 156 KiB, instead of 64 KiB.  An LP whose image stays
+    within 64 KiB is the LP it was; a larger one runs in the large build of its kind (`big_threads` threads, a compute unit to itself):
+    plain LPs and default-service trees, each with or without optional objectives.  A MIR, an enhanced or an incremental LP and any LP with a
+    tolerance keeps the 64 KiB rule.  `lds_limit` is the pack's limit, `is_big` the flags of the large LPs."""
 
     def __init__(self, lps, precision=1e-8, lib=None, device=0, trace_cap=0, max_pivots=0, integers=None, cut_rows=None, heap_cap=None,
                  max_nodes=0, optional_objectives=None, mir=None, row_extra=None, node_selection=None, branching=None, incremental=None,
-                 max_checkpoints=_capi.JSLPI_CHECKPOINTS_DEFAULT, tolerance=None, minimize=None):
+                 max_checkpoints=_capi.JSLPI_CHECKPOINTS_DEFAULT, tolerance=None, minimize=None, big_lds=False):
         self.lib = lib if lib is not None else _capi.load_hip()
+        self.big_lds = bool(big_lds)
+        self.lds_limit = _capi.JSLPB_LDS_LIMIT if self.big_lds else _capi.JSLPP_LDS_LIMIT
         self._lps = []
         for matrix, vibr, vibc, unr in lps:
             m = _capi.as_f64(matrix)
@@ -1267,6 +1276,13 @@ class TableauPack:
             if self.is_mir[i] or self.n_optional[i] > 0:
                 raise ValueError("TableauPack: LP %d: an enhanced LP (node_selection / branching) has neither `mir` nor optional objectives "
                                  "(include/jslpe_tree_enhanced.h)" % i)
+        if self.big_lds and self.lib.has_pack and not getattr(self.lib, "has_big_lds", False):
+            raise _capi.EngineError("TableauPack: %s does not export the big-LDS extension (include/jslpb_big_lds.h)" % self.lib.path)
+        self.big_threads = int(self.lib.jslpb_pack_big_threads()) if getattr(self.lib, "has_big_lds", False) else 0
+        # the LDS image of every LP at its row capacity (a MIR LP: with its isInteger bytes), and which LPs are large
+        self.lds_bytes = np.array([tree_mir_lds_bytes(h, w, rc) if mir_lp else pack_lds_bytes(rc, w, no) for h, w, rc, no, mir_lp
+                                   in zip(self.heights, self.widths, self.row_capacity, self.n_optional, self.is_mir)], dtype=np.int64).reshape(n)
+        self.is_big = self.lds_bytes > _capi.JSLPP_LDS_LIMIT
         if self.has_tolerance and self.lib.has_pack and not getattr(self.lib, "has_tree_tol", False):
             raise _capi.EngineError("TableauPack: %s does not export the tolerance extension (include/jslpg_tree_tolerance.h)" % self.lib.path)
         if self.has_incremental and self.lib.has_pack and not getattr(self.lib, "has_tree_inc", False):
@@ -1286,7 +1302,17 @@ class TableauPack:
             trees = [ptr(self.cut_rows), ptr(self.heap_cap)] if self.is_tree else []
             optional = ptr(self.n_optional) if self.has_optional else None
             flags = self.is_incremental.astype(np.int32)
-            if self.has_tolerance:
+            big = []
+            if self.big_lds and self.is_tree:  # (jslpg_tree_pack_create's tables -- the tolerance pair NULL in a pack without one -- then big_lds)
+                symbol = said = "jslpb_tree_pack_create"
+                tables = trees + [optional, ptr(self.row_extra), ptr(self.node_selection), ptr(self.branching), ptr(flags), ptr(self.max_checkpoints),
+                                  _capi.ptr_f64(self.tolerances) if self.has_tolerance else None, ptr(self.minimize) if self.has_tolerance else None]
+                big = [1]
+            elif self.big_lds:
+                symbol = said = "jslpb_pack_create"
+                tables = [optional]
+                big = [1]
+            elif self.has_tolerance:
                 symbol = said = "jslpg_tree_pack_create"
                 tables = trees + [optional, ptr(self.row_extra), ptr(self.node_selection), ptr(self.branching), ptr(flags), ptr(self.max_checkpoints),
                                   _capi.ptr_f64(self.tolerances), ptr(self.minimize)]
@@ -1307,7 +1333,7 @@ class TableauPack:
                 tables = trees
             caps = [self.trace_cap, self.max_pivots] + ([self.max_nodes] if self.is_tree else [])
             self.lib.check(getattr(self.lib, symbol)(_capi.C.byref(self._h), self.device, n, ptr(self.heights), ptr(self.widths), _capi.ptr_f64(self.precision),
-                                                     *tables, *caps), said)
+                                                     *tables, *caps, *big), said)
             try:
                 for i, (m, vibr, vibc, unr) in enumerate(self._lps):
                     self.lib.check(self.lib.jslpp_pack_set(self._h, i, _capi.ptr_f64(m), _capi.ptr_i32(vibr), _capi.ptr_i32(vibc), _capi.ptr_i32(unr),
@@ -1340,6 +1366,16 @@ class TableauPack:
                 if self.is_enhanced[i] and len(set(self.integers[i].tolist())) != self.integers[i].shape[0]:
                     raise _capi.EngineError("jslpt_pack_set_integers failed (%d): pack_set_integers: LP %d: the integer variables of an enhanced "
                                             "LP are distinct" % (_capi.JSLP_ERR_ARG, i))
+                if self.big_lds:  # (include/jslpb_big_lds.h: the library's refusals, in its words)
+                    said = "jslpb_tree_pack_create" if self.is_tree else "jslpb_pack_create"
+                    kind = ("enhanced LP's LDS image at its row capacity" if self.is_enhanced[i] else
+                            "LDS image of the LP with a tolerance" if self.is_tolerance[i] else None)
+                    if kind is not None and self.is_big[i]:
+                        raise _capi.EngineError("%s failed (%d): pack_create: LP %d: the %s exceeds 64 KiB" % (said, _capi.JSLP_ERR_UNSUPPORTED, i, kind))
+                    if not 0 < self.lds_bytes[i] <= _capi.JSLPB_LDS_LIMIT:
+                        raise _capi.EngineError("%s failed (%d): pack_create: LP %d: the tableau's LDS image%s exceeds JSLPB_LDS_LIMIT, 156 KiB"
+                                                % (said, _capi.JSLP_ERR_UNSUPPORTED, i, " at its row capacity" if self.is_tree else ""))
+                    continue
                 if self.is_tree and not 0 < tree_lds_bytes(h, w, rc, no) <= _capi.JSLPP_LDS_LIMIT:
                     raise _capi.EngineError("jslpt_pack_create failed (%d): pack_create: LP %d: the tableau's LDS image at its row capacity exceeds "
                                             "64 KiB" % (_capi.JSLP_ERR_UNSUPPORTED, i))

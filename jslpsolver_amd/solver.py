@@ -119,7 +119,7 @@ def _incremental_tree_in_scope(m, tolerance=False):
     return o.get("useIncremental") is True and not (m.useMIRCuts or (m.tolerance and not tolerance) or m.timeout or m.keep_solutions)
 
 
-def solve_packed(models, precision=None, lib=None, device=0, incremental=False, tolerance=False):
+def solve_packed(models, precision=None, lib=None, device=0, incremental=False, tolerance=False, big_lds=False):
     """[Solve(m, precision, lib=lib, device=device) for m in models], in order, for the workload of many SMALL models.  Every model
     whose tableau -- with its optional objectives, one row per soft constraint priority, when it has any (include/jslps_soft.h) -- fits the
     pack's LDS limit goes through an engine.TableauPack -- one arena, one upload, one launch per kernel build (64 or 256 threads, each with
@@ -146,6 +146,12 @@ def solve_packed(models, precision=None, lib=None, device=0, incremental=False, 
         the model's sense into the pack, and its walk ends on the reference's toleranceFlag inside the kernel, one node late as the
         reference's does (include/jslpg_tree_tolerance.h).  options.timeout (a clock) and keep_solutions still keep a model out.  Without
         the keyword a model with a tolerance goes through Solve.
+      * big_lds=True (opt-in, include/jslpb_big_lds.h): the packs take tableaus up to JSLPB_LDS_LIMIT, 156 KiB of LDS, instead of 64 KiB.  A
+        model that joins a pack under the rules above joins it exactly as without the keyword -- same cut rows, same build.  The keyword only
+        ADDS models those rules leave out: a model without integer variables, soft constraints or not, whose tableau fits the larger limit;
+        and a default-service tree (no tolerance), soft constraints or not, with min(2 per integer variable, the most cut rows that fit the
+        larger limit) >= 1.  They run in the large builds of the pack kernels.  MIR, enhanced and incremental models and models with a
+        tolerance keep the 64 KiB rules.  A large tree that reaches a capacity is solved again through Solve like any other.
     Every other model goes through Solve as it is.  A model Solve rejects raises the same exception before anything is solved."""
     lib = lib if lib is not None else _capi.load_hip()
     models = list(models)
@@ -155,6 +161,8 @@ def solve_packed(models, precision=None, lib=None, device=0, incremental=False, 
     policies = {}  # position -> (options.nodeSelection or None, options.branching or None) of the enhanced and the incremental LPs among them
     inc = set()    # positions of the incremental LPs among them (their row_extra is their row capacity: no MIR LPs)
     optional = [None] * len(models)  # per model its optional objectives (None: none)
+    big = set()    # positions of the models that only the larger limit of big_lds lets in (the large LPs)
+    big_limit = _capi.JSLPB_LDS_LIMIT if big_lds else None
     for k, (m, matrix, _, _) in enumerate(parsed):
         _priorities, optional_rows = m.optional_objectives()
         n_opt = 0
@@ -165,10 +173,18 @@ def solve_packed(models, precision=None, lib=None, device=0, incremental=False, 
         if n_int == 0:
             if pack_fits(*matrix.shape, lib=lib, n_optional=n_opt):
                 packed.append(k)
+            elif big_lds and pack_fits(*matrix.shape, lib=lib, n_optional=n_opt, limit=big_limit):
+                packed.append(k)
+                big.add(k)
         elif _tree_in_scope(m, tolerance):
             cut_rows = tree_cut_rows(matrix.shape[0], matrix.shape[1], n_int, lib=lib, n_optional=n_opt)
             if cut_rows >= 1:
                 trees.append((k, cut_rows, -1))
+            elif big_lds and not m.tolerance:  # (an LP with a tolerance keeps the 64 KiB rule)
+                cut_rows = tree_cut_rows(matrix.shape[0], matrix.shape[1], n_int, lib=lib, n_optional=n_opt, limit=big_limit)
+                if cut_rows >= 1:
+                    trees.append((k, cut_rows, -1))
+                    big.add(k)
         elif m.useMIRCuts and n_opt == 0 and _mir_tree_in_scope(m, tolerance):
             row_extra, cut_rows = tree_mir_rows(matrix.shape[0], matrix.shape[1], n_int, lib=lib)
             if row_extra >= 1:
@@ -188,7 +204,7 @@ def solve_packed(models, precision=None, lib=None, device=0, incremental=False, 
     if packed:
         pack = TableauPack([(parsed[k][1], parsed[k][2], parsed[k][3], parsed[k][0].unrestricted) for k in packed],
                            precision=[parsed[k][0].precision for k in packed], lib=lib, device=device,
-                           optional_objectives=[optional[k] for k in packed])
+                           optional_objectives=[optional[k] for k in packed], big_lds=any(k in big for k in packed))
         try:
             pack.simplex(check_cycles=[parsed[k][0].checkForCycles for k in packed])
             for i, k in enumerate(packed):
@@ -201,7 +217,7 @@ def solve_packed(models, precision=None, lib=None, device=0, incremental=False, 
         trees = [t for t in trees if t[2] < 0 or t[0] in inc]
         _solve_tree_pack(mir_trees, parsed, optional, lib, device, results, policies)
     for chunk in _within_checkpoint_budget(trees, inc, parsed, lib):
-        _solve_tree_pack(chunk, parsed, optional, lib, device, results, policies, inc)
+        _solve_tree_pack(chunk, parsed, optional, lib, device, results, policies, inc, big)
     for k, model in enumerate(models):
         if results[k] is None:
             results[k] = Solve(model, precision, lib=lib, device=device)
@@ -227,8 +243,9 @@ def _within_checkpoint_budget(trees, inc, parsed, lib):
     return [c for c in chunks if c]
 
 
-def _solve_tree_pack(trees, parsed, optional, lib, device, results, policies, inc=frozenset()):
-    """solve_packed's pack with trees: results[k] for every model of `trees` whose LP reached no capacity (the others stay None: Solve)"""
+def _solve_tree_pack(trees, parsed, optional, lib, device, results, policies, inc=frozenset(), big=frozenset()):
+    """solve_packed's pack with trees: results[k] for every model of `trees` whose LP reached no capacity (the others stay None: Solve).
+    big: the models among them that only the larger limit of big_lds lets in -- with any, the pack is made with big_lds"""
     if trees:
         with_mir = any(e >= 0 and k not in inc for k, _, e in trees)
         with_inc = any(k in inc for k, _, _ in trees)
@@ -244,7 +261,8 @@ def _solve_tree_pack(trees, parsed, optional, lib, device, results, policies, in
                            node_selection=[policies.get(k, (None, None))[0] for k, _, _ in trees],
                            branching=[policies.get(k, (None, None))[1] for k, _, _ in trees],
                            tolerance=[parsed[k][0].tolerance or None for k, _, _ in trees] if with_tol else None,
-                           minimize=[bool(parsed[k][0].isMinimization) for k, _, _ in trees] if with_tol else None)
+                           minimize=[bool(parsed[k][0].isMinimization) for k, _, _ in trees] if with_tol else None,
+                           big_lds=any(k in big for k, _, _ in trees))
         try:
             try:
                 pack.branch_and_cut(check_cycles=[parsed[k][0].checkForCycles for k, _, _ in trees])
